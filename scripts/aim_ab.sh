@@ -2,7 +2,7 @@
 # bf16 pose error budget: MODEL.AMD.POSE_FP32_PARTS "" vs "aim" (the two re-embedding MLPs on f32 operands) on the benchmark workload
 O=gpurun_out; F="--no-cpu-baseline --no-boundary --no-fp32-path --no-other-configs --no-tape --steps 30 --warmup 6"
 for parts in "" "aim" "aim fc"; do
-  python bench.py $F --pose-fp32-parts "$parts" > $O/aim_ab.json 2>> $O/aim_ab.err
+  python bench.py $F --full --pose-fp32-parts "$parts" > $O/aim_ab.json 2>> $O/aim_ab.err
   python - <<PY
 import json
 d=json.load(open('$O/aim_ab.json'))

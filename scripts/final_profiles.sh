@@ -12,7 +12,7 @@ case " $* " in *" retune "*)
   python bench.py $F --k 128 --fp8 --steps 8 --warmup 3 --retune --routing $O/routing_r${RND}_fp8_k128.json > /dev/null 2>> $O/${P}_bench.err
   cp $O/routing_r${RND}*.json profiles/;;          # (the box's copy of profiles/: everything below loads them; merged back via gpurun_out/)
 esac
-python bench.py --gpus 1 --steps 20 --warmup 5 --layers $O/${P}_gemm_layers.tsv > $O/${P}_bench.json 2>> $O/${P}_bench.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --layers $O/${P}_gemm_layers.tsv > $O/${P}_bench.json 2>> $O/${P}_bench.err
 python - <<PY
 import json
 d=json.load(open('$O/${P}_bench.json')); r=d['roofline']
@@ -24,7 +24,7 @@ print('cpu', d.get('cpu_baseline'), d.get('fp32_parity_path',{}).get('value'))
 PY
 bash scripts/prof_isolated.sh ${P} --routing $ROUT > $O/${P}_isolated.log 2>&1; cp $O/iso_${P}.tsv $O/${P}_isolated_kernel_costs.txt; head -3 $O/${P}_isolated.log | cut -c1-200
 export TMPDIR=/tmp; cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_${P}_stats -o bench -- python $R/bench.py --steps 32 --warmup 5 --no-cpu-baseline --no-accuracy --no-boundary --no-other-configs --no-tape --no-fp32-path --routing $ROUT > $R/$O/${P}_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_${P}_stats -o bench -- python $R/bench.py --steps 32 --warmup 5 --full --no-cpu-baseline --no-accuracy --no-boundary --no-other-configs --no-tape --no-fp32-path --routing $ROUT > $R/$O/${P}_stats.log 2>&1
 cd $R; cp $(find $O/prof_${P}_stats -name "*kernel_stats.csv" | head -1) $O/${P}_kernel_stats.csv; head -4 $O/${P}_kernel_stats.csv | cut -c1-200
 bash scripts/pmc_bench.sh --routing $ROUT > $O/${P}_pmc_bench.log 2>&1; cp $O/pmc_traffic.json $O/${P}_pmc_traffic.json; tail -3 $O/${P}_pmc_bench.log
 # PMC summaries of the dominant kernel and of this round's new kernels (counters only, separate passes)

@@ -2,7 +2,7 @@
 # 256x128-tile kernel A/B in the four-in-flight loop: routing B = profiles/routing_r5.json as committed; routing A = the same file with
 # every entry the new kernel is eligible for removed, so that ONLY those shapes are tuned again (now with configurations 13 / 14 on offer).
 O=gpurun_out; mkdir -p $O
-F="--no-cpu-baseline --no-boundary --no-fp32-path --no-accuracy --no-other-configs --no-tape --steps 40 --warmup 8"
+F="--full --no-cpu-baseline --no-boundary --no-fp32-path --no-accuracy --no-other-configs --no-tape --steps 40 --warmup 8"
 python - <<'PY'
 import json
 d=json.load(open('profiles/routing_r5.json'))

@@ -11,7 +11,7 @@ done
 if [ -z "$ROUTING" ]; then ROUTING=$R/profiles/routing_r5.json; ARGS+=(--routing "$ROUTING"); fi
 [ -f "$ROUTING" ] || { echo "pmc_bench.sh: routing file $ROUTING does not exist" >&2; exit 2; }
 export PMC_ROUTING_FILE=$ROUTING
-set -- "${ARGS[@]}"
+set -- --full "${ARGS[@]}"            # (--full: the 3 instrumented roofline steps are among the 6 forward passes counted below)
 cd /tmp
 [ -n "$PMC_SKIP_COLLECT" ] && set --          # (re-summarise the CSVs of an earlier collection)
 for c in $([ -n "$PMC_SKIP_COLLECT" ] || echo FETCH_SIZE WRITE_SIZE); do

@@ -117,7 +117,7 @@ for name, a in CASES:
     del keep
 # the whole benchmark loop, four batches in flight
 t0 = time.time()
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "500", "--warmup", "10", "--no-cpu-baseline", "--no-boundary", "--no-fp32-path",
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "500", "--warmup", "10", "--full", "--no-cpu-baseline", "--no-boundary", "--no-fp32-path",
                     "--no-accuracy", "--no-other-configs", "--no-tape"], capture_output=True, text=True, cwd=ROOT)
 t1 = time.time()
 line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -2,6 +2,7 @@
 # Per-kernel cost WITHOUT overlap: one batch in flight, pose net on the main stream, kernel-trace stats, totals per step.
 # Usage: bash scripts/prof_isolated.sh <tag> [bench args]
 TAG=${1:-iso}; shift
+set -- --full "$@"              # the run must end with the 3 instrumented roofline steps the summary below skips
 R=$PWD; export TMPDIR=/tmp; cd /tmp
 STEPS=6
 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/prof_${TAG} -o bench -- python $R/bench.py --steps $STEPS --warmup 2 --inflight 1 --single-stream --no-cpu-baseline --no-accuracy --no-boundary --no-other-configs --no-tape --no-fp32-path "$@" > $R/gpurun_out/prof_${TAG}.log 2>&1

@@ -3,7 +3,7 @@
 # four-in-flight overlap trace with power / clock samples.  usage: bash scripts/r6_measure.sh <tag>
 T=${1:-a}; O=$PWD/gpurun_out; R=$PWD; P=r6_${T}
 mkdir -p $O
-F="--no-cpu-baseline --no-boundary --no-fp32-path --no-accuracy --no-other-configs --no-tape"
+F="--full --no-cpu-baseline --no-boundary --no-fp32-path --no-accuracy --no-other-configs --no-tape"
 python bench.py --steps 20 --warmup 5 $F > $O/${P}_bench.json 2> $O/${P}_bench.err; cut -c1-300 $O/${P}_bench.json
 export TMPDIR=/tmp; cd /tmp
 # ---- K legs: kernel stats in the loop + isolated costs (one batch in flight, one stream)

@@ -599,8 +599,8 @@ def test_bench_two_gpus_rccl(launcher):
         pytest.skip("needs >= 2 GPUs")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    bench_cmd = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--pairs", "8", "--no-cpu-baseline", "--no-accuracy",
-                 "--no-fp32-path"]
+    bench_cmd = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--pairs", "8", "--full", "--no-cpu-baseline",
+                 "--no-accuracy", "--no-fp32-path"]
     cmd = [sys.executable] + (["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                                "29533"] if launcher == "torchrun" else []) + bench_cmd
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
@@ -650,7 +650,7 @@ def test_steps_in_flight_are_bit_identical(device):
 
 
 def test_bench_line_carries_the_launch_tape_leg(device):
-    """`python bench.py` (the driver's command, shortened): the JSON line must carry the contract's keys, `roofline`, and the `launch_tape`
+    """`python bench.py --full` (the driver's command, shortened): the JSON line must carry the contract's keys, `roofline`, and the `launch_tape`
     leg - whose capture check compares a replay of every in-flight slot with the slot's eager rows.  With the grouped gather (--gather-every
     > 1, the default) that check once read buffers the loop never writes and the leg was silently skipped: both gather modes are run."""
     import json
@@ -660,7 +660,7 @@ def test_bench_line_carries_the_launch_tape_leg(device):
     from tests.util import ROOT
     for gather in ("8", "1"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--pairs", "8", "--gather-every", gather,
-                            "--no-cpu-baseline", "--no-boundary", "--no-fp32-path", "--no-accuracy", "--no-other-configs", "--no-autotune"],
+                            "--full", "--no-cpu-baseline", "--no-boundary", "--no-fp32-path", "--no-accuracy", "--no-other-configs", "--no-autotune"],
                            capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         assert "capture failed" not in r.stderr, r.stderr[-2000:]
@@ -670,3 +670,41 @@ def test_bench_line_carries_the_launch_tape_leg(device):
         assert line["steps"] == 6 and line["n_gpus"] == 1 and line["value"] > 0 and line["config"]["steps_per_all_gather"] == int(gather)
         tape = line.get("launch_tape")
         assert tape and tape["value"] > 0 and tape["replay"] == "launch tape", tape
+
+
+def test_plain_bench_line_and_dumped_outputs(device, tmp_path):
+    """`python bench.py` without --full: the contract's keys, exactly --steps timed steps, none of the --full legs; --dump-outputs writes
+    the last timed step's arrays (float32 / float64, finite, the rows of every pair), and a second run with the same arguments writes
+    the same arrays (same seeded inputs, same kernels)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    from tests.util import ROOT
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--pairs", "8",
+                            "--no-autotune", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+            assert k in line, k
+        assert line["steps"] == 5 and line["warmup"] == 2 and line["unit"] == "pairs/s" and line["dtype"] == "bf16"
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 8e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+        for k in ("roofline", "launch_tape", "cpu_baseline", "boundary", "other_configs", "fp32_parity_path", "pose_err_vs_fp32_path"):
+            assert k not in line, k
+        got = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert {"rows", "camera_tran", "camera_rot", "camera_init_tran", "m"} <= set(got)
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert got["rows"].shape == (8, 16) and got["rows"][:, 12].tolist() == list(range(8)) and got["camera_tran"].shape == (8, 3)
+        assert all(np.isfinite(a).all() for a in got.values())
+        dumps.append(got)
+    a, b = dumps
+    assert a.keys() == b.keys()
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-5, err_msg=k)

@@ -200,13 +200,18 @@ def test_inflight_loop_gather_every_world2(tmp_path):
             assert a[rk, i, :, 12].tolist() == list(range(rk * B, rk * B + B))
 
 
+# the bench.py / CLI children below are CPU runs over gloo: on a machine with a GPU they must not see it (a stub rank r would take
+# cuda:r, and a one-GPU machine has no cuda:1)
+CPU_ONLY = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+
+
 def _run_bench(argv, env_extra=None, timeout=300):
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(env_extra or {})
+    env.update(CPU_ONLY, **(env_extra or {}))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv, capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, (json.loads(lines[-1]) if lines else None)
@@ -236,6 +241,33 @@ def test_bench_single_rank_stub():
     r, j = _run_bench(["--gpus", "1", "--stub-model", "--steps", "3", "--warmup", "1", "--pairs", "4"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert j["n_gpus"] == 1 and j["config"]["rccl_ranks"] == 1 and j["rows_gathered"] == 4
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one .npy per array the timed path returns, floating arrays as float32 (float64 kept),
+    integer / bool arrays as float64 with their values exact, and an array over its share of the byte cap replaced by the same seeded
+    sample of its elements every time."""
+    import bench
+    B = 4
+    rows = torch.arange(B * 16, dtype=torch.float32).view(B, 16)
+    cams = {k: (torch.full((B, 3), float(i)), torch.full((B, 4), 0.5 * i)) for i, k in enumerate(("camera_init", "camera"))}
+    d = {"sel": {"kept_idx": torch.arange(2 * B * 3, dtype=torch.int64).view(2 * B, 3), "scores": torch.rand(2 * B, 50).bfloat16(),
+                 "flags": torch.ones(2 * B, dtype=torch.bool), "planes": torch.rand(2 * B, 50, 3, dtype=torch.float64)},
+         "cam": {"cameras": cams, "m": torch.full((B,), 3, dtype=torch.int32), "refine": {"maps": {"trans_all": torch.rand(B, 33, 3)}}}}
+    bench.dump_outputs(str(tmp_path / "a"), rows, d)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"rows", "camera_init_tran", "camera_init_rot", "camera_tran", "camera_rot", "sel_kept_idx", "sel_scores",
+                        "sel_flags", "sel_planes", "m", "refine_trans_all"}
+    assert got["rows"].dtype == np.float32 and np.array_equal(got["rows"], rows.numpy())
+    assert got["camera_rot"].dtype == np.float32 and got["camera_rot"].shape == (B, 4) and (got["camera_rot"] == 0.5).all()
+    assert got["sel_scores"].dtype == np.float32 and got["sel_planes"].dtype == np.float64
+    assert got["sel_kept_idx"].dtype == np.float64 and np.array_equal(got["sel_kept_idx"], np.arange(2 * B * 3).reshape(2 * B, 3))
+    assert got["m"].dtype == np.float64 and (got["m"] == 3).all() and got["sel_flags"].dtype == np.float64
+    big = {"sel": {"planes": torch.arange(100000, dtype=torch.float32)}, "cam": {"cameras": {}}}
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), rows, big, max_bytes=2 * 4096)
+    s1, s2 = np.load(tmp_path / "b" / "sel_planes.npy"), np.load(tmp_path / "c" / "sel_planes.npy")
+    assert s1.shape == (1024,) and np.array_equal(s1, s2) and len(np.unique(s1)) == 1024 and (np.diff(s1) > 0).all()
 
 
 def test_bench_gpus8_global_batch_256_stub():
@@ -318,6 +350,7 @@ def _run_cli(argv, timeout=600):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(CPU_ONLY)
     return subprocess.run([sys.executable, "-m", "nopesac_amd.run"] + argv, capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
 
 
@@ -340,7 +373,8 @@ def test_cli_world8_stub_matches_single_rank(tmp_path):
             assert abs(a[k][kk] - b[k][kk]) < 1e-5, (k, kk, a[k][kk], b[k][kk])
     t = a["timing(rank0)"]
     assert t["pairs"] == 3 and t["pinned"] and t["decode_threads"] >= 1
+    from nopesac_amd.runner import cpu_budget
     cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    if cores >= 8:
-        assert t["cores_of_this_rank"] == cores // 8
+    if cores >= 8:                                         # an eighth of the cores, and of the CPU quota when the container has one
+        assert t["cores_of_this_rank"] == min(cores // 8, max(1, cpu_budget() // 8))
     assert not b["timing(rank0)"]["pinned"]
