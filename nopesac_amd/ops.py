@@ -5,6 +5,7 @@ All wrappers enqueue on torch's current stream and never synchronise.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
 
 import ctypes
@@ -192,6 +193,56 @@ def _frag_weights(w: torch.Tensor) -> torch.Tensor:
     return f
 
 
+ConvEligibility = namedtuple("ConvEligibility", "bfrag_ok halo_ok p8_ok p8_sk_ok p8n_ok p8n_splits p8n_split_ok")
+
+
+def conv_eligibility(x_dtype, w_dtype, out_dtype, B, H, W, Cin, Cout, KH, KW, stride, pad, has_residual, x_cs, y_cs, r_cs, batched,
+                     has_scale, has_bias, act, aligned) -> ConvEligibility:
+    """Which tuner-only kernel configurations conv2d may offer for one call (no GPU, no library): the Python mirror of the C entry
+    points' argument checks.  `act` is conv2d's act word (ACT_RES_AFTER / ACT_BIAS_BATCHED included); `aligned`: every buffer the
+    call touches (x, w, out, residual, scale, bias) is 16-byte aligned."""
+    OH = (H + 2 * pad - KH) // stride + 1
+    OW = (W + 2 * pad - KW) // stride + 1
+    # "A through LDS, B from L2" kernel (fragment-major weights, cached per weight tensor): only the autotuner selects it
+    bfrag_ok = (x_dtype == torch.bfloat16 and w_dtype == torch.bfloat16 and not batched and Cin % 64 == 0 and Cout % 128 == 0
+                and x_cs % 8 == 0 and KH * KW <= 32 and (act & ~(0xff | ACT_RES_AFTER)) == 0
+                and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31)
+
+    halo_ok = (bfrag_ok and KH == 3 and KW == 3 and stride == 1 and pad == 1 and not has_residual and x_cs == Cin and y_cs == Cout
+               and out_dtype == torch.bfloat16 and has_scale and has_bias and (act & ~0xff) == 0)
+
+    p8_ok = (x_dtype == torch.bfloat16 and w_dtype == torch.bfloat16 and not batched and Cin % 64 == 0 and Cout % 256 == 0
+             and x_cs % 8 == 0 and KH * KW <= 32 and (act & ~(0xff | ACT_RES_AFTER)) == 0
+             and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31 and B * H * W < 2 ** 23 and x_cs < 2 ** 24 and KH * KW * Cin < 2 ** 24
+             and Cout * KH * KW * Cin * 2 < 2 ** 31 and out_dtype in _DT and x_cs % 8 == 0
+             and (y_cs % (4 if out_dtype == torch.float32 else 8) == 0)
+             and (not has_residual or (r_cs % (4 if out_dtype == torch.float32 else 8) == 0 and out_dtype != torch.float8_e4m3fn))
+             and bool(aligned))
+
+    # stream-K only where whole rounds leave CUs idle: a few tiles per CU and a K loop long enough to cut
+    p8_sk_ok = p8_ok and (-(-(B * OH * OW) // 256)) * (Cout // 256) <= 1024 and KH * KW * Cin >= 512
+
+    p8n_ok = (x_dtype == torch.bfloat16 and w_dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and not batched and not has_residual
+              and Cin % 64 == 0 and Cout % 128 == 0 and x_cs % 8 == 0 and y_cs % 8 == 0 and KH * KW <= 32 and act in (ACT_NONE, ACT_RELU, ACT_LEAKY)
+              and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31 and B * H * W < 2 ** 23 and x_cs < 2 ** 24 and KH * KW * Cin < 2 ** 24
+              and Cout * KH * KW * Cin * 2 < 2 ** 31 and (B * OH * OW + 256) * y_cs * 2 < 2 ** 31
+              and bool(aligned))
+
+    # split-K on the p8n structure: fewer tiles than half the CUs and a K loop of >= 64 K-tiles; slices = CUs // tiles (at most 8)
+    p8n_tiles = (-(-(B * OH * OW) // 256)) * (Cout // 128) if Cout % 128 == 0 else 0
+    p8n_splits = min(8, Cin // 64, 256 // p8n_tiles) if p8n_tiles else 0
+    p8n_split_ok = p8n_ok and KH * KW * Cin >= 4096 and p8n_splits >= 2 and p8n_splits * B * OH * OW * Cout * 4 < 2 ** 31
+    return ConvEligibility(bfrag_ok, halo_ok, p8_ok, p8_sk_ok, p8n_ok, p8n_splits, p8n_split_ok)
+
+
+def conv_tuner_extras(el: ConvEligibility, KH: int, KW: int) -> tuple:
+    """The tuner-only configurations conv2d offers ConvTuner.choose on top of CANDIDATES (0-4), in the order it offers them."""
+    return (((CFG_BFRAG3, CFG_BFRAG32) if el.bfrag_ok else ()) + ((CFG_HALO16, CFG_HALO8) if el.halo_ok else ())
+            + ((CFG_P8,) if el.p8_ok else ()) + ((CFG_P8_SK,) if (el.p8_sk_ok and P8_SK_TUNABLE[0]) else ())
+            + (((CFG_P8N,) + ((CFG_P8N_TAP,) if KH * KW > 1 else ())) if (el.p8n_ok and P8N_TUNABLE[0]) else ())
+            + ((CFG_P8N_SPLIT,) if (el.p8n_split_ok and P8N_TUNABLE[0]) else ()))
+
+
 def conv2d(x: torch.Tensor, w: torch.Tensor, scale=None, bias=None, residual=None, *, stride=1, pad=0, act=ACT_NONE,
            out: Optional[torch.Tensor] = None, out_dtype=None, x_channels: Optional[int] = None,
            batched_weights: bool = False) -> torch.Tensor:
@@ -231,35 +282,10 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, scale=None, bias=None, residual=Non
         if v is not None:
             _chk(v, torch.float32)
             _require(v.numel() == Cout or (v is bias and (act & ACT_BIAS_BATCHED)), 'argument check failed: v.numel() == Cout or (v is bias and (act & ACT_BIAS_BATCHED))')
-    # "A through LDS, B from L2" kernel (fragment-major weights, cached per weight tensor): only the autotuner selects it
-    bfrag_ok = (x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and not batched_weights and Cin % 64 == 0 and Cout % 128 == 0
-                and x_cs % 8 == 0 and KH * KW <= 32 and (act & ~(0xff | ACT_RES_AFTER)) == 0
-                and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31)
-
-    halo_ok = (bfrag_ok and KH == 3 and KW == 3 and stride == 1 and pad == 1 and residual is None and x_cs == Cin and y_cs == Cout
-               and out_dtype == torch.bfloat16 and scale is not None and bias is not None and (act & ~0xff) == 0)
-
-    p8_ok = (x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and not batched_weights and Cin % 64 == 0 and Cout % 256 == 0
-             and x_cs % 8 == 0 and KH * KW <= 32 and (act & ~(0xff | ACT_RES_AFTER)) == 0
-             and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31 and B * H * W < 2 ** 23 and x_cs < 2 ** 24 and KH * KW * Cin < 2 ** 24
-             and Cout * KH * KW * Cin * 2 < 2 ** 31 and out_dtype in _DT and x_cs % 8 == 0
-             and (y_cs % (4 if out_dtype == torch.float32 else 8) == 0)
-             and (residual is None or (r_cs % (4 if out_dtype == torch.float32 else 8) == 0 and out_dtype != torch.float8_e4m3fn))
-             and all(t is None or t.data_ptr() % 16 == 0 for t in (x, w, out, residual, scale, bias)))
-
-    # stream-K only where whole rounds leave CUs idle: a few tiles per CU and a K loop long enough to cut
-    p8_sk_ok = p8_ok and (-(-(B * OH * OW) // 256)) * (Cout // 256) <= 1024 and KH * KW * Cin >= 512
-
-    p8n_ok = (x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and not batched_weights and residual is None
-              and Cin % 64 == 0 and Cout % 128 == 0 and x_cs % 8 == 0 and y_cs % 8 == 0 and KH * KW <= 32 and act in (ACT_NONE, ACT_RELU, ACT_LEAKY)
-              and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31 and B * H * W < 2 ** 23 and x_cs < 2 ** 24 and KH * KW * Cin < 2 ** 24
-              and Cout * KH * KW * Cin * 2 < 2 ** 31 and (B * OH * OW + 256) * y_cs * 2 < 2 ** 31
-              and all(t is None or t.data_ptr() % 16 == 0 for t in (x, w, out, scale, bias)))
-
-    # split-K on the p8n structure: fewer tiles than half the CUs and a K loop of >= 64 K-tiles; slices = CUs // tiles (at most 8)
-    p8n_tiles = (-(-(B * OH * OW) // 256)) * (Cout // 128) if Cout % 128 == 0 else 0
-    p8n_splits = min(8, Cin // 64, 256 // p8n_tiles) if p8n_tiles else 0
-    p8n_split_ok = p8n_ok and KH * KW * Cin >= 4096 and p8n_splits >= 2 and p8n_splits * B * OH * OW * Cout * 4 < 2 ** 31
+    el = conv_eligibility(x.dtype, w.dtype, out_dtype, B, H, W, Cin, Cout, KH, KW, stride, pad, residual is not None, x_cs, y_cs, r_cs,
+                          batched_weights, scale is not None, bias is not None, act,
+                          all(t is None or t.data_ptr() % 16 == 0 for t in (x, w, out, residual, scale, bias)))
+    p8n_splits = el.p8n_splits
 
     def launch(cfg):
         if cfg == CFG_P8N_SPLIT:
@@ -305,11 +331,8 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, scale=None, bias=None, residual=Non
     if TUNER.measuring or TUNER.best or TUNER.loaded:
         # everything that decides which kernel configurations are eligible (bfrag_ok / halo_ok) is part of the key
         key = (x.dtype, w.dtype, out_dtype, B, H, W, Cin, Cout, KH, KW, stride, pad, residual is not None, x_cs, y_cs, w_bs != 0,
-               scale is not None, bias is not None, act, bfrag_ok, halo_ok, p8_ok)
-        cfg = TUNER.choose(key, launch, ((CFG_BFRAG3, CFG_BFRAG32) if bfrag_ok else ()) + ((CFG_HALO16, CFG_HALO8) if halo_ok else ())
-                           + ((CFG_P8,) if p8_ok else ()) + ((CFG_P8_SK,) if (p8_sk_ok and P8_SK_TUNABLE[0]) else ())
-                           + (((CFG_P8N,) + ((CFG_P8N_TAP,) if KH * KW > 1 else ())) if (p8n_ok and P8N_TUNABLE[0]) else ())
-                           + ((CFG_P8N_SPLIT,) if (p8n_split_ok and P8N_TUNABLE[0]) else ()))
+               scale is not None, bias is not None, act, el.bfrag_ok, el.halo_ok, el.p8_ok)
+        cfg = TUNER.choose(key, launch, conv_tuner_extras(el, KH, KW))
     try:
         launch(cfg)
     except _lib.HipKernelError:
