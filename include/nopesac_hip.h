@@ -242,6 +242,36 @@ int nopesac_bottleneck_tail_bf16_ex(const void* b, const void* w3, const float* 
                                     int x2_H, int x2_W, int x2_stride, int C, int C4, int C2, void* y, const void* w1,
                                     const float* scale1, const float* bias1, int CN, void* o, int o_dt, void* stream);
 
+/* The kernel forms of the bottleneck tail (csrc/pwchain.hip).  rt4 / rt4_late / rt4_proj / rt8 store whole 128-pixel tiles and rt4h
+ * whole 64-pixel tiles: they are eligible only when B*OH*OW is a multiple of that. */
+#define NPS_TAIL_PW 0        /* pw_chain_kernel: 64 pixels per workgroup (C = 64) or 32 (C = 128); any M */
+#define NPS_TAIL_RT4 1       /* pw_chain_rt4_kernel, identity blocks of res2 / res3, residual prefetch before GEMM 1 (C = 64) */
+#define NPS_TAIL_RT4_LATE 2  /* the same kernel with the residual prefetch behind GEMM 1 (for C = 128 both builds are one kernel) */
+#define NPS_TAIL_RT4_PROJ 3  /* pw_chain_rt4_kernel with the projection GEMM: res2.0, a same-resolution stride-1 source */
+#define NPS_TAIL_RT4H 4      /* pw_chain_rt4h_kernel: res3's edge blocks, 64 pixels per four-wave workgroup */
+#define NPS_TAIL_RT8 5       /* pw_chain_rt8_kernel: res3's edge blocks (C = 128) or res4 identity blocks (C = 256, CN = 256) */
+#define NPS_TAIL_STREAM 6    /* pw_chain_stream_kernel: res4 identity blocks; any M */
+#define NPS_TAIL_WIDE 7      /* pw_chain_wide_kernel: every C = 256 configuration; any M */
+#define NPS_TAIL_FORMS 8
+/* A/B switch bits of the default selection: the environment variables NOPESAC_TAIL_NO_RT4, _NO_RT8, _RT4_LATE (read once per process by
+ * nopesac_bottleneck_tail_bf16_ex), _NO_RT4H, _RT8_WIDE and _NO_STREAM (read at every call). */
+#define NPS_TAIL_SW_NO_RT4 1
+#define NPS_TAIL_SW_NO_RT8 2
+#define NPS_TAIL_SW_RT4_LATE 4
+#define NPS_TAIL_SW_NO_RT4H 8
+#define NPS_TAIL_SW_RT8_WIDE 16
+#define NPS_TAIL_SW_NO_STREAM 32
+/* Host only (no GPU, no HIP call): the form nopesac_bottleneck_tail_bf16_ex launches for (C, C4, CN, C2) over M = B*OH*OW pixels under
+ * the switch bits, or -1 for an unsupported configuration.  C2 = 0 for an identity block; x2_same_res: x2_H == OH and x2_W == OW.
+ * *eligible (optional) receives the bitmask (1 << NPS_TAIL_*) of every form that can run the call, whatever the switches. */
+int nopesac_bottleneck_tail_forms(int C, int C4, int CN, int C2, long long M, int x2_stride, int x2_same_res, int switches,
+                                  unsigned* eligible);
+/* nopesac_bottleneck_tail_bf16_ex on the given form.  A form that is not eligible for the call returns NPS_E_ARG before any HIP call. */
+int nopesac_bottleneck_tail_bf16_form(const void* b, const void* w3, const float* scale3, const float* bias3, const void* residual,
+                                      const void* x2, const void* wsc, const float* scale_sc, const float* bias_sc, int B, int OH, int OW,
+                                      int x2_H, int x2_W, int x2_stride, int C, int C4, int C2, void* y, const void* w1,
+                                      const float* scale1, const float* bias1, int CN, void* o, int o_dt, int form, void* stream);
+
 /* (x - mean[c]) / std[c], NCHW f32 -> NHWC (C padded with zeros to Cpad), out_dt f32/bf16.
  * siamese_planeTR.py:85-89,534-542. */
 int nopesac_preprocess_nchw_to_nhwc(const float* x, void* y, const float* mean, const float* std,

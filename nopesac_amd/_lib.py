@@ -33,6 +33,8 @@ SIGNATURES = {
     "nopesac_stem_fused_raw_shifted_bf16": [P, P, P, P, P, P, I, I, I, P],
     "nopesac_bottleneck_tail_bf16": [P] * 9 + [I] * 9 + [P] * 4 + [I, P, P],
     "nopesac_bottleneck_tail_bf16_ex": [P] * 9 + [I] * 9 + [P] * 4 + [I, P, I, P],
+    "nopesac_bottleneck_tail_bf16_form": [P] * 9 + [I] * 9 + [P] * 4 + [I, P, I, I, P],
+    "nopesac_bottleneck_tail_forms": [I, I, I, I, L, I, I, I, P],
     "nopesac_conv2d_nhwc_fp8": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, L, I, I, I, P],
     "nopesac_gnn_layer_bf16": [P, I, P, I, P, I, I, I, P, P] + [P] * 10 + [P],
     "nopesac_gnn_layer_bf16_pf": [P, I, P, I, P, I, I, I, P, P] + [P] * 10 + [P, I, P],

@@ -989,10 +989,10 @@ static int pw_launch_rt4_proj(const PwArgs& a, hipStream_t stream) {
     return 0;
 }
 
+// late (NPS_TAIL_RT4_LATE, the NOPESAC_TAIL_RT4_LATE A/B switch): the residual prefetch goes out behind GEMM 1
 template <int C, int C4, int CN>
-static int pw_launch_rt4(const PwArgs& a, hipStream_t stream) {
+static int pw_launch_rt4(const PwArgs& a, bool late, hipStream_t stream) {
     constexpr size_t lds = PwRt4<C, C4, CN>::BYTES;
-    static const bool late = getenv("NOPESAC_TAIL_RT4_LATE") != nullptr;       // A/B switch: residual prefetch behind GEMM 1
     // measured (profiles/r3_c_tail_ab.txt): res2 (C = 64) gains 3-6 % from the residual prefetch going out before GEMM 1 (308 vs 326 us,
     // 361 vs 371 us); res3 (C = 128, 248 registers without it) loses 2 % even with only three of the eight loads early (197 vs 192 us)
     constexpr int EARLY = C >= 128 ? 0 : 8;
@@ -1633,6 +1633,136 @@ static int pw_launch(const PwArgs& a, hipStream_t stream) {
 
 extern "C" void nps_rt8_debug_buffer(void* buf) { nps::g_rt8_dbg = (unsigned long long*)buf; }
 
+namespace nps {
+
+// ---- form selection: which kernel runs a bottleneck tail (nopesac_bottleneck_tail_forms)
+static bool tail_cfg(int C, int C4, int CN, int c2, int c, int c4, int cn, int cc2) { return C == c && C4 == c4 && CN == cn && c2 == cc2; }
+
+// bitmask of the forms that can run (C, C4, CN, c2) over M pixels (c2 = 0: identity block); a form's launcher instantiates exactly these
+// configurations, and rt4 / rt4_proj / rt4h / rt8 store whole 128- / 64-pixel tiles with no M guard, hence the divisibility terms
+static unsigned tail_eligible(int C, int C4, int CN, int c2, long long M, int x2_stride, bool x2_same_res) {
+#define TC(c, c4, cn, cc2) tail_cfg(C, C4, CN, c2, c, c4, cn, cc2)
+    unsigned m = 0;
+    if (M % 128 == 0 && (TC(128, 512, 128, 0) || TC(128, 512, 0, 0) || TC(64, 256, 64, 0) || TC(64, 256, 128, 0) || TC(64, 256, 0, 0)))
+        m |= 1u << NPS_TAIL_RT4 | 1u << NPS_TAIL_RT4_LATE;
+    if (M % 128 == 0 && x2_stride == 1 && x2_same_res && (TC(64, 256, 64, 64) || TC(64, 256, 0, 64))) m |= 1u << NPS_TAIL_RT4_PROJ;
+    if (M % 64 == 0 && (TC(128, 512, 256, 0) || TC(128, 512, 128, 256))) m |= 1u << NPS_TAIL_RT4H;
+    if (M % 128 == 0 && (TC(128, 512, 256, 0) || TC(128, 512, 128, 256) || TC(256, 1024, 256, 0))) m |= 1u << NPS_TAIL_RT8;
+    if (TC(64, 256, 64, 0) || TC(64, 256, 128, 0) || TC(64, 256, 64, 64) || TC(64, 256, 0, 0) || TC(64, 256, 0, 64) || TC(128, 512, 128, 0) ||
+        TC(128, 512, 256, 0) || TC(128, 512, 128, 256) || TC(128, 512, 0, 0) || TC(128, 512, 0, 256))
+        m |= 1u << NPS_TAIL_PW;
+    if (TC(256, 1024, 256, 0) || TC(256, 1024, 0, 0)) m |= 1u << NPS_TAIL_STREAM;
+    if (TC(256, 1024, 256, 0) || TC(256, 1024, 512, 0) || TC(256, 1024, 256, 512) || TC(256, 1024, 0, 0) || TC(256, 1024, 0, 512))
+        m |= 1u << NPS_TAIL_WIDE;
+#undef TC
+    return m;
+}
+
+// the default form under the NPS_TAIL_SW_* switch bits, or -1 (unsupported configuration)
+static int tail_default(int C, unsigned m, int sw) {
+    const bool no_rt4 = sw & NPS_TAIL_SW_NO_RT4, no_rt8 = sw & NPS_TAIL_SW_NO_RT8;
+    auto has = [&](int f) { return (m >> f) & 1u; };
+    // identity blocks of res2 / res3: the four-row-tile kernel (a quarter of the L2 weight traffic); NOPESAC_TAIL_NO_RT4=1 keeps the
+    // round-1 form (A/B comparisons: scripts/tail_one.py)
+    if (!no_rt4 && has(NPS_TAIL_RT4)) return (sw & NPS_TAIL_SW_RT4_LATE) ? NPS_TAIL_RT4_LATE : NPS_TAIL_RT4;
+    // res3's edge blocks (CN = 256 into res4; the stride-2 projection of res3.0): the eight-wave form
+    // round 6: four-wave workgroups of 64 pixels, two per CU (NOPESAC_TAIL_NO_RT4H=1: the eight-wave 128-pixel form below)
+    if (!no_rt4 && !no_rt8 && !(sw & NPS_TAIL_SW_NO_RT4H) && has(NPS_TAIL_RT4H)) return NPS_TAIL_RT4H;
+    if (!no_rt4 && !no_rt8 && C == 128 && has(NPS_TAIL_RT8)) return NPS_TAIL_RT8;
+    // res2.0: projection shortcut from a same-resolution source (the stem output), in the same 128-pixel form
+    if (!no_rt4 && has(NPS_TAIL_RT4_PROJ)) return NPS_TAIL_RT4_PROJ;
+    // (measured in round 2: 64 pixels per workgroup for res3 - half the weight traffic from L2 but ONE 4-wave workgroup per CU - is
+    //  slower, 322 vs 272 us on the identity tail: the 32-pixel form stays)
+    if (has(NPS_TAIL_PW)) return NPS_TAIL_PW;
+    // res4 identity blocks on the eight-wave 128-pixel chunked form (round-5 experiment, NOPESAC_TAIL_RT8_WIDE=1)
+    if ((sw & NPS_TAIL_SW_RT8_WIDE) && C == 256 && has(NPS_TAIL_RT8)) return NPS_TAIL_RT8;
+    // identity blocks of res4 / res5: chunk-streaming kernel (weights shared by 128 / 64 pixels)
+    // (res5, C4 = 2048, was measured too: 0.185 ms fused vs 0.158 ms per-layer at 15x20 - only 300 workgroups - so it stays per-layer)
+    if (!(sw & NPS_TAIL_SW_NO_STREAM) && has(NPS_TAIL_STREAM)) return NPS_TAIL_STREAM;
+    if (has(NPS_TAIL_WIDE)) return NPS_TAIL_WIDE;
+    return -1;
+}
+
+static const char* tail_form_name(int form) {
+    static const char* names[NPS_TAIL_FORMS] = {"pw", "rt4", "rt4_late", "rt4_proj", "rt4h", "rt8", "stream", "wide"};
+    return form >= 0 && form < NPS_TAIL_FORMS ? names[form] : "?";
+}
+
+// launch an eligible form (tail_eligible has admitted (form, C, C4, CN, c2))
+static int tail_launch(int form, const PwArgs& a, int C, int C4, int CN, int c2, hipStream_t st) {
+    switch (form) {
+    case NPS_TAIL_RT4:
+    case NPS_TAIL_RT4_LATE: {
+        const bool late = form == NPS_TAIL_RT4_LATE;
+#define PW_RT4(c, c4, cn) if (C == c && C4 == c4 && CN == cn) { pw_launch_rt4<c, c4, cn>(a, late, st); NPS_LAUNCH_RET(); }
+        PW_RT4(128, 512, 128) PW_RT4(128, 512, 0) PW_RT4(64, 256, 64) PW_RT4(64, 256, 128) PW_RT4(64, 256, 0)
+#undef PW_RT4
+        break;
+    }
+    case NPS_TAIL_RT4_PROJ:
+        if (C == 64 && C4 == 256 && CN == 64 && c2 == 64) { pw_launch_rt4_proj<64, 256, 64, 64>(a, st); NPS_LAUNCH_RET(); }
+        if (C == 64 && C4 == 256 && CN == 0 && c2 == 64) { pw_launch_rt4_proj<64, 256, 0, 64>(a, st); NPS_LAUNCH_RET(); }
+        break;
+    case NPS_TAIL_RT4H:
+        if (C == 128 && C4 == 512 && CN == 256 && c2 == 0) { pw_launch_rt4h<128, 512, 256, 0>(a, st); NPS_LAUNCH_RET(); }
+        if (C == 128 && C4 == 512 && CN == 128 && c2 == 256) { pw_launch_rt4h<128, 512, 128, 256>(a, st); NPS_LAUNCH_RET(); }
+        break;
+    case NPS_TAIL_RT8:
+        if (C == 128 && C4 == 512 && CN == 256 && c2 == 0) { pw_launch_rt8<128, 512, 256, 0>(a, st); NPS_LAUNCH_RET(); }
+        if (C == 128 && C4 == 512 && CN == 128 && c2 == 256) { pw_launch_rt8<128, 512, 128, 256>(a, st); NPS_LAUNCH_RET(); }
+        if (C == 256 && C4 == 1024 && CN == 256 && c2 == 0) { pw_launch_rt8<256, 1024, 256, 0>(a, st); NPS_LAUNCH_RET(); }
+        break;
+    case NPS_TAIL_PW:
+#define PW_CASE(c, c4, cn, cc2, bm) if (C == c && C4 == c4 && CN == cn && c2 == cc2) { pw_launch<c, c4, cn, cc2, bm>(a, st); NPS_LAUNCH_RET(); }
+        PW_CASE(64, 256, 64, 0, 64) PW_CASE(64, 256, 128, 0, 64) PW_CASE(64, 256, 64, 64, 64) PW_CASE(64, 256, 0, 0, 64) PW_CASE(64, 256, 0, 64, 64)
+        PW_CASE(128, 512, 128, 0, 32) PW_CASE(128, 512, 256, 0, 32) PW_CASE(128, 512, 128, 256, 32) PW_CASE(128, 512, 0, 0, 32) PW_CASE(128, 512, 0, 256, 32)
+#undef PW_CASE
+        break;
+    case NPS_TAIL_STREAM:
+        if (C == 256 && C4 == 1024 && CN == 256 && c2 == 0) { pw_launch_stream<256, 1024, 256, 64>(a, st); NPS_LAUNCH_RET(); }
+        if (C == 256 && C4 == 1024 && CN == 0 && c2 == 0) { pw_launch_stream<256, 1024, 0, 64>(a, st); NPS_LAUNCH_RET(); }
+        break;
+    case NPS_TAIL_WIDE:
+#define PW_WIDE(c, c4, cn, cc2) if (C == c && C4 == c4 && CN == cn && c2 == cc2) { pw_launch_wide<c, c4, cn, cc2>(a, st); NPS_LAUNCH_RET(); }
+        PW_WIDE(256, 1024, 256, 0) PW_WIDE(256, 1024, 512, 0) PW_WIDE(256, 1024, 256, 512) PW_WIDE(256, 1024, 0, 0) PW_WIDE(256, 1024, 0, 512)
+#undef PW_WIDE
+        break;
+    }
+    set_error("bottleneck_tail: no %s launcher for C=%d C4=%d CN=%d C2=%d", tail_form_name(form), C, C4, CN, c2);
+    return NPS_E_ARG;
+}
+
+// the argument checks of every entry point, and the kernel arguments
+static int tail_args(PwArgs& a, const void* b, const void* w3, const float* scale3, const float* bias3, const void* residual, const void* x2,
+                     const void* wsc, const float* scale_sc, const float* bias_sc, int B, int OH, int OW, int x2_H, int x2_W, int x2_stride,
+                     int C2, void* y, const void* w1, const float* scale1, const float* bias1, int CN, void* o, int o_dt) {
+    NPS_CHECK_ARG(o_dt == NPS_DT_BF16 || o_dt == NPS_DT_FP8, "bottleneck_tail: o_dt must be NPS_DT_BF16 or NPS_DT_FP8");
+    NPS_CHECK_ARG(b && w3 && scale3 && bias3 && y && B > 0 && OH > 0 && OW > 0, "bottleneck_tail: bad args");
+    NPS_CHECK_ARG((residual != nullptr) != (x2 != nullptr), "bottleneck_tail: exactly one of residual / x2 (projection shortcut)");
+    NPS_CHECK_ARG(!x2 || (wsc && scale_sc && bias_sc && C2 > 0 && x2_stride >= 1 && (OH - 1) * x2_stride < x2_H && (OW - 1) * x2_stride < x2_W),
+                  "bottleneck_tail: projection shortcut arguments");
+    NPS_CHECK_ARG(CN == 0 || (w1 && scale1 && bias1 && o), "bottleneck_tail: next-conv1 arguments");
+    const void* ptrs[] = {b, w3, scale3, bias3, residual, x2, wsc, scale_sc, bias_sc, y, w1, scale1, bias1, o};
+    for (const void* q : ptrs) NPS_CHECK_ARG(((uintptr_t)q & 15) == 0, "bottleneck_tail: pointers must be 16-byte aligned");
+    memset(&a, 0, sizeof(a));
+    a.a1 = (const bf16_t*)b; a.w3 = (const bf16_t*)w3; a.s3 = scale3; a.b3 = bias3; a.res = (const bf16_t*)residual;
+    a.a2 = (const bf16_t*)x2; a.wsc = (const bf16_t*)wsc; a.ssc = scale_sc; a.bsc = bias_sc;
+    a.a2_H = x2_H; a.a2_W = x2_W; a.a2_stride = x2_stride; a.OH = OH; a.OW = OW;
+    a.y = (bf16_t*)y; a.w1 = (const bf16_t*)w1; a.s1 = scale1; a.b1 = bias1; a.o = (bf16_t*)o;
+    a.M = (long long)B * OH * OW;
+    a.o_fp8 = o_dt == NPS_DT_FP8 ? 1 : 0;
+    return 0;
+}
+
+}  // namespace nps
+
+extern "C" int nopesac_bottleneck_tail_forms(int C, int C4, int CN, int C2, long long M, int x2_stride, int x2_same_res, int switches,
+                                             unsigned* eligible) {
+    const unsigned m = M > 0 ? nps::tail_eligible(C, C4, CN, C2, M, x2_stride, x2_same_res != 0) : 0u;
+    if (eligible) *eligible = m;
+    return nps::tail_default(C, m, switches);
+}
+
 extern "C" int nopesac_bottleneck_tail_bf16(const void* b, const void* w3, const float* scale3, const float* bias3, const void* residual,
                                             const void* x2, const void* wsc, const float* scale_sc, const float* bias_sc, int B, int OH,
                                             int OW, int x2_H, int x2_W, int x2_stride, int C, int C4, int C2, void* y, const void* w1,
@@ -1646,68 +1776,39 @@ extern "C" int nopesac_bottleneck_tail_bf16_ex(const void* b, const void* w3, co
                                                int OW, int x2_H, int x2_W, int x2_stride, int C, int C4, int C2, void* y, const void* w1,
                                                const float* scale1, const float* bias1, int CN, void* o, int o_dt, void* stream) {
     using namespace nps;
-    NPS_CHECK_ARG(o_dt == NPS_DT_BF16 || o_dt == NPS_DT_FP8, "bottleneck_tail: o_dt must be NPS_DT_BF16 or NPS_DT_FP8");
-    NPS_CHECK_ARG(b && w3 && scale3 && bias3 && y && B > 0 && OH > 0 && OW > 0, "bottleneck_tail: bad args");
-    NPS_CHECK_ARG((residual != nullptr) != (x2 != nullptr), "bottleneck_tail: exactly one of residual / x2 (projection shortcut)");
-    NPS_CHECK_ARG(!x2 || (wsc && scale_sc && bias_sc && C2 > 0 && x2_stride >= 1 && (OH - 1) * x2_stride < x2_H && (OW - 1) * x2_stride < x2_W),
-                  "bottleneck_tail: projection shortcut arguments");
-    NPS_CHECK_ARG(CN == 0 || (w1 && scale1 && bias1 && o), "bottleneck_tail: next-conv1 arguments");
-    const void* ptrs[] = {b, w3, scale3, bias3, residual, x2, wsc, scale_sc, bias_sc, y, w1, scale1, bias1, o};
-    for (const void* q : ptrs) NPS_CHECK_ARG(((uintptr_t)q & 15) == 0, "bottleneck_tail: pointers must be 16-byte aligned");
     PwArgs a;
-    memset(&a, 0, sizeof(a));
-    a.a1 = (const bf16_t*)b; a.w3 = (const bf16_t*)w3; a.s3 = scale3; a.b3 = bias3; a.res = (const bf16_t*)residual;
-    a.a2 = (const bf16_t*)x2; a.wsc = (const bf16_t*)wsc; a.ssc = scale_sc; a.bsc = bias_sc;
-    a.a2_H = x2_H; a.a2_W = x2_W; a.a2_stride = x2_stride; a.OH = OH; a.OW = OW;
-    a.y = (bf16_t*)y; a.w1 = (const bf16_t*)w1; a.s1 = scale1; a.b1 = bias1; a.o = (bf16_t*)o;
-    a.M = (long long)B * OH * OW;
-    a.o_fp8 = o_dt == NPS_DT_FP8 ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream;
+    const int rc = tail_args(a, b, w3, scale3, bias3, residual, x2, wsc, scale_sc, bias_sc, B, OH, OW, x2_H, x2_W, x2_stride, C2, y, w1, scale1,
+                             bias1, CN, o, o_dt);
+    if (rc) return rc;
     const int c2 = x2 ? C2 : 0;
-    // identity blocks of res2 / res3: the four-row-tile kernel (a quarter of the L2 weight traffic); NOPESAC_TAIL_NO_RT4=1 keeps the
-    // round-1 form (A/B comparisons: scripts/tail_one.py)
+    // A/B switches: the first three are read once per process, the others at every call
     static const bool no_rt4 = getenv("NOPESAC_TAIL_NO_RT4") != nullptr;
-    if (!x2 && !no_rt4 && a.M % 128 == 0) {
-#define PW_RT4(c, c4, cn) if (C == c && C4 == c4 && CN == cn) { pw_launch_rt4<c, c4, cn>(a, st); NPS_LAUNCH_RET(); }
-        PW_RT4(128, 512, 128) PW_RT4(128, 512, 0) PW_RT4(64, 256, 64) PW_RT4(64, 256, 128) PW_RT4(64, 256, 0)
-#undef PW_RT4
-    }
-    // res3's edge blocks (CN = 256 into res4; the stride-2 projection of res3.0): the eight-wave form
     static const bool no_rt8 = getenv("NOPESAC_TAIL_NO_RT8") != nullptr;
-    // round 6: four-wave workgroups of 64 pixels, two per CU (NOPESAC_TAIL_NO_RT4H=1: the eight-wave 128-pixel form below)
-    if (!no_rt4 && !no_rt8 && a.M % 64 == 0 && C == 128 && C4 == 512 && !getenv("NOPESAC_TAIL_NO_RT4H")) {
-        if (!x2 && CN == 256) { pw_launch_rt4h<128, 512, 256, 0>(a, st); NPS_LAUNCH_RET(); }
-        if (x2 && CN == 128 && c2 == 256) { pw_launch_rt4h<128, 512, 128, 256>(a, st); NPS_LAUNCH_RET(); }
+    static const bool rt4_late = getenv("NOPESAC_TAIL_RT4_LATE") != nullptr;   // residual prefetch behind GEMM 1
+    const int sw = (no_rt4 ? NPS_TAIL_SW_NO_RT4 : 0) | (no_rt8 ? NPS_TAIL_SW_NO_RT8 : 0) | (rt4_late ? NPS_TAIL_SW_RT4_LATE : 0) |
+                   (getenv("NOPESAC_TAIL_NO_RT4H") ? NPS_TAIL_SW_NO_RT4H : 0) | (getenv("NOPESAC_TAIL_RT8_WIDE") ? NPS_TAIL_SW_RT8_WIDE : 0) |
+                   (getenv("NOPESAC_TAIL_NO_STREAM") ? NPS_TAIL_SW_NO_STREAM : 0);
+    const int form = tail_default(C, tail_eligible(C, C4, CN, c2, a.M, x2_stride, x2_H == OH && x2_W == OW), sw);
+    if (form < 0) {
+        set_error("bottleneck_tail: unsupported channel configuration C=%d C4=%d CN=%d C2=%d", C, C4, CN, c2);
+        return NPS_E_ARG;
     }
-    if (!no_rt4 && !no_rt8 && a.M % 128 == 0 && C == 128 && C4 == 512) {
-        if (!x2 && CN == 256) { pw_launch_rt8<128, 512, 256, 0>(a, st); NPS_LAUNCH_RET(); }
-        if (x2 && CN == 128 && c2 == 256) { pw_launch_rt8<128, 512, 128, 256>(a, st); NPS_LAUNCH_RET(); }
-    }
-    // res2.0: projection shortcut from a same-resolution source (the stem output), in the same 128-pixel form
-    if (x2 && !no_rt4 && a.M % 128 == 0 && x2_stride == 1 && x2_H == OH && x2_W == OW) {
-        if (C == 64 && C4 == 256 && CN == 64 && c2 == 64) { pw_launch_rt4_proj<64, 256, 64, 64>(a, st); NPS_LAUNCH_RET(); }
-        if (C == 64 && C4 == 256 && CN == 0 && c2 == 64) { pw_launch_rt4_proj<64, 256, 0, 64>(a, st); NPS_LAUNCH_RET(); }
-    }
-#define PW_CASE(c, c4, cn, cc2, bm) if (C == c && C4 == c4 && CN == cn && c2 == cc2) { pw_launch<c, c4, cn, cc2, bm>(a, st); NPS_LAUNCH_RET(); }
-    // (measured in round 2: 64 pixels per workgroup for res3 - half the weight traffic from L2 but ONE 4-wave workgroup per CU - is
-    //  slower, 322 vs 272 us on the identity tail: the 32-pixel form stays)
-    PW_CASE(64, 256, 64, 0, 64) PW_CASE(64, 256, 128, 0, 64) PW_CASE(64, 256, 64, 64, 64) PW_CASE(64, 256, 0, 0, 64) PW_CASE(64, 256, 0, 64, 64)
-    PW_CASE(128, 512, 128, 0, 32) PW_CASE(128, 512, 256, 0, 32) PW_CASE(128, 512, 128, 256, 32) PW_CASE(128, 512, 0, 0, 32) PW_CASE(128, 512, 0, 256, 32)
-#undef PW_CASE
-    // res4 identity blocks on the eight-wave 128-pixel chunked form (round-5 experiment, NOPESAC_TAIL_RT8_WIDE=1)
-    if (!x2 && a.M % 128 == 0 && C == 256 && C4 == 1024 && CN == 256 && getenv("NOPESAC_TAIL_RT8_WIDE")) {
-        pw_launch_rt8<256, 1024, 256, 0>(a, st);
-        NPS_LAUNCH_RET();
-    }
-    // identity blocks of res4 / res5: chunk-streaming kernel (weights shared by 128 / 64 pixels)
-    if (!x2 && !getenv("NOPESAC_TAIL_NO_STREAM")) {
-        if (C == 256 && C4 == 1024 && CN == 256) { pw_launch_stream<256, 1024, 256, 64>(a, st); NPS_LAUNCH_RET(); }
-        if (C == 256 && C4 == 1024 && CN == 0) { pw_launch_stream<256, 1024, 0, 64>(a, st); NPS_LAUNCH_RET(); }
-        // (res5, C4 = 2048, was measured too: 0.185 ms fused vs 0.158 ms per-layer at 15x20 - only 300 workgroups - so it stays per-layer)
-    }
-#define PW_WIDE(c, c4, cn, cc2) if (C == c && C4 == c4 && CN == cn && c2 == cc2) { pw_launch_wide<c, c4, cn, cc2>(a, st); NPS_LAUNCH_RET(); }
-    PW_WIDE(256, 1024, 256, 0) PW_WIDE(256, 1024, 512, 0) PW_WIDE(256, 1024, 256, 512) PW_WIDE(256, 1024, 0, 0) PW_WIDE(256, 1024, 0, 512)
-#undef PW_WIDE
-    set_error("bottleneck_tail: unsupported channel configuration C=%d C4=%d CN=%d C2=%d", C, C4, CN, c2);
-    return NPS_E_ARG;
+    return tail_launch(form, a, C, C4, CN, c2, (hipStream_t)stream);
+}
+
+extern "C" int nopesac_bottleneck_tail_bf16_form(const void* b, const void* w3, const float* scale3, const float* bias3, const void* residual,
+                                                 const void* x2, const void* wsc, const float* scale_sc, const float* bias_sc, int B, int OH,
+                                                 int OW, int x2_H, int x2_W, int x2_stride, int C, int C4, int C2, void* y, const void* w1,
+                                                 const float* scale1, const float* bias1, int CN, void* o, int o_dt, int form, void* stream) {
+    using namespace nps;
+    PwArgs a;
+    const int rc = tail_args(a, b, w3, scale3, bias3, residual, x2, wsc, scale_sc, bias_sc, B, OH, OW, x2_H, x2_W, x2_stride, C2, y, w1, scale1,
+                             bias1, CN, o, o_dt);
+    if (rc) return rc;
+    const int c2 = x2 ? C2 : 0;
+    NPS_CHECK_ARG(form >= 0 && form < NPS_TAIL_FORMS, "bottleneck_tail: form %d out of range [0, %d)", form, NPS_TAIL_FORMS);
+    const unsigned m = tail_eligible(C, C4, CN, c2, a.M, x2_stride, x2_H == OH && x2_W == OW);
+    NPS_CHECK_ARG((m >> form) & 1u, "bottleneck_tail: form %d (%s) is not eligible for C=%d C4=%d CN=%d C2=%d M=%lld x2_stride=%d (eligible mask 0x%x)",
+                  form, tail_form_name(form), C, C4, CN, c2, a.M, x2_stride, m);
+    return tail_launch(form, a, C, C4, CN, c2, (hipStream_t)stream);
 }

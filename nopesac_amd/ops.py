@@ -542,29 +542,60 @@ def conv2d_fp8(x: torch.Tensor, w8frag: torch.Tensor, scale: torch.Tensor, bias:
     return out
 
 
+# the kernel forms of the fused bottleneck tail, indexed by form id (NPS_TAIL_* of include/nopesac_hip.h)
+TAIL_FORMS = ("pw", "rt4", "rt4_late", "rt4_proj", "rt4h", "rt8", "stream", "wide")
+# A/B switch bits of the default selection (NPS_TAIL_SW_*), by the environment variable that sets each
+TAIL_SWITCHES = {"NOPESAC_TAIL_NO_RT4": 1, "NOPESAC_TAIL_NO_RT8": 2, "NOPESAC_TAIL_RT4_LATE": 4, "NOPESAC_TAIL_NO_RT4H": 8,
+                 "NOPESAC_TAIL_RT8_WIDE": 16, "NOPESAC_TAIL_NO_STREAM": 32}
+
+
+def bottleneck_tail_forms(C, C4, CN, C2, M, stride=1, same_res=False, switches=0):
+    """(default form id or -1, bitmask of eligible form ids) of a bottleneck tail over M pixels (C2 = 0: identity block; same_res: the
+    projection source has the output's height and width) under the NPS_TAIL_SW_* switch bits.  Host only: needs no GPU."""
+    mask = ctypes.c_uint(0)
+    form = _L().nopesac_bottleneck_tail_forms(C, C4, CN, C2, M, stride, int(bool(same_res)), switches, ctypes.byref(mask))
+    return form, mask.value
+
+
 def bottleneck_tail(b, w3, s3, b3, *, residual=None, x2=None, wsc=None, ssc=None, bsc=None, stride=1, w1=None, s1=None, b1=None,
-                    o_fp8: bool = False):
+                    o_fp8: bool = False, form=None, y=None, o=None):
     """Fused conv3 + shortcut + ReLU (+ the next block's conv1) of a bf16 bottleneck; returns (y, o or None).
     b [B,OH,OW,C]; residual [B,OH,OW,C4] or projection source x2 [B,H2,W2,C2] with wsc [C4,C2]; w1 [CN,C4].
-    The weight matrices are expected in `mfma_fragment_major` order.  o_fp8: o is written as float8_e4m3fn."""
+    The weight matrices are expected in `mfma_fragment_major` order.  o_fp8: o is written as float8_e4m3fn.
+    form: a TAIL_FORMS id to launch instead of the default selection (an ineligible one raises); y / o: contiguous output buffers
+    to write instead of new ones."""
     _chk(b, torch.bfloat16); _chk(w3, torch.bfloat16)
     B, OH, OW, C = b.shape
     C4 = w3.shape[0]
     CN = 0 if w1 is None else w1.shape[0]
     C2 = 0 if x2 is None else x2.shape[3]
     _require((C, C4, CN, C2) in BOTTLENECK_TAIL_CONFIGS, (C, C4, CN, C2))
-    y = torch.empty((B, OH, OW, C4), device=b.device, dtype=torch.bfloat16)
-    o = torch.empty((B, OH, OW, CN), device=b.device, dtype=torch.float8_e4m3fn if o_fp8 else torch.bfloat16) if CN else None
+    if y is None:
+        y = torch.empty((B, OH, OW, C4), device=b.device, dtype=torch.bfloat16)
+    _chk(y, torch.bfloat16)
+    _require(y.shape == (B, OH, OW, C4), 'argument check failed: y.shape == (B, OH, OW, C4)')
+    o_dt = torch.float8_e4m3fn if o_fp8 else torch.bfloat16
+    if CN and o is None:
+        o = torch.empty((B, OH, OW, CN), device=b.device, dtype=o_dt)
+    if CN:
+        _chk(o, o_dt)
+        _require(o.shape == (B, OH, OW, CN), 'argument check failed: o.shape == (B, OH, OW, CN)')
+    else:
+        _require(o is None, 'argument check failed: o is None without w1')
     if residual is not None:
         _chk(residual, torch.bfloat16)
         _require(residual.shape == y.shape, 'argument check failed: residual.shape == y.shape')
     if x2 is not None:
         _chk(x2, torch.bfloat16); _chk(wsc, torch.bfloat16)
     H2, W2 = (x2.shape[1], x2.shape[2]) if x2 is not None else (0, 0)
-    rc = _L().nopesac_bottleneck_tail_bf16_ex(_p(b), _p(w3), _p(s3), _p(b3), _p(residual), _p(x2), _p(wsc), _p(ssc), _p(bsc), B, OH, OW,
-                                              H2, W2, stride, C, C4, C2, _p(y), _p(w1), _p(s1), _p(b1), CN, _p(o),
-                                              FP8 if o_fp8 else BF16, _stream())
-    _lib.check(rc, "nopesac_bottleneck_tail_bf16_ex")
+    args = (_p(b), _p(w3), _p(s3), _p(b3), _p(residual), _p(x2), _p(wsc), _p(ssc), _p(bsc), B, OH, OW, H2, W2, stride, C, C4, C2, _p(y),
+            _p(w1), _p(s1), _p(b1), CN, _p(o), FP8 if o_fp8 else BF16)
+    if form is None:
+        rc = _L().nopesac_bottleneck_tail_bf16_ex(*args, _stream())
+        _lib.check(rc, "nopesac_bottleneck_tail_bf16_ex")
+    else:
+        rc = _L().nopesac_bottleneck_tail_bf16_form(*args, int(form), _stream())
+        _lib.check(rc, "nopesac_bottleneck_tail_bf16_form")
     return y, o
 
 
