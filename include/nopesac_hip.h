@@ -800,6 +800,45 @@ int nopesac_adamw_step(float* param, const float* grad, float* exp_avg, float* e
 int nopesac_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float weight_decay,
                      int first_step, void* stream);
 
+/* ---- backward of the pixel pose net's conv stacks (csrc/conv_bwd.hip; training.CameraHeadTrainer(conv_stacks=True)) ------------------
+ * f32, NHWC activations, f32 accumulation; every buffer (workspaces included) is the caller's; no atomics: cross-workgroup sums are
+ * reduced in a fixed order, so two runs give bit-identical results.
+ *  conv2d_dgrad:  dY [B,OH,OW,Cout] (channel stride dy_cstride), w [Cout][Cin][KH][KW] (state-dict layout) -> dX [B,H,W,Cin] (channel
+ *                 stride dx_cstride).  k 1 or 3, stride 1 or 2, pad < k.  Stride 1 (same-size conv): w is rotated / transposed into w_ws
+ *                 ([Cin][KH][KW][Cout], Cin * Cout * KH * KW floats) and dX is the f32 MFMA implicit-GEMM conv of dY with it; stride 2: a
+ *                 gather over the taps with an integral output position (w_ws unused, may be null).
+ *  conv2d_wgrad:  x [B,H,W,Cin] (channel stride x_cstride >= Cin: the extra channels get no gradient), dY -> dW [Cout][Cin][KH][KW].
+ *                 MFMA GEMM (M = Cout, N = KH KW Cin, K = B OH OW pixels) split into `splits` pixel ranges, partial tiles in ws
+ *                 (nopesac_conv2d_wgrad_workspace_bytes), then summed in split order.  Needs Cin, Cout and both channel strides % 4 == 0.
+ *  bn_act_forward / bn_act_backward: inference-mode BatchNorm (stored mean / var, affine gamma / beta) + act (NONE / RELU / LEAKY) on
+ *                 c [rows][C]: y = act(c s + beta - mean s), s = gamma / sqrt(var + eps); backward from the saved c: dc, dgamma, dbeta
+ *                 (ws: nopesac_bn_act_backward_workspace_floats).
+ *  groupnorm_backward: x (the GroupNorm input) [B][HW][C], dY -> dX, dgamma, dbeta (optional ReLU after the affine; C / groups divides
+ *                 256; ws: B * 2 * C floats).
+ *  maxpool2x2_backward: 2x2 / stride 2 pool of x [B,H,W,C]: dY goes to the window's first maximum in row-major order (torch's choice).
+ *  upsample2x_nearest_add_backward: y = lateral + nearest-2x(coarse [B,H,W,C]): dcoarse = 2x2 block sums of dY (dlateral = dY).
+ *  corr_softmax_backward: rows of a softmax A over C channels (row stride a_ld; padding beyond C ignored), dA -> dS = A (dA - sum dA A)
+ *                 as ds [B*P][C] and transposed per batch entry as ds_t [B][C][P].
+ *  transpose_batched: x [B][rows][cols] -> y [B][cols][rows]. */
+int nopesac_conv2d_dgrad_f32(const float* dy, const float* w, float* dx, float* w_ws, int64_t w_ws_bytes, int B, int H, int W, int Cin,
+                             int Cout, int KH, int KW, int stride, int pad, int64_t dy_cstride, int64_t dx_cstride, void* stream);
+int64_t nopesac_conv2d_wgrad_workspace_bytes(int Cout, int Cin, int KH, int KW, int splits);
+int nopesac_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, float* ws, int64_t ws_bytes, int B, int H, int W, int Cin, int Cout,
+                             int KH, int KW, int stride, int pad, int64_t x_cstride, int64_t dy_cstride, int splits, void* stream);
+int nopesac_bn_act_forward_f32(const float* c, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int act,
+                               int64_t rows, int C, float* y, void* stream);
+int64_t nopesac_bn_act_backward_workspace_floats(int rows, int C);
+int nopesac_bn_act_backward_f32(const float* dy, const float* c, const float* gamma, const float* beta, const float* mean, const float* var,
+                                float eps, int act, int rows, int C, float* dc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats,
+                                void* stream);
+int nopesac_groupnorm_backward_f32(const float* x, const float* dy, const float* gamma, const float* beta, int B, int HW, int C, int groups,
+                                   float eps, int relu, float* dx, float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
+int nopesac_maxpool2x2_backward_f32(const float* x, const float* dy, float* dx, int B, int H, int W, int C, void* stream);
+int nopesac_upsample2x_nearest_add_backward_f32(const float* dy, float* dx_coarse, int B, int H, int W, int C, void* stream);
+int nopesac_corr_softmax_backward_f32(const float* a, const float* da, int B, int P, int C, int64_t a_ld, int64_t da_ld, float* ds, float* ds_t,
+                                      void* stream);
+int nopesac_transpose_batched_f32(const float* x, int B, int rows, int cols, float* y, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

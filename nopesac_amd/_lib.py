@@ -120,12 +120,24 @@ SIGNATURES = {
     "nopesac_scale_by_f32": [P, L, P, P],
     "nopesac_adamw_step": [P, P, P, P, L, F, F, F, F, F, I, P],
     "nopesac_sgd_step": [P, P, P, L, F, F, F, I, P],
+    "nopesac_conv2d_dgrad_f32": [P, P, P, P, L, I, I, I, I, I, I, I, I, I, L, L, P],
+    "nopesac_conv2d_wgrad_workspace_bytes": [I, I, I, I, I],
+    "nopesac_conv2d_wgrad_f32": [P, P, P, P, L, I, I, I, I, I, I, I, I, I, L, L, I, P],
+    "nopesac_bn_act_forward_f32": [P, P, P, P, P, F, I, L, I, P, P],
+    "nopesac_bn_act_backward_workspace_floats": [I, I],
+    "nopesac_bn_act_backward_f32": [P, P, P, P, P, P, F, I, I, I, P, P, P, P, L, P],
+    "nopesac_groupnorm_backward_f32": [P, P, P, P, I, I, I, I, F, I, P, P, P, P, L, P],
+    "nopesac_maxpool2x2_backward_f32": [P, P, P, I, I, I, I, P],
+    "nopesac_upsample2x_nearest_add_backward_f32": [P, P, I, I, I, I, P],
+    "nopesac_corr_softmax_backward_f32": [P, P, I, I, I, L, L, P, P, P],
+    "nopesac_transpose_batched_f32": [P, I, I, I, P, P],
     "nopesac_mlp_padded_k": [I, I],
     "nopesac_mlp_packed_elems": [I, I],
     "nopesac_mlp_chain_bf16": [P, P],
 }
 _RESTYPE = {"nopesac_jpeg_prepare_scan": c_int64, "nopesac_last_error": c_char_p, "nopesac_rle_compress_batch_host": c_int64, "nopesac_mlp_packed_elems": c_int64,
-            "nopesac_conv2d_p8_sk_workspace_bytes": c_int64, "nopesac_inflate_zlib_host": c_int64, "nopesac_jpeg_batch_scan_host": c_void_p, "nopesac_jpeg_batch_free_host": None}
+            "nopesac_conv2d_p8_sk_workspace_bytes": c_int64, "nopesac_conv2d_wgrad_workspace_bytes": c_int64,
+            "nopesac_bn_act_backward_workspace_floats": c_int64, "nopesac_inflate_zlib_host": c_int64, "nopesac_jpeg_batch_scan_host": c_void_p, "nopesac_jpeg_batch_free_host": None}
 
 MLP_MAX_IN, MLP_MAX_WIDTH, MLP_MAX_LAYERS = 1280, 1024, 12       # NOPESAC_MLP_* of the header
 

@@ -232,8 +232,8 @@ class PlaneCameraHead(ParamModule):
         random poses (the reference draws them, :687-690, :718).  Planes are [B,nq,3] zero-padded with counts int32[B]; assignments
         [B,nq,nq]; gt_pose [B,7].  BatchNorm / GroupNorm layers run with their stored statistics: this evaluates the losses of a
         checkpoint (validation curves, loss parity).  The training step over the same losses - backward kernels for every Linear layer
-        of the head (pixel-pose FC + regressors, AIM, refinement head; the conv stacks stay frozen) + AdamW / SGD - is
-        nopesac_amd.training.CameraHeadTrainer (round 5).  Returns (losses, trans_list, rot_list) as the reference does."""
+        of the head (pixel-pose FC + regressors, AIM, refinement head; with conv_stacks=True also the pixel pose net's conv stacks, else
+        they stay frozen) + AdamW / SGD - is nopesac_amd.training.CameraHeadTrainer.  Returns (losses, trans_list, rot_list) as the reference does."""
         losses = {}
         trans0, rot0, tf0, rf0 = self.pixel_pose_net(feats, B, canonical_sign=False)
         lp = ops.camera_pose_loss(trans0, rot0, gt_pose[:, 0:3], gt_pose[:, 3:7], self.initial_cam_weight)

@@ -1344,3 +1344,187 @@ def conv3x3_c64(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, bias: tor
     _lib.check(_L().nopesac_conv3x3_c64_bf16(_p(x), _p(_frag_weights(w)), _p(scale), _p(bias), _p(y), B, H, W, act, _stream()),
                "nopesac_conv3x3_c64_bf16")
     return y
+
+
+# ---------------------------------------------------------------- backward of the pixel pose net's conv stacks (csrc/conv_bwd.hip)
+_WGRAD_WS = {}                         # (device index, stream handle, capturing) -> split-K workspace of conv2d_wgrad (grown on demand)
+
+
+def wgrad_workspace(device, nbytes: int) -> torch.Tensor:
+    """conv2d_wgrad's partial-tile workspace for the CURRENT stream of `device`, at least `nbytes` (launches of one stream are ordered,
+    so they share one; it only grows)."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(), torch.cuda.is_current_stream_capturing())
+    ws = _WGRAD_WS.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
+        _WGRAD_WS[key] = ws
+    return ws
+
+
+def wgrad_splits(pixels: int, Cout: int, N: int) -> int:
+    """Split-K factor of conv2d_wgrad: about 1024 workgroups over the 128 x 128 output tiles, at least 256 pixels per split."""
+    tiles = ((Cout + 127) // 128) * ((N + 127) // 128)
+    return max(1, min(256, -(-1024 // tiles), pixels // 256))
+
+
+def _nhwc_cs(t: torch.Tensor) -> int:
+    """Channel stride of a pixel-dense NHWC tensor (a channel slice of a wider buffer is allowed)."""
+    _require(t.dim() == 4 and t.stride(3) == 1, "NHWC tensor with unit channel stride expected")
+    B, H, W, _ = t.shape
+    cs = t.stride(2)
+    _require(t.stride(1) == W * cs and t.stride(0) == H * W * cs, "x must be pixel-dense NHWC")
+    return cs
+
+
+def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw, *, stride: int = 1, pad: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of conv2d with respect to its input.  dy [B,OH,OW,Cout] f32 NHWC, w [Cout,Cin,KH,KW] (state-dict layout), in_hw = (H, W)
+    -> dx [B,H,W,Cin] (or into `out`, which may be a channel slice of a wider buffer)."""
+    _chk(dy, torch.float32, contiguous=False); _chk(w, torch.float32)
+    _require(w.dim() == 4, "w must be [Cout, Cin, KH, KW]")
+    Cout, Cin, KH, KW = w.shape
+    B, OH, OW, C = dy.shape
+    _require(C == Cout, (C, Cout))
+    H, W = int(in_hw[0]), int(in_hw[1])
+    _require((H + 2 * pad - KH) // stride + 1 == OH and (W + 2 * pad - KW) // stride + 1 == OW, "dy does not match the input size")
+    if out is None:
+        out = torch.empty((B, H, W, Cin), device=dy.device, dtype=torch.float32)
+    _require(out.shape == (B, H, W, Cin) and out.dtype == torch.float32, "out must be [B, H, W, Cin] f32")
+    wws = torch.empty(w.numel() if stride == 1 else 0, device=dy.device, dtype=torch.float32)
+    rc = _L().nopesac_conv2d_dgrad_f32(_p(dy), _p(w), _p(out), _p(wws) if wws.numel() else None, wws.numel() * 4, B, H, W, Cin, Cout, KH, KW,
+                                       stride, pad, _nhwc_cs(dy), _nhwc_cs(out), _stream())
+    _lib.check(rc, "nopesac_conv2d_dgrad_f32")
+    return out
+
+
+def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, kernel_size: int, *, stride: int = 1, pad: int = 0, cin: Optional[int] = None,
+                 splits: Optional[int] = None) -> torch.Tensor:
+    """Gradient of conv2d with respect to its weights.  x [B,H,W,Cx] f32 NHWC (the first `cin` channels are the conv's input; the
+    rest - zero padding - get no gradient), dy [B,OH,OW,Cout] -> dw [Cout,cin,k,k] (state-dict layout).  Split-K over pixel ranges into
+    the cached workspace, reduced in a fixed order."""
+    _chk(x, torch.float32, contiguous=False); _chk(dy, torch.float32, contiguous=False)
+    B, H, W, Cx = x.shape
+    Cin = int(cin or Cx)
+    _require(Cin <= Cx, (Cin, Cx))
+    KH = KW = int(kernel_size)
+    Bd, OH, OW, Cout = dy.shape
+    _require(Bd == B and (H + 2 * pad - KH) // stride + 1 == OH and (W + 2 * pad - KW) // stride + 1 == OW, "dy does not match x")
+    S = int(splits or wgrad_splits(B * OH * OW, Cout, KH * KW * Cin))
+    nbytes = int(_L().nopesac_conv2d_wgrad_workspace_bytes(Cout, Cin, KH, KW, S))
+    ws = wgrad_workspace(x.device, nbytes)
+    dw = torch.empty((Cout, Cin, KH, KW), device=x.device, dtype=torch.float32)
+    rc = _L().nopesac_conv2d_wgrad_f32(_p(x), _p(dy), _p(dw), _p(ws), ws.numel() * 4, B, H, W, Cin, Cout, KH, KW, stride, pad, _nhwc_cs(x),
+                                       _nhwc_cs(dy), S, _stream())
+    _lib.check(rc, "nopesac_conv2d_wgrad_f32")
+    return dw
+
+
+def _bn_vecs(C, *vs):
+    for v in vs:
+        _chk(v, torch.float32)
+        _require(v.numel() == C, (v.numel(), C))
+
+
+def bn_act_forward(c: torch.Tensor, gamma, beta, mean, var, eps: float, act=ACT_LEAKY) -> torch.Tensor:
+    """Inference-mode BatchNorm (stored statistics, affine gamma / beta) + activation on a contiguous [..., C] f32 tensor."""
+    _chk(c, torch.float32)
+    C = c.shape[-1]
+    _bn_vecs(C, gamma, beta, mean, var)
+    y = torch.empty_like(c)
+    rc = _L().nopesac_bn_act_forward_f32(_p(c), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(act), c.numel() // C, C, _p(y), _stream())
+    _lib.check(rc, "nopesac_bn_act_forward_f32")
+    return y
+
+
+def bn_act_backward(dy: torch.Tensor, c: torch.Tensor, gamma, beta, mean, var, eps: float, act=ACT_LEAKY):
+    """Backward of bn_act_forward from the saved conv output c -> (dc, dgamma, dbeta)."""
+    _chk(dy, torch.float32); _chk(c, torch.float32)
+    _require(dy.shape == c.shape, (dy.shape, c.shape))
+    C = c.shape[-1]
+    rows = c.numel() // C
+    _bn_vecs(C, gamma, beta, mean, var)
+    dc = torch.empty_like(c)
+    dg = torch.empty(C, device=c.device, dtype=torch.float32)
+    db = torch.empty(C, device=c.device, dtype=torch.float32)
+    ws = torch.empty(int(_L().nopesac_bn_act_backward_workspace_floats(rows, C)), device=c.device, dtype=torch.float32)
+    rc = _L().nopesac_bn_act_backward_f32(_p(dy), _p(c), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(act), rows, C, _p(dc), _p(dg),
+                                          _p(db), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "nopesac_bn_act_backward_f32")
+    return dc, dg, db
+
+
+def groupnorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma, beta, groups: int, eps: float, act=ACT_NONE):
+    """Backward of groupnorm(x, gamma, beta, groups, eps, act) (act: NONE or RELU) -> (dx, dgamma, dbeta)."""
+    _chk(x, torch.float32); _chk(dy, torch.float32)
+    _require(dy.shape == x.shape and x.dim() == 4, (dy.shape, x.shape))
+    _require(act in (ACT_NONE, ACT_RELU), act)
+    B, H, W, C = x.shape
+    _chk(gamma, torch.float32); _chk(beta, torch.float32)
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, device=x.device, dtype=torch.float32)
+    db = torch.empty(C, device=x.device, dtype=torch.float32)
+    ws = torch.empty(B * 2 * C, device=x.device, dtype=torch.float32)
+    rc = _L().nopesac_groupnorm_backward_f32(_p(x), _p(dy), _p(gamma), _p(beta), B, H * W, C, groups, float(eps), int(act == ACT_RELU), _p(dx),
+                                             _p(dg), _p(db), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "nopesac_groupnorm_backward_f32")
+    return dx, dg, db
+
+
+def maxpool_backward(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """Backward of the 2x2 / stride-2 max-pool of x [B,H,W,C] f32: dY to the window's first maximum (row-major), as torch.max_pool2d."""
+    _chk(x, torch.float32); _chk(dy, torch.float32)
+    B, H, W, C = x.shape
+    _require(dy.shape == (B, H // 2, W // 2, C), (dy.shape, x.shape))
+    dx = torch.empty_like(x)
+    _lib.check(_L().nopesac_maxpool2x2_backward_f32(_p(x), _p(dy), _p(dx), B, H, W, C, _stream()), "nopesac_maxpool2x2_backward_f32")
+    return dx
+
+
+def upsample2x_nearest_add_backward(dy: torch.Tensor):
+    """Backward of upsample2x_nearest_add(x, lateral): (dx [B,H,W,C] = 2x2 block sums of dy, dlateral = dy)."""
+    _chk(dy, torch.float32)
+    B, H2, W2, C = dy.shape
+    _require(H2 % 2 == 0 and W2 % 2 == 0, dy.shape)
+    dx = torch.empty((B, H2 // 2, W2 // 2, C), device=dy.device, dtype=torch.float32)
+    _lib.check(_L().nopesac_upsample2x_nearest_add_backward_f32(_p(dy), _p(dx), B, H2 // 2, W2 // 2, C, _stream()),
+               "nopesac_upsample2x_nearest_add_backward_f32")
+    return dx, dy
+
+
+def transpose_batched(x: torch.Tensor) -> torch.Tensor:
+    """[B, rows, cols] f32 -> contiguous [B, cols, rows]."""
+    _chk(x, torch.float32)
+    _require(x.dim() == 3, x.shape)
+    B, R, Cc = x.shape
+    y = torch.empty((B, Cc, R), device=x.device, dtype=torch.float32)
+    _lib.check(_L().nopesac_transpose_batched_f32(_p(x), B, R, Cc, _p(y), _stream()), "nopesac_transpose_batched_f32")
+    return y
+
+
+def corr_softmax(x1: torch.Tensor, x2: torch.Tensor, pad_to: int = 0) -> torch.Tensor:
+    """The pixel pose net's correlation softmax (camera_head.py:1117-1133) in f32: x1, x2 [B,h,w,C] -> A [B,h,w,max(h w, pad_to)], channel =
+    view-2 position in (w, h) order, softmax over the h w channels, zeros beyond."""
+    _chk(x1, torch.float32); _chk(x2, torch.float32)
+    B, h, w, C = x1.shape
+    _require(x2.shape == x1.shape, (x1.shape, x2.shape))
+    x2t = transpose_hw_rows(x2.reshape(B, h * w, C), h, w)
+    corr = conv2d(x1, x2t.view(B, h * w, 1, 1, C), batched_weights=True)
+    return softmax_rows(corr, pad_to=pad_to)
+
+
+def corr_softmax_backward(a: torch.Tensor, da: torch.Tensor, x1: torch.Tensor, x2: torch.Tensor):
+    """Backward of corr_softmax: A [B,h,w,ld] (ld >= h w: the padded channels carry no gradient), dA like A, the inputs x1 / x2
+    [B,h,w,C] -> (dx1, dx2).  dS = A (dA - sum dA A); dx1 = dS x2t, dx2t = dS^T x1 on the batched f32 GEMM; dx2 back to (h, w) order."""
+    _chk(a, torch.float32); _chk(da, torch.float32); _chk(x1, torch.float32); _chk(x2, torch.float32)
+    B, h, w, C = x1.shape
+    P = h * w
+    _require(a.shape[:3] == (B, h, w) and a.shape[3] >= P and da.shape == a.shape and x2.shape == x1.shape, (a.shape, da.shape, x1.shape))
+    ld = a.shape[3]
+    ds = torch.empty((B, h, w, P), device=a.device, dtype=torch.float32)
+    ds_t = torch.empty((B, P, P), device=a.device, dtype=torch.float32)
+    _lib.check(_L().nopesac_corr_softmax_backward_f32(_p(a), _p(da), B, P, P, ld, ld, _p(ds), _p(ds_t), _stream()),
+               "nopesac_corr_softmax_backward_f32")
+    x2t = transpose_hw_rows(x2.reshape(B, P, C), h, w)                      # [B, P (w,h order), C]
+    dx1 = conv2d(ds, transpose_batched(x2t).view(B, C, 1, 1, P), batched_weights=True)            # [B,h,w,C]
+    dx2t = conv2d(ds_t.view(B, h, w, P), transpose_batched(x1.reshape(B, P, C)).view(B, C, 1, 1, P), batched_weights=True)
+    dx2 = transpose_hw_rows(dx2t.reshape(B, P, C), w, h).view(B, h, w, C)
+    return dx1, dx2

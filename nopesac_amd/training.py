@@ -8,10 +8,16 @@ plane geometry) and, for every Linear layer, dgrad = dY W and wgrad = dY^T X on 
 bias + the ReLU mask.  `torch.autograd.Function` only does the bookkeeping (which gradient goes where); concatenations and the
 broadcast of the initial-pose features are torch views / a [B, nq, 256] sum.  Everything is f32 and deterministic.
 
-What this is NOT: a trainer for the whole network.  The backbone, the plane head, the matcher and the pixel pose net have no backward
-kernels here - their outputs (the initial pose, its 256-d features, the plane sets and the assignment) are inputs of this stage, as they
-are of the reference function, and receive no gradient beyond `input_grads`.  Gated against torch.autograd on the oracle
-(tests/test_training_gpu.py)."""
+The pixel pose net's conv stacks (pixel decoder, convs_backbone, the two strided branches, the correlation softmax between them) are
+trainable on request: CameraHeadTrainer(conv_stacks=True) runs them from the trainer's own f32 parameters through the autograd Functions
+below, whose backward passes are the kernels of csrc/conv_bwd.hip (conv dgrad / wgrad, BatchNorm + LeakyReLU, GroupNorm, max-pool,
+upsample-add, correlation softmax).  BatchNorm runs with its stored statistics and a trainable affine (detectron2's FrozenBatchNorm2d
+regime, as forward_train); batch statistics and running-stat updates are not implemented.
+
+What this is NOT: a trainer for the whole network.  The backbone, the plane head and the matcher have no backward kernels here - their
+outputs (the backbone maps, the plane sets and the assignment) are inputs of this stage, as they are of the reference function, and
+receive no gradient beyond `input_grads`.  Gated against torch.autograd on the oracle (tests/test_training_gpu.py,
+tests/test_pose_net_training_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -21,6 +27,23 @@ import torch
 from . import _lib, ops
 
 PREFIX = "camera_head_list.0."
+CONV_STACKS = ("pixel_decoder", "convs_backbone", "convs_trans", "convs_rots")       # the pixel pose net's conv stacks (conv_stacks=True)
+BACKBONE_CONVS = (0, 1, 3, 4, 6, 7)
+BN_EPS, GN_EPS, GN_GROUPS = 1e-3, 1e-5, 32
+_BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked")
+
+
+def is_norm_parameter(key: str) -> bool:
+    """GroupNorm / BatchNorm affine tensors of the camera head (the modules the reference's build_optimizer gives WEIGHT_DECAY_NORM,
+    train_NopeSAC.py:94-128): pixel_decoder.*.norm.{weight,bias} and convs_*.i.1.{weight,bias}."""
+    parts = key[len(PREFIX):].split(".") if key.startswith(PREFIX) else key.split(".")
+    if parts[0] == "pixel_decoder":
+        return len(parts) == 4 and parts[2] == "norm"
+    if parts[0] in CONV_STACKS:
+        return len(parts) == 4 and parts[2] == "1" and parts[3] in ("weight", "bias")
+    return False
+
+
 MLPS = ("geo_encoder", "geo_proj_s1", "decoder_rot", "geo_proj_s2", "decoder_tran", "decoder_rot2", "decoder_tran2", "normal_score_proj",
         "param_score_proj")
 LINEARS = ("rots", "trans", "rot_score_reg", "trans_score_reg")
@@ -211,6 +234,129 @@ class _PoseLoss(torch.autograd.Function):
         return o[0], o[1], o[2], o[3], None, None
 
 
+def _ohwi(w: torch.Tensor, cin: int) -> torch.Tensor:
+    """State-dict conv weight [Cout, Cin, KH, KW] -> the forward conv's operand [Cout, KH, KW, cin] (zero channels beyond Cin)."""
+    w = w.detach().permute(0, 2, 3, 1)
+    if cin > w.shape[-1]:
+        w = torch.nn.functional.pad(w, (0, cin - w.shape[-1]))
+    return w.contiguous()
+
+
+def _conv_input_grads(ctx, x, w, dc, stride: int, pad: int):
+    """dX (zero in x's padding channels) and dW of a conv whose output gradient is dc."""
+    dx = dw = None
+    B, H, W, Cx = x.shape
+    Cin = w.shape[1]
+    if ctx.needs_input_grad[0]:
+        dx = torch.zeros_like(x) if Cx > Cin else torch.empty_like(x)
+        ops.conv2d_dgrad(dc, w, (H, W), stride=stride, pad=pad, out=dx[..., :Cin] if Cx > Cin else dx)
+    if ctx.needs_input_grad[1]:
+        dw = ops.conv2d_wgrad(x, dc, w.shape[2], stride=stride, pad=pad, cin=Cin)
+    return dx, dw
+
+
+class _ConvBNAct(torch.autograd.Function):
+    """conv (no bias) + inference-mode BatchNorm (trainable affine, stored statistics) + act; the raw conv output is saved."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, mean, var, stride: int, pad: int, act: int):
+        x = x.contiguous()
+        c = ops.conv2d(x, _ohwi(w, x.shape[3]), stride=stride, pad=pad)
+        ctx.conf = (stride, pad, act)
+        ctx.save_for_backward(x, w, c, gamma, beta, mean, var)
+        return ops.bn_act_forward(c, gamma, beta, mean, var, BN_EPS, act)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, c, gamma, beta, mean, var = ctx.saved_tensors
+        stride, pad, act = ctx.conf
+        dc, dgamma, dbeta = ops.bn_act_backward(g.contiguous(), c, gamma, beta, mean, var, BN_EPS, act)
+        dx, dw = _conv_input_grads(ctx, x, w, dc, stride, pad)
+        return dx, dw, dgamma, dbeta, None, None, None, None, None
+
+
+class _ConvGN(torch.autograd.Function):
+    """d2 Conv2d (no bias) + GroupNorm(32) [+ ReLU] of the pixel decoder (camera_modules.py:271-303)."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, pad: int, relu: bool):
+        x = x.contiguous()
+        c = ops.conv2d(x, _ohwi(w, x.shape[3]), pad=pad)
+        ctx.conf = (pad, ops.ACT_RELU if relu else ops.ACT_NONE)
+        ctx.save_for_backward(x, w, c, gamma, beta)
+        return ops.groupnorm(c, gamma, beta, GN_GROUPS, GN_EPS, ctx.conf[1])
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, c, gamma, beta = ctx.saved_tensors
+        pad, act = ctx.conf
+        dc, dgamma, dbeta = ops.groupnorm_backward(c, g.contiguous(), gamma, beta, GN_GROUPS, GN_EPS, act)
+        dx, dw = _conv_input_grads(ctx, x, w, dc, 1, pad)
+        return dx, dw, dgamma, dbeta, None, None
+
+
+class _ConvBias(torch.autograd.Function):
+    """conv + bias (pixel_decoder.mask_features); bias gradient = column sums of dY."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, pad: int):
+        x = x.contiguous()
+        ctx.pad = pad
+        ctx.save_for_backward(x, w)
+        return ops.conv2d(x, _ohwi(w, x.shape[3]), bias=b.detach().contiguous(), pad=pad)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g = g.contiguous()
+        dx, dw = _conv_input_grads(ctx, x, w, g, 1, ctx.pad)
+        db = col_sum(g.view(-1, g.shape[3])) if ctx.needs_input_grad[2] else None
+        return dx, dw, db, None
+
+
+class _MaxPool2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return ops.maxpool(x, 2, 2, 0)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool_backward(x, g.contiguous())
+
+
+class _UpsampleAdd(torch.autograd.Function):
+    """lateral + nearest 2x upsampling of x (the pixel decoder's top-down path)."""
+
+    @staticmethod
+    def forward(ctx, x, lateral):
+        return ops.upsample2x_nearest_add(x.contiguous(), lateral.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        dx, dlat = ops.upsample2x_nearest_add_backward(g.contiguous())
+        return dx, dlat
+
+
+class _CorrSoftmax(torch.autograd.Function):
+    """The correlation volume + softmax (camera_head.py:1117-1133) -> A [B, h, w, pad_to] (zero channels beyond h w)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, pad_to: int):
+        x1, x2 = x1.contiguous(), x2.contiguous()
+        a = ops.corr_softmax(x1, x2, pad_to)
+        ctx.save_for_backward(a, x1, x2)
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        a, x1, x2 = ctx.saved_tensors
+        dx1, dx2 = ops.corr_softmax_backward(a, g.contiguous(), x1, x2)
+        return dx1, dx2, None
+
+
 class RefineTrainer:
     """The refinement head's parameters as f32 leaf tensors + forward / backward / optimiser step.
 
@@ -314,11 +460,14 @@ class RefineTrainer:
 
     # ---- optimiser (train_NopeSAC.py:88-169: AdamW / SGD over per-parameter groups; norm / embedding groups do not occur in this head)
     def step(self, lr: float = 1e-4, optimizer: str = "ADAMW", weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8,
-             momentum: float = 0.9):
+             momentum: float = 0.9, weight_decay_norm: Optional[float] = None):
+        """`weight_decay_norm` (if given): the decay of the GroupNorm / BatchNorm affine tensors (is_norm_parameter) instead of
+        `weight_decay` - the reference's norm parameter groups."""
         self.steps += 1
         for k, p in self.params.items():
             if p.grad is None:
                 continue
+            wd = weight_decay if weight_decay_norm is None or not is_norm_parameter(k) else weight_decay_norm
             g = p.grad.contiguous()
             st = self.state.setdefault(k, {})
             with torch.no_grad():
@@ -326,13 +475,13 @@ class RefineTrainer:
                     if not st:
                         st["m1"], st["m2"] = torch.zeros_like(p), torch.zeros_like(p)
                     rc = _L().nopesac_adamw_step(_p(p), _p(g), _p(st["m1"]), _p(st["m2"]), p.numel(), float(lr), float(betas[0]), float(betas[1]),
-                                                 float(eps), float(weight_decay), self.steps, _st())
+                                                 float(eps), float(wd), self.steps, _st())
                     _lib.check(rc, "nopesac_adamw_step")
                 elif optimizer.upper() == "SGD":
                     first = "mom" not in st
                     if first:
                         st["mom"] = torch.zeros_like(p)
-                    rc = _L().nopesac_sgd_step(_p(p), _p(g), _p(st["mom"]), p.numel(), float(lr), float(momentum), float(weight_decay), int(first), _st())
+                    rc = _L().nopesac_sgd_step(_p(p), _p(g), _p(st["mom"]), p.numel(), float(lr), float(momentum), float(wd), int(first), _st())
                     _lib.check(rc, "nopesac_sgd_step")
                 else:
                     raise NotImplementedError(f"no optimizer type {optimizer}")           # train_NopeSAC.py:158
@@ -356,15 +505,17 @@ class RefineTrainer:
     def step_from_cfg(self, cfg):
         """One optimiser step with the reference's solver settings (Trainer.build_optimizer, train_NopeSAC.py:88-169): SOLVER.OPTIMIZER
         (ADAMW / SGD), BASE_LR, WEIGHT_DECAY, MOMENTUM, CLIP_GRADIENTS (CLIP_TYPE "full_model": global-norm clipping in front of the
-        step).  The per-module multipliers (BACKBONE / SEM_SEG_HEAD / PLANE_MATCHER_HEAD) and the norm / embedding weight decays apply
-        to modules this trainer does not hold; every camera-head parameter uses the defaults, as in the reference."""
+        step).  GroupNorm / BatchNorm affine tensors (held with CameraHeadTrainer(conv_stacks=True)) use WEIGHT_DECAY_NORM, as the
+        reference's norm module types do; the per-module multipliers (BACKBONE / SEM_SEG_HEAD / PLANE_MATCHER_HEAD) and the embedding
+        weight decay apply to modules this trainer does not hold."""
         S = cfg.SOLVER
         cg = S.CLIP_GRADIENTS
         if cg.ENABLED and cg.CLIP_TYPE == "full_model" and cg.CLIP_VALUE > 0.0:
             self.clip_grad_norm(float(cg.CLIP_VALUE))
         elif cg.ENABLED:
             raise NotImplementedError("SOLVER.CLIP_GRADIENTS.CLIP_TYPE %r (the reference's configs use full_model)" % (cg.CLIP_TYPE,))
-        self.step(lr=float(S.BASE_LR), optimizer=str(S.OPTIMIZER), weight_decay=float(S.WEIGHT_DECAY), momentum=float(S.MOMENTUM))
+        self.step(lr=float(S.BASE_LR), optimizer=str(S.OPTIMIZER), weight_decay=float(S.WEIGHT_DECAY), momentum=float(S.MOMENTUM),
+                  weight_decay_norm=float(S.WEIGHT_DECAY_NORM))
 
     def write_back(self, head):
         """Copy the trained parameters into the inference head (its packed / bf16 copies are rebuilt on the next forward)."""
@@ -377,23 +528,99 @@ class RefineTrainer:
 class CameraHeadTrainer(RefineTrainer):
     """The camera head in TRAINING mode (reference PlaneCameraHead.forward, camera_head.py:140-344) with every Linear layer trainable:
     the pixel pose net's FC layers + pose regressors (fc_trans / fc_rots / trans / rots), the AIM (rot_emb_proj / trans_emb_proj) and the
-    refinement head - 108 tensors.  The pixel pose net's CONVOLUTIONS (pixel decoder, correlation stack) have no backward kernels: their
-    output features [B, 768] are computed by the inference kernels and enter as constants, i.e. those layers are frozen.
+    refinement head - 108 tensors.  By default the pixel pose net's CONVOLUTIONS (pixel decoder, correlation stack) are frozen: their
+    output features [B, 768] are computed by the inference kernels and enter as constants (`conv_feats`).
+
+    conv_stacks=True trains them too (179 tensors: + 24 conv weights, mask_features.bias, 10 GroupNorm and 36 BatchNorm affine tensors,
+    the reference's step-2 / step-3 recipe): the pixel pose net runs in f32 from this trainer's parameters on the 2B images (view 1
+    first, siamese weights shared) and its backward is csrc/conv_bwd.hip.  BatchNorm uses the stored running statistics (buffers, never
+    updated) with a trainable affine - batch-statistics BatchNorm is not implemented.  feature_grads=True also returns the gradients of
+    the backbone maps in `input_grads["res3" / "res4" / "res5"]` (NHWC, [2B, h, w, C]).
     Detach points as in the reference: the AIM re-embeds a detached copy of the pixel pose (:694, :723); the geometry sequences are built
     from detached initial poses (:354-365)."""
 
     EXTRA_MLPS = ("rot_emb_proj", "trans_emb_proj")
     EXTRA_LINEARS = ("fc_trans", "fc_rots")
 
+    def __init__(self, params: Dict[str, torch.Tensor], nq: int, warp_in_ref: bool = True, buffers: Optional[Dict[str, torch.Tensor]] = None,
+                 conv_stacks: bool = False, feature_grads: bool = False):
+        super().__init__(params, nq, warp_in_ref)
+        self.conv_stacks, self.feature_grads = bool(conv_stacks), bool(feature_grads)
+        assert not self.feature_grads or self.conv_stacks, "feature_grads needs conv_stacks=True"
+        self.buffers = {k: v.detach().float().contiguous() for k, v in (buffers or {}).items()}
+        if self.conv_stacks:
+            missing = [k for k in self.parameter_names(list(self.params) + list(self.buffers), True) if k not in self.params]
+            assert not missing, missing
+
     @staticmethod
-    def parameter_names(sd_keys) -> List[str]:
+    def parameter_names(sd_keys, conv_stacks: bool = False) -> List[str]:
         out = []
+        groups = MLPS + LINEARS + CameraHeadTrainer.EXTRA_MLPS + CameraHeadTrainer.EXTRA_LINEARS + (CONV_STACKS if conv_stacks else ())
         for k in sd_keys:
-            if not k.startswith(PREFIX):
+            if not k.startswith(PREFIX) or k.split(".")[-1] in _BUFFER_LEAVES:
                 continue
-            if k[len(PREFIX):].split(".")[0] in MLPS + LINEARS + CameraHeadTrainer.EXTRA_MLPS + CameraHeadTrainer.EXTRA_LINEARS:
+            if k[len(PREFIX):].split(".")[0] in groups:
                 out.append(k)
         return sorted(out)
+
+    @staticmethod
+    def buffer_names(sd_keys) -> List[str]:
+        """The BatchNorm running statistics of the conv stacks (fixed inputs of the conv_stacks=True forward)."""
+        return sorted(k for k in sd_keys if k.startswith(PREFIX) and k[len(PREFIX):].split(".")[0] in CONV_STACKS
+                      and k.split(".")[-1] in ("running_mean", "running_var"))
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, nq: int, device, warp_in_ref: bool = True, conv_stacks: bool = False,
+                        feature_grads: bool = False) -> "CameraHeadTrainer":
+        return cls({k: sd[k].to(device) for k in cls.parameter_names(sd.keys(), conv_stacks)}, nq, warp_in_ref,
+                   {k: sd[k].to(device) for k in cls.buffer_names(sd.keys())} if conv_stacks else None, conv_stacks, feature_grads)
+
+    @classmethod
+    def from_head(cls, head, conv_stacks: bool = False, feature_grads: bool = False) -> "CameraHeadTrainer":
+        keys = [PREFIX + k for k in head._spec_keys]
+        names = cls.parameter_names(keys, conv_stacks)
+        bufs = {k: head.raw(k[len(PREFIX):]) for k in cls.buffer_names(keys)} if conv_stacks else None
+        return cls({k: head.raw(k[len(PREFIX):]) for k in names}, head.num_queries, head.warp_plane_in_cam_ref_on, bufs, conv_stacks,
+                   feature_grads)
+
+    # ---- the pixel pose net's conv stacks (conv_stacks=True), camera_head.py:642-667 / camera_modules.py:246-348
+    def _cbl(self, x, name: str, stride: int = 1):
+        """conv3x3 (no bias) + BatchNorm2d(eps 1e-3, stored statistics) + LeakyReLU(0.01) (camera_modules.py:36-48)."""
+        P, Bf = self.params, self.buffers
+        q = PREFIX + name
+        return _ConvBNAct.apply(x, P[q + ".0.weight"], P[q + ".1.weight"], P[q + ".1.bias"], Bf[q + ".1.running_mean"],
+                                Bf[q + ".1.running_var"], stride, 1, ops.ACT_LEAKY)
+
+    def _gn_conv(self, x, name: str, pad: int, relu: bool):
+        q = PREFIX + "pixel_decoder." + name
+        return _ConvGN.apply(x, self.params[q + ".weight"], self.params[q + ".norm.weight"], self.params[q + ".norm.bias"], pad, relu)
+
+    def pixel_pose_convs(self, feats: dict, B: int):
+        """The conv stacks on NHWC res3..res5 of 2B images (view 1 first) -> yt, yr [B, 768] in the reference's flatten order, with the
+        autograd tape attached."""
+        y = self._gn_conv(feats["res5"], "layer_3", 1, True)
+        y = _UpsampleAdd.apply(y, self._gn_conv(feats["res4"], "adapter_2", 0, False))
+        y = self._gn_conv(y, "layer_2", 1, True)
+        y = _UpsampleAdd.apply(y, self._gn_conv(feats["res3"], "adapter_1", 0, False))
+        y = self._gn_conv(y, "layer_1", 1, True)
+        q = PREFIX + "pixel_decoder.mask_features"
+        x = _ConvBias.apply(y, self.params[q + ".weight"], self.params[q + ".bias"], 1)
+        for i in BACKBONE_CONVS:
+            x = self._cbl(x, f"convs_backbone.{i}")
+            if i in (1, 4):
+                x = _MaxPool2.apply(x)
+        _, h, w, _ = x.shape
+        P = h * w
+        aff = _CorrSoftmax.apply(x[:B], x[B:], P + (-P) % 8)          # (300 -> 304 channels at 480 x 640, zeros beyond P)
+
+        def branch(name):
+            t = aff
+            for i in range(6):
+                t = self._cbl(t, f"{name}.{i}", 2 if i % 2 == 1 else 1)
+            Bt, th, tw, C = t.shape
+            return t.reshape(Bt, th * tw, C).transpose(1, 2).reshape(Bt, C * th * tw)       # NHWC -> the reference's c * hw + i order
+
+        return branch("convs_trans"), branch("convs_rots")
 
     def pixel_pose(self, yt: torch.Tensor, yr: torch.Tensor):
         """The FC layers + regressors on the conv features yt / yr [B, 768] in the REFERENCE's flatten order (channel-major: c * 6 + hw)."""
@@ -420,11 +647,23 @@ class CameraHeadTrainer(RefineTrainer):
     def camera_head_losses(self, head, feats: dict, B: int, gt_planes1, gt_planes2, gt_n1, gt_n2, gt_assignment, gt_pose, planes1=None, planes2=None,
                            n1=None, n2=None, assignment=None, rand_rot=None, rand_trans=None) -> Dict[str, torch.Tensor]:
         """All losses of the training-mode forward (the 34 of PlaneCameraHead.forward_train) with the autograd tape attached."""
-        with torch.no_grad():
-            yt, yr = head.pixel_pose_net(feats, B, features_only=True)          # [B, hw * 128 + c]: the inference kernels' NHWC order
-            to_ref = lambda y: y.view(B, 6, 128).transpose(1, 2).reshape(B, 768).contiguous().float()
-            yt, yr = to_ref(yt), to_ref(yr)
-        self.conv_feats = (yt, yr)                                # (what the frozen conv stacks handed to the trainable layers)
+        inputs = {}
+        if self.conv_stacks:
+            fm = {}
+            for k in ("res3", "res4", "res5"):
+                fm[k] = feats[k].detach().float().contiguous()
+                if self.feature_grads:
+                    fm[k].requires_grad_(True)
+                    inputs[k] = fm[k]
+            yt, yr = self.pixel_pose_convs(fm, B)
+            yt, yr = yt.contiguous(), yr.contiguous()
+            self.conv_feats = (yt.detach(), yr.detach())
+        else:
+            with torch.no_grad():
+                yt, yr = head.pixel_pose_net(feats, B, features_only=True)          # [B, hw * 128 + c]: the inference kernels' NHWC order
+                to_ref = lambda y: y.view(B, 6, 128).transpose(1, 2).reshape(B, 768).contiguous().float()
+                yt, yr = to_ref(yt), to_ref(yr)
+            self.conv_feats = (yt, yr)                            # (what the frozen conv stacks handed to the trainable layers)
         losses: Dict[str, torch.Tensor] = {}
         trans0, rot0, tf0, rf0 = self.pixel_pose(yt, yr)
         lp = _PoseLoss.apply(trans0, rot0, gt_pose[:, 0:3], gt_pose[:, 3:7], head.initial_cam_weight, 0.0)
@@ -441,7 +680,6 @@ class CameraHeadTrainer(RefineTrainer):
         if assignment is not None:
             passes.append(("_Aux", planes1, planes2, n1, n2, assignment, head.plane_cam_weight_predplane))
         self.recorded = {"trans": [trans0, rec_t], "rot": [rot0, rec_r]}
-        inputs = {}
         for sfx, pl1, pl2, c1, c2, A, w in passes:
             for name, it, ir, itf, irf in (("initCamRef", trans0, rot0, tf0, rf0), ("initRecCamRef", rec_t, rec_r, rec_tf, rec_rf)):
                 losses.update(self.losses(A, pl1, pl2, c1, c2, it, ir, itf, irf, gt_pose, suffix=name + sfx, weight=w))
