@@ -700,6 +700,32 @@ int nopesac_transformer_tail_bf16_pf(const void* attn, const float* src, const v
                                      void* proj_pos, int n_pos, const void* w_proj, const float* b_proj, void* proj, int n_proj, int M,
                                      const void* const* next_ptrs, const int64_t* next_bytes, int n_next, int next_workgroups, void* stream);
 
+/* The kernel forms of the transformer tail (csrc/enc_tail.hip).  The 64- / 96- / 128-token kernels compute the post-norm tail only
+ * (pre_norm = 0, skip_ffn = 0); the 32-token kernel computes every form with n_pos + n_proj <= 1024. */
+#define NPS_ETAIL_32 0       /* enc_tail_kernel: 32 tokens per workgroup, the only form with the weight prefetch of the _pf entry */
+#define NPS_ETAIL_64 1       /* enc_tail64_kernel: 64 tokens, bit-identical to the 32-token kernel */
+#define NPS_ETAIL_96 2       /* enc_tail128_kernel with 3 row tiles: 96 tokens */
+#define NPS_ETAIL_128 3      /* enc_tail128_kernel with 4 row tiles: 128 tokens */
+#define NPS_ETAIL_FORMS 4
+/* A/B switch bits of the default selection, from the environment at every call: NOPESAC_ENC_TAIL_32 set, NOPESAC_ENC_TAIL_64 set,
+ * NOPESAC_ENC_TAIL_ROWS set, and NOPESAC_ENC_TAIL_ROWS = 3 (any other value forces 128 tokens). */
+#define NPS_ETAIL_SW_32 1
+#define NPS_ETAIL_SW_64 2
+#define NPS_ETAIL_SW_ROWS 4
+#define NPS_ETAIL_SW_ROWS3 8
+/* Host only (no GPU, no HIP call): the form the transformer_tail / encoder_tail / decoder_tail entries launch for M tokens under the switch
+ * bits (n_proj_total = n_pos + n_proj of the requested projections).  *eligible (optional) receives the bitmask (1 << NPS_ETAIL_*) of every
+ * form that computes the call correctly, whatever the switches; the default is not in it when n_proj_total > 1024 (the call is refused). */
+int nopesac_transformer_tail_forms(long long M, int pre_norm, int skip_ffn, long long n_proj_total, int switches, unsigned* eligible);
+/* nopesac_transformer_tail_bf16_pf on the given form.  A form that is not eligible for the call returns NPS_E_ARG before any HIP call. */
+int nopesac_transformer_tail_bf16_form(const void* attn, const float* src, const void* wo, const float* bo, const float* lna_g,
+                                       const float* lna_b, const void* w1, const float* b1, const void* w2, const float* b2,
+                                       const float* lnb_g, const float* lnb_b, const float* pos, int pos_rows, float* y, void* y_bf16,
+                                       void* ypos_bf16, float* yn, int pre_norm, int skip_ffn, const void* w_pos, const float* b_pos,
+                                       void* proj_pos, int n_pos, const void* w_proj, const float* b_proj, void* proj, int n_proj, int M,
+                                       const void* const* next_ptrs, const int64_t* next_bytes, int n_next, int next_workgroups, int form,
+                                       void* stream);
+
 /* ---- COCO RLE of the kept plane masks (replaces pycocotools.mask.encode / toBbox at
  *      meta_arch/siamese_planeTR.py:703-704, 747-748; consumed by evaluation/mp3d_evaluation.py:203-205) ----
  * labels: winner uint8[V,H,W] (+ kept_idx int32[V,nq], n_kept int32[V], flags int32[V] from nopesac_postselect_planes)

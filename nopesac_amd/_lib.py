@@ -46,6 +46,8 @@ SIGNATURES = {
     "nopesac_decoder_tail_bf16": [P] * 13 + [I] + [P] * 4 + [I, P],
     "nopesac_transformer_tail_bf16": [P] * 13 + [I] + [P] * 4 + [I, I, P, P, P, I, P, P, P, I, I, P],
     "nopesac_transformer_tail_bf16_pf": [P] * 13 + [I] + [P] * 4 + [I, I, P, P, P, I, P, P, P, I, I, P, P, I, I, P],
+    "nopesac_transformer_tail_bf16_form": [P] * 13 + [I] + [P] * 4 + [I, I, P, P, P, I, P, P, P, I, I, P, P, I, I, I, P],
+    "nopesac_transformer_tail_forms": [L, I, I, L, I, P],
     "nopesac_conv3x3_c64_bf16": [P, P, P, P, P, I, I, I, I, P],
     "nopesac_conv3x3_halo_bf16": [P, P, P, P, P, I, I, I, I, I, I, I, P],
     "nopesac_rle_labels": [P, P, P, P, P, I, I, I, I, P],

@@ -1001,29 +1001,67 @@ __global__ __launch_bounds__(512, 1) void enc_tail128_kernel(const EncTailArgs p
 static unsigned long long* g_et_dbg = nullptr;
 extern "C" void nps_enc_tail_debug_buffer(void* buf) { g_et_dbg = (unsigned long long*)buf; }
 
-static int et_launch(const EncTailArgs& a, hipStream_t stream) {
+// ---- form selection: which kernel runs a transformer tail (nopesac_transformer_tail_forms)
+// bitmask of the forms that compute (M, pre_norm, skip_ffn, n_pos + n_proj) correctly.  The 64- / 96- / 128-token kernels have no pre-norm or
+// skip_ffn path (the normalised y1 is their second residual, they run the FFN and write no yn); every form guards or clamps its rows
+// against M and loops over any number of projection tiles, except the 32-token kernel's four unrolled rounds of 8 tiles: n_proj_total <= 1024
+static unsigned et_eligible(long long M, bool pre_norm, bool skip_ffn, long long n_proj_total) {
+    if (M <= 0) return 0u;
+    unsigned m = 0;
+    if (n_proj_total <= 1024) m |= 1u << NPS_ETAIL_32;
+    if (!pre_norm && !skip_ffn) m |= 1u << NPS_ETAIL_64 | 1u << NPS_ETAIL_96 | 1u << NPS_ETAIL_128;
+    return m;
+}
+
+// the default form under the NPS_ETAIL_SW_* switch bits (whether or not it is eligible: the 32-token kernel at n_pos + n_proj > 1024)
+static int et_default(long long M, bool pre_norm, bool skip_ffn, int sw) {
     // the encoder (post-norm, thousands of tokens) on the 64-token kernel; decoder forms and small inputs on the 32-token one
     // (NOPESAC_ENC_TAIL_64=1: the round-3 64-token kernel, NOPESAC_ENC_TAIL_32=1: the 32-token one - A/B runs and the bit-identity test of those two)
-    if (!a.pre_norm && !a.skip_ffn && a.M >= 2048 && !getenv("NOPESAC_ENC_TAIL_32") && !getenv("NOPESAC_ENC_TAIL_64")) {
+    if (!pre_norm && !skip_ffn && M >= 2048 && !(sw & NPS_ETAIL_SW_32) && !(sw & NPS_ETAIL_SW_64)) {
         // 96 tokens per workgroup when that fills more CUs than 128 do in one round (the encoder's 19200 tokens: 200 workgroups instead
         // of 150); NOPESAC_ENC_TAIL_ROWS=3|4 forces one form (A/B runs, tests)
-        int nr = ((a.M + 127) / 128 <= 160 && (a.M + 95) / 96 <= 256) ? 3 : 4;
-        if (const char* e = getenv("NOPESAC_ENC_TAIL_ROWS")) nr = atoi(e) == 3 ? 3 : 4;
+        int nr = ((M + 127) / 128 <= 160 && (M + 95) / 96 <= 256) ? 3 : 4;
+        if (sw & NPS_ETAIL_SW_ROWS) nr = (sw & NPS_ETAIL_SW_ROWS3) ? 3 : 4;
+        return nr == 3 ? NPS_ETAIL_96 : NPS_ETAIL_128;
+    }
+    if (!pre_norm && !skip_ffn && M >= 2048 && !(sw & NPS_ETAIL_SW_32)) return NPS_ETAIL_64;
+    return NPS_ETAIL_32;
+}
+
+static const char* et_form_name(int form) {
+    static const char* names[NPS_ETAIL_FORMS] = {"t32", "t64", "t96", "t128"};
+    return form >= 0 && form < NPS_ETAIL_FORMS ? names[form] : "?";
+}
+
+static int et_switches() {
+    const char* rows = getenv("NOPESAC_ENC_TAIL_ROWS");
+    return (getenv("NOPESAC_ENC_TAIL_32") ? NPS_ETAIL_SW_32 : 0) | (getenv("NOPESAC_ENC_TAIL_64") ? NPS_ETAIL_SW_64 : 0) |
+           (rows ? NPS_ETAIL_SW_ROWS : 0) | (rows && atoi(rows) == 3 ? NPS_ETAIL_SW_ROWS3 : 0);
+}
+
+// launch one form; NPS_E_ARG (before any HIP call) if it is not eligible for the call
+static int et_launch_form(int form, const EncTailArgs& a, hipStream_t stream) {
+    const long long nproj = (long long)(a.wpa ? a.npa : 0) + (a.wpb ? a.npb : 0);
+    const unsigned m = et_eligible(a.M, a.pre_norm != 0, a.skip_ffn != 0, nproj);
+    NPS_CHECK_ARG(form >= 0 && form < NPS_ETAIL_FORMS, "transformer_tail: form %d out of range [0, %d)", form, NPS_ETAIL_FORMS);
+    // the 32-token kernel issues its projection tiles in four unrolled rounds of 8 column tiles: 32 tiles = 1024 output columns
+    NPS_CHECK_ARG(form != NPS_ETAIL_32 || nproj <= 1024, "transformer_tail: n_pos + n_proj > 1024 on the 32-token kernel");
+    NPS_CHECK_ARG((m >> form) & 1u, "transformer_tail: form %d (%s) is not eligible for M=%d pre_norm=%d skip_ffn=%d n_pos+n_proj=%lld (eligible mask 0x%x)",
+                  form, et_form_name(form), a.M, a.pre_norm, a.skip_ffn, nproj, m);
+    if (form == NPS_ETAIL_96 || form == NPS_ETAIL_128) {
         auto go = [&](auto K, size_t lds, int bm) {
             NPS_ENSURE_LDS((int)lds, K);
             hipLaunchKernelGGL(K, dim3((a.M + bm - 1) / bm), dim3(512), lds, stream, a, g_et_dbg);
         };
         if (g_et_dbg) {                                       // tuning runs only (scripts/enc_tail_stamps.py)
-            if (nr == 3) go(enc_tail128_kernel<true, 3>, E8<3>::LDS_BYTES, 96); else go(enc_tail128_kernel<true, 4>, E8<4>::LDS_BYTES, 128);
+            if (form == NPS_ETAIL_96) go(enc_tail128_kernel<true, 3>, E8<3>::LDS_BYTES, 96); else go(enc_tail128_kernel<true, 4>, E8<4>::LDS_BYTES, 128);
         } else {
-            if (nr == 3) go(enc_tail128_kernel<false, 3>, E8<3>::LDS_BYTES, 96); else go(enc_tail128_kernel<false, 4>, E8<4>::LDS_BYTES, 128);
+            if (form == NPS_ETAIL_96) go(enc_tail128_kernel<false, 3>, E8<3>::LDS_BYTES, 96); else go(enc_tail128_kernel<false, 4>, E8<4>::LDS_BYTES, 128);
         }
-    } else if (!a.pre_norm && !a.skip_ffn && a.M >= 2048 && !getenv("NOPESAC_ENC_TAIL_32")) {
+    } else if (form == NPS_ETAIL_64) {
         NPS_ENSURE_LDS((int)E6_LDS_BYTES, enc_tail64_kernel);
         hipLaunchKernelGGL(enc_tail64_kernel, dim3((a.M + E6_BM - 1) / E6_BM), dim3(512), E6_LDS_BYTES, stream, a);
     } else {
-        // the 32-token kernel issues its projection tiles in four unrolled rounds of 8 column tiles: 32 tiles = 1024 output columns
-        NPS_CHECK_ARG((a.wpa ? a.npa : 0) + (a.wpb ? a.npb : 0) <= 1024, "transformer_tail: n_pos + n_proj > 1024 on the 32-token kernel");
         NPS_ENSURE_LDS((int)ET_LDS_BYTES, enc_tail_kernel);
         EncTailArgs b = a;
         b.n_work = (a.M + ET_BM - 1) / ET_BM;
@@ -1033,6 +1071,11 @@ static int et_launch(const EncTailArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(enc_tail_kernel, dim3(b.n_work + extra), dim3(512), ET_LDS_BYTES, stream, b);
     }
     return 0;
+}
+
+// the default selection: the A/B switches are read from the environment at every call
+static int et_launch(const EncTailArgs& a, hipStream_t stream) {
+    return et_launch_form(et_default(a.M, a.pre_norm != 0, a.skip_ffn != 0, et_switches()), a, stream);
 }
 
 }  // namespace nps
@@ -1108,14 +1151,13 @@ extern "C" int nopesac_transformer_tail_bf16(const void* attn, const float* src,
                                             stream);
 }
 
-extern "C" int nopesac_transformer_tail_bf16_pf(const void* attn, const float* src, const void* wo, const float* bo, const float* lna_g,
-                                                const float* lna_b, const void* w1, const float* b1, const void* w2, const float* b2,
-                                                const float* lnb_g, const float* lnb_b, const float* pos, int pos_rows, float* y, void* y_bf16,
-                                                void* ypos_bf16, float* yn, int pre_norm, int skip_ffn, const void* w_pos, const float* b_pos,
-                                                void* proj_pos, int n_pos, const void* w_proj, const float* b_proj, void* proj, int n_proj, int M,
-                                                const void* const* next_ptrs, const int64_t* next_bytes, int n_next, int next_workgroups,
-                                                void* stream) {
-    using namespace nps;
+namespace nps {
+// the argument checks of the transformer_tail entries, and the kernel arguments
+static int tt_args(EncTailArgs& a, const void* attn, const float* src, const void* wo, const float* bo, const float* lna_g, const float* lna_b,
+                   const void* w1, const float* b1, const void* w2, const float* b2, const float* lnb_g, const float* lnb_b, const float* pos,
+                   int pos_rows, float* y, void* y_bf16, void* ypos_bf16, float* yn, int pre_norm, int skip_ffn, const void* w_pos,
+                   const float* b_pos, void* proj_pos, int n_pos, const void* w_proj, const float* b_proj, void* proj, int n_proj, int M,
+                   const void* const* next_ptrs, const int64_t* next_bytes, int n_next, int next_workgroups) {
     NPS_CHECK_ARG(n_next >= 0 && n_next <= ET_PF_MAX && (n_next == 0 || (next_ptrs && next_bytes && next_workgroups > 0)),
                   "transformer_tail: bad prefetch list (at most %d ranges)", ET_PF_MAX);
     NPS_CHECK_ARG(attn && src && wo && bo && lna_g && lna_b && M > 0, "transformer_tail: null pointer");
@@ -1128,7 +1170,6 @@ extern "C" int nopesac_transformer_tail_bf16_pf(const void* attn, const float* s
     const void* ptrs[] = {attn, src, wo, bo, lna_g, lna_b, w1, b1, w2, b2, lnb_g, lnb_b, pos, y, y_bf16, ypos_bf16, yn, w_pos, b_pos, proj_pos,
                           w_proj, b_proj, proj};
     for (const void* q : ptrs) NPS_CHECK_ARG(((uintptr_t)q & 15) == 0, "transformer_tail: pointers must be 16-byte aligned");
-    EncTailArgs a;
     a.attn = (const bf16_t*)attn; a.src = src; a.wo = (const bf16_t*)wo; a.bo = bo; a.g1 = lna_g; a.be1 = lna_b;
     a.w1 = (const bf16_t*)w1; a.b1 = b1; a.w2 = (const bf16_t*)w2; a.b2 = b2; a.g2 = lnb_g; a.be2 = lnb_b;
     a.pos = pos; a.pos_rows = pos_rows; a.y = y; a.y16 = (bf16_t*)y_bf16; a.ypos16 = (bf16_t*)ypos_bf16; a.M = M;
@@ -1141,6 +1182,42 @@ extern "C" int nopesac_transformer_tail_bf16_pf(const void* attn, const float* s
                       "transformer_tail: prefetch range %d null / unaligned / too large", i);
         a.pf[i] = (const unsigned char*)next_ptrs[i]; a.pf_bytes[i] = (int)next_bytes[i];
     }
+    return 0;
+}
+}  // namespace nps
+
+extern "C" int nopesac_transformer_tail_bf16_pf(const void* attn, const float* src, const void* wo, const float* bo, const float* lna_g,
+                                                const float* lna_b, const void* w1, const float* b1, const void* w2, const float* b2,
+                                                const float* lnb_g, const float* lnb_b, const float* pos, int pos_rows, float* y, void* y_bf16,
+                                                void* ypos_bf16, float* yn, int pre_norm, int skip_ffn, const void* w_pos, const float* b_pos,
+                                                void* proj_pos, int n_pos, const void* w_proj, const float* b_proj, void* proj, int n_proj, int M,
+                                                const void* const* next_ptrs, const int64_t* next_bytes, int n_next, int next_workgroups,
+                                                void* stream) {
+    using namespace nps;
+    EncTailArgs a;
+    if (const int rc = tt_args(a, attn, src, wo, bo, lna_g, lna_b, w1, b1, w2, b2, lnb_g, lnb_b, pos, pos_rows, y, y_bf16, ypos_bf16, yn, pre_norm, skip_ffn, w_pos,
+                           b_pos, proj_pos, n_pos, w_proj, b_proj, proj, n_proj, M, next_ptrs, next_bytes, n_next, next_workgroups)) return rc;
     if (const int rc = et_launch(a, (hipStream_t)stream)) return rc;
     NPS_LAUNCH_RET();
+}
+
+extern "C" int nopesac_transformer_tail_bf16_form(const void* attn, const float* src, const void* wo, const float* bo, const float* lna_g,
+                                                  const float* lna_b, const void* w1, const float* b1, const void* w2, const float* b2,
+                                                  const float* lnb_g, const float* lnb_b, const float* pos, int pos_rows, float* y, void* y_bf16,
+                                                  void* ypos_bf16, float* yn, int pre_norm, int skip_ffn, const void* w_pos, const float* b_pos,
+                                                  void* proj_pos, int n_pos, const void* w_proj, const float* b_proj, void* proj, int n_proj, int M,
+                                                  const void* const* next_ptrs, const int64_t* next_bytes, int n_next, int next_workgroups,
+                                                  int form, void* stream) {
+    using namespace nps;
+    EncTailArgs a;
+    if (const int rc = tt_args(a, attn, src, wo, bo, lna_g, lna_b, w1, b1, w2, b2, lnb_g, lnb_b, pos, pos_rows, y, y_bf16, ypos_bf16, yn, pre_norm, skip_ffn, w_pos,
+                           b_pos, proj_pos, n_pos, w_proj, b_proj, proj, n_proj, M, next_ptrs, next_bytes, n_next, next_workgroups)) return rc;
+    if (const int rc = et_launch_form(form, a, (hipStream_t)stream)) return rc;
+    NPS_LAUNCH_RET();
+}
+
+extern "C" int nopesac_transformer_tail_forms(long long M, int pre_norm, int skip_ffn, long long n_proj_total, int switches, unsigned* eligible) {
+    const unsigned m = nps::et_eligible(M, pre_norm != 0, skip_ffn != 0, n_proj_total);
+    if (eligible) *eligible = m;
+    return nps::et_default(M, pre_norm != 0, skip_ffn != 0, switches);
 }

@@ -1264,28 +1264,52 @@ def decoder_tail(attn: torch.Tensor, tgt: torch.Tensor, W: dict, pos=None, want=
 
 
 TAIL_PREFETCH = os.environ.get("NOPESAC_TAIL_PREFETCH", "1") != "0"
+# the kernel forms of the transformer tail, indexed by form id (NPS_ETAIL_* of include/nopesac_hip.h): tokens per workgroup
+TRANSFORMER_TAIL_FORMS = ("t32", "t64", "t96", "t128")
+# A/B switch bits of the default selection (NPS_ETAIL_SW_*); NOPESAC_ENC_TAIL_ROWS sets ROWS, and ROWS3 as well when it is 3
+TRANSFORMER_TAIL_SWITCHES = {"NOPESAC_ENC_TAIL_32": 1, "NOPESAC_ENC_TAIL_64": 2, "NOPESAC_ENC_TAIL_ROWS": 4, "NOPESAC_ENC_TAIL_ROWS=3": 8}
+
+
+def transformer_tail_forms(M, pre_norm, skip_ffn=False, n_proj_total=0, switches=0):
+    """(default form id, bitmask of eligible form ids) of a transformer tail over M tokens whose projections are n_proj_total = n_pos +
+    n_proj wide, under the NPS_ETAIL_SW_* switch bits.  Host only: needs no GPU."""
+    mask = ctypes.c_uint(0)
+    form = _L().nopesac_transformer_tail_forms(M, int(bool(pre_norm)), int(bool(skip_ffn)), n_proj_total, switches, ctypes.byref(mask))
+    return form, mask.value
 
 
 def transformer_tail(attn: torch.Tensor, src: torch.Tensor, W: dict, *, pre_norm: bool, skip_ffn: bool = False, pos=None,
-                     want=("y",), proj_pos=None, proj=None, prefetch=None) -> dict:
+                     want=("y",), proj_pos=None, proj=None, prefetch=None, form=None, out=None) -> dict:
     """The tail of a transformer layer + the input projections of the next attention in one launch (nopesac_transformer_tail_bf16).
     W: "wo", "bo", "ga", "bea" (first norm) and - unless skip_ffn - "w1", "b1", "w2", "b2", "gb", "beb" (second norm); fragment-major
     bf16 matrices, f32 vectors.  proj_pos / proj = (fragment-major weight, f32 bias or None, width): projections of the normalised
     result + pos / of the normalised result, returned as "proj_pos" / "proj" (bf16 [M, width]).  want: any of "y", "y16", "ypos16", "yn".
     prefetch = (tensors, workgroups): the weight tensors and the workgroup count of the NEXT tail launch - with few rows (one pair per
-    call) extra workgroups of this launch read them into the L2s the next launch will run on (nopesac_transformer_tail_bf16_pf)."""
+    call) extra workgroups of this launch read them into the L2s the next launch will run on (nopesac_transformer_tail_bf16_pf).
+    form: a TRANSFORMER_TAIL_FORMS id to launch instead of the default selection (an ineligible one raises); out: contiguous output
+    buffers to write (by the names above) instead of new ones."""
     _chk(attn, torch.bfloat16); _chk(src, torch.float32)
     M = src.shape[0]
     _require(attn.shape == (M, 256) and src.shape == (M, 256), "transformer_tail: attn / src [M, 256]")
-    out = {k: torch.empty(M, 256, device=src.device, dtype=torch.float32 if k in ("y", "yn") else torch.bfloat16) for k in want}
+    given = dict(out or {})
     if pos is not None:
         _chk(pos, torch.float32)
     wa, ba, na = proj_pos if proj_pos is not None else (None, None, 0)
     wb, bb, nb = proj if proj is not None else (None, None, 0)
+    shapes = {k: (256, torch.float32 if k in ("y", "yn") else torch.bfloat16) for k in want}
     if na:
-        out["proj_pos"] = torch.empty(M, na, device=src.device, dtype=torch.bfloat16)
+        shapes["proj_pos"] = (na, torch.bfloat16)
     if nb:
-        out["proj"] = torch.empty(M, nb, device=src.device, dtype=torch.bfloat16)
+        shapes["proj"] = (nb, torch.bfloat16)
+    _require(set(given) <= set(shapes), "transformer_tail: out holds a buffer that was not asked for")
+    out = {}
+    for k, (n, dt) in shapes.items():
+        t = given.get(k)
+        if t is None:
+            t = torch.empty(M, n, device=src.device, dtype=dt)
+        _chk(t, dt)
+        _require(t.shape == (M, n), "transformer_tail: out[%s] must be [M, %d]" % (k, n))
+        out[k] = t
     g = W.get
     nptr = nbytes = None
     n_next = next_wg = 0
@@ -1295,12 +1319,16 @@ def transformer_tail(attn: torch.Tensor, src: torch.Tensor, W: dict, *, pre_norm
             n_next, next_wg = len(tens), int(prefetch[1])
             nptr = (ctypes.c_void_p * n_next)(*[_p(t) for t in tens])
             nbytes = (ctypes.c_int64 * n_next)(*[t.numel() * t.element_size() for t in tens])
-    rc = _L().nopesac_transformer_tail_bf16_pf(
-        _p(attn), _p(src), _p(W["wo"]), _p(W["bo"]), _p(W["ga"]), _p(W["bea"]), _p(g("w1")), _p(g("b1")), _p(g("w2")), _p(g("b2")),
-        _p(g("gb")), _p(g("beb")), _p(pos), 0 if pos is None else pos.shape[0], _p(out.get("y")), _p(out.get("y16")), _p(out.get("ypos16")),
-        _p(out.get("yn")), int(pre_norm), int(skip_ffn), _p(wa), _p(ba), _p(out.get("proj_pos")), na, _p(wb), _p(bb), _p(out.get("proj")), nb, M,
-        nptr, nbytes, n_next, next_wg, _stream())
-    _lib.check(rc, "nopesac_transformer_tail_bf16_pf")
+    args = (_p(attn), _p(src), _p(W["wo"]), _p(W["bo"]), _p(W["ga"]), _p(W["bea"]), _p(g("w1")), _p(g("b1")), _p(g("w2")), _p(g("b2")),
+            _p(g("gb")), _p(g("beb")), _p(pos), 0 if pos is None else pos.shape[0], _p(out.get("y")), _p(out.get("y16")), _p(out.get("ypos16")),
+            _p(out.get("yn")), int(pre_norm), int(skip_ffn), _p(wa), _p(ba), _p(out.get("proj_pos")), na, _p(wb), _p(bb), _p(out.get("proj")), nb,
+            M, nptr, nbytes, n_next, next_wg)
+    if form is None:
+        rc = _L().nopesac_transformer_tail_bf16_pf(*args, _stream())
+        _lib.check(rc, "nopesac_transformer_tail_bf16_pf")
+    else:
+        rc = _L().nopesac_transformer_tail_bf16_form(*args, int(form), _stream())
+        _lib.check(rc, "nopesac_transformer_tail_bf16_form")
     return out
 
 
