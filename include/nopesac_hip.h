@@ -140,6 +140,30 @@ int nopesac_conv2d_nhwc_p8n_splitk(const void* x, const void* w, const float* sc
                                    int Cin, int Cout, int KH, int KW, int stride, int pad, int64_t x_cstride, int64_t y_cstride, int act,
                                    int variant, int splits, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- which of the kernels above may run one convolution (csrc/conv_forms.h; host only: no HIP call, needs no GPU) -----------------
+ * A kernel configuration of nopesac_amd.ops.conv2d is NPS_CONV_AUTO .. NPS_CONV_DMA32 (nopesac_conv2d_nhwc_ex) or one of: */
+#define NPS_CONV_CFG_BFRAG3 7     /* nopesac_conv2d_nhwc_bfrag, variant 3 */
+#define NPS_CONV_CFG_BFRAG32 8    /* nopesac_conv2d_nhwc_bfrag, variant 32 */
+#define NPS_CONV_CFG_HALO16 9     /* nopesac_conv3x3_halo_bf16, tile 0 */
+#define NPS_CONV_CFG_HALO8 10     /* nopesac_conv3x3_halo_bf16, tile 1 */
+#define NPS_CONV_CFG_P8 11        /* nopesac_conv2d_nhwc_p8 */
+#define NPS_CONV_CFG_P8_SK 12     /* nopesac_conv2d_nhwc_p8_sk */
+#define NPS_CONV_CFG_P8N 13       /* nopesac_conv2d_nhwc_p8n, channel-major K order */
+#define NPS_CONV_CFG_P8N_TAP 14   /* nopesac_conv2d_nhwc_p8n, tap-major K order */
+#define NPS_CONV_CFG_P8N_SPLIT 15 /* nopesac_conv2d_nhwc_p8n_splitk */
+/* Returns the bitmask (1 << configuration) of the configurations the autotuner may time for the call, or NPS_E_ARG (stride <= 0);
+ * *splits (optional) receives the slice count it hands nopesac_conv2d_nhwc_p8n_splitk.  x_dt / w_dt / out_dt: NPS_DT_* of the buffers
+ * in memory; batched: w_bstride != 0; act: the whole act word; aligned: x, w, y, residual, scale and bias are all 16-byte aligned.
+ * The call is taken to be well formed (positive dims, a non-empty output, channel strides >= channel counts: the entry points check
+ * that).  Bits 0-4 are always set: T128 .. DMA32 fall back to the heuristic where they do not apply.  The entry points above check
+ * their arguments with the same predicates and refuse a call outside its bit before any HIP call.  An entry point asks for a little
+ * more than its bit says, because the bfrag / halo / p8 bits are part of the autotuner's routing keys and stay as they were tuned:
+ * bfrag and halo need their own pointers 16-byte aligned whatever the other buffers are, bfrag with an fp8 output needs no residual
+ * and 8-channel-aligned y / scale / bias, p8 needs B * OH * OW < 2^23. */
+int nopesac_conv2d_nhwc_forms(int x_dt, int w_dt, int out_dt, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                              int64_t x_cstride, int64_t y_cstride, int64_t r_cstride, int batched, int has_residual, int has_scale,
+                              int has_bias, int act, int aligned, int* splits);
+
 /* ---- a stack of Linear(+bias)(+activation) layers in ONE launch (csrc/mlp_chain.hip) --------------------------------------------
  * Replaces one nopesac_conv2d_nhwc launch per layer for the row-wise MLP stacks of the heads in bf16 mode (reference:
  * camera_net/camera_head.py:957-990 geo_encoder / geo_proj_s1 / decoder_rot / geo_proj_s2 / decoder_tran / decoder_rot2 /

@@ -9,6 +9,7 @@
 // weights stream fragment-major from L2 through a rolling register ring, wave w owning output-channel tile w, every fragment
 // feeding TH*TW/32 MFMAs (8 for the 16x16 tile).  Between two barriers a wave issues 36 x TH*TW/32 MFMAs.
 #include "common.h"
+#include "conv_forms.h"
 
 namespace nps {
 
@@ -132,12 +133,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const HaloArgs p) 
 extern "C" int nopesac_conv3x3_halo_bf16(const void* x, const void* w_frag, const float* scale, const float* bias, void* y, int B, int H,
                                          int W, int Cin, int Cout, int act, int tile, void* stream) {
     using namespace nps;
-    NPS_CHECK_ARG(x && w_frag && scale && bias && y && B > 0 && H > 0 && W > 0, "conv3x3_halo: bad args");
-    NPS_CHECK_ARG(Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 128 == 0, "conv3x3_halo: needs Cin %% 64 == 0 and Cout %% 128 == 0");
-    NPS_CHECK_ARG(act >= 0 && act <= 3, "conv3x3_halo: bad act %d", act);
+    NPS_CHECK_ARG(x && w_frag && scale && bias && y, "conv3x3_halo: null pointer");
+    const ConvCall c = {NPS_DT_BF16, NPS_DT_BF16, NPS_DT_BF16, B, H, W, Cin, Cout, 3, 3, 1, 1, Cin, Cout, 0, false, false, true, true, act,
+                        conv_aligned({x, w_frag, scale, bias, y}), true};
+    NPS_CHECK_CONV("conv3x3_halo", conv_call_refusal(c));
+    NPS_CHECK_CONV("conv3x3_halo", conv_halo_refusal(c));
+    NPS_CHECK_ARG(c.aligned, "conv3x3_halo: pointers must be 16-byte aligned");
     NPS_CHECK_ARG(tile == 0 || tile == 1, "conv3x3_halo: tile must be 0 (16x16 pixels) or 1 (16 rows x 8 columns)");
-    const void* ptrs[] = {x, w_frag, scale, bias, y};
-    for (const void* q : ptrs) NPS_CHECK_ARG(((uintptr_t)q & 15) == 0, "conv3x3_halo: pointers must be 16-byte aligned");
     HaloArgs a;
     a.x = (const bf16_t*)x; a.wfrag = (const bf16_t*)w_frag; a.scale = scale; a.bias = bias; a.y = (bf16_t*)y;
     a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act;

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "conv_forms.h"
 
 namespace nps {
 
@@ -878,35 +879,30 @@ static int bfrag_launch(bool fp8, const void* x, const void* w_frag, const float
                         int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int64_t x_cstride,
                         int64_t y_cstride, int64_t r_cstride, int act, int out_dt, int nstage, void* stream) {
     using namespace nps;
-    const int eb = fp8 ? 1 : 2;
     NPS_CHECK_ARG(x && w_frag && y, "conv2d_bfrag: null pointer");
-    NPS_CHECK_ARG(B > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && KH * KW <= 32, "conv2d_bfrag: bad dims");
-    NPS_CHECK_ARG(Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 128 == 0, "conv2d_bfrag: needs Cin %% 64 == 0 and Cout %% 128 == 0");
-    NPS_CHECK_ARG(out_dt == NPS_DT_F32 || out_dt == NPS_DT_BF16 || out_dt == NPS_DT_FP8, "conv2d_bfrag: bad out_dt %d", out_dt);
+    const int dt = fp8 ? NPS_DT_FP8 : NPS_DT_BF16;
+    const ConvCall c = {dt, dt, out_dt, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, r_cstride, false, residual != nullptr,
+                        scale != nullptr, bias != nullptr, act, conv_aligned({x, w_frag, y, residual, scale, bias}), true};
+    NPS_CHECK_CONV("conv2d_bfrag", conv_call_refusal(c));
+    NPS_CHECK_CONV("conv2d_bfrag", conv_bfrag_refusal(c));
+    NPS_CHECK_ARG(conv_aligned({x, w_frag}), "conv2d_bfrag: x / w_frag must be 16-byte aligned");    // (a bf16 / f32 y may be unaligned: epi_vec)
     const int kmajor = (nstage >> 8) & 1;       // + 256: channel-major K order (better L2 reuse of the taps of a KxK conv)
     nstage &= 0xff;
     NPS_CHECK_ARG(nstage == 3 || nstage == 32, "conv2d_bfrag: variant must be 3 (3-stage ring, K-tile 64) or 32 (4-stage ring, K-tile 32), + 256: channel-major K");
     NPS_CHECK_ARG(!(fp8 && nstage == 3) || Cin % 128 == 0, "conv2d_fp8: variant 3 (K-tile 128) needs Cin %% 128 == 0");
-    NPS_CHECK_ARG(x_cstride >= Cin && x_cstride % (16 / eb) == 0 && y_cstride >= Cout && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w_frag % 16 == 0),
-                  "conv2d_bfrag: strides / alignment");
-    NPS_CHECK_ARG(!residual || (r_cstride >= Cout && out_dt != NPS_DT_FP8), "conv2d_bfrag: residual stride / residual with fp8 output");
     const int res_after = (act & NPS_ACT_RES_AFTER) ? 1 : 0;
-    NPS_CHECK_ARG((act & ~(0xff | NPS_ACT_RES_AFTER)) == 0, "conv2d_bfrag: unsupported act flags");
     act &= 0xff;
-    NPS_CHECK_ARG(act >= 0 && act <= 3, "conv2d_bfrag: bad act %d", act);
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.w = w_frag; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
     p.OH = (H + 2 * pad - KH) / stride + 1;
     p.OW = (W + 2 * pad - KW) / stride + 1;
-    NPS_CHECK_ARG(p.OH > 0 && p.OW > 0, "conv2d_bfrag: empty output");
     p.x_cs = x_cstride; p.y_cs = y_cstride; p.r_cs = r_cstride; p.w_bs = 0;
     p.rows_per_b = p.OH * p.OW;
     p.batched = 0;
     p.M = B * p.rows_per_b; p.N = Cout; p.K = KH * KW * Cin;
     p.act = act; p.out_dt = out_dt; p.res_after = res_after; p.force = kmajor;
-    NPS_CHECK_ARG((long long)B * H * W * x_cstride * eb + ((long long)pad * W + pad) * x_cstride * eb < (1ll << 31), "conv2d_bfrag: input larger than 2 GB");
     {
         const int al = out_dt == NPS_DT_F32 ? 4 : 8;
         bool ok = (y_cstride % al == 0) && ((uintptr_t)y % 16 == 0);
@@ -914,7 +910,6 @@ static int bfrag_launch(bool fp8, const void* x, const void* w_frag, const float
         if (scale) ok = ok && ((uintptr_t)scale % 16 == 0);
         if (bias) ok = ok && ((uintptr_t)bias % 16 == 0);
         p.epi_vec = ok ? 1 : 0;
-        NPS_CHECK_ARG(ok || out_dt != NPS_DT_FP8, "conv2d_fp8: fp8 output needs 8-channel-aligned y / scale / bias");
     }
     p.tiles_m = (p.M + 127) / 128;
     p.tiles_n = p.N / 128;
@@ -943,4 +938,26 @@ extern "C" int nopesac_conv2d_nhwc_fp8(const void* x, const void* w_frag8, const
                                        void* stream) {
     return bfrag_launch(true, x, w_frag8, scale, bias, residual, y, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, r_cstride,
                         act, out_dt, variant, stream);
+}
+
+// Host only.  The bitmask (1 << NPS_CONV_CFG_*) of the configurations nopesac_amd.ops.conv2d may launch the call through, from the
+// predicates of conv_forms.h ("can the kernel run it") and its policy ("does the tuner offer it"); *splits: the split-K slice count.
+extern "C" int nopesac_conv2d_nhwc_forms(int x_dt, int w_dt, int out_dt, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                                         int pad, int64_t x_cstride, int64_t y_cstride, int64_t r_cstride, int batched, int has_residual,
+                                         int has_scale, int has_bias, int act, int aligned, int* splits) {
+    using namespace nps;
+    NPS_CHECK_ARG(stride > 0, "conv2d_forms: stride must be positive");
+    const ConvCall c = {x_dt, w_dt, out_dt, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, r_cstride, batched != 0,
+                        has_residual != 0, has_scale != 0, has_bias != 0, act, aligned != 0, false};
+    unsigned m = 1u << NPS_CONV_AUTO | 1u << NPS_CONV_T128 | 1u << NPS_CONV_T64 | 1u << NPS_CONV_DMA64 | 1u << NPS_CONV_DMA32;
+    const bool bf16 = x_dt == NPS_DT_BF16;      // (7 - 15 are the bf16 entry points; bfrag's fp8-operand form is nopesac_conv2d_nhwc_fp8)
+    if (bf16 && !conv_bfrag_refusal(c)) m |= 1u << NPS_CONV_CFG_BFRAG3 | 1u << NPS_CONV_CFG_BFRAG32;
+    if (bf16 && !conv_halo_refusal(c)) m |= 1u << NPS_CONV_CFG_HALO16 | 1u << NPS_CONV_CFG_HALO8;
+    if (!conv_p8_refusal(c)) m |= 1u << NPS_CONV_CFG_P8;
+    if (!conv_p8_sk_refusal(c) && conv_p8_sk_offered(c)) m |= 1u << NPS_CONV_CFG_P8_SK;
+    if (!conv_p8n_refusal(c)) m |= 1u << NPS_CONV_CFG_P8N | (conv_p8n_tap_offered(c) ? 1u << NPS_CONV_CFG_P8N_TAP : 0u);
+    const int s = conv_p8n_split_slices(c);
+    if (!conv_p8n_split_refusal(c, s) && conv_p8n_split_offered(c, s)) m |= 1u << NPS_CONV_CFG_P8N_SPLIT;
+    if (splits) *splits = s;
+    return (int)m;
 }

@@ -37,6 +37,7 @@
 // ds_read (the lagging wave group reads one interval later and its reads retire after the following barrier); a staged piece
 // is read >= 1 phase after the wait that retires it (both groups have then passed their own vmcnt and a common barrier).
 #include "conv_common.h"
+#include "conv_forms.h"
 
 namespace nps {
 
@@ -54,7 +55,6 @@ constexpr int P8_FLAG_OFF = P8_TAB_OFF + P8_BM * 8;                // stream-K: 
 constexpr int P8_LDS = P8_FLAG_OFF + 16;                           // 131 KB (ONE __shared__ object: a second one makes hipcc drain vmcnt before every ds_read)
 // ---- stream-K (conv_igemm_p8_kernel<.., SK = true>): the workspace = [P8_SK_MAX_TILES arrival counters][slabs]; a slab = one partial
 //      256 x 256 f32 accumulator tile in REGISTER order: 16-byte element (b * 4 + q) * 512 + tid, b = accumulator block i * 2 + j
-constexpr int P8_SK_MAX_TILES = 4096;
 constexpr int P8_SK_HDR = P8_SK_MAX_TILES * 4;
 constexpr int P8_SK_SLAB = P8_BM * P8_BN * 4;                      // 256 KB
 
@@ -941,45 +941,28 @@ static int p8_launch(const void* x, const void* w, const float* scale, const flo
     using namespace nps;
     const bool sk = ws != nullptr;
     NPS_CHECK_ARG(x && w && y, "conv2d_p8: null pointer");
-    NPS_CHECK_ARG(B > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && KH * KW <= 32, "conv2d_p8: bad dims");
-    NPS_CHECK_ARG(Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 256 == 0, "conv2d_p8: needs Cin %% 64 == 0 and Cout %% 256 == 0");
-    NPS_CHECK_ARG(out_dt == NPS_DT_F32 || out_dt == NPS_DT_BF16 || out_dt == NPS_DT_FP8, "conv2d_p8: bad out_dt %d", out_dt);
+    const ConvCall c = {NPS_DT_BF16, NPS_DT_BF16, out_dt, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, r_cstride, false,
+                        residual != nullptr, scale != nullptr, bias != nullptr, act, conv_aligned({x, w, y, residual, scale, bias}), true};
+    NPS_CHECK_CONV("conv2d_p8", conv_call_refusal(c));
+    NPS_CHECK_CONV("conv2d_p8", sk ? conv_p8_sk_refusal(c) : conv_p8_refusal(c));
     const int kmajor = (variant >> 5) & 1;      // + 32: channel-major K order
     const int generic_epi = (variant >> 6) & 1; // + 64: force the generic (run-time decided) epilogue build
     const int grid_cap = variant >> 8;          // tuning aid: (cap << 8) limits the number of persistent workgroups
     variant &= 0x9f;
     NPS_CHECK_ARG(variant == 0 || (variant == 24 && !sk), "conv2d_p8: variant must be 0 (+32: channel-major K order); 24 = cycle-stamp build");
-    NPS_CHECK_ARG(x_cstride >= Cin && x_cstride % 8 == 0 && y_cstride >= Cout && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0),
-                  "conv2d_p8: strides / alignment");
-    NPS_CHECK_ARG(!residual || (r_cstride >= Cout && out_dt != NPS_DT_FP8), "conv2d_p8: residual stride / residual with fp8 output");
     const int res_after = (act & NPS_ACT_RES_AFTER) ? 1 : 0;
-    NPS_CHECK_ARG((act & ~(0xff | NPS_ACT_RES_AFTER)) == 0, "conv2d_p8: unsupported act flags");
     act &= 0xff;
-    NPS_CHECK_ARG(act >= 0 && act <= 3, "conv2d_p8: bad act %d", act);
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
     p.OH = (H + 2 * pad - KH) / stride + 1;
     p.OW = (W + 2 * pad - KW) / stride + 1;
-    NPS_CHECK_ARG(p.OH > 0 && p.OW > 0, "conv2d_p8: empty output");
     p.x_cs = x_cstride; p.y_cs = y_cstride; p.r_cs = r_cstride; p.w_bs = 0;
     p.rows_per_b = p.OH * p.OW;
     p.M = B * p.rows_per_b; p.N = Cout; p.K = KH * KW * Cin;
     p.act = act; p.out_dt = out_dt; p.res_after = res_after; p.force = kmajor;
-    NPS_CHECK_ARG((long long)B * H * W * x_cstride * 2 + ((long long)pad * W + pad) * x_cstride * 2 < (1ll << 31), "conv2d_p8: input larger than 2 GB");
-    NPS_CHECK_ARG((long long)p.N * p.K * 2 < (1ll << 31), "conv2d_p8: weights larger than 2 GB");
-    NPS_CHECK_ARG(p.M < (1 << 23) && (long long)B * H * W < (1 << 24) && x_cstride < (1 << 24) && p.K < (1 << 24) && Cout < (1 << 24),
-                  "conv2d_p8: pixel count / strides beyond the 24-bit index math of this kernel");
-    {
-        const int al = out_dt == NPS_DT_F32 ? 4 : 8;
-        bool ok = (y_cstride % al == 0) && ((uintptr_t)y % 16 == 0);
-        if (residual) ok = ok && (r_cstride % al == 0) && ((uintptr_t)residual % 16 == 0);
-        if (scale) ok = ok && ((uintptr_t)scale % 16 == 0);
-        if (bias) ok = ok && ((uintptr_t)bias % 16 == 0);
-        p.epi_vec = ok ? 1 : 0;
-        NPS_CHECK_ARG(ok, "conv2d_p8: y / residual / scale / bias must be 16-byte aligned with 8-channel-aligned strides");
-    }
+    p.epi_vec = 1;                                 // (conv_p8_refusal: every buffer and stride 16-byte aligned)
     p.tiles_m = (p.M + P8_BM - 1) / P8_BM;
     p.tiles_n = p.N / P8_BN;
     const int ntiles = p.tiles_m * p.tiles_n;
@@ -989,7 +972,6 @@ static int p8_launch(const void* x, const void* w, const float* scale, const flo
         // stream-K: every XCD's run of tiles must hold at least one K-tile unit per workgroup of that XCD (smallest run x K-tiles >= the
         // largest per-XCD workgroup count), else fewer workgroups
         const int nkt = p.K / P8_BK;
-        NPS_CHECK_ARG(ntiles <= P8_SK_MAX_TILES, "conv2d_p8_sk: more than %d tiles (use the plain kernel: nothing to balance)", P8_SK_MAX_TILES);
         NPS_CHECK_ARG((uintptr_t)ws % 16 == 0, "conv2d_p8_sk: workspace alignment");
         while (nwg > 1) {
             const int nx = nwg < 8 ? nwg : 8;

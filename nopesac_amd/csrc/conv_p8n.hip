@@ -28,6 +28,7 @@
 // Epilogue forms: no residual, bf16 output, ReLU / none / LeakyReLU (every Cout = 128 layer on the path is one of these); anything else is
 // rejected by the entry point and stays on the other conv kernels.
 #include "conv_common.h"
+#include "conv_forms.h"
 
 namespace nps {
 
@@ -446,39 +447,31 @@ static int p8n_launch(const void* x, const void* w, const float* scale, const fl
                       int variant, int splits, void* workspace, int64_t workspace_bytes, void* stream) {
     using namespace nps;
     NPS_CHECK_ARG(x && w && y, "conv2d_p8n: null pointer");
-    NPS_CHECK_ARG(B > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && KH * KW <= 32, "conv2d_p8n: bad dims");
-    NPS_CHECK_ARG(Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 128 == 0, "conv2d_p8n: needs Cin %% 64 == 0 and Cout %% 128 == 0");
-    NPS_CHECK_ARG(act == NPS_ACT_NONE || act == NPS_ACT_RELU || act == NPS_ACT_LEAKY, "conv2d_p8n: act must be none / ReLU / LeakyReLU (no residual forms)");
+    const ConvCall c = {NPS_DT_BF16, NPS_DT_BF16, NPS_DT_BF16, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, 0, false, false,
+                        scale != nullptr, bias != nullptr, act, conv_aligned({x, w, y, scale, bias}), true};
+    NPS_CHECK_CONV("conv2d_p8n", conv_call_refusal(c));
+    NPS_CHECK_CONV("conv2d_p8n", splits > 1 ? conv_p8n_split_refusal(c, splits) : conv_p8n_refusal(c));
     const int kmajor = (variant >> 5) & 1;
     const int grid_cap = variant >> 8;
     NPS_CHECK_ARG((variant & 0xdf) == 0, "conv2d_p8n: variant must be 0 (+ 32: channel-major K order, + (n << 8): grid cap)");
-    NPS_CHECK_ARG(x_cstride >= Cin && x_cstride % 8 == 0 && y_cstride >= Cout && y_cstride % 8 == 0 && ((uintptr_t)x % 16 == 0) &&
-                      ((uintptr_t)w % 16 == 0) && ((uintptr_t)y % 16 == 0) && (!scale || (uintptr_t)scale % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0),
-                  "conv2d_p8n: strides / alignment");
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.w = w; p.scale = scale; p.bias = bias; p.res = nullptr; p.y = y;
     p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
     p.OH = (H + 2 * pad - KH) / stride + 1;
     p.OW = (W + 2 * pad - KW) / stride + 1;
-    NPS_CHECK_ARG(p.OH > 0 && p.OW > 0, "conv2d_p8n: empty output");
     p.x_cs = x_cstride; p.y_cs = y_cstride;
     p.rows_per_b = p.OH * p.OW;
     p.M = B * p.rows_per_b; p.N = Cout; p.K = KH * KW * Cin;
     p.act = act; p.out_dt = NPS_DT_BF16; p.force = kmajor;
-    NPS_CHECK_ARG((long long)B * H * W * x_cstride * 2 + ((long long)pad * W + pad) * x_cstride * 2 < (1ll << 31), "conv2d_p8n: input larger than 2 GB");
-    NPS_CHECK_ARG((long long)p.N * p.K * 2 < (1ll << 31), "conv2d_p8n: weights larger than 2 GB");
-    NPS_CHECK_ARG(((long long)p.M + 256) * y_cstride * 2 < (1ll << 31), "conv2d_p8n: output larger than 2 GB");
-    NPS_CHECK_ARG(p.M < (1 << 23) && (long long)B * H * W < (1 << 24) && x_cstride < (1 << 24) && p.K < (1 << 24) && Cout < (1 << 24),
-                  "conv2d_p8n: pixel count / strides beyond the 24-bit index math of this kernel");
     p.tiles_m = (p.M + N8_BM - 1) / N8_BM;
     p.tiles_n = p.N / N8_BN;
     const hipStream_t st = (hipStream_t)stream;
     if (splits > 1) {
         const long long need = (long long)splits * p.M * p.N * 4;
-        NPS_CHECK_ARG(kmajor && splits <= Cin / 64 && splits <= 16, "conv2d_p8n_splitk: channel-major K order, 2 <= splits <= min(Cin / 64, 16)");
-        NPS_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= need && need < (1ll << 31),
-                      "conv2d_p8n_splitk: workspace of splits * M * N * 4 bytes (< 2 GB), 16-byte aligned");
+        NPS_CHECK_ARG(kmajor, "conv2d_p8n_splitk: variant must carry + 32 (channel-major K order)");
+        NPS_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= need,
+                      "conv2d_p8n_splitk: workspace of splits * M * N * 4 bytes, 16-byte aligned");
         p.ksplit = splits; p.sk_ws = workspace; p.sk_ws_bytes = (int)need;
         const int units = p.tiles_m * p.tiles_n * splits;
         int nwg = nps_p8_num_cus();

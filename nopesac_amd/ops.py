@@ -9,6 +9,7 @@ from collections import namedtuple
 from typing import Optional
 
 import ctypes
+import functools
 import os
 
 import torch
@@ -94,9 +95,10 @@ class ConvTuner:
                 launch(c)                                 # warm (first-touch, icache)
                 ok.append(c)
             except _lib.HipKernelError:
-                # the C side rejects this shape for this configuration (an eligibility test above that does not mirror every
-                # check of the entry point, or a stale routing entry): the candidate is dropped, tuning goes on.  Configuration 0
-                # (the library's own heuristic) must work - its failure is the caller's error
+                # the entry point refuses the call: a configuration from a stale routing file, or one of the few conditions the
+                # entry points add to the eligibility mask (csrc/conv_forms.h: the bfrag / halo pointers' own alignment, bfrag's
+                # fp8-output form).  The candidate is dropped, tuning goes on.  Configuration 0 (the library's own heuristic) must
+                # work - its failure is the caller's error
                 if c == 0:
                     raise
         cands = tuple(ok)
@@ -196,43 +198,20 @@ def _frag_weights(w: torch.Tensor) -> torch.Tensor:
 ConvEligibility = namedtuple("ConvEligibility", "bfrag_ok halo_ok p8_ok p8_sk_ok p8n_ok p8n_splits p8n_split_ok")
 
 
+@functools.lru_cache(maxsize=None)
 def conv_eligibility(x_dtype, w_dtype, out_dtype, B, H, W, Cin, Cout, KH, KW, stride, pad, has_residual, x_cs, y_cs, r_cs, batched,
                      has_scale, has_bias, act, aligned) -> ConvEligibility:
-    """Which tuner-only kernel configurations conv2d may offer for one call (no GPU, no library): the Python mirror of the C entry
-    points' argument checks.  `act` is conv2d's act word (ACT_RES_AFTER / ACT_BIAS_BATCHED included); `aligned`: every buffer the
-    call touches (x, w, out, residual, scale, bias) is 16-byte aligned."""
-    OH = (H + 2 * pad - KH) // stride + 1
-    OW = (W + 2 * pad - KW) // stride + 1
-    # "A through LDS, B from L2" kernel (fragment-major weights, cached per weight tensor): only the autotuner selects it
-    bfrag_ok = (x_dtype == torch.bfloat16 and w_dtype == torch.bfloat16 and not batched and Cin % 64 == 0 and Cout % 128 == 0
-                and x_cs % 8 == 0 and KH * KW <= 32 and (act & ~(0xff | ACT_RES_AFTER)) == 0
-                and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31)
-
-    halo_ok = (bfrag_ok and KH == 3 and KW == 3 and stride == 1 and pad == 1 and not has_residual and x_cs == Cin and y_cs == Cout
-               and out_dtype == torch.bfloat16 and has_scale and has_bias and (act & ~0xff) == 0)
-
-    p8_ok = (x_dtype == torch.bfloat16 and w_dtype == torch.bfloat16 and not batched and Cin % 64 == 0 and Cout % 256 == 0
-             and x_cs % 8 == 0 and KH * KW <= 32 and (act & ~(0xff | ACT_RES_AFTER)) == 0
-             and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31 and B * H * W < 2 ** 23 and x_cs < 2 ** 24 and KH * KW * Cin < 2 ** 24
-             and Cout * KH * KW * Cin * 2 < 2 ** 31 and out_dtype in _DT and x_cs % 8 == 0
-             and (y_cs % (4 if out_dtype == torch.float32 else 8) == 0)
-             and (not has_residual or (r_cs % (4 if out_dtype == torch.float32 else 8) == 0 and out_dtype != torch.float8_e4m3fn))
-             and bool(aligned))
-
-    # stream-K only where whole rounds leave CUs idle: a few tiles per CU and a K loop long enough to cut
-    p8_sk_ok = p8_ok and (-(-(B * OH * OW) // 256)) * (Cout // 256) <= 1024 and KH * KW * Cin >= 512
-
-    p8n_ok = (x_dtype == torch.bfloat16 and w_dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and not batched and not has_residual
-              and Cin % 64 == 0 and Cout % 128 == 0 and x_cs % 8 == 0 and y_cs % 8 == 0 and KH * KW <= 32 and act in (ACT_NONE, ACT_RELU, ACT_LEAKY)
-              and (B * H * W + pad * W + pad) * x_cs * 2 < 2 ** 31 and B * H * W < 2 ** 23 and x_cs < 2 ** 24 and KH * KW * Cin < 2 ** 24
-              and Cout * KH * KW * Cin * 2 < 2 ** 31 and (B * OH * OW + 256) * y_cs * 2 < 2 ** 31
-              and bool(aligned))
-
-    # split-K on the p8n structure: fewer tiles than half the CUs and a K loop of >= 64 K-tiles; slices = CUs // tiles (at most 8)
-    p8n_tiles = (-(-(B * OH * OW) // 256)) * (Cout // 128) if Cout % 128 == 0 else 0
-    p8n_splits = min(8, Cin // 64, 256 // p8n_tiles) if p8n_tiles else 0
-    p8n_split_ok = p8n_ok and KH * KW * Cin >= 4096 and p8n_splits >= 2 and p8n_splits * B * OH * OW * Cout * 4 < 2 ** 31
-    return ConvEligibility(bfrag_ok, halo_ok, p8_ok, p8_sk_ok, p8n_ok, p8n_splits, p8n_split_ok)
+    """Which tuner-only kernel configurations conv2d may offer for one call (no GPU; the library decides: nopesac_conv2d_nhwc_forms,
+    whose predicates are also the entry points' argument checks).  `act` is conv2d's act word (ACT_RES_AFTER / ACT_BIAS_BATCHED
+    included); `aligned`: every buffer the call touches (x, w, out, residual, scale, bias) is 16-byte aligned.  Memoised: conv2d asks
+    on every launch."""
+    splits = ctypes.c_int(0)
+    m = _L().nopesac_conv2d_nhwc_forms(_DT.get(x_dtype, -1), _DT.get(w_dtype, -1), _DT.get(out_dtype, -1), B, H, W, Cin, Cout, KH, KW, stride,
+                                       pad, x_cs, y_cs, r_cs, bool(batched), bool(has_residual), bool(has_scale), bool(has_bias), act,
+                                       bool(aligned), ctypes.byref(splits))
+    _lib.check(min(m, 0), "nopesac_conv2d_nhwc_forms")
+    return ConvEligibility(*(bool(m >> c & 1) for c in (CFG_BFRAG3, CFG_HALO16, CFG_P8, CFG_P8_SK, CFG_P8N)), splits.value,
+                           bool(m >> CFG_P8N_SPLIT & 1))
 
 
 def conv_tuner_extras(el: ConvEligibility, KH: int, KW: int) -> tuple:

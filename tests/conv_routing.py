@@ -71,7 +71,7 @@ def key_seed(key_str):
 
 
 def eligibility(case, aligned=True):
-    """ops.conv_eligibility of the key's call (a contiguous residual)."""
+    """ops.conv_eligibility of the key's call (a contiguous residual).  Needs no GPU; it asks the built library."""
     from nopesac_amd import ops
     return ops.conv_eligibility(case.x_dtype, case.w_dtype, case.out_dtype, case.B, case.H, case.W, case.Cin, case.Cout, case.KH, case.KW,
                                 case.stride, case.pad, case.residual, case.x_cs, case.y_cs, case.Cout if case.residual else 0, case.batched,

@@ -112,25 +112,86 @@ def test_conv2d_hands_the_tuner_the_routing_key_and_candidates(key, monkeypatch)
     assert extra == _legacy_eligibility(*_args(c))[1]
 
 
+def _random_calls():
+    """3000 argument tuples: random shapes, dtypes, strides, epilogue words and alignment around the kernels' limits.  The lists hold
+    B * H * W on both sides of 2 ** 23 and of 2 ** 24 (B 2 / 3 x H 480 x W 19200, B 64 x H 240 x W 640), M over 2 ** 23, and few
+    256 x 128 tiles under a long K (B 1 - 4, H 1 / 15, W 20 / 80, Cin 2048: 256 // tiles over the cap of 8); repeated values weight the
+    sample towards calls some kernel is eligible for."""
+    rnd = random.Random(5)
+    bf16 = (torch.bfloat16, torch.bfloat16)
+    dts = [bf16, (torch.float32, torch.bfloat16), (torch.float32, torch.float32), bf16, bf16]
+    outs = [torch.bfloat16, torch.float32, torch.float8_e4m3fn, torch.bfloat16]
+    acts = [0, 1, 2, 3, 0x101, 0x102, 0x200, 0x201, 0, 1]
+    for _ in range(3000):
+        xd, wd = rnd.choice(dts)
+        Cin, Cout = rnd.choice([3, 64, 128, 320, 2048, 256, 2048]), rnd.choice([4, 128, 256, 300, 512, 128])
+        k = rnd.choice([1, 3, 7, 3])
+        yield (xd, wd, rnd.choice(outs), rnd.choice([1, 2, 3, 4, 64, 700, 2]), rnd.choice([1, 15, 60, 240, 480, 15]),
+               rnd.choice([20, 80, 640, 19200, 20]), Cin, Cout, k, k, rnd.choice([1, 2, 1]), rnd.choice([0, k // 2]), rnd.random() < 0.3,
+               Cin + rnd.choice([0, 0, 4, 8, 0, 0]), Cout + rnd.choice([0, 0, 4, 8, 0, 0]), rnd.choice([Cout, Cout + 4]), rnd.random() < 0.1,
+               rnd.random() < 0.7, rnd.random() < 0.7, rnd.choice(acts), rnd.random() < 0.9)
+
+
 def test_conv_eligibility_matches_the_inline_block_off_the_routed_shapes():
     """Random shapes, dtypes, strides, epilogue words and alignment around the kernels' limits."""
     from nopesac_amd import ops
-    rnd = random.Random(5)
-    dts = [(torch.bfloat16, torch.bfloat16), (torch.float32, torch.bfloat16), (torch.float32, torch.float32)]
-    outs = [torch.bfloat16, torch.float32, torch.float8_e4m3fn]
-    acts = [0, 1, 2, 3, 0x101, 0x102, 0x200, 0x201]
-    for _ in range(3000):
-        xd, wd = rnd.choice(dts)
-        Cin, Cout = rnd.choice([3, 64, 128, 320, 2048]), rnd.choice([4, 128, 256, 300, 512])
-        k = rnd.choice([1, 3, 7])
-        args = (xd, wd, rnd.choice(outs), rnd.choice([1, 4, 64, 700]), rnd.choice([1, 15, 60, 480]), rnd.choice([20, 80, 640, 19200]),
-                Cin, Cout, k, k, rnd.choice([1, 2]), rnd.choice([0, k // 2]), rnd.random() < 0.3, Cin + rnd.choice([0, 0, 4, 8]),
-                Cout + rnd.choice([0, 0, 4, 8]), rnd.choice([Cout, Cout + 4]), rnd.random() < 0.1, rnd.random() < 0.7, rnd.random() < 0.7,
-                rnd.choice(acts), rnd.random() < 0.9)
+    for args in _random_calls():
         legacy, extra = _legacy_eligibility(*args)
         el = ops.conv_eligibility(*args)
         assert tuple(el) == legacy, args
         assert ops.conv_tuner_extras(el, args[8], args[9]) == extra
+
+
+def test_the_random_sample_takes_every_flag_both_ways():
+    """The legacy function alone over the sample: every flag is True for some calls and False for others, the slice count runs from
+    below 2 up to the cap of 8, and each limit the C entry points and the old Python mirror stated differently is hit from both sides
+    (a flag that is constant over the sample would test nothing)."""
+    from nopesac_amd import ops
+    flags = {n: [0, 0] for n in ops.ConvEligibility._fields if n != "p8n_splits"}
+    splits, mid, big_m, capped = set(), 0, 0, 0
+    for args in _random_calls():
+        el = ops.ConvEligibility(*_legacy_eligibility(*args)[0])
+        for n in flags:
+            flags[n][bool(getattr(el, n))] += 1
+        splits.add(el.p8n_splits)
+        B, H, W, Cin, Cout, k, _, stride, pad = args[3:12]
+        M = B * ((H + 2 * pad - k) // stride + 1) * ((W + 2 * pad - k) // stride + 1)
+        mid += 2 ** 23 <= B * H * W < 2 ** 24
+        big_m += M >= 2 ** 23
+        tiles = -(-M // 256) * (Cout // 128) if Cout % 128 == 0 else 0
+        capped += tiles > 0 and min(Cin // 64, 256 // tiles) > 8
+    print("random sample, legacy flags [False, True]: %s; B*H*W in [2**23, 2**24): %d, M >= 2**23: %d, slice count capped at 8: %d"
+          % (flags, mid, big_m, capped))
+    assert all(f and t for f, t in flags.values()), flags
+    assert {0, 1, 2, 8} <= splits and max(splits) == 8
+    assert mid and big_m and capped
+
+
+def test_config_ids_match_the_header_and_the_launchers_share_one_predicate():
+    """NPS_CONV_CFG_* of the header are ops.CFG_* and, with NPS_CONV_T128 .. DMA32, the keys of CONV_CFG_KERNEL; every launcher source
+    checks its arguments through csrc/conv_forms.h and holds no dims / 2 GB / 24-bit check of its own."""
+    import os
+    import re
+    from nopesac_amd import _lib, ops
+    text = open(_lib.HEADER_PATH).read()
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define NPS_CONV_CFG_(\w+) (\d+)", text)}
+    assert ids and ids == {n[4:]: v for n, v in vars(ops).items() if n.startswith("CFG_")}
+    base = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define NPS_CONV_(AUTO|T128|T64|DMA64|DMA32) (\d+)", text)}
+    assert sorted(base.values()) == list(ops.ConvTuner.CANDIDATES)
+    assert set(ids.values()) | set(base.values()) - {0} == set(ops.CONV_CFG_KERNEL)
+    csrc = os.path.join(os.path.dirname(_lib.HEADER_PATH), "..", "nopesac_amd", "csrc")
+    forms = open(os.path.join(csrc, "conv_forms.h")).read()
+    for name, calls in (("conv_igemm.hip", ["conv_bfrag_refusal(c)"]), ("conv_p8.hip", ["conv_p8_refusal(c)", "conv_p8_sk_refusal(c)"]),
+                        ("conv_p8n.hip", ["conv_p8n_refusal(c)", "conv_p8n_split_refusal(c, splits)"]),
+                        ("conv3x3_halo.hip", ["conv_halo_refusal(c)"])):
+        src = open(os.path.join(csrc, name)).read()
+        launcher = src[src.index("static int bfrag_launch("):] if name == "conv_igemm.hip" else src      # (nopesac_conv2d_nhwc_ex: not routed by a mask)
+        assert '#include "conv_forms.h"' in src and "conv_call_refusal(c)" in launcher, name
+        for call in calls:
+            assert call in launcher and "inline const char* %s(" % call.split("(")[0] in forms, (name, call)
+        checks = " ".join(re.findall(r"NPS_CHECK_ARG\(.*?\);", launcher, flags=re.S))          # the argument checks the launcher keeps
+        for own in ("B > 0", "KH * KW <= 32", "Cin % 64", "Cout % 128", "Cout % 256", "1 << 23", "1 << 24", "2 GB", "x_cstride >= Cin"):
+            assert own not in checks, (name, own)
 
 
 @pytest.mark.parametrize("key, want, extra", [

@@ -107,6 +107,48 @@ def test_every_candidate_at_the_routed_shape_matches_f64(key, device, monkeypatc
     torch.cuda.empty_cache()
 
 
+# one routed key per kernel whose eligibility bit is clear for a reason its entry point can see (Cout = 64 / Cout = 128: no 128- / 256-wide
+# column tile); the 64 -> 64 key is the only routed bf16 key outside bfrag's, halo's and p8n's bits
+_K64 = "bfloat16|bfloat16|bfloat16|64|120|160|64|64|1|1|1|0|False|64|64|False|True|True|1|False|False|False"
+_K128 = "bfloat16|bfloat16|bfloat16|64|60|80|128|128|3|3|1|1|False|128|128|False|True|True|1|True|True|False"
+REFUSED = {"bfrag": (_K64, "bfrag_ok"), "halo": (_K64, "halo_ok"), "p8": (_K128, "p8_ok"), "p8n": (_K64, "p8n_ok"),
+           "p8n_splitk": (_K64, "p8n_split_ok")}
+
+
+@pytest.mark.parametrize("kernel", sorted(REFUSED))
+def test_entry_point_refuses_a_routed_call_outside_its_bit(kernel, device):
+    """The entry point, called directly on the key's real tensors, turns the call down with the argument error (HipKernelError from
+    _lib.check) before any launch: the output buffer keeps its NaN fill."""
+    from nopesac_amd import _lib, ops
+    key, flag = REFUSED[kernel]
+    assert key in KEYS
+    c = CR.parse_key(key)
+    call = CR.build_call(c, device, CR.key_seed(key))
+    assert not getattr(call.el, flag)
+    out, wide = call.new_out()
+    L, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    x, w, sc, bi, y = (t.data_ptr() for t in (call.x, call.w, call.scale, call.bias, out))
+    dims = (c.B, c.H, c.W, c.Cin, c.Cout, c.KH, c.KW, c.stride, c.pad)
+    if kernel == "bfrag":
+        rc = L.nopesac_conv2d_nhwc_bfrag(x, w, sc, bi, None, y, *dims, c.x_cs, c.y_cs, 0, c.act, ops.BF16, 3, st)
+    elif kernel == "halo":
+        rc = L.nopesac_conv3x3_halo_bf16(x, w, sc, bi, y, c.B, c.H, c.W, c.Cin, c.Cout, c.act, 0, st)
+    elif kernel == "p8":
+        rc = L.nopesac_conv2d_nhwc_p8(x, w, sc, bi, None, y, *dims, c.x_cs, c.y_cs, 0, c.act, ops.BF16, 32, st)
+    elif kernel == "p8n":
+        rc = L.nopesac_conv2d_nhwc_p8n(x, w, sc, bi, y, *dims, c.x_cs, c.y_cs, c.act, 32, st)
+    else:
+        ws = torch.empty(2 * call.M * c.Cout, device=device, dtype=torch.float32)
+        rc = L.nopesac_conv2d_nhwc_p8n_splitk(x, w, sc, bi, y, *dims, c.x_cs, c.y_cs, c.act, 32, 2, ws.data_ptr(), ws.numel() * 4, st)
+    with pytest.raises(_lib.HipKernelError, match="needs Cin % 64 == 0 and Cout %"):
+        _lib.check(rc, "nopesac_conv2d_nhwc_" + kernel)
+    assert rc == -1
+    torch.cuda.synchronize()
+    assert bool(wide.isnan().all())
+    del call, out, wide
+    torch.cuda.empty_cache()
+
+
 # the benchmark's three legs (bench.py): headline mp3d K = 32, and the `other_configs` legs with the routing file each one loads
 LEGS = {"headline_mp3d_k32": ("mp3d", 32, "routing_r5.json"), "scannet_k64": ("scannet", 64, "routing_r5_scannet_k64.json"),
         "bf16_k128": ("mp3d", 128, "routing_r5_fp8_k128.json")}
