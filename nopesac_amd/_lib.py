@@ -1,4 +1,5 @@
-"""ctypes binding of libnopesac_hip.so (the C ABI declared in include/nopesac_hip.h).
+"""ctypes binding of libnopesac_hip.so, read from the header that declares its C ABI (include/nopesac_hip.h): prototypes, constants
+and structs are stated there once, and every kernel file is compiled against the same text.
 
 There is NO fallback: if the shared library is missing or a symbol cannot be resolved, importing
 the ops raises.  Build it with `python -m nopesac_amd.build` (or `__graft_entry__.build()`).
@@ -8,152 +9,128 @@ from __future__ import annotations
 import ctypes
 import os
 import re
+from collections import namedtuple
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from types import SimpleNamespace
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libnopesac_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "nopesac_hip.h")
 
-P, I, L, F = c_void_p, c_int, c_int64, c_float
 
-# name -> argtypes (return type is int unless listed in _RESTYPE)
-SIGNATURES = {
-    "nopesac_version": [],
-    "nopesac_last_error": [],
-    "nopesac_conv2d_nhwc": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, L, L, I, I, I, P],
-    "nopesac_conv2d_nhwc_bfrag": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, L, I, I, I, P],
-    "nopesac_conv2d_nhwc_p8": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, L, I, I, I, P],
-    "nopesac_conv2d_nhwc_p8_sk": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, L, I, I, I, P, L, P],
-    "nopesac_conv2d_p8_sk_workspace_bytes": [],
-    "nopesac_conv2d_nhwc_p8n": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, I, I, P],
-    "nopesac_conv2d_nhwc_p8n_splitk": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, I, I, I, P, L, P],
-    "nopesac_conv2d_nhwc_forms": [I] * 12 + [L, L, L] + [I] * 6 + [P],
-    "nopesac_conv2d_nhwc_ex": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, L, L, I, I, I, I, P],
-    "nopesac_stem_fused_bf16": [P, P, P, P, P, I, I, I, P],
-    "nopesac_stem_fused_raw_bf16": [P, P, P, P, P, P, P, I, I, I, P],
-    "nopesac_stem_fused_raw_shifted_bf16": [P, P, P, P, P, P, I, I, I, P],
-    "nopesac_bottleneck_tail_bf16": [P] * 9 + [I] * 9 + [P] * 4 + [I, P, P],
-    "nopesac_bottleneck_tail_bf16_ex": [P] * 9 + [I] * 9 + [P] * 4 + [I, P, I, P],
-    "nopesac_bottleneck_tail_bf16_form": [P] * 9 + [I] * 9 + [P] * 4 + [I, P, I, I, P],
-    "nopesac_bottleneck_tail_forms": [I, I, I, I, L, I, I, I, P],
-    "nopesac_conv2d_nhwc_fp8": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, L, L, L, I, I, I, P],
-    "nopesac_gnn_layer_bf16": [P, I, P, I, P, I, I, I, P, P] + [P] * 10 + [P],
-    "nopesac_gnn_layer_bf16_pf": [P, I, P, I, P, I, I, I, P, P] + [P] * 10 + [P, I, P],
-    "nopesac_encoder_tail_bf16": [P] * 13 + [I] + [P] * 3 + [I, P],
-    "nopesac_resize_bilinear_u8": [P, I, I, I, P, I, I, P],
-    "nopesac_resize_bilinear_u8_batch": [P, I, L, I, I, I, P, I, I, I, P],
-    "nopesac_mask_head_bf16": [P] * 9 + [I] * 5 + [P],
-    "nopesac_mask_operands": [P, I, P, P, I, I, I, P],
-    "nopesac_decoder_tail_bf16": [P] * 13 + [I] + [P] * 4 + [I, P],
-    "nopesac_transformer_tail_bf16": [P] * 13 + [I] + [P] * 4 + [I, I, P, P, P, I, P, P, P, I, I, P],
-    "nopesac_transformer_tail_bf16_pf": [P] * 13 + [I] + [P] * 4 + [I, I, P, P, P, I, P, P, P, I, I, P, P, I, I, P],
-    "nopesac_transformer_tail_bf16_form": [P] * 13 + [I] + [P] * 4 + [I, I, P, P, P, I, P, P, P, I, I, P, P, I, I, I, P],
-    "nopesac_transformer_tail_forms": [L, I, I, L, I, P],
-    "nopesac_conv3x3_c64_bf16": [P, P, P, P, P, I, I, I, I, P],
-    "nopesac_conv3x3_halo_bf16": [P, P, P, P, P, I, I, I, I, I, I, I, P],
-    "nopesac_rle_labels": [P, P, P, P, P, I, I, I, I, P],
-    "nopesac_rle_transitions": [P, P, P, P, P, I, I, I, P],
-    "nopesac_rle_compress_host": [P, I, I, I, P, I, P],
-    "nopesac_rle_compress_device": [P, P, P, I, I, I, P, P, P, P, P],
-    "nopesac_rle_compress_device_capped": [P, P, P, I, I, I, P, P, P, L, P],
-    "nopesac_decode_masks": [P, P, P, P, P, P, I, I, I, I, P],
-    "nopesac_rle_compress_batch_host": [P, P, P, I, I, I, P, L, P, P],
-    "nopesac_preprocess_nchw_to_nhwc": [P, P, P, P, I, I, I, I, I, I, P],
-    "nopesac_maxpool_nhwc": [P, P, I, I, I, I, I, I, I, I, P],
-    "nopesac_upsample2x_bilinear_nhwc": [P, P, P, I, I, I, I, I, I, P],
-    "nopesac_upsample2x_nearest_add_nhwc": [P, P, P, I, I, I, I, I, P],
-    "nopesac_groupnorm_nhwc": [P, P, P, P, I, I, I, I, F, I, I, P, P],
-    "nopesac_layernorm": [P, P, P, P, P, P, I, P, I, I, F, P],
-    "nopesac_layernorm_ex": [P, P, P, P, P, P, I, P, P, P, I, I, F, P],
-    "nopesac_add_rows": [P, P, P, I, I, I, P],
-    "nopesac_softmax_rows": [P, P, I, I, P],
-    "nopesac_softmax_rows_pad": [P, P, I, I, I, I, P],
-    "nopesac_add_rows_bf16": [P, P, P, P, I, I, I, P],
-    "nopesac_concat_cols": [P, I, P, I, P, I, P],
-    "nopesac_metric_rows": [P, P, P, P, P, P, P, P, I, P, I, P],
-    "nopesac_attention_small": [P, L, P, L, P, L, P, L, I, I, I, I, F, P, P, P],
-    "nopesac_attention_small_bf16": [P, L, P, L, P, L, P, L, I, I, I, I, F, P, P, P],
-    "nopesac_attention_small_bf16io": [P, L, P, L, P, L, P, L, I, I, I, I, F, P, P, P],
-    "nopesac_transpose_hw_rows": [P, P, I, I, I, I, P],
-    "nopesac_postselect_planes": [P, P, P, P, I, I, I, I, I, I, I, F, F, F, P, P, P, P, P, P, P, P, P, P, P],
-    "nopesac_postselect_planes_ex": [P, P, P, P, I, I, I, I, I, I, I, F, F, F, P, P, P, P, P, P, P, P, P, P, I, P],
-    "nopesac_matcher_sinkhorn": [P, P, P, P, P, P, P, F, F, I, F, I, I, P, P, P],
-    "nopesac_geo_sequence": [P, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P],
-    "nopesac_ransac_score_maps": [P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P],
-    "nopesac_ransac_soft_vote": [P] * 21 + [I, I, I] + [P] * 6 + [P],
-    "nopesac_plane_cam_ref_losses": [P] * 11 + [I, I, F, P, P],
-    "nopesac_camera_pose_loss": [P, P, P, I, P, I, I, F, F, P, P],
-    "nopesac_refilter_assignment": [P, P, P, P, P, P, P, I, I, P, P],
-    "nopesac_tape_create": [P, ctypes.POINTER(c_void_p), P],
-    "nopesac_tape_create_ex": [P, I, ctypes.POINTER(c_void_p), P],
-    "nopesac_tape_replay": [P, P],
-    "nopesac_tape_replay_on": [P, P, P, I],
-    "nopesac_posenet_branch_tail_bf16": [P, P, P, P, P, P, P, I, I, I, I, P],
-    "nopesac_tape_destroy": [P],
-    "nopesac_lds_canary": [I, I, L, I, P, P, I, P],
-    "nopesac_force_k_select": [P, I, P, P, P, I, I, I, I, P, P, P],
-    "nopesac_normalize_rows": [P, P, I, I, I, P],
-    "nopesac_count_nonfinite": [P, L, P, P],
-    "nopesac_count_nonfinite_batch": [P, P, I, P, P],
-    "nopesac_clock_probe": [P, L, P],
-    "nopesac_u8_to_f32": [P, P, L, P],
-    "nopesac_gather_bytes": [P, P, P, P, I, P, P],
-    "nopesac_jpeg_huffman": [P, P, P, P, P, I, P, L, P, P, P],
-    "nopesac_jpeg_huffman_parallel": [P, P, P, I, P, L, P, L, P, P, P, P, P, P, P, P],
-    "nopesac_jpeg_prepare_scan": [P, L, I, P, L, P, P, P, L, P],
-    "nopesac_jpeg_batch_scan_host": [P, I, I, I, P, P],
-    "nopesac_jpeg_batch_fill_host": [P, P, P, P, P, P, P, P, P],
-    "nopesac_jpeg_batch_free_host": [P],
-    "nopesac_jpeg_idct": [P, P, P, I, I, P, P, P],
-    "nopesac_jpeg_color": [P, P, I, I, P, P, I, P],
-    "nopesac_png_info_host": [P, L, P, P, P, P],
-    "nopesac_png_decode_host": [P, L, P, L, I],
-    "nopesac_png_decode_files_host": [P, I, P, L, I, I, I, I, P],
-    "nopesac_inflate_zlib_host": [P, L, P, L],
-    "nopesac_refine_losses_backward": [P] * 11 + [I, I, F] + [P] * 7 + [P],
-    "nopesac_refine_vote_backward": [P] * 15 + [I, I] + [P] * 20 + [P],
-    "nopesac_refine_score_maps_backward": [P] * 6 + [I, I] + [P] * 7 + [P],
-    "nopesac_transpose_f32": [P, I, I, L, P, P],
-    "nopesac_col_sum_f32": [P, I, I, L, P, P],
-    "nopesac_relu_backward_f32": [P, P, L, P, P],
-    "nopesac_normalize_rows_backward": [P, P, I, I, I, P, P],
-    "nopesac_camera_pose_loss_backward": [P, P, P, I, P, I, I, F, F, P, P, P, P, P, P],
-    "nopesac_sumsq_accumulate_f32": [P, L, P, P],
-    "nopesac_clip_coefficient": [P, F, P, P],
-    "nopesac_scale_by_f32": [P, L, P, P],
-    "nopesac_adamw_step": [P, P, P, P, L, F, F, F, F, F, I, P],
-    "nopesac_sgd_step": [P, P, P, L, F, F, F, I, P],
-    "nopesac_conv2d_dgrad_f32": [P, P, P, P, L, I, I, I, I, I, I, I, I, I, L, L, P],
-    "nopesac_conv2d_wgrad_workspace_bytes": [I, I, I, I, I],
-    "nopesac_conv2d_wgrad_f32": [P, P, P, P, L, I, I, I, I, I, I, I, I, I, L, L, I, P],
-    "nopesac_bn_act_forward_f32": [P, P, P, P, P, F, I, L, I, P, P],
-    "nopesac_bn_act_backward_workspace_floats": [I, I],
-    "nopesac_bn_act_backward_f32": [P, P, P, P, P, P, F, I, I, I, P, P, P, P, L, P],
-    "nopesac_groupnorm_backward_f32": [P, P, P, P, I, I, I, I, F, I, P, P, P, P, L, P],
-    "nopesac_maxpool2x2_backward_f32": [P, P, P, I, I, I, I, P],
-    "nopesac_upsample2x_nearest_add_backward_f32": [P, P, I, I, I, I, P],
-    "nopesac_corr_softmax_backward_f32": [P, P, I, I, I, L, L, P, P, P],
-    "nopesac_transpose_batched_f32": [P, I, I, I, P, P],
-    "nopesac_mlp_padded_k": [I, I],
-    "nopesac_mlp_packed_elems": [I, I],
-    "nopesac_mlp_chain_bf16": [P, P],
-}
-_RESTYPE = {"nopesac_jpeg_prepare_scan": c_int64, "nopesac_last_error": c_char_p, "nopesac_rle_compress_batch_host": c_int64, "nopesac_mlp_packed_elems": c_int64,
-            "nopesac_conv2d_p8_sk_workspace_bytes": c_int64, "nopesac_conv2d_wgrad_workspace_bytes": c_int64,
-            "nopesac_bn_act_backward_workspace_floats": c_int64, "nopesac_inflate_zlib_host": c_int64, "nopesac_jpeg_batch_scan_host": c_void_p, "nopesac_jpeg_batch_free_host": None}
-
-MLP_MAX_IN, MLP_MAX_WIDTH, MLP_MAX_LAYERS = 1280, 1024, 12       # NOPESAC_MLP_* of the header
+class HeaderError(RuntimeError):
+    """include/nopesac_hip.h holds something the reader below does not know.  The reader never guesses a type."""
 
 
-class MlpLayer(ctypes.Structure):           # nopesac_mlp_layer
-    _fields_ = [("w", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("out_ld", c_int64), ("K", c_int), ("N", c_int), ("act", c_int),
-                ("reserved", c_int)]
+Header = namedtuple("Header", "signatures restypes constants structs")
+_SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "float": c_float}
+_RETURNS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "const char*": c_char_p, "void*": c_void_p, "void": None}
 
 
-class MlpChain(ctypes.Structure):           # nopesac_mlp_chain
-    _fields_ = [("x", c_void_p), ("x_ld", c_int64), ("xb", c_void_p), ("xb_ld", c_int64), ("x_width", c_int), ("xb_width", c_int),
-                ("xb_rows_per", c_int), ("rows", c_int), ("n_layers", c_int), ("reserved", c_int), ("layers", MlpLayer * MLP_MAX_LAYERS)]
+def _norm(ctype: str) -> str:
+    return re.sub(r"\s*\*\s*", "*", " ".join(ctype.split()))
 
+
+def _declarator(text: str, where: str):
+    """'const float* bias' -> ('const float*', 'bias'): one declarator, its name last."""
+    m = re.fullmatch(r"(.*[\s*])(\w+)", text.strip(), re.S)
+    if not m:
+        raise HeaderError(f"{where}: cannot split {text.strip()!r} into a type and a name")
+    return _norm(m[1]), m[2]
+
+
+def _ctype(ctype: str, where: str):
+    """ctypes class of a parameter or field of type `ctype`.  Every pointer travels as c_void_p (the wrappers pass tensor.data_ptr()),
+    except the tape handle's out-parameter."""
+    if ctype in _SCALARS:
+        return _SCALARS[ctype]
+    if ctype == "void**":
+        return ctypes.POINTER(c_void_p)
+    if ctype.endswith("*"):
+        return c_void_p
+    raise HeaderError(f"{where}: unknown type {ctype!r}")
+
+
+def _constant(name: str, value: str, known: dict) -> int:
+    """An integer #define: a literal, a parenthesised negative, or a sum of products of literals and constants defined above it."""
+    value = value.strip()
+    terms = value[1:-1] if value.startswith("(") and value.endswith(")") else value
+    total = 0
+    for term in terms.split("+"):
+        product = 1
+        for factor in (f.strip() for f in term.split("*")):
+            if factor in known:
+                product *= known[factor]
+            elif re.fullmatch(r"-?(0[xX][0-9a-fA-F]+|[1-9][0-9]*|0)", factor):
+                product *= int(factor, 0)
+            else:
+                raise HeaderError(f"{name}: cannot evaluate {value!r}")
+        total += product
+    return total
+
+
+def _struct(name: str, body: str, constants: dict, structs: dict):
+    """ctypes.Structure of a `typedef struct` body: `type a, b, c;` field lists and arrays sized by a constant."""
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        first, *more = decl.split(",")
+        array = re.fullmatch(r"(.*)\[\s*(\w+)\s*\]", first, re.S)
+        ctype, field = _declarator(array[1] if array else first, name)
+        cls = structs[ctype] if ctype in structs else _ctype(ctype, f"{name}.{field}")
+        if array:
+            if array[2] not in constants:
+                raise HeaderError(f"{name}.{field}: unknown array size {array[2]!r}")
+            cls = cls * constants[array[2]]
+        if more and (array or "*" in ctype or not all(re.fullmatch(r"\w+", n.strip()) for n in more)):
+            raise HeaderError(f"{name}: cannot read the field list {decl!r}")
+        fields += [(f, cls) for f in [field] + [n.strip() for n in more]]
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
+def read_header(text: str) -> Header:
+    """The C ABI as the text of include/nopesac_hip.h states it: argtypes and restype of every `ret nopesac_*(args);` prototype, the
+    integer NPS_* / NOPESAC_* constants, the `typedef struct`s as ctypes.Structure classes.  Not a C parser: it reads the narrow
+    grammar this header keeps, and raises HeaderError, naming the symbol, on anything else."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants, structs, signatures, restypes = {}, {}, {}, {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+((?:NPS|NOPESAC)_\w+)[ \t]+(\S.*)$", text, flags=re.M):   # (a guard has no value)
+        constants[name] = _constant(name, value, constants)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    block = re.search(r'extern\s+"C"\s*\{(.*)\}', text, flags=re.S)
+    text = block[1] if block else text
+
+    def take_struct(m):
+        if m[1] != m[3] or m[1] in structs:
+            raise HeaderError(f"{m[3]}: struct tag and typedef name differ, or defined twice")
+        structs[m[1]] = _struct(m[1], m[2], constants, structs)
+        return ""
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", take_struct, text, flags=re.S)
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = re.fullmatch(r"(.+?)\b(nopesac_\w+)\s*\((.*)\)", stmt, re.S)
+        if not m:
+            raise HeaderError(f"cannot read the declaration {' '.join(stmt.split())[:80]!r}")
+        ret, name, params = _norm(m[1]), m[2], m[3].strip()
+        if ret not in _RETURNS or name in signatures:
+            raise HeaderError(f"{name}: unknown return type {ret!r}, or declared twice")
+        restypes[name] = _RETURNS[ret]
+        signatures[name] = [] if params == "void" else [_ctype(_declarator(p, name)[0], name) for p in params.split(",")]
+    return Header(signatures, restypes, constants, structs)
+
+
+def load_header(path: str = HEADER_PATH) -> Header:
+    try:
+        with open(path) as f:
+            return read_header(f.read())
+    except OSError as e:
+        raise RuntimeError(f"{path} not readable ({e.strerror}): nopesac_amd binds libnopesac_hip.so from its header") from e
+
+
+# Read at import: the wrappers bind their constants (nopesac_amd.ops, nopesac_amd.jpeg) when they are imported, before any load().
+_HEADER = load_header()
+SIGNATURES, RESTYPES = _HEADER.signatures, _HEADER.restypes     # name -> argtypes, name -> restype
+H = SimpleNamespace(**_HEADER.constants)                        # H.NPS_ACT_RELU, H.NOPESAC_JPEG_IMG_I32, ...
+MlpLayer, MlpChain = _HEADER.structs["nopesac_mlp_layer"], _HEADER.structs["nopesac_mlp_chain"]
+MLP_MAX_IN, MLP_MAX_WIDTH, MLP_MAX_LAYERS = H.NOPESAC_MLP_MAX_IN, H.NOPESAC_MLP_MAX_WIDTH, H.NOPESAC_MLP_MAX_LAYERS
 
 _lib = None
 
@@ -183,7 +160,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.argtypes = argtypes
-        fn.restype = _RESTYPE.get(name, c_int)
+        fn.restype = RESTYPES[name]
     _lib = lib
     return lib
 

@@ -31,10 +31,11 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
 
 # layout constants shared with csrc/jpeg.hip (include/nopesac_hip.h NOPESAC_JPEG_*)
 LOOK_BITS = 9
-HUFF_BYTES = 1536                 # one Huffman table: look u16[512] | maxcode i32[18] | valoffset i32[18] | huffval u8[256] | pad
-TABLES_BYTES = 4 * HUFF_BYTES + 3 * 128          # DC0, DC1, AC0, AC1, then three quantisation tables u16[64] (natural order)
-IMG_I32, IMG_I64, SEG_I32, SEG_I64 = 32, 8, 4, 2
-SUB_WORDS, SYNC_PASSES = 64, 12                # NOPESAC_JPEG_SUB_WORDS / NOPESAC_JPEG_SYNC_PASSES
+_H = _lib.H                       # the layout constants below are include/nopesac_hip.h's NOPESAC_JPEG_*
+HUFF_BYTES = _H.NOPESAC_JPEG_HUFF_BYTES          # one Huffman table: look u16[512] | maxcode i32[18] | valoffset i32[18] | huffval u8[256] | pad
+TABLES_BYTES = _H.NOPESAC_JPEG_TABLES_BYTES      # DC0, DC1, AC0, AC1, then three quantisation tables u16[64] (natural order)
+IMG_I32, IMG_I64, SEG_I32, SEG_I64 = _H.NOPESAC_JPEG_IMG_I32, _H.NOPESAC_JPEG_IMG_I64, _H.NOPESAC_JPEG_SEG_I32, _H.NOPESAC_JPEG_SEG_I64
+SUB_WORDS, SYNC_PASSES = _H.NOPESAC_JPEG_SUB_WORDS, _H.NOPESAC_JPEG_SYNC_PASSES
 PARALLEL_MIN_BYTES = 4 * SUB_WORDS * 4         # shorter restart-free streams stay on the one-wave-per-interval kernel
 
 

@@ -16,11 +16,11 @@ import torch
 
 from . import _lib
 
-F32, BF16 = 0, 1
-ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
-ACT_RES_AFTER = 0x100      # OR-able: residual is added after the activation
-ACT_BIAS_BATCHED = 0x200   # OR-able (set by conv2d): with batched weights, bias is [B, Cout]
-FP8 = 3                    # NPS_DT_FP8: OCP e4m3fn bytes
+_H = _lib.H                                     # the constants of include/nopesac_hip.h (H is a height below)
+F32, BF16, FP8 = _H.NPS_DT_F32, _H.NPS_DT_BF16, _H.NPS_DT_FP8         # FP8: OCP e4m3fn bytes
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = _H.NPS_ACT_NONE, _H.NPS_ACT_RELU, _H.NPS_ACT_LEAKY, _H.NPS_ACT_SIGMOID
+ACT_RES_AFTER = _H.NPS_ACT_RES_AFTER         # OR-able: residual is added after the activation
+ACT_BIAS_BATCHED = _H.NPS_ACT_BIAS_BATCHED   # OR-able (set by conv2d): with batched weights, bias is [B, Cout]
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float8_e4m3fn: FP8}
 
 
@@ -144,12 +144,12 @@ class ConvTuner:
 
 
 TUNER = ConvTuner()
-CFG_BFRAG3, CFG_BFRAG32 = 7, 8         # tuner-only configurations: nopesac_conv2d_nhwc_bfrag, K-tile 64 / 32
-CFG_HALO16, CFG_HALO8 = 9, 10          # tuner-only: nopesac_conv3x3_halo_bf16, 16x16 / 16x8 pixel tiles
-CFG_P8 = 11                            # tuner-only: nopesac_conv2d_nhwc_p8 (256x256x64 tiles, phase-interleaved 8-wave schedule)
-CFG_P8N, CFG_P8N_TAP = 13, 14          # tuner-only: nopesac_conv2d_nhwc_p8n (256x128 tiles: the Cout % 128 == 0 layers, round 5), channel- / tap-major K order
-CFG_P8N_SPLIT = 15                     # tuner-only: nopesac_conv2d_nhwc_p8n_splitk (few tiles x long K: the pose net's first conv; round 6)
-CFG_P8_SK = 12                         # tuner-only: nopesac_conv2d_nhwc_p8_sk (the same kernel with stream-K work distribution, round 5)
+CFG_BFRAG3, CFG_BFRAG32 = _H.NPS_CONV_CFG_BFRAG3, _H.NPS_CONV_CFG_BFRAG32       # tuner-only configurations: nopesac_conv2d_nhwc_bfrag, K-tile 64 / 32
+CFG_HALO16, CFG_HALO8 = _H.NPS_CONV_CFG_HALO16, _H.NPS_CONV_CFG_HALO8          # tuner-only: nopesac_conv3x3_halo_bf16, 16x16 / 16x8 pixel tiles
+CFG_P8 = _H.NPS_CONV_CFG_P8             # tuner-only: nopesac_conv2d_nhwc_p8 (256x256x64 tiles, phase-interleaved 8-wave schedule)
+CFG_P8N, CFG_P8N_TAP = _H.NPS_CONV_CFG_P8N, _H.NPS_CONV_CFG_P8N_TAP            # tuner-only: nopesac_conv2d_nhwc_p8n (256x128 tiles: the Cout % 128 == 0 layers, round 5), channel- / tap-major K order
+CFG_P8N_SPLIT = _H.NPS_CONV_CFG_P8N_SPLIT                                    # tuner-only: nopesac_conv2d_nhwc_p8n_splitk (few tiles x long K: the pose net's first conv; round 6)
+CFG_P8_SK = _H.NPS_CONV_CFG_P8_SK       # tuner-only: nopesac_conv2d_nhwc_p8_sk (the same kernel with stream-K work distribution, round 5)
 # NOPESAC_P8_CAP_1X1=n (experiment, round 5): persistent workgroups of the p8 kernel on 1x1 layers (the HBM-bound ones) capped at n
 P8_CAP_1X1 = [int(os.environ.get("NOPESAC_P8_CAP_1X1", "0"))]
 P8_VARIANT = [32]                      # variant handed to nopesac_conv2d_nhwc_p8: 32 = channel-major K order (better L2 reuse of the taps)
@@ -521,11 +521,18 @@ def conv2d_fp8(x: torch.Tensor, w8frag: torch.Tensor, scale: torch.Tensor, bias:
     return out
 
 
+def _forms_by_id(ids: dict, count: int) -> tuple:
+    """Form names in the order of their header ids, which must be exactly 0 .. count - 1 (count: the header's NPS_*_FORMS)."""
+    _require(sorted(ids.values()) == list(range(count)), f"form ids {ids} are not 0 .. {count - 1}")
+    return tuple(sorted(ids, key=ids.get))
+
+
 # the kernel forms of the fused bottleneck tail, indexed by form id (NPS_TAIL_* of include/nopesac_hip.h)
-TAIL_FORMS = ("pw", "rt4", "rt4_late", "rt4_proj", "rt4h", "rt8", "stream", "wide")
+TAIL_FORMS = _forms_by_id({"pw": _H.NPS_TAIL_PW, "rt4": _H.NPS_TAIL_RT4, "rt4_late": _H.NPS_TAIL_RT4_LATE, "rt4_proj": _H.NPS_TAIL_RT4_PROJ,
+                           "rt4h": _H.NPS_TAIL_RT4H, "rt8": _H.NPS_TAIL_RT8, "stream": _H.NPS_TAIL_STREAM, "wide": _H.NPS_TAIL_WIDE},
+                          _H.NPS_TAIL_FORMS)
 # A/B switch bits of the default selection (NPS_TAIL_SW_*), by the environment variable that sets each
-TAIL_SWITCHES = {"NOPESAC_TAIL_NO_RT4": 1, "NOPESAC_TAIL_NO_RT8": 2, "NOPESAC_TAIL_RT4_LATE": 4, "NOPESAC_TAIL_NO_RT4H": 8,
-                 "NOPESAC_TAIL_RT8_WIDE": 16, "NOPESAC_TAIL_NO_STREAM": 32}
+TAIL_SWITCHES = {"NOPESAC_TAIL_" + sw: getattr(_H, "NPS_TAIL_SW_" + sw) for sw in ("NO_RT4", "NO_RT8", "RT4_LATE", "NO_RT4H", "RT8_WIDE", "NO_STREAM")}
 
 
 def bottleneck_tail_forms(C, C4, CN, C2, M, stride=1, same_res=False, switches=0):
@@ -757,8 +764,8 @@ def count_nonfinite(tensors, counter: Optional[torch.Tensor] = None) -> torch.Te
     if counter is None:
         counter = torch.zeros(1, device=tensors[0].device, dtype=torch.int32)
     tensors = [t for t in tensors if t.numel()]
-    for i in range(0, len(tensors), 16):                      # NOPESAC_NONFINITE_MAX_TENSORS per launch
-        grp = tensors[i:i + 16]
+    for i in range(0, len(tensors), _H.NOPESAC_NONFINITE_MAX_TENSORS):
+        grp = tensors[i:i + _H.NOPESAC_NONFINITE_MAX_TENSORS]
         for t in grp:
             _chk(t, torch.float32)
         ptrs = (ctypes.c_void_p * len(grp))(*[_p(t) for t in grp])
@@ -776,7 +783,7 @@ class HostFetch:
     private_views = True (a fetch recorded in a graph: the buffer is written again by every replay): views() snapshots the buffer.
     dynamic = {name: int64[1] device tensor}: only that many leading BYTES of the named tensor are valid (known on the device only); the
     rest of its host view is undefined.  Such a tensor does not count towards the 16 MB bound of the kernel path."""
-    KERNEL_MAX_BYTES, KERNEL_MAX_SEGMENTS, ALIGN = 16 << 20, 32, 16
+    KERNEL_MAX_BYTES, KERNEL_MAX_SEGMENTS, ALIGN = 16 << 20, _H.NOPESAC_GATHER_MAX_SEGMENTS, 16
     _zero_pad = {}
 
     def __init__(self, tensors: dict, private_views: bool = False, dynamic: Optional[dict] = None, host: Optional[torch.Tensor] = None):
@@ -804,7 +811,7 @@ class HostFetch:
             if host is not None:
                 _require(host.dtype == torch.uint8 and host.is_pinned() and host.numel() >= off, "HostFetch: host buffer too small / not pinned")
             self.host = host[:off] if host is not None else torch.empty(off, dtype=torch.uint8, pin_memory=True)
-            for i in range(0, len(segs), self.KERNEL_MAX_SEGMENTS):             # NOPESAC_GATHER_MAX_SEGMENTS per launch
+            for i in range(0, len(segs), self.KERNEL_MAX_SEGMENTS):
                 grp = segs[i:i + self.KERNEL_MAX_SEGMENTS]
                 n = len(grp)
                 for _, _, _, dyn in grp:
@@ -1244,9 +1251,10 @@ def decoder_tail(attn: torch.Tensor, tgt: torch.Tensor, W: dict, pos=None, want=
 
 TAIL_PREFETCH = os.environ.get("NOPESAC_TAIL_PREFETCH", "1") != "0"
 # the kernel forms of the transformer tail, indexed by form id (NPS_ETAIL_* of include/nopesac_hip.h): tokens per workgroup
-TRANSFORMER_TAIL_FORMS = ("t32", "t64", "t96", "t128")
+TRANSFORMER_TAIL_FORMS = _forms_by_id({"t32": _H.NPS_ETAIL_32, "t64": _H.NPS_ETAIL_64, "t96": _H.NPS_ETAIL_96, "t128": _H.NPS_ETAIL_128}, _H.NPS_ETAIL_FORMS)
 # A/B switch bits of the default selection (NPS_ETAIL_SW_*); NOPESAC_ENC_TAIL_ROWS sets ROWS, and ROWS3 as well when it is 3
-TRANSFORMER_TAIL_SWITCHES = {"NOPESAC_ENC_TAIL_32": 1, "NOPESAC_ENC_TAIL_64": 2, "NOPESAC_ENC_TAIL_ROWS": 4, "NOPESAC_ENC_TAIL_ROWS=3": 8}
+TRANSFORMER_TAIL_SWITCHES = {"NOPESAC_ENC_TAIL_32": _H.NPS_ETAIL_SW_32, "NOPESAC_ENC_TAIL_64": _H.NPS_ETAIL_SW_64,
+                             "NOPESAC_ENC_TAIL_ROWS": _H.NPS_ETAIL_SW_ROWS, "NOPESAC_ENC_TAIL_ROWS=3": _H.NPS_ETAIL_SW_ROWS3}
 
 
 def transformer_tail_forms(M, pre_norm, skip_ffn=False, n_proj_total=0, switches=0):

@@ -10,11 +10,123 @@ from tests.util import ROOT
 def test_library_exports_every_declared_symbol():
     from nopesac_amd import _lib
     lib = _lib.load()
-    declared = _lib.declared_symbols()
+    declared = _lib.declared_symbols()                     # a regex over names; SIGNATURES: the header reader's prototypes
     assert len(declared) >= 20 and set(declared) == set(_lib.SIGNATURES)
+    assert len(declared) >= 119 and set(_lib.RESTYPES) == set(_lib.SIGNATURES)
     for name in declared:
         assert hasattr(lib, name), name
+        assert getattr(lib, name).argtypes == _lib.SIGNATURES[name] and getattr(lib, name).restype is _lib.RESTYPES[name], name
     assert lib.nopesac_version() >= 100
+
+
+def test_header_reader_binds_the_types_the_header_states():
+    """The binding read from include/nopesac_hip.h against rows written here by hand from the header's text, one entry point per rule
+    of the reader: int / int64_t / float scalars, plain and const-qualified pointers, pointers to pointers, the tape handle's void**
+    out-parameter, a struct pointer, (void), and every return type.  The two structs: sizes and offsets as the C
+    compiler lays the header's field lists out (8-byte pointers and int64_t, 4-byte int, no padding needed)."""
+    import ctypes
+    from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_void_p
+    from nopesac_amd import _lib
+    p, i, l, f = c_void_p, c_int, c_int64, c_float
+    want = {
+        "nopesac_conv2d_nhwc": (i, [p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, l, l, l, l, i, i, i, p]),
+        "nopesac_conv2d_nhwc_forms": (i, [i, i, i, i, i, i, i, i, i, i, i, i, l, l, l, i, i, i, i, i, i, p]),
+        "nopesac_tape_create_ex": (i, [p, i, POINTER(c_void_p), p]),
+        "nopesac_last_error": (c_char_p, []),
+        "nopesac_jpeg_prepare_scan": (l, [p, l, i, p, l, p, p, p, l, p]),
+        "nopesac_jpeg_batch_scan_host": (p, [p, i, i, i, p, p]),
+        "nopesac_jpeg_batch_free_host": (None, [p]),
+        "nopesac_adamw_step": (i, [p, p, p, p, l, f, f, f, f, f, i, p]),
+        "nopesac_mlp_chain_bf16": (i, [p, p]),
+    }
+    for name, (restype, argtypes) in want.items():
+        assert _lib.SIGNATURES[name] == argtypes, name
+        assert _lib.RESTYPES[name] is restype, name
+    layer = [("w", p, 0), ("bias", p, 8), ("out", p, 16), ("out_ld", l, 24), ("K", i, 32), ("N", i, 36), ("act", i, 40), ("reserved", i, 44)]
+    chain = [("x", p, 0), ("x_ld", l, 8), ("xb", p, 16), ("xb_ld", l, 24), ("x_width", i, 32), ("xb_width", i, 36), ("xb_rows_per", i, 40),
+             ("rows", i, 44), ("n_layers", i, 48), ("reserved", i, 52), ("layers", _lib.MlpLayer * 12, 56)]
+    assert issubclass(_lib.MlpLayer, ctypes.Structure) and issubclass(_lib.MlpChain, ctypes.Structure)
+    assert ctypes.sizeof(_lib.MlpLayer) == 48 and ctypes.sizeof(_lib.MlpChain) == 56 + 12 * 48
+    for cls, fields in ((_lib.MlpLayer, layer), (_lib.MlpChain, chain)):
+        assert [(n, t, getattr(cls, n).offset) for n, t in cls._fields_] == fields, cls
+    assert (_lib.MLP_MAX_IN, _lib.MLP_MAX_WIDTH, _lib.MLP_MAX_LAYERS) == (1280, 1024, 12)
+    assert _lib.H.NPS_E_ARG == -1 and _lib.H.NPS_ACT_RES_AFTER == 256 and _lib.H.NOPESAC_JPEG_TABLES_BYTES == 4 * 1536 + 3 * 128
+    assert not hasattr(_lib.H, "NOPESAC_HIP_H")                       # the include guard is no constant
+    with pytest.raises(RuntimeError, match="/nonexistent/nopesac_hip.h"):
+        _lib.load_header("/nonexistent/nopesac_hip.h")
+
+
+def test_header_reader_follows_the_text_and_refuses_what_it_does_not_know():
+    """Planted faults: a changed or a dropped parameter must change the row the reader returns (it reads the text, no table stands behind
+    it); an unknown type in a prototype or a struct, an unnamed parameter, an unknown return type, a statement that is no prototype and
+    a #define it cannot evaluate must raise and name the symbol - never bind as int."""
+    from ctypes import c_int, c_int64
+    from nopesac_amd import _lib
+    text = open(_lib.HEADER_PATH).read()
+    good = _lib.read_header(text)
+    assert good.signatures == _lib.SIGNATURES and good.constants == vars(_lib.H)
+
+    def planted(old, new):
+        assert text.count(old) == 1, old
+        return text.replace(old, new)
+    row = good.signatures["nopesac_count_nonfinite"]
+    assert row[1] is c_int64
+    narrowed = _lib.read_header(planted("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x, int n,"))
+    assert narrowed.signatures["nopesac_count_nonfinite"] == [row[0], c_int, row[2], row[3]]
+    dropped = _lib.read_header(planted("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x,"))
+    assert dropped.signatures["nopesac_count_nonfinite"] == [row[0], row[2], row[3]]
+    for other in (narrowed, dropped):
+        assert {k: v for k, v in other.signatures.items() if k != "nopesac_count_nonfinite"} == {
+            k: v for k, v in good.signatures.items() if k != "nopesac_count_nonfinite"}
+    for old, new, names in (
+            ("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x, size_t n,", "nopesac_count_nonfinite.*size_t"),
+            ("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x, int64_t,", "nopesac_count_nonfinite"),
+            ("int nopesac_tape_destroy(void* tape);", "unsigned nopesac_tape_destroy(void* tape);", "nopesac_tape_destroy.*unsigned"),
+            ("int nopesac_tape_destroy(void* tape);", "int nopesac_tape_destroy(void* tape);\nstatic int counter;", "static int counter"),
+            ("    int64_t out_ld;", "    size_t out_ld;", "nopesac_mlp_layer.out_ld.*size_t"),
+            ("#define NOPESAC_GATHER_MAX_SEGMENTS 32", "#define NOPESAC_GATHER_MAX_SEGMENTS (1 << 5)", "NOPESAC_GATHER_MAX_SEGMENTS")):
+        with pytest.raises(_lib.HeaderError, match=names):
+            _lib.read_header(planted(old, new))
+
+
+def test_python_constants_equal_the_header():
+    """Every Python name that mirrors a #define of include/nopesac_hip.h, against the header's value as a regex over the text finds it
+    here (not through the reader), and the form-name tuples against the header's form counts and ids."""
+    import re
+    from nopesac_amd import _lib, jpeg, ops
+    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+    h = {k: int(v, 0) for k, v in re.findall(r"#define (\w+) \(?(-?(?:0x[0-9a-fA-F]+|\d+))\)?\s*$", text, flags=re.M)}
+    h["NOPESAC_JPEG_TABLES_BYTES"] = 4 * h["NOPESAC_JPEG_HUFF_BYTES"] + 3 * 128          # the header's one arithmetic definition
+    assert h == vars(_lib.H) and len(h) >= 64
+    mirrors = {
+        "NPS_DT_F32": ops.F32, "NPS_DT_BF16": ops.BF16, "NPS_DT_FP8": ops.FP8,
+        "NPS_ACT_NONE": ops.ACT_NONE, "NPS_ACT_RELU": ops.ACT_RELU, "NPS_ACT_LEAKY": ops.ACT_LEAKY, "NPS_ACT_SIGMOID": ops.ACT_SIGMOID,
+        "NPS_ACT_RES_AFTER": ops.ACT_RES_AFTER, "NPS_ACT_BIAS_BATCHED": ops.ACT_BIAS_BATCHED,
+        "NPS_CONV_CFG_BFRAG3": ops.CFG_BFRAG3, "NPS_CONV_CFG_BFRAG32": ops.CFG_BFRAG32, "NPS_CONV_CFG_HALO16": ops.CFG_HALO16,
+        "NPS_CONV_CFG_HALO8": ops.CFG_HALO8, "NPS_CONV_CFG_P8": ops.CFG_P8, "NPS_CONV_CFG_P8_SK": ops.CFG_P8_SK, "NPS_CONV_CFG_P8N": ops.CFG_P8N,
+        "NPS_CONV_CFG_P8N_TAP": ops.CFG_P8N_TAP, "NPS_CONV_CFG_P8N_SPLIT": ops.CFG_P8N_SPLIT,
+        "NOPESAC_GATHER_MAX_SEGMENTS": ops.HostFetch.KERNEL_MAX_SEGMENTS,
+        "NOPESAC_MLP_MAX_IN": _lib.MLP_MAX_IN, "NOPESAC_MLP_MAX_WIDTH": _lib.MLP_MAX_WIDTH, "NOPESAC_MLP_MAX_LAYERS": _lib.MLP_MAX_LAYERS,
+        "NOPESAC_JPEG_HUFF_BYTES": jpeg.HUFF_BYTES, "NOPESAC_JPEG_TABLES_BYTES": jpeg.TABLES_BYTES, "NOPESAC_JPEG_IMG_I32": jpeg.IMG_I32,
+        "NOPESAC_JPEG_IMG_I64": jpeg.IMG_I64, "NOPESAC_JPEG_SEG_I32": jpeg.SEG_I32, "NOPESAC_JPEG_SEG_I64": jpeg.SEG_I64,
+        "NOPESAC_JPEG_SUB_WORDS": jpeg.SUB_WORDS, "NOPESAC_JPEG_SYNC_PASSES": jpeg.SYNC_PASSES,
+    }
+    for name, value in mirrors.items():
+        assert h[name] == value, name
+    assert len(ops.TAIL_FORMS) == h["NPS_TAIL_FORMS"] == 8 and len(ops.TRANSFORMER_TAIL_FORMS) == h["NPS_ETAIL_FORMS"] == 4
+    assert [h["NPS_TAIL_" + n.upper()] for n in ops.TAIL_FORMS] == list(range(8))
+    assert [h["NPS_ETAIL_" + n[1:]] for n in ops.TRANSFORMER_TAIL_FORMS] == list(range(4))
+    assert ops.TAIL_SWITCHES == {"NOPESAC_TAIL_" + k[len("NPS_TAIL_SW_"):]: v for k, v in h.items() if k.startswith("NPS_TAIL_SW_")}
+    assert len(ops.TAIL_SWITCHES) == 6
+    assert ops.TRANSFORMER_TAIL_SWITCHES == {"NOPESAC_ENC_TAIL_32": h["NPS_ETAIL_SW_32"], "NOPESAC_ENC_TAIL_64": h["NPS_ETAIL_SW_64"],
+                                             "NOPESAC_ENC_TAIL_ROWS": h["NPS_ETAIL_SW_ROWS"], "NOPESAC_ENC_TAIL_ROWS=3": h["NPS_ETAIL_SW_ROWS3"]}
+    # the values themselves, as every routing file and tuner log on disk holds them
+    assert (ops.F32, ops.BF16, ops.FP8, ops.ACT_RES_AFTER, ops.ACT_BIAS_BATCHED) == (0, 1, 3, 0x100, 0x200)
+    assert (ops.CFG_BFRAG3, ops.CFG_BFRAG32, ops.CFG_HALO16, ops.CFG_HALO8, ops.CFG_P8, ops.CFG_P8_SK, ops.CFG_P8N, ops.CFG_P8N_TAP,
+            ops.CFG_P8N_SPLIT) == (7, 8, 9, 10, 11, 12, 13, 14, 15)
+    assert ops.TAIL_FORMS == ("pw", "rt4", "rt4_late", "rt4_proj", "rt4h", "rt8", "stream", "wide")
+    assert ops.TRANSFORMER_TAIL_FORMS == ("t32", "t64", "t96", "t128")
+    assert h["NOPESAC_NONFINITE_MAX_TENSORS"] == 16
 
 
 def test_argument_errors_are_reported_without_a_gpu():
