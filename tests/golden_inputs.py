@@ -88,11 +88,12 @@ def _blob_field(h, w, g, cells=6):
     return F.interpolate(coarse, size=(h, w), mode="bilinear", align_corners=True)[0, 0]
 
 
-def postselect_case(kind: str, seed: int, nq: int = 50, h: int = 120, w: int = 160):
+def postselect_case(kind: str, seed: int, nq: int = 50, h: int = 120, w: int = 160, n_valid: int | None = None):
     """(pred_logits [nq,2], pred_params [nq,3], mask_logits [nq,h,w], query_feat [nq,256]).
     kinds: 'multi' (several disjoint planes), 'none_pass' (no query beats the score threshold ->
     arg-max fallback), 'all_overlap_rejected' (every candidate loses its area -> max-overlap
-    fallback), 'full' (every query is a plane)."""
+    fallback), 'full' (every query is a plane).  n_valid: the number of queries that get a mask region and (except 'none_pass') pass the
+    score test, instead of the kind's own count."""
     g = _g(seed)
     logits = torch.zeros(nq, 2)
     logits[:, 1] = 2.0 + torch.rand(nq, generator=g)           # non-plane by default
@@ -100,6 +101,8 @@ def postselect_case(kind: str, seed: int, nq: int = 50, h: int = 120, w: int = 1
     feat = torch.randn(nq, 256, generator=g)
     mask = -6.0 + 0.5 * torch.randn(nq, h, w, generator=g)
     n_on = {"multi": min(9, nq), "none_pass": 4, "all_overlap_rejected": 5, "full": nq}[kind]
+    if n_valid is not None:
+        n_on = n_valid
     on = torch.randperm(nq, generator=g)[:n_on].sort().values
     # label map: vertical/horizontal stripes of unequal width with wavy borders
     lab = torch.zeros(h, w, dtype=torch.long)
