@@ -889,6 +889,46 @@ int nopesac_corr_softmax_backward_f32(const float* a, const float* da, int B, in
                                       void* stream);
 int nopesac_transpose_batched_f32(const float* x, int B, int rows, int cols, float* y, void* stream);
 
+/* ---- backward kernels of the matching head (csrc/matcher_bwd.hip; nopesac_amd/training.py::MatchingHeadTrainer) ------------------------
+ * All f32, deterministic (no atomics), argument errors -> NPS_E_ARG + nopesac_last_error.
+ * nopesac_attention_small_backward: gradient of nopesac_attention_small (head dim 32, Lq, Lk <= 128) at q / k / v for the output gradient
+ *   d_out; every matrix is row-major with its own row stride (elements), so column slices of a [rows, 768] q|k|v buffer are taken as
+ *   they are.  The softmax is recomputed.  Rows >= qlen[b] get zero dq; keys >= klen[b] get zero dk / dv and take no part in the softmax.
+ * nopesac_layernorm_backward: y = LayerNorm(x) gamma + beta over D = 256 -> dx [rows, D], dgamma [D], dbeta [D]; ws holds per-block
+ *   partials of the two column reductions (nopesac_layernorm_backward_workspace_floats(rows) floats), reduced in a fixed order.
+ * nopesac_matcher_sinkhorn_train: the couplings and the iters log-Sinkhorn iterations of nopesac_matcher_sinkhorn without the
+ *   assignment; gt_corr uint8 [B, nq+1, nq+1] in the layout of log_scores (dustbin at index nq; entries outside a pair's live rows
+ *   (< n1, nq) x columns (< n2, nq) are ignored).  Outputs: log_scores; uv [B, iters, 2, nq+1] = every iteration's potentials (compact
+ *   indices, dustbin at n1 / n2) for the backward pass; pair_stats [B, 2] = (sum of -min(score, 0) over the pair's selected entries,
+ *   their count); loss [2] = (2 * sum / count over the WHOLE batch - 0 when nothing is selected -, count).  Pairs with n1 == 0 or
+ *   n2 == 0 select nothing and get log_scores = -1e30 everywhere.
+ * nopesac_matcher_emb_loss: pair_stats and loss as above from log scores that already exist (the output of nopesac_matcher_sinkhorn):
+ *   the training forward runs the inference kernel itself, so its scores are the inference head's bit for bit, and the potentials
+ *   are produced by nopesac_matcher_sinkhorn_train as a replay when the backward pass starts.
+ * nopesac_matcher_sinkhorn_train_backward: gradient of loss[0] (times g_loss[0], a device scalar) through the UNROLLED iterations ->
+ *   d_desc_dot [B, nq, nq] (zero outside the live block) and d_bin_pairs [B] (per-pair partials of d bin_score; sum them in order).
+ * nopesac_desc_dot_backward: dots = D0 D1^T / 16 per pair (D = 256) -> dD0 = G D1 / 16, dD1 = G^T D0 / 16 over the live block, zero rows
+ *   beyond n1 / n2. */
+int nopesac_attention_small_backward(const float* q, int64_t q_stride, const float* k, int64_t k_stride, const float* v, int64_t v_stride,
+                                     const float* d_out, int64_t do_stride, int B, int Lq, int Lk, int heads, float scale,
+                                     const int32_t* qlen, const int32_t* klen, float* dq, int64_t dq_stride, float* dk, int64_t dk_stride,
+                                     float* dv, int64_t dv_stride, void* stream);
+int64_t nopesac_layernorm_backward_workspace_floats(int rows);
+int nopesac_layernorm_backward(const float* x, const float* gamma, const float* dy, int rows, int D, float eps, float* dx, float* dgamma,
+                               float* dbeta, float* ws, int64_t ws_floats, void* stream);
+int nopesac_matcher_sinkhorn_train(const float* desc_dot, const float* planes1, const float* planes2, const float* cam7, const int32_t* n1,
+                                   const int32_t* n2, const float* bin_score, float offset_mult, float normal_mult, int iters,
+                                   const uint8_t* gt_corr, int B, int nq, float* log_scores, float* uv, float* pair_stats, float* loss,
+                                   void* stream);
+int nopesac_matcher_emb_loss(const float* log_scores, const uint8_t* gt_corr, const int32_t* n1, const int32_t* n2, int B, int nq,
+                             float* pair_stats, float* loss, void* stream);
+int nopesac_matcher_sinkhorn_train_backward(const float* desc_dot, const float* planes1, const float* planes2, const float* cam7,
+                                            const int32_t* n1, const int32_t* n2, const float* bin_score, float offset_mult,
+                                            float normal_mult, int iters, const uint8_t* gt_corr, const float* uv, const float* loss,
+                                            const float* g_loss, int B, int nq, float* d_desc_dot, float* d_bin_pairs, void* stream);
+int nopesac_desc_dot_backward(const float* d_desc_dot, const float* d0, const float* d1, const int32_t* n1, const int32_t* n2, int B, int nq,
+                              int D, float* dd0, float* dd1, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

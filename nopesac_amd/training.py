@@ -14,10 +14,17 @@ below, whose backward passes are the kernels of csrc/conv_bwd.hip (conv dgrad / 
 upsample-add, correlation softmax).  BatchNorm runs with its stored statistics and a trainable affine (detectron2's FrozenBatchNorm2d
 regime, as forward_train); batch statistics and running-stat updates are not implemented.
 
-What this is NOT: a trainer for the whole network.  The backbone, the plane head and the matcher have no backward kernels here - their
-outputs (the backbone maps, the plane sets and the assignment) are inputs of this stage, as they are of the reference function, and
-receive no gradient beyond `input_grads`.  Gated against torch.autograd on the oracle (tests/test_training_gpu.py,
-tests/test_pose_net_training_gpu.py)."""
+The matching head (matching_net/matching_head.py:43-139: planeApp_proj, the 18 GNN layers, planeDesc_proj, the Sinkhorn with its
+bin_score and the embedding loss) is trained by MatchingHeadTrainer: the forward is the unfused f32 route of modeling/matching_head.py
+(ops.linear, ops.attention with lengths, ops.layernorm with addend, ops.matcher_sinkhorn) from the trainer's own parameters, launch for
+launch - the same parameters give the inference head's log scores bit for bit; the backward is the kernels of csrc/matcher_bwd.hip
+(ragged attention, LayerNorm, the unrolled Sinkhorn + loss, the descriptor dot) plus the Linear dgrad / wgrad above.
+
+What this is NOT: a trainer for the whole network.  The backbone and the plane head have no backward kernels here - their outputs (the
+backbone maps, the plane sets and their appearance features) are inputs of these stages, as they are of the reference functions, and
+receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
+against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py,
+tests/test_matcher_training_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -33,9 +40,18 @@ BN_EPS, GN_EPS, GN_GROUPS = 1e-3, 1e-5, 32
 _BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked")
 
 
+MATCHER_PREFIX = "matching_head."
+GNN_LAYERS, GNN_HEADS, LN_EPS = 18, 8, 1e-5
+
+
 def is_norm_parameter(key: str) -> bool:
     """GroupNorm / BatchNorm affine tensors of the camera head (the modules the reference's build_optimizer gives WEIGHT_DECAY_NORM,
-    train_NopeSAC.py:94-128): pixel_decoder.*.norm.{weight,bias} and convs_*.i.1.{weight,bias}."""
+    train_NopeSAC.py:94-128): pixel_decoder.*.norm.{weight,bias} and convs_*.i.1.{weight,bias}; and the LayerNorm affine tensors of the
+    matching head's GNN (torch.nn.LayerNorm is one of the reference's norm_module_types, train_NopeSAC.py:106):
+    matching_head.gnn.layers.N.norm{1,2}.{weight,bias}."""
+    if key.startswith(MATCHER_PREFIX):
+        parts = key[len(MATCHER_PREFIX):].split(".")
+        return len(parts) == 5 and parts[:2] == ["gnn", "layers"] and parts[3] in ("norm1", "norm2") and parts[4] in ("weight", "bias")
     parts = key[len(PREFIX):].split(".") if key.startswith(PREFIX) else key.split(".")
     if parts[0] == "pixel_decoder":
         return len(parts) == 4 and parts[2] == "norm"
@@ -355,6 +371,195 @@ class _CorrSoftmax(torch.autograd.Function):
         a, x1, x2 = ctx.saved_tensors
         dx1, dx2 = ops.corr_softmax_backward(a, g.contiguous(), x1, x2)
         return dx1, dx2, None
+
+
+class _Attention(torch.autograd.Function):
+    """ops.attention (f32, head dim 32, ragged by qlen / klen) on row-major q / k / v that may be column slices of a wider matrix;
+    backward: nopesac_attention_small_backward (softmax recomputed)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, B: int, Lq: int, Lk: int, heads: int, scale: float, qlen, klen):
+        o = ops.attention(q, k, v, B, Lq, Lk, heads, scale, qlen, klen)
+        ctx.conf = (B, Lq, Lk, heads, float(scale))
+        ctx.save_for_backward(q, k, v, qlen, klen)
+        return o
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, qlen, klen = ctx.saved_tensors
+        B, Lq, Lk, heads, scale = ctx.conf
+        g = g.contiguous()
+        dq, dk, dv = (torch.empty(t.shape[0], heads * 32, device=q.device, dtype=torch.float32) for t in (q, k, v))
+        rc = _L().nopesac_attention_small_backward(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(g), g.stride(0), B, Lq, Lk,
+                                                   heads, scale, _p(qlen), _p(klen), _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv),
+                                                   dv.stride(0), _st())
+        _lib.check(rc, "nopesac_attention_small_backward")
+        return dq, dk, dv, None, None, None, None, None, None, None
+
+
+class _AttentionFused(torch.autograd.Function):
+    """The same attention on the projections as the inference head lays them out (MatchingHead._gnn_layer): a self layer passes
+    q = None and packed = q|k|v [rows, 768], a cross layer q [rows, 256] and packed = k|v [rows, 512].  The kernels take the column
+    slices as they are, and the backward writes dq / dk / dv straight into one gradient of the packed matrix."""
+
+    @staticmethod
+    def forward(ctx, q, packed, B: int, Lq: int, Lk: int, heads: int, scale: float, qlen, klen):
+        W = heads * 32
+        packed = packed.contiguous()
+        if q is None:
+            qv, kv, vv = packed[:, :W], packed[:, W:2 * W], packed[:, 2 * W:]
+        else:
+            q = q.contiguous()
+            qv, kv, vv = q, packed[:, :W], packed[:, W:]
+        o = ops.attention(qv, kv, vv, B, Lq, Lk, heads, scale, qlen, klen)
+        ctx.conf = (B, Lq, Lk, heads, float(scale), q is None)
+        ctx.save_for_backward(q, packed, qlen, klen)
+        return o
+
+    @staticmethod
+    def backward(ctx, g):
+        q, packed, qlen, klen = ctx.saved_tensors
+        B, Lq, Lk, heads, scale, self_layer = ctx.conf
+        W = heads * 32
+        g = g.contiguous()
+        dpacked = torch.empty_like(packed)
+        if self_layer:
+            dq = None
+            qv, kv, vv = packed[:, :W], packed[:, W:2 * W], packed[:, 2 * W:]
+            gq, gk, gv = dpacked[:, :W], dpacked[:, W:2 * W], dpacked[:, 2 * W:]
+        else:
+            dq = torch.empty_like(q)
+            qv, kv, vv = q, packed[:, :W], packed[:, W:]
+            gq, gk, gv = dq, dpacked[:, :W], dpacked[:, W:]
+        rc = _L().nopesac_attention_small_backward(_p(qv), qv.stride(0), _p(kv), kv.stride(0), _p(vv), vv.stride(0), _p(g), g.stride(0), B, Lq, Lk,
+                                                   heads, scale, _p(qlen), _p(klen), _p(gq), gq.stride(0), _p(gk), gk.stride(0), _p(gv),
+                                                   gv.stride(0), _st())
+        _lib.check(rc, "nopesac_attention_small_backward")
+        return dq, dpacked, None, None, None, None, None, None, None
+
+
+class _LinearSplit(torch.autograd.Function):
+    """y = relu([a | b] W^T) computed as the inference head computes mlp.0: a W[:, :Da]^T first, then b W[:, Da:]^T with the first
+    product as the residual in front of the ReLU (two GEMMs, no concatenated copy).  Backward: that of _Linear on [a | b]
+    (ops.concat_cols) - dgrad split into two column slices, wgrad in one GEMM."""
+
+    @staticmethod
+    def forward(ctx, a, b, w):
+        a, b = a.contiguous(), b.contiguous()
+        Da = a.shape[1]
+        h = ops.linear(a, w[:, :Da].contiguous())
+        y = ops.linear(b, w[:, Da:].contiguous(), residual=h, act=ops.ACT_RELU)
+        ctx.Da = Da
+        ctx.save_for_backward(a, b, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, w, y = ctx.saved_tensors
+        g = g.contiguous()
+        gm = torch.empty_like(g)
+        _lib.check(_L().nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(gm), _st()), "nopesac_relu_backward_f32")
+        ga = gb = gw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gx = ops.linear(gm, transpose(w))
+            ga, gb = gx[:, :ctx.Da], gx[:, ctx.Da:]
+        if ctx.needs_input_grad[2]:
+            gw = ops.linear(transpose(gm), transpose(ops.concat_cols(a, b)))
+        return ga, gb, gw
+
+
+class _LayerNorm(torch.autograd.Function):
+    """LayerNorm(x) gamma + beta over D = 256 [+ addend] (ops.layernorm); the addend's gradient is the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, addend):
+        x = x.contiguous()
+        ctx.save_for_backward(x, gamma)
+        if addend is None:
+            return ops.layernorm(x, gamma, beta, eps=LN_EPS)
+        return ops.layernorm(x, gamma, beta, addend=addend.contiguous(), eps=LN_EPS)[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, gamma = ctx.saved_tensors
+        g = g.contiguous()
+        D = x.shape[-1]
+        rows = x.numel() // D
+        dx, dgamma, dbeta = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
+        n_ws = _L().nopesac_layernorm_backward_workspace_floats(rows)
+        ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
+        rc = _L().nopesac_layernorm_backward(_p(x), _p(gamma), _p(g), rows, D, LN_EPS, _p(dx), _p(dgamma), _p(dbeta), _p(ws), n_ws, _st())
+        _lib.check(rc, "nopesac_layernorm_backward")
+        return dx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None)
+
+
+class _DescDot(torch.autograd.Function):
+    """dots[b] = D0[b] D1[b]^T / sqrt(256) on the batched-weights f32 GEMM (as MatchingHead.forward); backward:
+    nopesac_desc_dot_backward over the live n1 x n2 block - padded descriptor rows get exactly zero."""
+
+    @staticmethod
+    def forward(ctx, d0, d1, n1, n2):
+        d0, d1 = d0.contiguous(), d1.contiguous()
+        B, nq, D = d0.shape
+        scale = torch.full((nq,), 1.0 / D ** 0.5, device=d0.device, dtype=torch.float32)
+        ctx.save_for_backward(d0, d1, n1, n2)
+        return ops.conv2d(d0.view(B, 1, nq, D), d1.view(B, nq, 1, 1, D), scale, batched_weights=True).view(B, nq, nq)
+
+    @staticmethod
+    def backward(ctx, g):
+        d0, d1, n1, n2 = ctx.saved_tensors
+        B, nq, D = d0.shape
+        g = g.contiguous()
+        dd0, dd1 = torch.empty_like(d0), torch.empty_like(d1)
+        rc = _L().nopesac_desc_dot_backward(_p(g), _p(d0), _p(d1), _p(n1), _p(n2), B, nq, D, _p(dd0), _p(dd1), _st())
+        _lib.check(rc, "nopesac_desc_dot_backward")
+        return dd0, dd1, None, None
+
+
+class _SinkhornEmbLoss(torch.autograd.Function):
+    """ops.matcher_sinkhorn + embedding_loss_forward (matching_head.py:135-139) -> (loss, log_scores_padded).  The forward IS the
+    inference launch (its assignment output is dropped), so log_scores_padded are the inference head's scores bit for bit;
+    loss = 2 * mean(-min(log_scores, 0)) over the entries gt_corr selects in the whole batch (nopesac_matcher_emb_loss).  The geometric
+    terms are constants (detached in the reference, :98-99).  Backward: nopesac_matcher_sinkhorn_train replays the iterations and keeps
+    every iteration's potentials (a workspace that lives only inside the backward pass), then the gradient of the unrolled iterations.
+    DEVIATION: a batch that selects no entry gives loss 0 and zero gradients (the reference's mean of nothing is NaN)."""
+
+    @staticmethod
+    def forward(ctx, dots, bin_score, planes1, planes2, cam7, n1, n2, gt_corr, offset_mult: float, normal_mult: float, iters: int):
+        dots, bin_score = dots.contiguous(), bin_score.contiguous()
+        B, nq, _ = dots.shape
+        f32 = dict(device=dots.device, dtype=torch.float32)
+        log_scores, _assignment = ops.matcher_sinkhorn(dots, planes1, planes2, cam7, n1, n2, bin_score, float(offset_mult), float(normal_mult),
+                                                       int(iters), 0.0)
+        stats, loss = torch.empty(B, 2, **f32), torch.empty(2, **f32)
+        rc = _L().nopesac_matcher_emb_loss(_p(log_scores), _p(gt_corr), _p(n1), _p(n2), B, nq, _p(stats), _p(loss), _st())
+        _lib.check(rc, "nopesac_matcher_emb_loss")
+        ctx.conf = (float(offset_mult), float(normal_mult), int(iters))
+        ctx.save_for_backward(dots, bin_score, planes1, planes2, cam7, n1, n2, gt_corr)
+        ctx.loss = loss
+        ctx.mark_non_differentiable(log_scores)
+        return loss[:1].view(()), log_scores
+
+    @staticmethod
+    def backward(ctx, g, _g_scores):
+        dots, bin_score, planes1, planes2, cam7, n1, n2, gt_corr = ctx.saved_tensors
+        offset_mult, normal_mult, iters = ctx.conf
+        B, nq, _ = dots.shape
+        f32 = dict(device=dots.device, dtype=torch.float32)
+        g = g.contiguous().view(1)
+        uv = torch.empty(B, iters, 2, nq + 1, **f32)
+        scratch = (torch.empty(B, nq + 1, nq + 1, **f32), torch.empty(B, 2, **f32), torch.empty(2, **f32))
+        rc = _L().nopesac_matcher_sinkhorn_train(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
+                                                 normal_mult, iters, _p(gt_corr), B, nq, _p(scratch[0]), _p(uv), _p(scratch[1]), _p(scratch[2]),
+                                                 _st())
+        _lib.check(rc, "nopesac_matcher_sinkhorn_train")
+        d_dots = torch.empty_like(dots)
+        d_bin = torch.empty(B, 1, **f32)
+        rc = _L().nopesac_matcher_sinkhorn_train_backward(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
+                                                          normal_mult, iters, _p(gt_corr), _p(uv), _p(ctx.loss), _p(g), B, nq, _p(d_dots),
+                                                          _p(d_bin), _st())
+        _lib.check(rc, "nopesac_matcher_sinkhorn_train_backward")
+        return d_dots, col_sum(d_bin).view_as(bin_score), None, None, None, None, None, None, None, None, None
 
 
 class RefineTrainer:
@@ -689,3 +894,106 @@ class CameraHeadTrainer(RefineTrainer):
             rec(rand_trans, rand_rot, "_randCamRecLBS_N1")
         self._inputs = inputs
         return losses
+
+
+class MatchingHeadTrainer(RefineTrainer):
+    """The matching head in TRAINING mode (reference MatchingHead.forward + embedding_loss_forward, matching_net/matching_head.py:43-139;
+    LoFTR-style GNN, transformer/gnn.py:73-134): every floating tensor under `matching_head.` is trainable - 185 tensors: 18 layers x
+    (q_proj, k_proj, v_proj, merge, mlp.0, mlp.2, norm1 weight / bias, norm2 weight / bias), planeApp_proj and planeDesc_proj weight / bias
+    and bin_score.
+
+        tr = MatchingHeadTrainer.from_state_dict(sd, nq, device)        # or .from_head(model.matching_head)
+        losses = tr.matching_losses(app, n_all, cam7, planes1, planes2, gt_corr, suffix)
+        grads = tr.backward(losses); tr.step(lr=1e-4); tr.write_back(model.matching_head)
+
+    Ragged plane sets are padded to nq rows with int32 lengths, as everywhere in this code base.  The reference's masked subsets of
+    queries (`indices1` / `indices2`, matching_head.py:51-69) are passed COMPACTED to a prefix: a masked row gets zero weight in the
+    attention (gnn.py masks) and -1e5 in the Sinkhorn, and its gt_corr entries are cleared by the logical_and of :69 - exactly what a row
+    beyond the length is here - so the caller gathers the selected queries (and the matching rows / columns of gt_corr) to the front.
+
+    Optimiser groups (train_NopeSAC.py:88-135): the 72 LayerNorm tensors take WEIGHT_DECAY_NORM (is_norm_parameter), bin_score and every
+    other tensor the plain WEIGHT_DECAY.  SOLVER.PLANE_MATCHER_HEAD_MULTIPLIER is NOT applied: the reference keys it on
+    "plane_matcher_net" in module_name, the module is called `matching_head`, so it never fires there either."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], nq: int, offset_multiplier: float = 4.0, normal_multiplier: float = 8.0,
+                 sinkhorn_iterations: int = 200):
+        super().__init__(params, nq)
+        self.offset_multiplier, self.normal_multiplier = float(offset_multiplier), float(normal_multiplier)
+        self.sinkhorn_iterations = int(sinkhorn_iterations)                       # matching_head.py:38
+        self._inputs: Dict[str, torch.Tensor] = {}
+
+    @staticmethod
+    def parameter_names(sd_keys) -> List[str]:
+        return sorted(k for k in sd_keys if k.startswith(MATCHER_PREFIX) and k.split(".")[-1] not in _BUFFER_LEAVES)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, nq: int, device, **kw) -> "MatchingHeadTrainer":
+        names = [k for k in cls.parameter_names(sd.keys()) if torch.is_tensor(sd[k]) and sd[k].is_floating_point()]
+        return cls({k: sd[k].to(device) for k in names}, nq, **kw)
+
+    @classmethod
+    def from_head(cls, head) -> "MatchingHeadTrainer":
+        names = cls.parameter_names(MATCHER_PREFIX + k for k in head._spec_keys)
+        return cls({k: head.raw(k[len(MATCHER_PREFIX):]) for k in names}, head.num_queries, head.offset_multiplier, head.normal_multiplier,
+                   head.sinkhorn_iterations)
+
+    def write_back(self, head):
+        """Copy the trained parameters into the inference MatchingHead (its packed and fragment-major copies are rebuilt on the next forward)."""
+        with torch.no_grad():
+            for k, p in self.params.items():
+                head.raw(k[len(MATCHER_PREFIX):]).copy_(p)
+        head.invalidate()
+
+    # ---- forward
+    def _gnn_layer(self, i: int, x, src, nb: int, qlen, klen):
+        """x + LN2(mlp(cat[x, LN1(merge(attention(q(x), k(src), v(src))))])) (gnn.py:73-96) with the GEMMs grouped exactly as
+        MatchingHead._gnn_layer groups them on its f32 route - one q|k|v projection in a self layer, q and k|v in a cross layer, mlp.0 as
+        two products - so that the same parameters give the inference head's values bit for bit.  The concatenated weights are autograd
+        views of the per-tensor leaves: their gradients come back as row slices."""
+        P, nq, p = self.params, self.nq, f"{MATCHER_PREFIX}gnn.layers.{i}"
+        w = lambda name: P[f"{p}.{name}.weight"]
+        scale = 32 ** -0.5
+        if x is src:
+            qkv = _Linear.apply(x, torch.cat([w("q_proj"), w("k_proj"), w("v_proj")], 0), None, False)
+            msg = _AttentionFused.apply(None, qkv, nb, nq, nq, GNN_HEADS, scale, qlen, klen)
+        else:
+            q = _Linear.apply(x, w("q_proj"), None, False)
+            kv = _Linear.apply(src, torch.cat([w("k_proj"), w("v_proj")], 0), None, False)
+            msg = _AttentionFused.apply(q, kv, nb, nq, nq, GNN_HEADS, scale, qlen, klen)
+        msg = _LayerNorm.apply(_Linear.apply(msg, w("merge"), None, False), P[p + ".norm1.weight"], P[p + ".norm1.bias"], None)
+        out = _Linear.apply(_LinearSplit.apply(x, msg, w("mlp.0")), w("mlp.2"), None, False)
+        return _LayerNorm.apply(out, P[p + ".norm2.weight"], P[p + ".norm2.bias"], x)
+
+    def matching_losses(self, app, n_all, cam7, planes1, planes2, gt_corr, suffix: str = "",
+                        iterations: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """app [2B, nq, 256] (view-1 sets first), n_all int32[2B], cam7 [B, 7] = (t, q), planes1 / planes2 [B, nq, 3], gt_corr uint8 / bool
+        [B, nq+1, nq+1] (dustbin at index nq; entries outside a pair's live block are ignored) -> {"losses_emb_<suffix>": scalar} with
+        the autograd tape attached; `last["log_scores_padded"]` keeps the Sinkhorn output.  `app` may require grad (its gradient lands in
+        `input_grads["app"]`, zero in padded rows).  A batch whose gt_corr selects nothing gives loss 0 and zero gradients (the reference
+        returns NaN there)."""
+        P, nq = self.params, self.nq
+        B = cam7.shape[0]
+        rows = B * nq
+        iters = self.sinkhorn_iterations if iterations is None else int(iterations)
+        n_all = n_all.contiguous()
+        n1, n2 = n_all[:B].contiguous(), n_all[B:].contiguous()
+        gt = gt_corr.to(torch.uint8).contiguous()
+        assert app.shape == (2 * B, nq, 256) and gt.shape == (B, nq + 1, nq + 1) and n_all.dtype == torch.int32, (app.shape, gt.shape)
+        q = MATCHER_PREFIX
+        f = _Linear.apply(app.reshape(2 * rows, 256), P[q + "planeApp_proj.weight"].view(256, 256), P[q + "planeApp_proj.bias"], False)
+        for i in range(GNN_LAYERS):
+            if i % 2 == 0:                       # 'self' (gnn.py:128-130): both sets in one call
+                f = self._gnn_layer(i, f, f, 2 * B, n_all, n_all)
+            else:                                # 'cross' (gnn.py:131-133): feat1 attends to the UPDATED feat0
+                f0 = self._gnn_layer(i, f[:rows], f[rows:], B, n1, n2)
+                f1 = self._gnn_layer(i, f[rows:], f0, B, n2, n1)
+                f = torch.cat([f0, f1], 0)
+        d = _Linear.apply(f, P[q + "planeDesc_proj.weight"].view(256, 256), P[q + "planeDesc_proj.bias"], False)
+        dots = _DescDot.apply(d[:rows].view(B, nq, 256), d[rows:].view(B, nq, 256), n1, n2)
+        loss, log_scores = _SinkhornEmbLoss.apply(dots, P[q + "bin_score"].view(1), planes1.contiguous(), planes2.contiguous(), cam7.contiguous(),
+                                                  n1, n2, gt, self.offset_multiplier, self.normal_multiplier, iters)
+        self._inputs = {"app": app}
+        if app.requires_grad and not app.is_leaf:
+            app.retain_grad()
+        self.last = {"log_scores_padded": log_scores, "desc_dot": dots.detach()}
+        return {"losses_emb_%s" % suffix: loss}
