@@ -929,6 +929,84 @@ int nopesac_matcher_sinkhorn_train_backward(const float* desc_dot, const float* 
 int nopesac_desc_dot_backward(const float* d_desc_dot, const float* d0, const float* d1, const int32_t* n1, const int32_t* n2, int B, int nq,
                               int D, float* dd0, float* dd1, void* stream);
 
+/* ---- set criterion of the plane head (csrc/plane_criterion.hip; nopesac_amd/training.py::PlaneCriterion) -------------------------------
+ * Reference: modeling/matcher.py (HungarianMatcher), modeling/criterion.py (SetCriterion), siamese_planeTR.py prepare_targets and
+ * process_plane_corr_matrix.  All f32, deterministic (no atomics); argument errors -> NPS_E_ARG + nopesac_last_error before any HIP call.
+ * An IMAGE is one (supervised decoder layer, batch element): i = layer * B + b with layer 0 = the last decoder layer and layers 1.. the
+ * auxiliary ones (aux_outputs[0], ...); targets are read at b = i % B.  One argument block serves the cost, loss and gradient entries:
+ *   predictions  pred_logits [L*B, nq, 2], pred_centers [L*B, nq, 2], pred_params [L*B, nq, 3]; pred_mask_logits with element strides
+ *                (image, query, y, x) over h x w; pixel_centers (last layer only, optional) with strides (batch, channel, y, x);
+ *   targets      masks uint8 [B, nmax, H, W] (H = s h, W = s w, integer s >= 1), n int32 [B] on the device and n_host, the same values
+ *                on the host (1 <= n[b] <= min(nq, nmax, 50): checked), tgt_centers [B, nmax, 2], tgt_params [B, nmax, 3],
+ *                tgt_pixel_centers [B, 2, H, W], depth [B, H, W], k_inv_dot_xy1 [B, 3, H, W]; every target is of class 0 (num_classes = 2
+ *                logits: plane, no object);
+ *   matching     cost [L*B, nq, nmax] (0 at j >= n[b]); match_q int32 [L*B, nmax] = query of target j (-1 at j >= n[b]); match_gt int32
+ *                [L*B, nq] = target of query q (-1 if unmatched);
+ *   losses       losses [6 L + 2] unweighted: per layer (loss_ce, loss_mask, loss_dice, loss_center_ins, loss_param_l1, loss_param_cos),
+ *                then loss_center_pixel and loss_q of the last layer; num_masks <= 0 means max(sum n, 1).  Kept for the backward pass:
+ *                mask_stats [L*B, nmax, 4], q_valid uint8 [B, H, W], q_stats [B, 2];
+ *   gradients    g_losses [6 L + 2] (device) = one upstream scalar per loss; d_logits, d_centers, d_params in the shapes of the inputs,
+ *                d_mask_logits and d_pixel_centers with the STRIDES of pred_mask_logits / pixel_centers.  Unmatched queries get exactly 0 in
+ *                d_mask_logits, d_centers and d_params;
+ *   ws           nopesac_plane_criterion_workspace_floats(L, B, nq, nmax, h, w) floats, shared by the three entries (the loss entry's
+ *                content must survive until its backward entry has run). */
+#define NPS_PLANE_MAX_QUERIES 128
+#define NPS_PLANE_MAX_TARGETS 50
+#define NPS_PLANE_MAX_LAYERS 8
+typedef struct nopesac_plane_criterion {
+    const float* pred_logits;
+    const float* pred_mask_logits;
+    const float* pred_centers;
+    const float* pred_params;
+    const float* pixel_centers;
+    int64_t ml_stride_i, ml_stride_q, ml_stride_y, ml_stride_x;
+    int64_t pc_stride_b, pc_stride_c, pc_stride_y, pc_stride_x;
+    const uint8_t* masks;
+    const int32_t* n;
+    const int32_t* n_host;
+    const float* tgt_centers;
+    const float* tgt_params;
+    const float* tgt_pixel_centers;
+    const float* depth;
+    const float* k_inv_dot_xy1;
+    int L, B, nq, nmax, h, w, H, W, num_classes, reserved;
+    float cost_class, cost_mask, cost_dice, cost_center, cost_param, cost_offset, cost_angle;
+    float eos_coef, num_masks, reserved_f;
+    float* cost;
+    int32_t* match_q;
+    int32_t* match_gt;
+    float* losses;
+    float* mask_stats;
+    uint8_t* q_valid;
+    float* q_stats;
+    const float* g_losses;
+    float* d_logits;
+    float* d_mask_logits;
+    float* d_centers;
+    float* d_params;
+    float* d_pixel_centers;
+    float* ws;
+    int64_t ws_floats;
+} nopesac_plane_criterion;
+int64_t nopesac_plane_criterion_workspace_floats(int L, int B, int nq, int nmax, int h, int w);
+/* plane_centers [B, nmax, 2] = centroid of (x / W, y / H) over each mask (0 at j >= n[b]); pixel_centers [B, 2, H, W] = sum over planes of
+ * centre * mask (prepare_targets, siamese_planeTR.py:498-504) */
+int nopesac_plane_targets(const uint8_t* masks, const int32_t* n_host, const int32_t* n, int B, int nmax, int H, int W, float* plane_centers,
+                          float* pixel_centers, void* stream);
+/* the matcher's seven-term cost matrix (class probability, focal and dice against the NEAREST-downsampled masks, centre L2, parameter L1,
+ * normal angle in degrees, offset) -> a->cost */
+int nopesac_plane_match_costs(const nopesac_plane_criterion* a, void* stream);
+/* rectangular linear sum assignment per image on the device (n[b] <= nq <= 128): shortest augmenting paths, one wave per image */
+int nopesac_plane_assign(const float* cost, const int32_t* n_host, const int32_t* n, int L, int B, int nq, int nmax, int32_t* match_q,
+                         int32_t* match_gt, void* stream);
+int nopesac_plane_losses(const nopesac_plane_criterion* a, void* stream);
+int nopesac_plane_losses_backward(const nopesac_plane_criterion* a, void* stream);
+/* gt correspondences of the PREDICTED planes (process_plane_corr_matrix, siamese_planeTR.py:566-623): gt_corrs int32 [B, K, 2] = (gt plane of
+ * view 1, of view 2), rows padded with -1; pairs with an index >= 50 are dropped; match1 / match2 int32 [B, nmax] = the last layer's match_q
+ * of the two views -> out uint8 [B, nq+1, nq+1] with the dustbin row and column, the form nopesac_matcher_sinkhorn_train takes */
+int nopesac_plane_corr_matrix(const int32_t* gt_corrs, int K, const int32_t* match1, const int32_t* match2, int B, int nq, int nmax,
+                              uint8_t* out, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

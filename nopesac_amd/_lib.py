@@ -130,6 +130,7 @@ _HEADER = load_header()
 SIGNATURES, RESTYPES = _HEADER.signatures, _HEADER.restypes     # name -> argtypes, name -> restype
 H = SimpleNamespace(**_HEADER.constants)                        # H.NPS_ACT_RELU, H.NOPESAC_JPEG_IMG_I32, ...
 MlpLayer, MlpChain = _HEADER.structs["nopesac_mlp_layer"], _HEADER.structs["nopesac_mlp_chain"]
+PlaneCriterionArgs = _HEADER.structs["nopesac_plane_criterion"]
 MLP_MAX_IN, MLP_MAX_WIDTH, MLP_MAX_LAYERS = H.NOPESAC_MLP_MAX_IN, H.NOPESAC_MLP_MAX_WIDTH, H.NOPESAC_MLP_MAX_LAYERS
 
 _lib = None

@@ -1543,3 +1543,117 @@ def corr_softmax_backward(a: torch.Tensor, da: torch.Tensor, x1: torch.Tensor, x
     dx2t = conv2d(ds_t.view(B, h, w, P), transpose_batched(x1.reshape(B, P, C)).view(B, C, 1, 1, P), batched_weights=True)
     dx2 = transpose_hw_rows(dx2t.reshape(B, P, C), w, h).view(B, h, w, C)
     return dx1, dx2
+
+
+# ---- set criterion of the plane head (csrc/plane_criterion.hip) --------------------------------------------------------------------------
+PLANE_MAX_QUERIES, PLANE_MAX_TARGETS, PLANE_MAX_LAYERS = _lib.H.NPS_PLANE_MAX_QUERIES, _lib.H.NPS_PLANE_MAX_TARGETS, _lib.H.NPS_PLANE_MAX_LAYERS
+PLANE_COST_NAMES = ("cost_class", "cost_mask", "cost_dice", "cost_center", "cost_param", "cost_offset", "cost_angle")
+
+
+def plane_targets(masks: torch.Tensor, n_host: torch.Tensor, n: torch.Tensor):
+    """prepare_targets (siamese_planeTR.py:498-504): masks uint8 [B, nmax, H, W], n int32 [B] on the host and on the device -> plane_centers
+    [B, nmax, 2] (centroid of (x / W, y / H) per mask) and pixel_centers [B, 2, H, W] (sum of centre x mask)."""
+    _chk(masks, torch.uint8); _chk(n, torch.int32)
+    _require(n_host.dtype == torch.int32 and not n_host.is_cuda and n_host.is_contiguous(), "n_host: contiguous int32 on the host")
+    B, nmax, H, W = masks.shape
+    centers = torch.empty(B, nmax, 2, device=masks.device, dtype=torch.float32)
+    pixel = torch.empty(B, 2, H, W, device=masks.device, dtype=torch.float32)
+    _lib.check(_L().nopesac_plane_targets(_p(masks), n_host.data_ptr(), _p(n), B, nmax, H, W, _p(centers), _p(pixel), _stream()), "nopesac_plane_targets")
+    return centers, pixel
+
+
+class PlaneCriterionCall:
+    """One argument block (nopesac_plane_criterion) for the cost, loss and gradient entries, filled from tensors that it keeps alive.
+    preds: pred_logits [L*B, nq, 2], pred_mask_logits [L*B, nq, h, w] in ANY dense stride order, pred_centers [L*B, nq, 2], pred_params
+    [L*B, nq, 3], pixel_centers [B, 2, h, w] (any dense stride order) or None; targets: masks, n, n_host, plane_centers, plane_params,
+    pixel_centers, depth, k_inv_dot_xy1."""
+
+    def __init__(self, L: int, preds: dict, targets: dict, weights: dict, num_masks: float = 0.0):
+        lg, ml, ce, pa, px = (preds.get(k) for k in ("pred_logits", "pred_mask_logits", "pred_centers", "pred_params", "pixel_centers"))
+        for t in (lg, ce, pa, targets["plane_centers"], targets["plane_params"], targets["pixel_centers"], targets["depth"], targets["k_inv_dot_xy1"]):
+            _chk(t, torch.float32)
+        _chk(targets["masks"], torch.uint8); _chk(targets["n"], torch.int32)
+        nh = targets["n_host"]
+        _require(nh.dtype == torch.int32 and not nh.is_cuda and nh.is_contiguous(), "n_host: contiguous int32 on the host")
+        LB, nq, h, w = ml.shape
+        B, nmax, H, W = targets["masks"].shape
+        _require(LB == L * B and ml.dtype == torch.float32 and lg.shape == (LB, nq, 2) and ce.shape == (LB, nq, 2) and pa.shape == (LB, nq, 3),
+                 (ml.shape, lg.shape, ce.shape, pa.shape))
+        _require(px is None or (px.shape == (B, 2, h, w) and px.dtype == torch.float32), "pixel_centers")
+        dev = ml.device
+        self.keep = (preds, targets)
+        self.dims = (L, B, nq, nmax, h, w, H, W)
+        self.ml, self.px = ml, px
+        f32 = dict(device=dev, dtype=torch.float32)
+        ws_floats = int(_L().nopesac_plane_criterion_workspace_floats(L, B, nq, nmax, h, w))
+        self.ws = torch.empty(max(ws_floats, 1), **f32)
+        self.cost = torch.empty(LB, nq, nmax, **f32)
+        self.match_q = torch.empty(LB, nmax, device=dev, dtype=torch.int32)
+        self.match_gt = torch.empty(LB, nq, device=dev, dtype=torch.int32)
+        self.losses = torch.empty(6 * L + 2, **f32)
+        self.mask_stats = torch.empty(LB, nmax, 4, **f32)
+        self.q_valid = torch.empty(B, H, W, device=dev, dtype=torch.uint8)
+        self.q_stats = torch.empty(B, 2, **f32)
+        a = self.args = _lib.PlaneCriterionArgs()
+        a.pred_logits, a.pred_mask_logits, a.pred_centers, a.pred_params, a.pixel_centers = _p(lg), _p(ml), _p(ce), _p(pa), _p(px)
+        a.ml_stride_i, a.ml_stride_q, a.ml_stride_y, a.ml_stride_x = ml.stride()
+        if px is not None:
+            a.pc_stride_b, a.pc_stride_c, a.pc_stride_y, a.pc_stride_x = px.stride()
+        a.masks, a.n, a.n_host = _p(targets["masks"]), _p(targets["n"]), nh.data_ptr()
+        a.tgt_centers, a.tgt_params, a.tgt_pixel_centers = _p(targets["plane_centers"]), _p(targets["plane_params"]), _p(targets["pixel_centers"])
+        a.depth, a.k_inv_dot_xy1 = _p(targets["depth"]), _p(targets["k_inv_dot_xy1"])
+        a.L, a.B, a.nq, a.nmax, a.h, a.w, a.H, a.W, a.num_classes = L, B, nq, nmax, h, w, H, W, lg.shape[-1]
+        for k in PLANE_COST_NAMES:
+            setattr(a, k, float(weights[k]))
+        a.eos_coef, a.num_masks = float(weights["eos_coef"]), float(num_masks or 0.0)
+        a.cost, a.match_q, a.match_gt = _p(self.cost), _p(self.match_q), _p(self.match_gt)
+        a.losses, a.mask_stats, a.q_valid, a.q_stats = _p(self.losses), _p(self.mask_stats), _p(self.q_valid), _p(self.q_stats)
+        a.ws, a.ws_floats = _p(self.ws), ws_floats
+
+
+def plane_match_costs(call: PlaneCriterionCall) -> torch.Tensor:
+    """The matcher's cost matrices [L*B, nq, nmax] (matcher.py:98-163)."""
+    _lib.check(_L().nopesac_plane_match_costs(ctypes.byref(call.args), _stream()), "nopesac_plane_match_costs")
+    return call.cost
+
+
+def plane_assign(call: PlaneCriterionCall):
+    """Linear sum assignment of call.cost on the device -> (match_q int32 [L*B, nmax], match_gt int32 [L*B, nq])."""
+    L, B, nq, nmax = call.dims[:4]
+    _lib.check(_L().nopesac_plane_assign(_p(call.cost), call.args.n_host, call.args.n, L, B, nq, nmax, _p(call.match_q), _p(call.match_gt), _stream()),
+               "nopesac_plane_assign")
+    return call.match_q, call.match_gt
+
+
+def plane_losses(call: PlaneCriterionCall) -> torch.Tensor:
+    """The unweighted losses [6 L + 2] for call.match_q / call.match_gt (criterion.py)."""
+    _lib.check(_L().nopesac_plane_losses(ctypes.byref(call.args), _stream()), "nopesac_plane_losses")
+    return call.losses
+
+
+def plane_losses_backward(call: PlaneCriterionCall, g_losses: torch.Tensor):
+    """Gradients of sum(g_losses * losses) -> (d_logits, d_mask_logits, d_centers, d_params, d_pixel_centers or None), the mask and centre-map
+    gradients in the stride order of the inputs."""
+    _chk(g_losses, torch.float32)
+    L, B, nq = call.dims[:3]
+    _require(g_losses.numel() == 6 * L + 2, g_losses.shape)
+    f32 = dict(device=call.ml.device, dtype=torch.float32)
+    d_lg, d_ce, d_pa = torch.empty(L * B, nq, 2, **f32), torch.empty(L * B, nq, 2, **f32), torch.empty(L * B, nq, 3, **f32)
+    d_ml = torch.empty_strided(call.ml.shape, call.ml.stride(), **f32)
+    d_px = None if call.px is None else torch.empty_strided(call.px.shape, call.px.stride(), **f32)
+    a = call.args
+    a.g_losses, a.d_logits, a.d_mask_logits, a.d_centers, a.d_params, a.d_pixel_centers = _p(g_losses), _p(d_lg), _p(d_ml), _p(d_ce), _p(d_pa), _p(d_px)
+    _lib.check(_L().nopesac_plane_losses_backward(ctypes.byref(a), _stream()), "nopesac_plane_losses_backward")
+    return d_lg, d_ml, d_ce, d_pa, d_px
+
+
+def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torch.Tensor, nq: int) -> torch.Tensor:
+    """process_plane_corr_matrix (siamese_planeTR.py:566-623): gt_corrs int32 [B, K, 2] (rows padded with -1), match1 / match2 int32 [B, nmax]
+    (query of each gt plane in the two views) -> uint8 [B, nq+1, nq+1] with the dustbin row and column."""
+    _chk(gt_corrs, torch.int32); _chk(match1, torch.int32); _chk(match2, torch.int32)
+    B, K, _ = gt_corrs.shape
+    _require(match1.shape == match2.shape and match1.shape[0] == B, (match1.shape, match2.shape))
+    out = torch.empty(B, nq + 1, nq + 1, device=gt_corrs.device, dtype=torch.uint8)
+    _lib.check(_L().nopesac_plane_corr_matrix(_p(gt_corrs), K, _p(match1), _p(match2), B, nq, match1.shape[1], _p(out), _stream()),
+               "nopesac_plane_corr_matrix")
+    return out

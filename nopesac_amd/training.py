@@ -20,11 +20,18 @@ bin_score and the embedding loss) is trained by MatchingHeadTrainer: the forward
 launch - the same parameters give the inference head's log scores bit for bit; the backward is the kernels of csrc/matcher_bwd.hip
 (ragged attention, LayerNorm, the unrolled Sinkhorn + loss, the descriptor dot) plus the Linear dgrad / wgrad above.
 
-What this is NOT: a trainer for the whole network.  The backbone and the plane head have no backward kernels here - their outputs (the
-backbone maps, the plane sets and their appearance features) are inputs of these stages, as they are of the reference functions, and
-receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
-against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py,
-tests/test_matcher_training_gpu.py)."""
+The plane head's set criterion (modeling/matcher.py HungarianMatcher + modeling/criterion.py SetCriterion, as forward_single calls them) is
+PlaneCriterion: targets preparation, the matcher's cost matrices, the Hungarian match and the nine detection losses of every supervised
+decoder layer run on the device (csrc/plane_criterion.hip) with no host round trip, and their gradients with respect to the head's
+outputs (class logits, low-resolution mask logits, centres, parameters, the pixel centre map) come back through one autograd Function.
+plane_corr_matrix turns the match of both views into the gt_corr MatchingHeadTrainer.matching_losses takes.
+
+What this is NOT: a trainer for the whole network.  The backbone and the plane head's transformer / mask head have no backward kernels here -
+the criterion's gradients stop at the head's outputs; the backbone maps, the plane sets and their appearance features are inputs of the
+other stages, as they are of the reference functions, and receive no gradient beyond `input_grads`; the assignment between the matcher and
+the camera head is discrete and carries none.  Gated against torch.autograd on the oracle (tests/test_training_gpu.py,
+tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py) and against a float64 restatement pinned to the reference
+(tests/test_plane_criterion_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -997,3 +1004,129 @@ class MatchingHeadTrainer(RefineTrainer):
             app.retain_grad()
         self.last = {"log_scores_padded": log_scores, "desc_dot": dots.detach()}
         return {"losses_emb_%s" % suffix: loss}
+
+
+# ---- the plane head's set criterion ------------------------------------------------------------------------------------------------------
+PLANE_LAYER_LOSSES = ("loss_ce", "loss_mask", "loss_dice", "loss_center_ins", "loss_param_l1", "loss_param_cos")
+PLANE_LAST_LOSSES = ("loss_center_pixel", "loss_q")
+
+
+class _PlaneLosses(torch.autograd.Function):
+    """ops.plane_losses / ops.plane_losses_backward on a PlaneCriterionCall whose match is already made: (pred_logits, pred_mask_logits,
+    pred_centers, pred_params [L*B, ...], pixel_centers or None) -> losses [6 L + 2].  Bookkeeping only."""
+
+    @staticmethod
+    def forward(ctx, call, logits, mask_logits, centers, params, pixel_centers):
+        ctx.call = call
+        return ops.plane_losses(call).clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        d_lg, d_ml, d_ce, d_pa, d_px = ops.plane_losses_backward(ctx.call, g.contiguous().float())
+        return None, d_lg, d_ml, d_ce, d_pa, d_px
+
+
+class PlaneCriterion:
+    """HungarianMatcher + SetCriterion of the plane head on the device.  criterion(outputs, targets) -> (losses, indices):
+    outputs = the reference's dict - pred_logits [B, nq, 2], pred_mask_logits [B, nq, h, w] (any dense stride order: the head's
+    [B, h, w, nq] tensor goes in as .permute(0, 3, 1, 2) without a copy), pred_centers [B, nq, 2], pred_params [B, nq, 3], pixel_centers
+    [B, 2, h, w] (likewise) and aux_outputs = a list of dicts with the first four;
+    targets = masks uint8 [B, nmax, H, W], n (int32 on the host, or a list: the planes per image, 1..min(nq, 50)), plane_params [B, nmax, 3],
+    depth [B, H, W], k_inv_dot_xy1 [B, 3, H, W];
+    losses = the reference's names (aux layers with _0, _1, ...), unweighted, attached to autograd; weighted(losses) applies weight_dict
+    as forward_single does; indices = {"match_q" int32 [L, B, nmax], "match_gt" int32 [L, B, nq], "n"} on the device, layer 0 = the last
+    decoder layer.  The reference's all-reduce of num_masks over ranks is the caller's: pass the reduced value as num_masks."""
+
+    def __init__(self, cost_class=1.0, cost_mask=20.0, cost_dice=1.0, cost_center=0.5, cost_param=0.5, cost_offset=0.01, cost_angle=0.0028,
+                 eos_coef=0.1, weight_dict: Optional[Dict[str, float]] = None, num_classes: int = 1):
+        self.weights = dict(cost_class=cost_class, cost_mask=cost_mask, cost_dice=cost_dice, cost_center=cost_center, cost_param=cost_param,
+                            cost_offset=cost_offset, cost_angle=cost_angle, eos_coef=eos_coef)
+        self.weight_dict = dict(weight_dict or {})
+        self.num_classes = int(num_classes)
+
+    @classmethod
+    def from_cfg(cls, cfg):
+        """The weights of from_config (siamese_planeTR.py:136-185)."""
+        H = cfg.MODEL.SEM_SEG_HEAD
+        wd = {"loss_ce": 1, "loss_param_l1": H.PARAM_WEIGHT_L1, "loss_param_cos": H.PARAM_WEIGHT_COS, "loss_q": H.PARAM_WEIGHT_Q,
+              "loss_center_ins": H.PARAM_WEIGHT_CENTER_INS, "loss_center_pixel": 1.0, "loss_depth_pixel": 1.0, "loss_mask": H.MASK_WEIGHT,
+              "loss_dice": H.DICE_WEIGHT}
+        if H.DEEP_SUPERVISION:
+            aux = {}
+            for i in range(H.DEC_LAYERS - 1):
+                aux.update({k + f"_{i}": v for k, v in wd.items()})
+            wd.update(aux)
+        return cls(cost_class=1, cost_mask=H.MASK_WEIGHT, cost_dice=H.DICE_WEIGHT, cost_center=H.PARAM_WEIGHT_CENTER_INS,
+                   cost_param=H.PARAM_HM_WEIGHT_L1, cost_offset=H.PARAM_WEIGHT_OFFSET, cost_angle=H.PARAM_WEIGHT_ANGLE,
+                   eos_coef=H.NO_OBJECT_WEIGHT, weight_dict=wd, num_classes=H.NUM_CLASSES)
+
+    def prepare_targets(self, targets: dict) -> dict:
+        """Adds n (device) / n_host, plane_centers and pixel_centers (prepare_targets, siamese_planeTR.py:498-504) unless they are there."""
+        t = dict(targets)
+        dev = t["masks"].device
+        n = t["n_host"] if "n_host" in t else t["n"]
+        n_host = torch.as_tensor(n, dtype=torch.int32).cpu().contiguous()
+        t["n_host"] = n_host
+        if not (torch.is_tensor(t.get("n")) and t["n"].is_cuda and t["n"].dtype == torch.int32):
+            t["n"] = n_host.to(dev)
+        t["masks"] = t["masks"].contiguous()
+        for k in ("plane_params", "depth", "k_inv_dot_xy1"):
+            t[k] = t[k].float().contiguous()
+        if "plane_centers" not in t or "pixel_centers" not in t:
+            t["plane_centers"], t["pixel_centers"] = ops.plane_targets(t["masks"], n_host, t["n"])
+        return t
+
+    def __call__(self, outputs: dict, targets: dict, num_masks: Optional[float] = None):
+        layers = [outputs] + list(outputs.get("aux_outputs", []))
+        L = len(layers)
+        B, nq = outputs["pred_logits"].shape[:2]
+        t = self.prepare_targets(targets)
+        if L == 1:
+            ml = outputs["pred_mask_logits"]
+            if torch.empty_like(ml).stride() != ml.stride():
+                ml = ml.contiguous()
+            stack = lambda k: outputs[k].contiguous()
+        else:
+            ml = torch.stack([o["pred_mask_logits"] for o in layers]).flatten(0, 1)
+            stack = lambda k: torch.stack([o[k] for o in layers]).flatten(0, 1)
+        px = outputs.get("pixel_centers")
+        if px is not None and torch.empty_like(px).stride() != px.stride():
+            px = px.contiguous()
+        preds = {"pred_logits": stack("pred_logits"), "pred_mask_logits": ml, "pred_centers": stack("pred_centers"),
+                 "pred_params": stack("pred_params"), "pixel_centers": px}
+        call = ops.PlaneCriterionCall(L, {k: (None if v is None else v.detach()) for k, v in preds.items()}, t, self.weights, num_masks or 0.0)
+        ops.plane_match_costs(call)
+        ops.plane_assign(call)
+        vec = _PlaneLosses.apply(call, preds["pred_logits"], ml, preds["pred_centers"], preds["pred_params"], px)
+        losses = {}
+        for l in range(L):
+            sfx = "" if l == 0 else "_%d" % (l - 1)
+            for k, name in enumerate(PLANE_LAYER_LOSSES):
+                losses[name + sfx] = vec[6 * l + k]
+        if px is not None:
+            losses["loss_center_pixel"] = vec[6 * L]
+        losses["loss_q"] = vec[6 * L + 1]
+        nmax = t["masks"].shape[1]
+        self.last = {"cost": call.cost.view(L, B, nq, nmax), "targets": t}
+        return losses, {"match_q": call.match_q.view(L, B, nmax), "match_gt": call.match_gt.view(L, B, nq), "n": t["n_host"].tolist()}
+
+    def weighted(self, losses: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """forward_single's weighting (siamese_planeTR.py:329-334): losses without an entry in weight_dict are dropped."""
+        return {k: v * self.weight_dict[k] for k, v in losses.items() if k in self.weight_dict}
+
+    @staticmethod
+    def indices_as_reference(indices: dict, layer: int = 0):
+        """The reference's form of one layer's match: per image (src sorted ascending, tgt) int64 pairs (a host copy)."""
+        mq = indices["match_q"][layer].cpu().long()
+        out = []
+        for b, nb in enumerate(indices["n"]):
+            src, order = torch.sort(mq[b, :nb])
+            out.append((src, order))
+        return out
+
+
+def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torch.Tensor, nq: int) -> torch.Tensor:
+    """gt correspondences of the predicted planes (process_plane_corr_matrix, siamese_planeTR.py:566-623) in the form
+    MatchingHeadTrainer.matching_losses takes: gt_corrs int32 [B, K, 2] on the device (rows padded with -1), match1 / match2 = the two
+    views' indices["match_q"][0] -> uint8 [B, nq+1, nq+1].  One launch, no host sync."""
+    return ops.plane_corr_matrix(gt_corrs.contiguous(), match1.contiguous(), match2.contiguous(), nq)
