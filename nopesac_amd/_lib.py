@@ -22,9 +22,10 @@ class HeaderError(RuntimeError):
     """include/nopesac_hip.h holds something the reader below does not know.  The reader never guesses a type."""
 
 
-Header = namedtuple("Header", "signatures restypes constants structs")
+Header = namedtuple("Header", "signatures restypes constants structs status")
 _SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "float": c_float}
-_RETURNS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "const char*": c_char_p, "void*": c_void_p, "void": None}
+_RETURNS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "const char*": c_char_p, "void*": c_void_p, "void": None,
+            "nps_status": c_int}      # nps_status: the header's `typedef int`, 0 = enqueued, < 0 = NPS_E_*, > 0 = hipError_t
 
 
 def _norm(ctype: str) -> str:
@@ -89,10 +90,11 @@ def _struct(name: str, body: str, constants: dict, structs: dict):
 
 def read_header(text: str) -> Header:
     """The C ABI as the text of include/nopesac_hip.h states it: argtypes and restype of every `ret nopesac_*(args);` prototype, the
-    integer NPS_* / NOPESAC_* constants, the `typedef struct`s as ctypes.Structure classes.  Not a C parser: it reads the narrow
-    grammar this header keeps, and raises HeaderError, naming the symbol, on anything else."""
+    set of those declared `nps_status` (their result is a status, every other result a value), the integer NPS_* / NOPESAC_*
+    constants, the `typedef struct`s as ctypes.Structure classes.  Not a C parser: it reads the narrow grammar this header keeps, and
+    raises HeaderError, naming the symbol, on anything else."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    constants, structs, signatures, restypes = {}, {}, {}, {}
+    constants, structs, signatures, restypes, status = {}, {}, {}, {}, set()
     for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+((?:NPS|NOPESAC)_\w+)[ \t]+(\S.*)$", text, flags=re.M):   # (a guard has no value)
         constants[name] = _constant(name, value, constants)
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
@@ -105,6 +107,7 @@ def read_header(text: str) -> Header:
         structs[m[1]] = _struct(m[1], m[2], constants, structs)
         return ""
     text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", take_struct, text, flags=re.S)
+    text = re.sub(r"typedef\s+int\s+nps_status\s*;", "", text)
     for stmt in filter(None, (s.strip() for s in text.split(";"))):
         m = re.fullmatch(r"(.+?)\b(nopesac_\w+)\s*\((.*)\)", stmt, re.S)
         if not m:
@@ -113,8 +116,10 @@ def read_header(text: str) -> Header:
         if ret not in _RETURNS or name in signatures:
             raise HeaderError(f"{name}: unknown return type {ret!r}, or declared twice")
         restypes[name] = _RETURNS[ret]
+        if ret == "nps_status":
+            status.add(name)
         signatures[name] = [] if params == "void" else [_ctype(_declarator(p, name)[0], name) for p in params.split(",")]
-    return Header(signatures, restypes, constants, structs)
+    return Header(signatures, restypes, constants, structs, frozenset(status))
 
 
 def load_header(path: str = HEADER_PATH) -> Header:
@@ -128,6 +133,7 @@ def load_header(path: str = HEADER_PATH) -> Header:
 # Read at import: the wrappers bind their constants (nopesac_amd.ops, nopesac_amd.jpeg) when they are imported, before any load().
 _HEADER = load_header()
 SIGNATURES, RESTYPES = _HEADER.signatures, _HEADER.restypes     # name -> argtypes, name -> restype
+STATUS = _HEADER.status                                         # the entry points whose int result is a status, not a value
 H = SimpleNamespace(**_HEADER.constants)                        # H.NPS_ACT_RELU, H.NOPESAC_JPEG_IMG_I32, ...
 MlpLayer, MlpChain = _HEADER.structs["nopesac_mlp_layer"], _HEADER.structs["nopesac_mlp_chain"]
 PlaneCriterionArgs = _HEADER.structs["nopesac_plane_criterion"]
@@ -162,6 +168,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.argtypes = argtypes
         fn.restype = RESTYPES[name]
+    vars(C).update({name: _raising(getattr(lib, name)) if name in STATUS else getattr(lib, name) for name in SIGNATURES})
     _lib = lib
     return lib
 
@@ -174,3 +181,28 @@ def check(rc: int, name: str):
     if rc != 0:
         msg = load().nopesac_last_error()
         raise HipKernelError(f"{name} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+def _raising(fn):
+    def call(*args):
+        rc = fn(*args)
+        if rc:
+            check(rc, fn.__name__)
+    return call
+
+
+class _Checked:
+    """The library as the wrappers call it: C.nopesac_x(...) raises HipKernelError when a status entry point (STATUS) does not return
+    0, and is the raw function for an entry point that returns a value.  load() fills it once with every entry point, so a call costs
+    one attribute read of this object; only the first read, before load(), comes through __getattr__.  The raw library (load()) is for
+    the few callers that branch on a status themselves."""
+
+    def __getattr__(self, name):
+        load()
+        try:
+            return self.__dict__[name]
+        except KeyError:
+            raise AttributeError(f"include/nopesac_hip.h declares no entry point {name!r}") from None
+
+
+C = _Checked()

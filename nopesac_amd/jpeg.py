@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ops import _C, _p, _stream
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
@@ -203,8 +204,8 @@ def _prepare_scan(info: JpegInfo, data: bytes, p: int):
     so, sc, sb = (np.empty(cap_segs, np.int64) for _ in range(3))
     consumed = ctypes.c_int64(0)
     base = ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p).value
-    k = _lib.load().nopesac_jpeg_prepare_scan(ctypes.c_void_p(base + p), n, 1 if info.dri else 0, words.ctypes.data, words.size, so.ctypes.data,
-                                              sc.ctypes.data, sb.ctypes.data, cap_segs, ctypes.byref(consumed))
+    k = _C.nopesac_jpeg_prepare_scan(ctypes.c_void_p(base + p), n, 1 if info.dri else 0, words.ctypes.data, words.size, so.ctypes.data,
+                                     sc.ctypes.data, sb.ctypes.data, cap_segs, ctypes.byref(consumed))      # a value: the interval count
     if k < 1:
         raise JpegUnsupported("scan data could not be prepared")
     if p + consumed.value + 1 >= len(data):
@@ -378,14 +379,13 @@ def prepare_files(paths: Sequence[str], threads: int = 4, parallel: bool = True)
     walk, checks, stuffing removal, tables, launch arrays - parse() + prepare_batch() without the interpreter).  Returns (HostBatch, None)
     or (None, status list) when a file is outside what that path takes (the caller falls back to parse() per file, which decides what
     PIL must decode)."""
-    L = _lib.load()
     n = len(paths)
     if n == 0:
         return None, []
     arr = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
     status = (ctypes.c_int * n)()
     totals = (ctypes.c_int64 * 8)()
-    h = L.nopesac_jpeg_batch_scan_host(arr, n, max(1, int(threads)), 1 if parallel else 0, status, totals)
+    h = _C.nopesac_jpeg_batch_scan_host(arr, n, max(1, int(threads)), 1 if parallel else 0, status, totals)
     if not h:
         return None, [-1] * n
     try:
@@ -400,16 +400,16 @@ def prepare_files(paths: Sequence[str], threads: int = 4, parallel: bool = True)
         hb.words = torch.empty(n_words, dtype=torch.int32)
         hb.lane_img = torch.empty(n_lanes, dtype=torch.int32) if n_lanes else None
         geo = torch.empty((n, 2), dtype=torch.int32)
-        rc = L.nopesac_jpeg_batch_fill_host(h, hb.img32.data_ptr(), hb.img64.data_ptr(), hb.tables.data_ptr(), hb.seg32.data_ptr(), hb.seg64.data_ptr(),
-                                            hb.words.data_ptr(), hb.lane_img.data_ptr() if n_lanes else None, geo.data_ptr())
-        if rc != 0:
+        rc = _C.nopesac_jpeg_batch_fill_host(h, hb.img32.data_ptr(), hb.img64.data_ptr(), hb.tables.data_ptr(), hb.seg32.data_ptr(), hb.seg64.data_ptr(),
+                                             hb.words.data_ptr(), hb.lane_img.data_ptr() if n_lanes else None, geo.data_ptr())
+        if rc != 0:                                       # a value: the code of why the batch stays off this path
             return None, [rc] * n
         hb.infos = [_Geometry(hh, ww) for hh, ww in geo.tolist()]
         hb.n_seg, hb.n_lanes, hb.n_blocks, hb.max_px = n_segs, n_lanes, n_blocks, max_px
         hb.coef_off, hb.plane_off, hb.out_off = coef_off, plane_off, out_off
         return hb, None
     finally:
-        L.nopesac_jpeg_batch_free_host(h)
+        _C.nopesac_jpeg_batch_free_host(h)
 
 
 def decode_batch(files: Sequence[bytes], device, bgr: bool = False, infos: Sequence[JpegInfo] = None, parallel: bool = True,
@@ -438,9 +438,7 @@ def decode_batch(files: Sequence[bytes], device, bgr: bool = False, infos: Seque
     coef = torch.zeros(host.coef_off, device=dev, dtype=torch.int16)
     planes = torch.empty(host.plane_off, device=dev, dtype=torch.uint8)
     out = torch.empty(host.out_off, device=dev, dtype=torch.uint8)
-    L = _lib.load()
-    st = torch.cuda.current_stream(dev).cuda_stream
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    st = _stream()
     par_done, work = None, []
     if n_lanes:
         t_lane = up(host.lane_img)
@@ -452,16 +450,15 @@ def decode_batch(files: Sequence[bytes], device, bgr: bool = False, infos: Seque
         par_done = torch.zeros(n, device=dev, dtype=torch.int32)
         if _force_unsettled:                              # test hook: pretend lanes still moved in the last pass -> the serial kernel decodes
             changed[(SYNC_PASSES - 1) * n:] = 1
-        _lib.check(L.nopesac_jpeg_huffman_parallel(p(t_img32), p(t_img64), p(t_tab), n, p(t_lane), n_lanes, p(t_words), int(t_words.numel()),
-                                                   p(exit_state), p(entry_used), p(n_blk), p(first_block), p(changed), p(par_done), p(coef), st),
-                   "nopesac_jpeg_huffman_parallel")
+        _C.nopesac_jpeg_huffman_parallel(_p(t_img32), _p(t_img64), _p(t_tab), n, _p(t_lane), n_lanes, _p(t_words), int(t_words.numel()),
+                                         _p(exit_state), _p(entry_used), _p(n_blk), _p(first_block), _p(changed), _p(par_done), _p(coef), st)
         work = [t_lane, exit_state, entry_used, n_blk, first_block, changed, par_done]
         if stats is not None:
             stats["par_done"], stats["changed"] = par_done, changed.view(SYNC_PASSES, n)
-    _lib.check(L.nopesac_jpeg_huffman(p(t_img32), p(t_img64), p(t_tab), p(t_seg32), p(t_seg64), host.n_seg, p(t_words), int(t_words.numel()), p(coef),
-                                      p(par_done) if par_done is not None else None, st), "nopesac_jpeg_huffman")
-    _lib.check(L.nopesac_jpeg_idct(p(t_img32), p(t_img64), p(t_tab), n, n_blocks, p(coef), p(planes), st), "nopesac_jpeg_idct")
-    _lib.check(L.nopesac_jpeg_color(p(t_img32), p(t_img64), n, max_px, p(planes), p(out), 1 if bgr else 0, st), "nopesac_jpeg_color")
+    _C.nopesac_jpeg_huffman(_p(t_img32), _p(t_img64), _p(t_tab), _p(t_seg32), _p(t_seg64), host.n_seg, _p(t_words), int(t_words.numel()), _p(coef),
+                            _p(par_done), st)
+    _C.nopesac_jpeg_idct(_p(t_img32), _p(t_img64), _p(t_tab), n, n_blocks, _p(coef), _p(planes), st)
+    _C.nopesac_jpeg_color(_p(t_img32), _p(t_img64), n, max_px, _p(planes), _p(out), 1 if bgr else 0, st)
     res = []
     for i, f in enumerate(infos):
         o = int(img64[i, 6])

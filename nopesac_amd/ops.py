@@ -34,7 +34,11 @@ def _require(cond, msg="argument check failed"):
         raise OpsArgumentError(msg if isinstance(msg, str) else repr(msg))
 
 
+_C = _lib.C                                     # the library as the wrappers call it: a refused call raises HipKernelError by itself
+
+
 def _L():
+    """The raw library, for callers that read an entry point's status themselves (tests, scripts)."""
     return _lib.load()
 
 
@@ -173,7 +177,7 @@ def p8_sk_workspace(device) -> torch.Tensor:
     key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(), torch.cuda.is_current_stream_capturing())
     ws = _P8_SK_WS.get(key)
     if ws is None:
-        n = int(_L().nopesac_conv2d_p8_sk_workspace_bytes())
+        n = int(_C.nopesac_conv2d_p8_sk_workspace_bytes())
         ws = torch.empty(n, device=device, dtype=torch.uint8)
         ws[:16384].zero_()
         _P8_SK_WS[key] = ws
@@ -206,10 +210,10 @@ def conv_eligibility(x_dtype, w_dtype, out_dtype, B, H, W, Cin, Cout, KH, KW, st
     included); `aligned`: every buffer the call touches (x, w, out, residual, scale, bias) is 16-byte aligned.  Memoised: conv2d asks
     on every launch."""
     splits = ctypes.c_int(0)
-    m = _L().nopesac_conv2d_nhwc_forms(_DT.get(x_dtype, -1), _DT.get(w_dtype, -1), _DT.get(out_dtype, -1), B, H, W, Cin, Cout, KH, KW, stride,
-                                       pad, x_cs, y_cs, r_cs, bool(batched), bool(has_residual), bool(has_scale), bool(has_bias), act,
-                                       bool(aligned), ctypes.byref(splits))
-    _lib.check(min(m, 0), "nopesac_conv2d_nhwc_forms")
+    forms = _C.nopesac_conv2d_nhwc_forms
+    m = forms(_DT.get(x_dtype, -1), _DT.get(w_dtype, -1), _DT.get(out_dtype, -1), B, H, W, Cin, Cout, KH, KW, stride, pad, x_cs, y_cs, r_cs,
+              bool(batched), bool(has_residual), bool(has_scale), bool(has_bias), act, bool(aligned), ctypes.byref(splits))
+    _lib.check(min(m, 0), forms.__name__)             # the result is a value: the mask, or NPS_E_ARG
     return ConvEligibility(*(bool(m >> c & 1) for c in (CFG_BFRAG3, CFG_HALO16, CFG_P8, CFG_P8_SK, CFG_P8N)), splits.value,
                            bool(m >> CFG_P8N_SPLIT & 1))
 
@@ -269,42 +273,35 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, scale=None, bias=None, residual=Non
     def launch(cfg):
         if cfg == CFG_P8N_SPLIT:
             ws = torch.empty(p8n_splits * B * OH * OW * Cout, device=x.device, dtype=torch.float32)    # (caching allocator: capture-safe)
-            rc = _L().nopesac_conv2d_nhwc_p8n_splitk(_p(x), _p(w), _p(scale), _p(bias), _p(out), B, H, W, Cin, Cout, KH, KW, stride, pad, x_cs,
-                                                     y_cs, act, 32, p8n_splits, _p(ws), ws.numel() * 4, _stream())
-            _lib.check(rc, "nopesac_conv2d_nhwc_p8n_splitk")
+            _C.nopesac_conv2d_nhwc_p8n_splitk(_p(x), _p(w), _p(scale), _p(bias), _p(out), B, H, W, Cin, Cout, KH, KW, stride, pad, x_cs,
+                                              y_cs, act, 32, p8n_splits, _p(ws), ws.numel() * 4, _stream())
             return
         if cfg in (CFG_P8N, CFG_P8N_TAP):
-            rc = _L().nopesac_conv2d_nhwc_p8n(_p(x), _p(w), _p(scale), _p(bias), _p(out), B, H, W, Cin, Cout, KH, KW, stride, pad, x_cs, y_cs,
-                                              act, 32 if cfg == CFG_P8N else 0, _stream())
-            _lib.check(rc, "nopesac_conv2d_nhwc_p8n")
+            _C.nopesac_conv2d_nhwc_p8n(_p(x), _p(w), _p(scale), _p(bias), _p(out), B, H, W, Cin, Cout, KH, KW, stride, pad, x_cs, y_cs,
+                                       act, 32 if cfg == CFG_P8N else 0, _stream())
             return
         if cfg == CFG_P8_SK:
             ws = p8_sk_workspace(x.device)
-            rc = _L().nopesac_conv2d_nhwc_p8_sk(_p(x), _p(w), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, KH, KW, stride,
-                                                pad, x_cs, y_cs, r_cs, act, _DT[out_dtype], P8_VARIANT[0], _p(ws), ws.numel(), _stream())
-            _lib.check(rc, "nopesac_conv2d_nhwc_p8_sk")
+            _C.nopesac_conv2d_nhwc_p8_sk(_p(x), _p(w), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, KH, KW, stride,
+                                         pad, x_cs, y_cs, r_cs, act, _DT[out_dtype], P8_VARIANT[0], _p(ws), ws.numel(), _stream())
             return
         if cfg == CFG_P8:
-            rc = _L().nopesac_conv2d_nhwc_p8(_p(x), _p(w), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, KH, KW, stride,
-                                             pad, x_cs, y_cs, r_cs, act, _DT[out_dtype],
-                                             P8_VARIANT[0] | ((P8_CAP_1X1[0] << 8) if KH * KW == 1 else 0), _stream())
-            _lib.check(rc, "nopesac_conv2d_nhwc_p8")
+            _C.nopesac_conv2d_nhwc_p8(_p(x), _p(w), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, KH, KW, stride,
+                                      pad, x_cs, y_cs, r_cs, act, _DT[out_dtype],
+                                      P8_VARIANT[0] | ((P8_CAP_1X1[0] << 8) if KH * KW == 1 else 0), _stream())
             return
         if cfg in (CFG_HALO16, CFG_HALO8):
-            rc = _L().nopesac_conv3x3_halo_bf16(_p(x), _p(_frag_weights(w)), _p(scale), _p(bias), _p(out), B, H, W, Cin, Cout, act,
-                                                0 if cfg == CFG_HALO16 else 1, _stream())
-            _lib.check(rc, "nopesac_conv3x3_halo_bf16")
+            _C.nopesac_conv3x3_halo_bf16(_p(x), _p(_frag_weights(w)), _p(scale), _p(bias), _p(out), B, H, W, Cin, Cout, act,
+                                         0 if cfg == CFG_HALO16 else 1, _stream())
             return
         if cfg in (CFG_BFRAG3, CFG_BFRAG32):
-            rc = _L().nopesac_conv2d_nhwc_bfrag(_p(x), _p(_frag_weights(w)), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout,
-                                                KH, KW, stride, pad, x_cs, y_cs, r_cs, act, _DT[out_dtype],
-                                                (3 if cfg == CFG_BFRAG3 else 32) + (BFRAG_KMAJOR[0] if (KH * KW > 1 and stride == 1) else 0), _stream())
-            _lib.check(rc, "nopesac_conv2d_nhwc_bfrag")
+            _C.nopesac_conv2d_nhwc_bfrag(_p(x), _p(_frag_weights(w)), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout,
+                                         KH, KW, stride, pad, x_cs, y_cs, r_cs, act, _DT[out_dtype],
+                                         (3 if cfg == CFG_BFRAG3 else 32) + (BFRAG_KMAJOR[0] if (KH * KW > 1 and stride == 1) else 0), _stream())
             return
-        rc = _L().nopesac_conv2d_nhwc_ex(_p(x), _p(w), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, KH, KW,
-                                         stride, pad, x_cs, y_cs, r_cs, w_bs, act, 2 if mixed else _DT[x.dtype], _DT[out_dtype],
-                                         cfg, _stream())
-        _lib.check(rc, "nopesac_conv2d_nhwc_ex")
+        _C.nopesac_conv2d_nhwc_ex(_p(x), _p(w), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, KH, KW,
+                                  stride, pad, x_cs, y_cs, r_cs, w_bs, act, 2 if mixed else _DT[x.dtype], _DT[out_dtype],
+                                  cfg, _stream())
 
     cfg = 0
     if TUNER.measuring or TUNER.best or TUNER.loaded:
@@ -350,9 +347,8 @@ def preprocess(images_nchw: torch.Tensor, mean: torch.Tensor, std: torch.Tensor,
     x = _chk(images_nchw, torch.float32)
     B, C, H, W = x.shape
     y = torch.empty((B, H, W, cpad), device=x.device, dtype=out_dtype)
-    rc = _L().nopesac_preprocess_nchw_to_nhwc(_p(x), _p(y), _p(_chk(mean, torch.float32)), _p(_chk(std, torch.float32)), B, C, H, W,
-                                              cpad, _DT[out_dtype], _stream())
-    _lib.check(rc, "nopesac_preprocess_nchw_to_nhwc")
+    _C.nopesac_preprocess_nchw_to_nhwc(_p(x), _p(y), _p(_chk(mean, torch.float32)), _p(_chk(std, torch.float32)), B, C, H, W,
+                                       cpad, _DT[out_dtype], _stream())
     return y
 
 
@@ -364,7 +360,7 @@ def stem_fused(x: torch.Tensor, w224: torch.Tensor, scale: torch.Tensor, bias: t
     CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
     y = torch.empty((B, PH, PW, 64), device=x.device, dtype=torch.bfloat16)
-    _lib.check(_L().nopesac_stem_fused_bf16(_p(x), _p(w224), _p(scale), _p(bias), _p(y), B, H, W, _stream()), "nopesac_stem_fused_bf16")
+    _C.nopesac_stem_fused_bf16(_p(x), _p(w224), _p(scale), _p(bias), _p(y), B, H, W, _stream())
     return y
 
 
@@ -378,8 +374,7 @@ def stem_fused_raw(images: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, 
     CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
     y = torch.empty((B, PH, PW, 64), device=images.device, dtype=torch.bfloat16)
-    _lib.check(_L().nopesac_stem_fused_raw_bf16(_p(images), _p(mean), _p(std), _p(w224), _p(scale), _p(bias), _p(y), B, H, W, _stream()),
-               "nopesac_stem_fused_raw_bf16")
+    _C.nopesac_stem_fused_raw_bf16(_p(images), _p(mean), _p(std), _p(w224), _p(scale), _p(bias), _p(y), B, H, W, _stream())
     return y
 
 
@@ -393,8 +388,7 @@ def stem_fused_raw_shifted(images: torch.Tensor, pad3: torch.Tensor, w224_folded
     CH, CW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     PH, PW = (CH + 2 - 3) // 2 + 1, (CW + 2 - 3) // 2 + 1
     y = torch.empty((B, PH, PW, 64), device=images.device, dtype=torch.bfloat16)
-    _lib.check(_L().nopesac_stem_fused_raw_shifted_bf16(_p(images), _p(pad3), _p(w224_folded), _p(scale), _p(bias_folded), _p(y), B, H, W, _stream()),
-               "nopesac_stem_fused_raw_shifted_bf16")
+    _C.nopesac_stem_fused_raw_shifted_bf16(_p(images), _p(pad3), _p(w224_folded), _p(scale), _p(bias_folded), _p(y), B, H, W, _stream())
     return y
 
 
@@ -474,7 +468,7 @@ def mlp_chain(x: torch.Tensor, layers, acts, outs, x_bcast: Optional[torch.Tenso
         if o is not None:
             _require(o.dtype == torch.float32 and o.dim() == 2 and o.shape == (rows, l.N) and o.stride(1) == 1, "mlp_chain: out tensor")
             e.out, e.out_ld = _p(o), o.stride(0)
-    _lib.check(_L().nopesac_mlp_chain_bf16(ctypes.byref(c), _stream()), "nopesac_mlp_chain_bf16")
+    _C.nopesac_mlp_chain_bf16(ctypes.byref(c), _stream())
     return outs[-1]
 
 
@@ -515,9 +509,8 @@ def conv2d_fp8(x: torch.Tensor, w8frag: torch.Tensor, scale: torch.Tensor, bias:
         _require(residual.shape == out.shape, 'argument check failed: residual.shape == out.shape')
     if not variant:
         variant = 3 if Cin % 128 == 0 else 32
-    rc = _L().nopesac_conv2d_nhwc_fp8(_p(x), _p(w8frag), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, ksize, ksize,
-                                      stride, pad, Cin, Cout, Cout if residual is not None else 0, act, _DT[out_dtype], variant, _stream())
-    _lib.check(rc, "nopesac_conv2d_nhwc_fp8")
+    _C.nopesac_conv2d_nhwc_fp8(_p(x), _p(w8frag), _p(scale), _p(bias), _p(residual), _p(out), B, H, W, Cin, Cout, ksize, ksize,
+                               stride, pad, Cin, Cout, Cout if residual is not None else 0, act, _DT[out_dtype], variant, _stream())
     return out
 
 
@@ -539,7 +532,7 @@ def bottleneck_tail_forms(C, C4, CN, C2, M, stride=1, same_res=False, switches=0
     """(default form id or -1, bitmask of eligible form ids) of a bottleneck tail over M pixels (C2 = 0: identity block; same_res: the
     projection source has the output's height and width) under the NPS_TAIL_SW_* switch bits.  Host only: needs no GPU."""
     mask = ctypes.c_uint(0)
-    form = _L().nopesac_bottleneck_tail_forms(C, C4, CN, C2, M, stride, int(bool(same_res)), switches, ctypes.byref(mask))
+    form = _C.nopesac_bottleneck_tail_forms(C, C4, CN, C2, M, stride, int(bool(same_res)), switches, ctypes.byref(mask))
     return form, mask.value
 
 
@@ -577,11 +570,9 @@ def bottleneck_tail(b, w3, s3, b3, *, residual=None, x2=None, wsc=None, ssc=None
     args = (_p(b), _p(w3), _p(s3), _p(b3), _p(residual), _p(x2), _p(wsc), _p(ssc), _p(bsc), B, OH, OW, H2, W2, stride, C, C4, C2, _p(y),
             _p(w1), _p(s1), _p(b1), CN, _p(o), FP8 if o_fp8 else BF16)
     if form is None:
-        rc = _L().nopesac_bottleneck_tail_bf16_ex(*args, _stream())
-        _lib.check(rc, "nopesac_bottleneck_tail_bf16_ex")
+        _C.nopesac_bottleneck_tail_bf16_ex(*args, _stream())
     else:
-        rc = _L().nopesac_bottleneck_tail_bf16_form(*args, int(form), _stream())
-        _lib.check(rc, "nopesac_bottleneck_tail_bf16_form")
+        _C.nopesac_bottleneck_tail_bf16_form(*args, int(form), _stream())
     return y, o
 
 
@@ -590,7 +581,7 @@ def maxpool(x: torch.Tensor, k: int, stride: int, pad: int) -> torch.Tensor:
     B, H, W, C = x.shape
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     y = torch.empty((B, OH, OW, C), device=x.device, dtype=x.dtype)
-    _lib.check(_L().nopesac_maxpool_nhwc(_p(x), _p(y), B, H, W, C, k, stride, pad, _DT[x.dtype], _stream()), "nopesac_maxpool_nhwc")
+    _C.nopesac_maxpool_nhwc(_p(x), _p(y), B, H, W, C, k, stride, pad, _DT[x.dtype], _stream())
     return y
 
 
@@ -601,8 +592,7 @@ def upsample2x_bilinear(x: torch.Tensor, addend=None, act=ACT_NONE) -> torch.Ten
     if addend is not None:
         _chk(addend, x.dtype)
         _require(addend.shape == y.shape, 'argument check failed: addend.shape == y.shape')
-    _lib.check(_L().nopesac_upsample2x_bilinear_nhwc(_p(x), _p(addend), _p(y), B, H, W, C, act, _DT[x.dtype], _stream()),
-               "nopesac_upsample2x_bilinear_nhwc")
+    _C.nopesac_upsample2x_bilinear_nhwc(_p(x), _p(addend), _p(y), B, H, W, C, act, _DT[x.dtype], _stream())
     return y
 
 
@@ -611,8 +601,7 @@ def upsample2x_nearest_add(x: torch.Tensor, lateral: torch.Tensor) -> torch.Tens
     B, H, W, C = x.shape
     _require(lateral.shape == (B, 2 * H, 2 * W, C), 'argument check failed: lateral.shape == (B, 2 * H, 2 * W, C)')
     y = torch.empty_like(lateral)
-    _lib.check(_L().nopesac_upsample2x_nearest_add_nhwc(_p(x), _p(lateral), _p(y), B, H, W, C, _DT[x.dtype], _stream()),
-               "nopesac_upsample2x_nearest_add_nhwc")
+    _C.nopesac_upsample2x_nearest_add_nhwc(_p(x), _p(lateral), _p(y), B, H, W, C, _DT[x.dtype], _stream())
     return y
 
 
@@ -621,8 +610,8 @@ def groupnorm(x: torch.Tensor, gamma, beta, groups: int, eps: float, act=ACT_NON
     B, H, W, C = x.shape
     y = torch.empty_like(x)
     ws = torch.empty(B * 16 * groups * 2, device=x.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_groupnorm_nhwc(_p(x), _p(_chk(gamma, torch.float32)), _p(_chk(beta, torch.float32)), _p(y), B, H * W, C,
-                                           groups, eps, act, _DT[x.dtype], _p(ws), _stream()), "nopesac_groupnorm_nhwc")
+    _C.nopesac_groupnorm_nhwc(_p(x), _p(_chk(gamma, torch.float32)), _p(_chk(beta, torch.float32)), _p(y), B, H * W, C,
+                              groups, eps, act, _DT[x.dtype], _p(ws), _stream())
     return y
 
 
@@ -637,8 +626,8 @@ def layernorm(x: torch.Tensor, gamma, beta, res=None, addend=None, eps=1e-5):
         _chk(res, torch.float32)
         _require(res.shape == x.shape, 'argument check failed: res.shape == x.shape')
     a_rows = 0 if addend is None else _chk(addend, torch.float32).numel() // D
-    _lib.check(_L().nopesac_layernorm(_p(x), _p(res), _p(_chk(gamma, torch.float32)), _p(_chk(beta, torch.float32)), _p(y),
-                                      _p(addend), a_rows, _p(y2), rows, D, eps, _stream()), "nopesac_layernorm")
+    _C.nopesac_layernorm(_p(x), _p(res), _p(_chk(gamma, torch.float32)), _p(_chk(beta, torch.float32)), _p(y),
+                         _p(addend), a_rows, _p(y2), rows, D, eps, _stream())
     return (y, y2) if addend is not None else y
 
 
@@ -655,9 +644,9 @@ def layernorm_ex(x: torch.Tensor, gamma, beta, res=None, addend=None, eps=1e-5, 
         _require(res.shape == x.shape, 'argument check failed: res.shape == x.shape')
     a_rows = 0 if addend is None else _chk(addend, torch.float32).numel() // D
     _require(addend is not None or not ({"y2", "y2_16"} & set(want)), 'argument check failed: addend is not None or not ({"y2", "y2_16"} & set(want))')
-    _lib.check(_L().nopesac_layernorm_ex(_p(x), _p(res), _p(_chk(gamma, torch.float32)), _p(_chk(beta, torch.float32)), _p(out.get("y")),
-                                         _p(addend), a_rows, _p(out.get("y2")), _p(out.get("y16")), _p(out.get("y2_16")), rows, D, eps,
-                                         _stream()), "nopesac_layernorm_ex")
+    _C.nopesac_layernorm_ex(_p(x), _p(res), _p(_chk(gamma, torch.float32)), _p(_chk(beta, torch.float32)), _p(out.get("y")),
+                            _p(addend), a_rows, _p(out.get("y2")), _p(out.get("y16")), _p(out.get("y2_16")), rows, D, eps,
+                            _stream())
     return out
 
 
@@ -665,7 +654,7 @@ def add_rows(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     _chk(a, torch.float32); _chk(b, torch.float32)
     D = a.shape[-1]
     out = torch.empty_like(a)
-    _lib.check(_L().nopesac_add_rows(_p(a), _p(b), _p(out), a.numel() // D, D, b.numel() // D, _stream()), "nopesac_add_rows")
+    _C.nopesac_add_rows(_p(a), _p(b), _p(out), a.numel() // D, D, b.numel() // D, _stream())
     return out
 
 
@@ -677,11 +666,11 @@ def softmax_rows(x: torch.Tensor, out_dtype=None, pad_to: int = 0) -> torch.Tens
     out_dtype = out_dtype or torch.float32
     if out_dtype == torch.float32 and pad_to <= D:
         y = torch.empty_like(x)
-        _lib.check(_L().nopesac_softmax_rows(_p(x), _p(y), x.numel() // D, D, _stream()), "nopesac_softmax_rows")
+        _C.nopesac_softmax_rows(_p(x), _p(y), x.numel() // D, D, _stream())
         return y
     ld = max(D, pad_to)
     y = torch.empty(x.shape[:-1] + (ld,), device=x.device, dtype=out_dtype)
-    _lib.check(_L().nopesac_softmax_rows_pad(_p(x), _p(y), x.numel() // D, D, ld, _DT[out_dtype], _stream()), "nopesac_softmax_rows_pad")
+    _C.nopesac_softmax_rows_pad(_p(x), _p(y), x.numel() // D, D, ld, _DT[out_dtype], _stream())
     return y
 
 
@@ -710,8 +699,8 @@ def metric_rows(trans, rot, n1, n2, m, pair_idx0: int, t_err=None, r_err=None, n
     if nonfinite is not None:
         _chk(nonfinite, torch.int32)
     rows = torch.empty(B, 16, device=trans.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_metric_rows(_p(trans), _p(rot), _p(n1), _p(n2), _p(m), _p(t_err), _p(r_err), _p(nonfinite), int(pair_idx0), _p(rows),
-                                        B, _stream()), "nopesac_metric_rows")
+    _C.nopesac_metric_rows(_p(trans), _p(rot), _p(n1), _p(n2), _p(m), _p(t_err), _p(r_err), _p(nonfinite), int(pair_idx0), _p(rows),
+                           B, _stream())
     return rows
 
 
@@ -721,7 +710,7 @@ def concat_cols(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     rows, Da, Db = a.shape[0], a.shape[-1], b.shape[-1]
     _require(a.dim() == 2 and b.dim() == 2 and b.shape[0] == rows, "concat_cols: [rows, Da], [rows, Db]")
     out = torch.empty(rows, Da + Db, device=a.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_concat_cols(_p(a), Da, _p(b), Db, _p(out), rows, _stream()), "nopesac_concat_cols")
+    _C.nopesac_concat_cols(_p(a), Da, _p(b), Db, _p(out), rows, _stream())
     return out
 
 
@@ -731,7 +720,7 @@ def add_rows_bf16(a: torch.Tensor, b: torch.Tensor):
     D = a.shape[-1]
     a16 = torch.empty(a.shape, device=a.device, dtype=torch.bfloat16)
     ab16 = torch.empty(a.shape, device=a.device, dtype=torch.bfloat16)
-    _lib.check(_L().nopesac_add_rows_bf16(_p(a), _p(b), _p(a16), _p(ab16), a.numel() // D, D, b.numel() // D, _stream()), "nopesac_add_rows_bf16")
+    _C.nopesac_add_rows_bf16(_p(a), _p(b), _p(a16), _p(ab16), a.numel() // D, D, b.numel() // D, _stream())
     return a16, ab16
 
 
@@ -744,10 +733,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, Lq: int
     _require(q.dtype == torch.float32 or (io16 and mfma_bf16), 'argument check failed: q.dtype == torch.float32 or (io16 and mfma_bf16)')
     _require(q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk, 'argument check failed: q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk')
     o = torch.empty((B * Lq, heads * 32), device=q.device, dtype=q.dtype)
-    fn = _L().nopesac_attention_small_bf16io if io16 else (_L().nopesac_attention_small_bf16 if mfma_bf16 else _L().nopesac_attention_small)
-    rc = fn(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0), B, Lq, Lk,
-            heads, scale, _p(qlen), _p(klen), _stream())
-    _lib.check(rc, "nopesac_attention_small" + ("_bf16" if mfma_bf16 else ""))
+    fn = _C.nopesac_attention_small_bf16io if io16 else (_C.nopesac_attention_small_bf16 if mfma_bf16 else _C.nopesac_attention_small)
+    fn(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0), B, Lq, Lk,
+       heads, scale, _p(qlen), _p(klen), _stream())
     return o
 
 
@@ -755,7 +743,7 @@ def transpose_hw_rows(x: torch.Tensor, H: int, W: int) -> torch.Tensor:
     _chk(x, torch.float32)
     B, C = x.shape[0], x.shape[-1]
     y = torch.empty_like(x)
-    _lib.check(_L().nopesac_transpose_hw_rows(_p(x), _p(y), B, H, W, C, _stream()), "nopesac_transpose_hw_rows")
+    _C.nopesac_transpose_hw_rows(_p(x), _p(y), B, H, W, C, _stream())
     return y
 
 
@@ -770,7 +758,7 @@ def count_nonfinite(tensors, counter: Optional[torch.Tensor] = None) -> torch.Te
             _chk(t, torch.float32)
         ptrs = (ctypes.c_void_p * len(grp))(*[_p(t) for t in grp])
         cnts = (ctypes.c_int64 * len(grp))(*[t.numel() for t in grp])
-        _lib.check(_L().nopesac_count_nonfinite_batch(ptrs, cnts, len(grp), _p(counter), _stream()), "nopesac_count_nonfinite_batch")
+        _C.nopesac_count_nonfinite_batch(ptrs, cnts, len(grp), _p(counter), _stream())
     return counter
 
 
@@ -821,7 +809,7 @@ class HostFetch:
                 sizes = (ctypes.c_int64 * n)(*[nb for _, nb, _, _ in grp])
                 dyns = (ctypes.c_void_p * n)(*[_p(dyn) for _, _, _, dyn in grp])
                 offs = (ctypes.c_int64 * n)(*[o for _, _, o, _ in grp])
-                _lib.check(_L().nopesac_gather_bytes(ptrs, sizes, dyns, offs, n, self.host.data_ptr(), _stream()), "nopesac_gather_bytes")
+                _C.nopesac_gather_bytes(ptrs, sizes, dyns, offs, n, self.host.data_ptr(), _stream())
             self._keep = [(t, dyn) for t, _, _, dyn in segs]                     # sources stay allocated until the object goes
             return
         _require(host is None, "HostFetch: more than KERNEL_MAX_BYTES of fixed-size tensors cannot go into a caller-provided buffer")
@@ -874,7 +862,7 @@ def u8_to_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
         out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     _chk(out, torch.float32)
     _require(out.numel() == x.numel(), "u8_to_f32: sizes differ")
-    _lib.check(_L().nopesac_u8_to_f32(_p(x), _p(out), x.numel(), _stream()), "nopesac_u8_to_f32")
+    _C.nopesac_u8_to_f32(_p(x), _p(out), x.numel(), _stream())
     return out
 
 
@@ -882,7 +870,7 @@ def clock_probe(spin_cycles: int = 400000, stream=None) -> torch.Tensor:
     """Enqueue the engine-clock probe (one wave, ~0.2 ms) on `stream` (default: current); returns an int64[2] device tensor
     (shader cycles, 100 MHz ticks) valid once the stream has passed it: MHz = 100 * t[0] / t[1]."""
     out = torch.zeros(2, device="cuda", dtype=torch.int64)
-    _lib.check(_L().nopesac_clock_probe(_p(out), int(spin_cycles), stream.cuda_stream if stream is not None else _stream()), "nopesac_clock_probe")
+    _C.nopesac_clock_probe(_p(out), int(spin_cycles), stream.cuda_stream if stream is not None else _stream())
     return out
 
 
@@ -890,7 +878,7 @@ def normalize_rows(x: torch.Tensor, canonical_sign: bool = False) -> torch.Tenso
     _chk(x, torch.float32)
     D = x.shape[-1]
     y = torch.empty_like(x)
-    _lib.check(_L().nopesac_normalize_rows(_p(x), _p(y), x.numel() // D, D, int(canonical_sign), _stream()), "nopesac_normalize_rows")
+    _C.nopesac_normalize_rows(_p(x), _p(y), x.numel() // D, D, int(canonical_sign), _stream())
     return y
 
 
@@ -914,11 +902,10 @@ def postselect_planes(cls_logits, mask_prob, params, query_feat, H, W, score_thr
         "flags": torch.empty(B, **i32),
     }
     work = torch.empty(B, 9 * nq + 8, **i32)
-    rc = _L().nopesac_postselect_planes_ex(_p(cls_logits), _p(mask_prob), _p(params), _p(query_feat), B, nq, D, h, w, H, W,
-                                           score_thr, mask_thr, overlap_thr, _p(out["n_kept"]), _p(out["kept_idx"]),
-                                           _p(out["planes"]), _p(out["feats"]), _p(out["scores"]), _p(out["areas"]),
-                                           _p(out["centers"]), _p(out["winner"]), _p(out["flags"]), _p(work), int(planar), _stream())
-    _lib.check(rc, "nopesac_postselect_planes_ex")
+    _C.nopesac_postselect_planes_ex(_p(cls_logits), _p(mask_prob), _p(params), _p(query_feat), B, nq, D, h, w, H, W,
+                                    score_thr, mask_thr, overlap_thr, _p(out["n_kept"]), _p(out["kept_idx"]),
+                                    _p(out["planes"]), _p(out["feats"]), _p(out["scores"]), _p(out["areas"]),
+                                    _p(out["centers"]), _p(out["winner"]), _p(out["flags"]), _p(work), int(planar), _stream())
     return out
 
 
@@ -929,9 +916,8 @@ def matcher_sinkhorn(desc_dot, planes1, planes2, cam7, n1, n2, bin_score, offset
     _chk(n1, torch.int32); _chk(n2, torch.int32)
     log_scores = torch.empty(B, nq + 1, nq + 1, device=desc_dot.device, dtype=torch.float32)
     assignment = torch.empty(B, nq, nq, device=desc_dot.device, dtype=torch.float32)
-    rc = _L().nopesac_matcher_sinkhorn(_p(desc_dot), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score),
-                                       offset_mult, normal_mult, iters, match_thr, B, nq, _p(log_scores), _p(assignment), _stream())
-    _lib.check(rc, "nopesac_matcher_sinkhorn")
+    _C.nopesac_matcher_sinkhorn(_p(desc_dot), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score),
+                                offset_mult, normal_mult, iters, match_thr, B, nq, _p(log_scores), _p(assignment), _stream())
     return log_scores, assignment
 
 
@@ -944,9 +930,8 @@ def geo_sequence(assignment, planes1, planes2, n1, n2, init_trans, init_rot, war
     geo_local, geo_global = torch.empty(B, nq, 6, **f32), torch.empty(B, nq, 6, **f32)
     sig, geo_enc = torch.empty(B, nq, **f32), torch.empty(B, nq, 8, **f32)
     m = torch.empty(B, device=dev, dtype=torch.int32)
-    rc = _L().nopesac_geo_sequence(_p(assignment), _p(planes1), _p(planes2), _p(n1), _p(n2), _p(init_trans), _p(init_rot), B, nq,
-                                   int(warp_in_ref), _p(geo_local), _p(geo_global), _p(sig), _p(geo_enc), _p(m), _stream())
-    _lib.check(rc, "nopesac_geo_sequence")
+    _C.nopesac_geo_sequence(_p(assignment), _p(planes1), _p(planes2), _p(n1), _p(n2), _p(init_trans), _p(init_rot), B, nq,
+                            int(warp_in_ref), _p(geo_local), _p(geo_global), _p(sig), _p(geo_enc), _p(m), _stream())
     return geo_local, geo_global, sig, geo_enc, m
 
 
@@ -962,11 +947,10 @@ def ransac_score_maps(geo_local, rot_raw, trans_raw, init_rot, init_trans, m, di
     if diagnostics:
         for k in ("l2_dist", "normal_angle", "offset_dist"):
             out[k] = torch.empty(B, nq + 1, nq, **f32)
-    rc = _L().nopesac_ransac_score_maps(_p(geo_local), _p(rot_raw), _p(trans_raw), _p(init_rot), _p(init_trans), _p(m), B, nq,
-                                        _p(out["rots_all"]), _p(out["trans_all"]), _p(out["normal_score"]), _p(out["param_score"]),
-                                        _p(out.get("l2_dist")), _p(out.get("normal_angle")), _p(out.get("offset_dist")),
-                                        _p(out["dn_sum"]), _p(out["dl2_sum"]), _stream())
-    _lib.check(rc, "nopesac_ransac_score_maps")
+    _C.nopesac_ransac_score_maps(_p(geo_local), _p(rot_raw), _p(trans_raw), _p(init_rot), _p(init_trans), _p(m), B, nq,
+                                 _p(out["rots_all"]), _p(out["trans_all"]), _p(out["normal_score"]), _p(out["param_score"]),
+                                 _p(out.get("l2_dist")), _p(out.get("normal_angle")), _p(out.get("offset_dist")),
+                                 _p(out["dn_sum"]), _p(out["dl2_sum"]), _stream())
     return out
 
 
@@ -983,9 +967,8 @@ def ransac_soft_vote(sf_rot, sf_trans, reg_rot_w, reg_rot_b, reg_trans_w, reg_tr
             init_rot, init_trans]
     for t in args:
         _chk(t, torch.float32)
-    rc = _L().nopesac_ransac_soft_vote(*[_p(t) for t in args], _p(m), B, nq, mode, _p(out["pred_rot"]), _p(out["pred_trans"]),
-                                       _p(out["avg_rot"]), _p(out["avg_trans"]), _p(out["score_rot"]), _p(out["score_trans"]), _stream())
-    _lib.check(rc, "nopesac_ransac_soft_vote")
+    _C.nopesac_ransac_soft_vote(*[_p(t) for t in args], _p(m), B, nq, mode, _p(out["pred_rot"]), _p(out["pred_trans"]),
+                                _p(out["avg_rot"]), _p(out["avg_trans"]), _p(out["score_rot"]), _p(out["score_trans"]), _stream())
     return out
 
 
@@ -1006,8 +989,7 @@ def plane_cam_ref_losses(vote: dict, maps: dict, m, gt_pose, weight: float = 1.0
     for t in args:
         _chk(t, torch.float32)
     losses = torch.empty(7, device=gt_pose.device, dtype=torch.float32)
-    rc = _L().nopesac_plane_cam_ref_losses(*[_p(t) for t in args], _p(m), _p(gt_pose), B, NH - 1, float(weight), _p(losses), _stream())
-    _lib.check(rc, "nopesac_plane_cam_ref_losses")
+    _C.nopesac_plane_cam_ref_losses(*[_p(t) for t in args], _p(m), _p(gt_pose), B, NH - 1, float(weight), _p(losses), _stream())
     return losses
 
 
@@ -1023,18 +1005,16 @@ def camera_pose_loss(est_trans, est_rot, gt_trans, gt_rot, weight: float = 1.0, 
     _require(tuple(est_trans.shape) == (B, 3) and tuple(est_rot.shape) == (B, 4) and tuple(gt_trans.shape) == (B, 3) and
              tuple(gt_rot.shape) == (B, 4), "camera_pose_loss: shapes")
     out = torch.empty(2, device=est_trans.device, dtype=torch.float32)
-    rc = _L().nopesac_camera_pose_loss(_p(est_trans), _p(est_rot), _p(gt_trans), gt_trans.stride(0), _p(gt_rot), gt_rot.stride(0), B,
-                                       float(trans_eps), float(weight), _p(out), _stream())
-    _lib.check(rc, "nopesac_camera_pose_loss")
+    _C.nopesac_camera_pose_loss(_p(est_trans), _p(est_rot), _p(gt_trans), gt_trans.stride(0), _p(gt_rot), gt_rot.stride(0), B,
+                                float(trans_eps), float(weight), _p(out), _stream())
     return out
 
 
 def refilter_assignment(assignment, planes1, planes2, n1, n2, rot, trans):
     B, nq, _ = assignment.shape
     out = torch.empty_like(assignment)
-    rc = _L().nopesac_refilter_assignment(_p(_chk(assignment, torch.float32)), _p(planes1), _p(planes2), _p(n1), _p(n2), _p(_chk(rot, torch.float32)),
-                                          _p(_chk(trans, torch.float32)), B, nq, _p(out), _stream())
-    _lib.check(rc, "nopesac_refilter_assignment")
+    _C.nopesac_refilter_assignment(_p(_chk(assignment, torch.float32)), _p(planes1), _p(planes2), _p(n1), _p(n2), _p(_chk(rot, torch.float32)),
+                                   _p(_chk(trans, torch.float32)), B, nq, _p(out), _stream())
     return out
 
 
@@ -1046,8 +1026,7 @@ def force_k_select(logits: torch.Tensor, query_feat: torch.Tensor, perm: torch.T
              "force_k_select: shapes")
     feats = torch.empty(2 * B, nq, D, device=logits.device, dtype=torch.float32)
     n_kept = torch.empty(2 * B, device=logits.device, dtype=torch.int32)
-    _lib.check(_L().nopesac_force_k_select(_p(logits), n_cls, _p(query_feat), _p(perm), _p(noise), B, nq, K, D, _p(feats), _p(n_kept), _stream()),
-               "nopesac_force_k_select")
+    _C.nopesac_force_k_select(_p(logits), n_cls, _p(query_feat), _p(perm), _p(noise), B, nq, K, D, _p(feats), _p(n_kept), _stream())
     return feats, n_kept
 
 
@@ -1056,8 +1035,8 @@ def rle_labels(winner: torch.Tensor, kept_idx: torch.Tensor, n_kept: torch.Tenso
     _chk(winner, torch.uint8); _chk(kept_idx, torch.int32); _chk(n_kept, torch.int32); _chk(flags, torch.int32)
     V, H, W = winner.shape
     labels = torch.empty((V, W, H), device=winner.device, dtype=torch.uint8)
-    _lib.check(_L().nopesac_rle_labels(_p(winner), _p(kept_idx), _p(n_kept), _p(flags), _p(labels), V, H, W, kept_idx.shape[1],
-                                       _stream()), "nopesac_rle_labels")
+    _C.nopesac_rle_labels(_p(winner), _p(kept_idx), _p(n_kept), _p(flags), _p(labels), V, H, W, kept_idx.shape[1],
+                          _stream())
     return labels
 
 
@@ -1070,9 +1049,8 @@ def rle_transitions(labels: torch.Tensor, n_kept: torch.Tensor, nq: int, offsets
     counts = torch.empty((V, nq), device=labels.device, dtype=torch.int32)
     if positions is not None:
         _chk(offsets, torch.int64); _chk(positions, torch.int32)
-    _lib.check(_L().nopesac_rle_transitions(_p(labels), _p(n_kept), _p(offsets) if positions is not None else None, _p(counts),
-                                            _p(positions) if positions is not None else None, V, W * H, nq, _stream()),
-               "nopesac_rle_transitions")
+    _C.nopesac_rle_transitions(_p(labels), _p(n_kept), _p(offsets) if positions is not None else None, _p(counts),
+                               _p(positions) if positions is not None else None, V, W * H, nq, _stream())
     return counts
 
 
@@ -1084,8 +1062,8 @@ def decode_masks(winner: torch.Tensor, kept_idx: torch.Tensor, n_kept: torch.Ten
     n64 = n_kept.to(torch.int64)
     offsets = (torch.cumsum(n64, 0) - n64).contiguous()
     masks = torch.empty((max(total, 1), H, W), device=winner.device, dtype=torch.uint8)
-    _lib.check(_L().nopesac_decode_masks(_p(winner), _p(kept_idx), _p(n_kept), _p(flags), _p(offsets), _p(masks), V, H, W, kept_idx.shape[1],
-                                         _stream()), "nopesac_decode_masks")
+    _C.nopesac_decode_masks(_p(winner), _p(kept_idx), _p(n_kept), _p(flags), _p(offsets), _p(masks), V, H, W, kept_idx.shape[1],
+                            _stream())
     return masks[:total].view(torch.bool)
 
 
@@ -1098,15 +1076,12 @@ def rle_compress(positions: torch.Tensor, offsets: torch.Tensor, counts: torch.T
     dev = counts.device
     lens = torch.empty(n, device=dev, dtype=torch.int32)
     bbox = torch.empty(n, 4, device=dev, dtype=torch.float64)
-    L = _L()
-    _lib.check(L.nopesac_rle_compress_device(_p(positions), _p(offsets), _p(counts), n, H, W, _p(lens), _p(bbox), None, None, _stream()),
-               "nopesac_rle_compress_device")
+    _C.nopesac_rle_compress_device(_p(positions), _p(offsets), _p(counts), n, H, W, _p(lens), _p(bbox), None, None, _stream())
     ends = torch.cumsum(lens.to(torch.int64), 0)
     out_off = (ends - lens).contiguous()
     total = int(ends[-1].item())                                         # host sync
     out = torch.empty(max(total, 1), device=dev, dtype=torch.uint8)
-    _lib.check(L.nopesac_rle_compress_device(_p(positions), _p(offsets), _p(counts), n, H, W, None, None, _p(out), _p(out_off), _stream()),
-               "nopesac_rle_compress_device")
+    _C.nopesac_rle_compress_device(_p(positions), _p(offsets), _p(counts), n, H, W, None, None, _p(out), _p(out_off), _stream())
     return out[:total], out_off, lens, bbox
 
 
@@ -1119,14 +1094,12 @@ def rle_compress_capped(positions: torch.Tensor, offsets: torch.Tensor, counts: 
     dev = counts.device
     lens = torch.empty(n, device=dev, dtype=torch.int32)
     bbox = torch.empty(n, 4, device=dev, dtype=torch.float64)
-    L = _L()
-    _lib.check(L.nopesac_rle_compress_device(_p(positions), _p(offsets), _p(counts), n, H, W, _p(lens), _p(bbox), None, None, _stream()),
-               "nopesac_rle_compress_device")
+    _C.nopesac_rle_compress_device(_p(positions), _p(offsets), _p(counts), n, H, W, _p(lens), _p(bbox), None, None, _stream())
     ends = torch.cumsum(lens.to(torch.int64), 0)
     out_off = (ends - lens).contiguous()
     out = torch.empty(int(cap), device=dev, dtype=torch.uint8)
-    _lib.check(L.nopesac_rle_compress_device_capped(_p(positions), _p(offsets), _p(counts), n, H, W, _p(lens), _p(out), _p(out_off), int(cap),
-                                                    _stream()), "nopesac_rle_compress_device_capped")
+    _C.nopesac_rle_compress_device_capped(_p(positions), _p(offsets), _p(counts), n, H, W, _p(lens), _p(out), _p(out_off), int(cap),
+                                          _stream())
     return out, out_off, lens, bbox, ends[-1:]
 
 
@@ -1150,10 +1123,9 @@ def gnn_layer(x: torch.Tensor, x_off: int, src: torch.Tensor, src_off: int, out:
     nxt = None
     if W_next is not None and GNN_PREFETCH and next_sets > 0:
         nxt = (ctypes.c_void_p * 6)(*[_p(W_next[k]) for k in ("wq", "wk", "wv", "wm", "w0", "w2")])
-    rc = _L().nopesac_gnn_layer_bf16_pf(_p(x), x_off, _p(src), src_off, _p(out), out_off, n_sets, nq, _p(lens), _p(lens),
-                                        _p(W["wq"]), _p(W["wk"]), _p(W["wv"]), _p(W["wm"]), _p(W["w0"]), _p(W["w2"]),
-                                        _p(W["g1"]), _p(W["b1"]), _p(W["g2"]), _p(W["b2"]), nxt, int(next_sets) if nxt is not None else 0, _stream())
-    _lib.check(rc, "nopesac_gnn_layer_bf16_pf")
+    _C.nopesac_gnn_layer_bf16_pf(_p(x), x_off, _p(src), src_off, _p(out), out_off, n_sets, nq, _p(lens), _p(lens),
+                                 _p(W["wq"]), _p(W["wk"]), _p(W["wv"]), _p(W["wm"]), _p(W["w0"]), _p(W["w2"]),
+                                 _p(W["g1"]), _p(W["b1"]), _p(W["g2"]), _p(W["b2"]), nxt, int(next_sets) if nxt is not None else 0, _stream())
     return out
 
 
@@ -1166,10 +1138,9 @@ def encoder_tail(attn: torch.Tensor, src: torch.Tensor, W: dict, pos=None, want=
     out = {k: torch.empty(M, 256, device=src.device, dtype=torch.float32 if k == "y" else torch.bfloat16) for k in want}
     if pos is not None:
         _chk(pos, torch.float32)
-    rc = _L().nopesac_encoder_tail_bf16(_p(attn), _p(src), _p(W["wo"]), _p(W["bo"]), _p(W["g1"]), _p(W["be1"]), _p(W["w1"]), _p(W["b1"]),
-                                        _p(W["w2"]), _p(W["b2"]), _p(W["g2"]), _p(W["be2"]), _p(pos), 0 if pos is None else pos.shape[0],
-                                        _p(out.get("y")), _p(out.get("y16")), _p(out.get("ypos16")), M, _stream())
-    _lib.check(rc, "nopesac_encoder_tail_bf16")
+    _C.nopesac_encoder_tail_bf16(_p(attn), _p(src), _p(W["wo"]), _p(W["bo"]), _p(W["g1"]), _p(W["be1"]), _p(W["w1"]), _p(W["b1"]),
+                                 _p(W["w2"]), _p(W["b2"]), _p(W["g2"]), _p(W["be2"]), _p(pos), 0 if pos is None else pos.shape[0],
+                                 _p(out.get("y")), _p(out.get("y16")), _p(out.get("ypos16")), M, _stream())
     return out
 
 
@@ -1178,7 +1149,7 @@ def resize_bilinear_u8(img: torch.Tensor, out_h: int, out_w: int) -> torch.Tenso
     _chk(img, torch.uint8)
     H, W, C = img.shape
     out = torch.empty((out_h, out_w, C), device=img.device, dtype=torch.uint8)
-    _lib.check(_L().nopesac_resize_bilinear_u8(_p(img), H, W, C, _p(out), out_h, out_w, _stream()), "nopesac_resize_bilinear_u8")
+    _C.nopesac_resize_bilinear_u8(_p(img), H, W, C, _p(out), out_h, out_w, _stream())
     return out
 
 
@@ -1195,8 +1166,7 @@ def resize_bilinear_u8_batch(imgs, out_h: int, out_w: int, chw: bool = True) -> 
                                  or im.untyped_storage().data_ptr() != st for k, im in enumerate(imgs)):
         return None
     out = torch.empty((n, C, out_h, out_w) if chw else (n, out_h, out_w, C), device=a.device, dtype=torch.uint8)
-    _lib.check(_L().nopesac_resize_bilinear_u8_batch(_p(a), n, stride, H, W, C, _p(out), out_h, out_w, 1 if chw else 0, _stream()),
-               "nopesac_resize_bilinear_u8_batch")
+    _C.nopesac_resize_bilinear_u8_batch(_p(a), n, stride, H, W, C, _p(out), out_h, out_w, 1 if chw else 0, _stream())
     return out
 
 
@@ -1217,7 +1187,7 @@ def mask_head(c1: torch.Tensor, t1: torch.Tensor, w_lat_frag: torch.Tensor, scal
         _require(fold.dim() == 2 and fold.shape[0] == B * nq and fold.shape[1] >= 257 and fold.is_contiguous(), "mask_head: fold [B * nq, >= 257]")
         mw = torch.empty(B, nqp // 32, 16, 2, 32, 8, device=c1.device, dtype=torch.bfloat16)
         mb = torch.empty(B, nqp, device=c1.device, dtype=torch.float32)
-        _lib.check(_L().nopesac_mask_operands(_p(fold), fold.shape[1], _p(mw), _p(mb), B, nq, nqp, _stream()), "nopesac_mask_operands")
+        _C.nopesac_mask_operands(_p(fold), fold.shape[1], _p(mw), _p(mb), B, nq, nqp, _stream())
     else:
         mw = torch.zeros(B, nqp, 256, device=c1.device, dtype=torch.bfloat16)
         mw[:, :nq] = mask_w
@@ -1226,9 +1196,8 @@ def mask_head(c1: torch.Tensor, t1: torch.Tensor, w_lat_frag: torch.Tensor, scal
         mb[:, :nq] = mask_b
     prob = torch.empty((B, nq, H, W) if planar else (B, H, W, nq), device=c1.device, dtype=torch.float32)
     p1 = torch.empty(B, H, W, 256, device=c1.device, dtype=torch.bfloat16) if want_p1 else None
-    rc = _L().nopesac_mask_head_bf16(_p(c1), _p(t1), _p(w_lat_frag), _p(scale), _p(bias), _p(mw), _p(mb), _p(prob), _p(p1), B, H, W, nq,
-                                     int(sigmoid) | (2 if planar else 0) | (4 if taps1 else 0) | (8 if pipe else 0), _stream())
-    _lib.check(rc, "nopesac_mask_head_bf16")
+    _C.nopesac_mask_head_bf16(_p(c1), _p(t1), _p(w_lat_frag), _p(scale), _p(bias), _p(mw), _p(mb), _p(prob), _p(p1), B, H, W, nq,
+                              int(sigmoid) | (2 if planar else 0) | (4 if taps1 else 0) | (8 if pipe else 0), _stream())
     return (prob, p1) if want_p1 else prob
 
 
@@ -1242,10 +1211,9 @@ def decoder_tail(attn: torch.Tensor, tgt: torch.Tensor, W: dict, pos=None, want=
     out = {k: torch.empty(M, 256, device=tgt.device, dtype=torch.float32 if k in ("y", "yn") else torch.bfloat16) for k in want}
     if pos is not None:
         _chk(pos, torch.float32)
-    rc = _L().nopesac_decoder_tail_bf16(_p(attn), _p(tgt), _p(W["wo"]), _p(W["bo"]), _p(W["g3"]), _p(W["be3"]), _p(W["w1"]), _p(W["b1"]),
-                                        _p(W["w2"]), _p(W["b2"]), _p(W["gn"]), _p(W["ben"]), _p(pos), 0 if pos is None else pos.shape[0],
-                                        _p(out.get("y")), _p(out.get("y16")), _p(out.get("ypos16")), _p(out.get("yn")), M, _stream())
-    _lib.check(rc, "nopesac_decoder_tail_bf16")
+    _C.nopesac_decoder_tail_bf16(_p(attn), _p(tgt), _p(W["wo"]), _p(W["bo"]), _p(W["g3"]), _p(W["be3"]), _p(W["w1"]), _p(W["b1"]),
+                                 _p(W["w2"]), _p(W["b2"]), _p(W["gn"]), _p(W["ben"]), _p(pos), 0 if pos is None else pos.shape[0],
+                                 _p(out.get("y")), _p(out.get("y16")), _p(out.get("ypos16")), _p(out.get("yn")), M, _stream())
     return out
 
 
@@ -1261,7 +1229,7 @@ def transformer_tail_forms(M, pre_norm, skip_ffn=False, n_proj_total=0, switches
     """(default form id, bitmask of eligible form ids) of a transformer tail over M tokens whose projections are n_proj_total = n_pos +
     n_proj wide, under the NPS_ETAIL_SW_* switch bits.  Host only: needs no GPU."""
     mask = ctypes.c_uint(0)
-    form = _L().nopesac_transformer_tail_forms(M, int(bool(pre_norm)), int(bool(skip_ffn)), n_proj_total, switches, ctypes.byref(mask))
+    form = _C.nopesac_transformer_tail_forms(M, int(bool(pre_norm)), int(bool(skip_ffn)), n_proj_total, switches, ctypes.byref(mask))
     return form, mask.value
 
 
@@ -1311,11 +1279,9 @@ def transformer_tail(attn: torch.Tensor, src: torch.Tensor, W: dict, *, pre_norm
             _p(out.get("yn")), int(pre_norm), int(skip_ffn), _p(wa), _p(ba), _p(out.get("proj_pos")), na, _p(wb), _p(bb), _p(out.get("proj")), nb,
             M, nptr, nbytes, n_next, next_wg)
     if form is None:
-        rc = _L().nopesac_transformer_tail_bf16_pf(*args, _stream())
-        _lib.check(rc, "nopesac_transformer_tail_bf16_pf")
+        _C.nopesac_transformer_tail_bf16_pf(*args, _stream())
     else:
-        rc = _L().nopesac_transformer_tail_bf16_form(*args, int(form), _stream())
-        _lib.check(rc, "nopesac_transformer_tail_bf16_form")
+        _C.nopesac_transformer_tail_bf16_form(*args, int(form), _stream())
     return out
 
 
@@ -1345,8 +1311,7 @@ def posenet_branch_tail(x_trans: torch.Tensor, x_rots: torch.Tensor, packed: Pos
     _require(x_rots.shape == x_trans.shape, "pose-net branch tail: the two branches have the same shape")
     yt = torch.empty((B, 2, 3, 128), device=x_trans.device, dtype=torch.float32)
     yr = torch.empty_like(yt)
-    _lib.check(_L().nopesac_posenet_branch_tail_bf16(_p(x_trans), _p(x_rots), packed.w, packed.s, packed.b, _p(yt), _p(yr), B, H, W, C, _stream()),
-               "nopesac_posenet_branch_tail_bf16")
+    _C.nopesac_posenet_branch_tail_bf16(_p(x_trans), _p(x_rots), packed.w, packed.s, packed.b, _p(yt), _p(yr), B, H, W, C, _stream())
     return yt, yr
 
 
@@ -1356,8 +1321,7 @@ def conv3x3_c64(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, bias: tor
     B, H, W, C = x.shape
     _require(C == 64 and tuple(w.shape) == (64, 3, 3, 64), 'argument check failed: C == 64 and tuple(w.shape) == (64, 3, 3, 64)')
     y = torch.empty_like(x)
-    _lib.check(_L().nopesac_conv3x3_c64_bf16(_p(x), _p(_frag_weights(w)), _p(scale), _p(bias), _p(y), B, H, W, act, _stream()),
-               "nopesac_conv3x3_c64_bf16")
+    _C.nopesac_conv3x3_c64_bf16(_p(x), _p(_frag_weights(w)), _p(scale), _p(bias), _p(y), B, H, W, act, _stream())
     return y
 
 
@@ -1405,9 +1369,8 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw, *, stride: int = 1, p
         out = torch.empty((B, H, W, Cin), device=dy.device, dtype=torch.float32)
     _require(out.shape == (B, H, W, Cin) and out.dtype == torch.float32, "out must be [B, H, W, Cin] f32")
     wws = torch.empty(w.numel() if stride == 1 else 0, device=dy.device, dtype=torch.float32)
-    rc = _L().nopesac_conv2d_dgrad_f32(_p(dy), _p(w), _p(out), _p(wws) if wws.numel() else None, wws.numel() * 4, B, H, W, Cin, Cout, KH, KW,
-                                       stride, pad, _nhwc_cs(dy), _nhwc_cs(out), _stream())
-    _lib.check(rc, "nopesac_conv2d_dgrad_f32")
+    _C.nopesac_conv2d_dgrad_f32(_p(dy), _p(w), _p(out), _p(wws) if wws.numel() else None, wws.numel() * 4, B, H, W, Cin, Cout, KH, KW,
+                                stride, pad, _nhwc_cs(dy), _nhwc_cs(out), _stream())
     return out
 
 
@@ -1424,12 +1387,11 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, kernel_size: int, *, stride:
     Bd, OH, OW, Cout = dy.shape
     _require(Bd == B and (H + 2 * pad - KH) // stride + 1 == OH and (W + 2 * pad - KW) // stride + 1 == OW, "dy does not match x")
     S = int(splits or wgrad_splits(B * OH * OW, Cout, KH * KW * Cin))
-    nbytes = int(_L().nopesac_conv2d_wgrad_workspace_bytes(Cout, Cin, KH, KW, S))
+    nbytes = int(_C.nopesac_conv2d_wgrad_workspace_bytes(Cout, Cin, KH, KW, S))
     ws = wgrad_workspace(x.device, nbytes)
     dw = torch.empty((Cout, Cin, KH, KW), device=x.device, dtype=torch.float32)
-    rc = _L().nopesac_conv2d_wgrad_f32(_p(x), _p(dy), _p(dw), _p(ws), ws.numel() * 4, B, H, W, Cin, Cout, KH, KW, stride, pad, _nhwc_cs(x),
-                                       _nhwc_cs(dy), S, _stream())
-    _lib.check(rc, "nopesac_conv2d_wgrad_f32")
+    _C.nopesac_conv2d_wgrad_f32(_p(x), _p(dy), _p(dw), _p(ws), ws.numel() * 4, B, H, W, Cin, Cout, KH, KW, stride, pad, _nhwc_cs(x),
+                                _nhwc_cs(dy), S, _stream())
     return dw
 
 
@@ -1445,8 +1407,7 @@ def bn_act_forward(c: torch.Tensor, gamma, beta, mean, var, eps: float, act=ACT_
     C = c.shape[-1]
     _bn_vecs(C, gamma, beta, mean, var)
     y = torch.empty_like(c)
-    rc = _L().nopesac_bn_act_forward_f32(_p(c), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(act), c.numel() // C, C, _p(y), _stream())
-    _lib.check(rc, "nopesac_bn_act_forward_f32")
+    _C.nopesac_bn_act_forward_f32(_p(c), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(act), c.numel() // C, C, _p(y), _stream())
     return y
 
 
@@ -1460,10 +1421,9 @@ def bn_act_backward(dy: torch.Tensor, c: torch.Tensor, gamma, beta, mean, var, e
     dc = torch.empty_like(c)
     dg = torch.empty(C, device=c.device, dtype=torch.float32)
     db = torch.empty(C, device=c.device, dtype=torch.float32)
-    ws = torch.empty(int(_L().nopesac_bn_act_backward_workspace_floats(rows, C)), device=c.device, dtype=torch.float32)
-    rc = _L().nopesac_bn_act_backward_f32(_p(dy), _p(c), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(act), rows, C, _p(dc), _p(dg),
-                                          _p(db), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "nopesac_bn_act_backward_f32")
+    ws = torch.empty(int(_C.nopesac_bn_act_backward_workspace_floats(rows, C)), device=c.device, dtype=torch.float32)
+    _C.nopesac_bn_act_backward_f32(_p(dy), _p(c), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(act), rows, C, _p(dc), _p(dg),
+                                   _p(db), _p(ws), ws.numel(), _stream())
     return dc, dg, db
 
 
@@ -1478,9 +1438,8 @@ def groupnorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma, beta, groups: i
     dg = torch.empty(C, device=x.device, dtype=torch.float32)
     db = torch.empty(C, device=x.device, dtype=torch.float32)
     ws = torch.empty(B * 2 * C, device=x.device, dtype=torch.float32)
-    rc = _L().nopesac_groupnorm_backward_f32(_p(x), _p(dy), _p(gamma), _p(beta), B, H * W, C, groups, float(eps), int(act == ACT_RELU), _p(dx),
-                                             _p(dg), _p(db), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "nopesac_groupnorm_backward_f32")
+    _C.nopesac_groupnorm_backward_f32(_p(x), _p(dy), _p(gamma), _p(beta), B, H * W, C, groups, float(eps), int(act == ACT_RELU), _p(dx),
+                                      _p(dg), _p(db), _p(ws), ws.numel(), _stream())
     return dx, dg, db
 
 
@@ -1490,7 +1449,7 @@ def maxpool_backward(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     B, H, W, C = x.shape
     _require(dy.shape == (B, H // 2, W // 2, C), (dy.shape, x.shape))
     dx = torch.empty_like(x)
-    _lib.check(_L().nopesac_maxpool2x2_backward_f32(_p(x), _p(dy), _p(dx), B, H, W, C, _stream()), "nopesac_maxpool2x2_backward_f32")
+    _C.nopesac_maxpool2x2_backward_f32(_p(x), _p(dy), _p(dx), B, H, W, C, _stream())
     return dx
 
 
@@ -1500,8 +1459,7 @@ def upsample2x_nearest_add_backward(dy: torch.Tensor):
     B, H2, W2, C = dy.shape
     _require(H2 % 2 == 0 and W2 % 2 == 0, dy.shape)
     dx = torch.empty((B, H2 // 2, W2 // 2, C), device=dy.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_upsample2x_nearest_add_backward_f32(_p(dy), _p(dx), B, H2 // 2, W2 // 2, C, _stream()),
-               "nopesac_upsample2x_nearest_add_backward_f32")
+    _C.nopesac_upsample2x_nearest_add_backward_f32(_p(dy), _p(dx), B, H2 // 2, W2 // 2, C, _stream())
     return dx, dy
 
 
@@ -1511,7 +1469,7 @@ def transpose_batched(x: torch.Tensor) -> torch.Tensor:
     _require(x.dim() == 3, x.shape)
     B, R, Cc = x.shape
     y = torch.empty((B, Cc, R), device=x.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_transpose_batched_f32(_p(x), B, R, Cc, _p(y), _stream()), "nopesac_transpose_batched_f32")
+    _C.nopesac_transpose_batched_f32(_p(x), B, R, Cc, _p(y), _stream())
     return y
 
 
@@ -1536,8 +1494,7 @@ def corr_softmax_backward(a: torch.Tensor, da: torch.Tensor, x1: torch.Tensor, x
     ld = a.shape[3]
     ds = torch.empty((B, h, w, P), device=a.device, dtype=torch.float32)
     ds_t = torch.empty((B, P, P), device=a.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_corr_softmax_backward_f32(_p(a), _p(da), B, P, P, ld, ld, _p(ds), _p(ds_t), _stream()),
-               "nopesac_corr_softmax_backward_f32")
+    _C.nopesac_corr_softmax_backward_f32(_p(a), _p(da), B, P, P, ld, ld, _p(ds), _p(ds_t), _stream())
     x2t = transpose_hw_rows(x2.reshape(B, P, C), h, w)                      # [B, P (w,h order), C]
     dx1 = conv2d(ds, transpose_batched(x2t).view(B, C, 1, 1, P), batched_weights=True)            # [B,h,w,C]
     dx2t = conv2d(ds_t.view(B, h, w, P), transpose_batched(x1.reshape(B, P, C)).view(B, C, 1, 1, P), batched_weights=True)
@@ -1558,7 +1515,7 @@ def plane_targets(masks: torch.Tensor, n_host: torch.Tensor, n: torch.Tensor):
     B, nmax, H, W = masks.shape
     centers = torch.empty(B, nmax, 2, device=masks.device, dtype=torch.float32)
     pixel = torch.empty(B, 2, H, W, device=masks.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_plane_targets(_p(masks), n_host.data_ptr(), _p(n), B, nmax, H, W, _p(centers), _p(pixel), _stream()), "nopesac_plane_targets")
+    _C.nopesac_plane_targets(_p(masks), n_host.data_ptr(), _p(n), B, nmax, H, W, _p(centers), _p(pixel), _stream())
     return centers, pixel
 
 
@@ -1585,7 +1542,7 @@ class PlaneCriterionCall:
         self.dims = (L, B, nq, nmax, h, w, H, W)
         self.ml, self.px = ml, px
         f32 = dict(device=dev, dtype=torch.float32)
-        ws_floats = int(_L().nopesac_plane_criterion_workspace_floats(L, B, nq, nmax, h, w))
+        ws_floats = int(_C.nopesac_plane_criterion_workspace_floats(L, B, nq, nmax, h, w))
         self.ws = torch.empty(max(ws_floats, 1), **f32)
         self.cost = torch.empty(LB, nq, nmax, **f32)
         self.match_q = torch.empty(LB, nmax, device=dev, dtype=torch.int32)
@@ -1613,21 +1570,20 @@ class PlaneCriterionCall:
 
 def plane_match_costs(call: PlaneCriterionCall) -> torch.Tensor:
     """The matcher's cost matrices [L*B, nq, nmax] (matcher.py:98-163)."""
-    _lib.check(_L().nopesac_plane_match_costs(ctypes.byref(call.args), _stream()), "nopesac_plane_match_costs")
+    _C.nopesac_plane_match_costs(ctypes.byref(call.args), _stream())
     return call.cost
 
 
 def plane_assign(call: PlaneCriterionCall):
     """Linear sum assignment of call.cost on the device -> (match_q int32 [L*B, nmax], match_gt int32 [L*B, nq])."""
     L, B, nq, nmax = call.dims[:4]
-    _lib.check(_L().nopesac_plane_assign(_p(call.cost), call.args.n_host, call.args.n, L, B, nq, nmax, _p(call.match_q), _p(call.match_gt), _stream()),
-               "nopesac_plane_assign")
+    _C.nopesac_plane_assign(_p(call.cost), call.args.n_host, call.args.n, L, B, nq, nmax, _p(call.match_q), _p(call.match_gt), _stream())
     return call.match_q, call.match_gt
 
 
 def plane_losses(call: PlaneCriterionCall) -> torch.Tensor:
     """The unweighted losses [6 L + 2] for call.match_q / call.match_gt (criterion.py)."""
-    _lib.check(_L().nopesac_plane_losses(ctypes.byref(call.args), _stream()), "nopesac_plane_losses")
+    _C.nopesac_plane_losses(ctypes.byref(call.args), _stream())
     return call.losses
 
 
@@ -1643,7 +1599,7 @@ def plane_losses_backward(call: PlaneCriterionCall, g_losses: torch.Tensor):
     d_px = None if call.px is None else torch.empty_strided(call.px.shape, call.px.stride(), **f32)
     a = call.args
     a.g_losses, a.d_logits, a.d_mask_logits, a.d_centers, a.d_params, a.d_pixel_centers = _p(g_losses), _p(d_lg), _p(d_ml), _p(d_ce), _p(d_pa), _p(d_px)
-    _lib.check(_L().nopesac_plane_losses_backward(ctypes.byref(a), _stream()), "nopesac_plane_losses_backward")
+    _C.nopesac_plane_losses_backward(ctypes.byref(a), _stream())
     return d_lg, d_ml, d_ce, d_pa, d_px
 
 
@@ -1654,6 +1610,5 @@ def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torc
     B, K, _ = gt_corrs.shape
     _require(match1.shape == match2.shape and match1.shape[0] == B, (match1.shape, match2.shape))
     out = torch.empty(B, nq + 1, nq + 1, device=gt_corrs.device, dtype=torch.uint8)
-    _lib.check(_L().nopesac_plane_corr_matrix(_p(gt_corrs), K, _p(match1), _p(match2), B, nq, match1.shape[1], _p(out), _stream()),
-               "nopesac_plane_corr_matrix")
+    _C.nopesac_plane_corr_matrix(_p(gt_corrs), K, _p(match1), _p(match2), B, nq, match1.shape[1], _p(out), _stream())
     return out

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .ops import _C
 
 
 def flip_positions(winner: torch.Tensor, kept_idx: torch.Tensor, n_kept: torch.Tensor, flags: torch.Tensor):
@@ -35,21 +36,20 @@ def flip_positions(winner: torch.Tensor, kept_idx: torch.Tensor, n_kept: torch.T
 
 def compress(positions: np.ndarray, H: int, W: int):
     """One mask's ascending flip positions -> (counts bytes, bbox [x,y,w,h] list of float)."""
-    L = _lib.load()
     positions = np.ascontiguousarray(positions, dtype=np.uint32)
     cap = 6 * (len(positions) + 1)
     buf = ctypes.create_string_buffer(cap)
     bbox = (ctypes.c_double * 4)()
-    n = L.nopesac_rle_compress_host(positions.ctypes.data if len(positions) else None, len(positions), H, W,
-                                    ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.cast(bbox, ctypes.c_void_p))
-    if n < 0:
-        _lib.check(n, "nopesac_rle_compress_host")
+    fn = _C.nopesac_rle_compress_host
+    n = fn(positions.ctypes.data if len(positions) else None, len(positions), H, W, ctypes.cast(buf, ctypes.c_void_p), cap,
+           ctypes.cast(bbox, ctypes.c_void_p))
+    if n < 0:                                             # the result is a value: the string's length, or NPS_E_ARG
+        _lib.check(n, fn.__name__)
     return buf.raw[:n], [float(b) for b in bbox]
 
 
 def compress_batch(positions: np.ndarray, offsets: np.ndarray, counts: np.ndarray, H: int, W: int):
     """All masks of a batch in ONE library call: -> (list of counts bytes, bbox float64 [n,4])."""
-    L = _lib.load()
     n = int(len(counts))
     positions = np.ascontiguousarray(positions, dtype=np.uint32)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -58,10 +58,11 @@ def compress_batch(positions: np.ndarray, offsets: np.ndarray, counts: np.ndarra
     buf = np.empty(cap, np.uint8)
     out_off = np.empty(n + 1, np.int64)
     bbox = np.empty((max(n, 1), 4), np.float64)
-    r = L.nopesac_rle_compress_batch_host(positions.ctypes.data if positions.size else None, offsets.ctypes.data, counts.ctypes.data, n, H, W,
-                                          buf.ctypes.data, cap, out_off.ctypes.data, bbox.ctypes.data)
-    if r < 0:
-        _lib.check(int(r), "nopesac_rle_compress_batch_host")
+    fn = _C.nopesac_rle_compress_batch_host
+    r = fn(positions.ctypes.data if positions.size else None, offsets.ctypes.data, counts.ctypes.data, n, H, W, buf.ctypes.data, cap,
+           out_off.ctypes.data, bbox.ctypes.data)
+    if r < 0:                                             # the result is a value: the total length, or NPS_E_ARG
+        _lib.check(int(r), fn.__name__)
     raw = buf.tobytes()
     return [raw[out_off[i]:out_off[i + 1]] for i in range(n)], bbox[:n]
 

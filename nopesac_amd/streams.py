@@ -24,6 +24,8 @@ from typing import List, Optional
 
 import torch
 
+from .ops import _C, _p
+
 _SPIN = 2_000_000          # shader cycles of the blocking probe (~0.8 ms)
 
 
@@ -31,16 +33,14 @@ def shares_queue(a: "torch.cuda.Stream", b: "torch.cuda.Stream", scratch: torch.
     """True iff work enqueued on `b` waits for earlier work on `a` (= one hardware queue).  Both streams must be idle.
     `scratch`: int64[4] on the device (allocated HERE it would come from the caching allocator's pool of the current stream - and a
     stream's first allocation is a hipMalloc, which waits for the whole device: every pair would look shared)."""
-    from . import _lib
-    L = _lib.load()
     if scratch is None:
         scratch = torch.zeros(4, device=a.device, dtype=torch.int64)
         torch.cuda.synchronize(a.device)
     s0, s1, t1 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
     s0.record(a)
-    _lib.check(L.nopesac_clock_probe(scratch.data_ptr(), _SPIN, a.cuda_stream), "nopesac_clock_probe")
+    _C.nopesac_clock_probe(_p(scratch), _SPIN, a.cuda_stream)
     s1.record(a)
-    _lib.check(L.nopesac_clock_probe(scratch.data_ptr() + 16, 2000, b.cuda_stream), "nopesac_clock_probe")
+    _C.nopesac_clock_probe(_p(scratch) + 16, 2000, b.cuda_stream)
     t1.record(b)
     s1.synchronize()
     t1.synchronize()
@@ -66,9 +66,8 @@ class StreamSet:
             scratch = torch.zeros(4, device=self.device, dtype=torch.int64)
             torch.cuda.synchronize()
             self.pool: List[torch.cuda.Stream] = [torch.cuda.Stream(device=self.device) for _ in range(max(candidates, 2 * self.n))]
-            from . import _lib
             for s in self.pool:            # first use: the runtime creates the stream's queue object now (milliseconds) - not inside a probe
-                _lib.check(_lib.load().nopesac_clock_probe(scratch.data_ptr(), 1000, s.cuda_stream), "nopesac_clock_probe")
+                _C.nopesac_clock_probe(_p(scratch), 1000, s.cuda_stream)
             torch.cuda.synchronize()
 
             def classify():

@@ -11,9 +11,8 @@ from __future__ import annotations
 
 import ctypes
 
-import torch
-
 from . import _lib
+from .ops import _C, _stream
 
 
 class TapeUnsupported(RuntimeError):
@@ -28,7 +27,7 @@ class LaunchTape:
             raw = graph.raw_cuda_graph()
         except Exception as e:                                   # not created with keep_graph=True
             raise TapeUnsupported("raw_cuda_graph(): %r" % (e,))
-        lib = _lib.load()
+        lib = _lib.load()                                        # the raw library: a refused capture is TapeUnsupported, the caller's fallback
         handle = ctypes.c_void_p()
         counts = (ctypes.c_int32 * 4)()
         rc = lib.nopesac_tape_create_ex(ctypes.c_void_p(int(raw)), int(max_streams), ctypes.byref(handle), counts)
@@ -37,22 +36,18 @@ class LaunchTape:
             raise TapeUnsupported("nopesac_tape_create failed (rc=%d): %s" % (rc, msg.decode() if msg else ""))
         self._lib, self._h, self._graph = lib, handle, graph     # the graph's nodes own the argument blocks the tape points at
         self.counts = {"kernels": counts[0], "memsets": counts[1], "memcpys": counts[2], "streams": counts[3]}
-        self._get_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
     def replay(self, stream: int = None, sides=None):
         """Enqueue the recorded launches on `stream` (a raw hipStream_t as int; default: torch's current stream).  `sides`: streams
         (torch.cuda.Stream or raw ints) for the tape's side chains instead of its own ones - see streams.StreamSet."""
         if stream is None:
-            stream = (self._get_stream(torch._C._cuda_getDevice()) if self._get_stream is not None
-                      else torch.cuda.current_stream().cuda_stream)
+            stream = _stream()
         if sides:
             raw = [int(getattr(s, "cuda_stream", s)) for s in sides]
             arr = (ctypes.c_void_p * len(raw))(*raw)
-            rc = self._lib.nopesac_tape_replay_on(self._h, stream, arr, len(raw))
+            _C.nopesac_tape_replay_on(self._h, stream, arr, len(raw))
         else:
-            rc = self._lib.nopesac_tape_replay(self._h, stream)
-        if rc != 0:
-            _lib.check(rc, "nopesac_tape_replay")
+            _C.nopesac_tape_replay(self._h, stream)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

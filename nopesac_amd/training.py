@@ -38,7 +38,8 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _lib, ops
+from . import ops
+from .ops import _C, _p, _stream
 
 PREFIX = "camera_head_list.0."
 CONV_STACKS = ("pixel_decoder", "convs_backbone", "convs_trans", "convs_rots")       # the pixel pose net's conv stacks (conv_stacks=True)
@@ -72,30 +73,18 @@ MLPS = ("geo_encoder", "geo_proj_s1", "decoder_rot", "geo_proj_s2", "decoder_tra
 LINEARS = ("rots", "trans", "rot_score_reg", "trans_score_reg")
 
 
-def _L():
-    return _lib.load()
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def transpose(x: torch.Tensor) -> torch.Tensor:
     """[rows, cols] f32 (rows may be strided) -> contiguous [cols, rows]."""
     assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
     y = torch.empty(x.shape[1], x.shape[0], device=x.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_transpose_f32(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(y), _st()), "nopesac_transpose_f32")
+    _C.nopesac_transpose_f32(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(y), _stream())
     return y
 
 
 def col_sum(x: torch.Tensor) -> torch.Tensor:
     assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
     out = torch.empty(x.shape[1], device=x.device, dtype=torch.float32)
-    _lib.check(_L().nopesac_col_sum_f32(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(out), _st()), "nopesac_col_sum_f32")
+    _C.nopesac_col_sum_f32(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(out), _stream())
     return out
 
 
@@ -116,7 +105,7 @@ class _Linear(torch.autograd.Function):
         g = g.contiguous()
         if ctx.relu:
             gm = torch.empty_like(g)
-            _lib.check(_L().nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(gm), _st()), "nopesac_relu_backward_f32")
+            _C.nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(gm), _stream())
             g = gm
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
@@ -146,9 +135,8 @@ class _ScoreMaps(torch.autograd.Function):
         g_ns, g_ps, g_l2 = (z(t, ref) for t in (g_ns, g_ps, g_l2))
         g_rot, g_tr = torch.empty_like(rot_raw), torch.empty_like(trans_raw)
         g_ir, g_it = torch.empty_like(init_rot), torch.empty_like(init_trans)
-        rc = _L().nopesac_refine_score_maps_backward(_p(geo_local), _p(rot_raw.contiguous()), _p(trans_raw.contiguous()), _p(init_rot), _p(init_trans),
-                                                     _p(m), B, nq, _p(g_ns), _p(g_ps), _p(g_l2), _p(g_rot), _p(g_tr), _p(g_ir), _p(g_it), _st())
-        _lib.check(rc, "nopesac_refine_score_maps_backward")
+        _C.nopesac_refine_score_maps_backward(_p(geo_local), _p(rot_raw.contiguous()), _p(trans_raw.contiguous()), _p(init_rot), _p(init_trans),
+                                              _p(m), B, nq, _p(g_ns), _p(g_ps), _p(g_l2), _p(g_rot), _p(g_tr), _p(g_ir), _p(g_it), _stream())
         return None, g_rot, g_tr, g_ir, g_it, None
 
 
@@ -180,12 +168,11 @@ class _Vote(torch.autograd.Function):
              "pb_rw": torch.empty(B, 4 * 256, **f32), "pb_rb": torch.empty(B, 4, **f32), "pb_tw": torch.empty(B, 3 * 256, **f32),
              "pb_tb": torch.empty(B, 3, **f32), "pb_rrw": torch.empty(B, 64, **f32), "pb_rrb": torch.empty(B, 1, **f32),
              "pb_rtw": torch.empty(B, 64, **f32), "pb_rtb": torch.empty(B, 1, **f32)}
-        rc = _L().nopesac_refine_vote_backward(
-            _p(sf_rot), _p(sf_trans), _p(reg_rot_w), _p(reg_rot_b), _p(reg_trans_w), _p(reg_trans_b), _p(init_rot_feat), _p(init_trans_feat), _p(fused_rot),
-            _p(fused_trans), _p(rots_w), _p(rots_b), _p(trans_w), _p(trans_b), _p(m), B, nq, _p(g_pr), _p(g_pt), _p(g_ar), _p(g_at), _p(g_sr), _p(g_st),
-            _p(o["g_sf_rot"]), _p(o["g_sf_trans"]), _p(o["g_irf"]), _p(o["g_itf"]), _p(o["g_fr"]), _p(o["g_ft"]), _p(o["pb_rw"]), _p(o["pb_rb"]),
-            _p(o["pb_tw"]), _p(o["pb_tb"]), _p(o["pb_rrw"]), _p(o["pb_rrb"]), _p(o["pb_rtw"]), _p(o["pb_rtb"]), _st())
-        _lib.check(rc, "nopesac_refine_vote_backward")
+        _C.nopesac_refine_vote_backward(
+     _p(sf_rot), _p(sf_trans), _p(reg_rot_w), _p(reg_rot_b), _p(reg_trans_w), _p(reg_trans_b), _p(init_rot_feat), _p(init_trans_feat), _p(fused_rot),
+     _p(fused_trans), _p(rots_w), _p(rots_b), _p(trans_w), _p(trans_b), _p(m), B, nq, _p(g_pr), _p(g_pt), _p(g_ar), _p(g_at), _p(g_sr), _p(g_st),
+     _p(o["g_sf_rot"]), _p(o["g_sf_trans"]), _p(o["g_irf"]), _p(o["g_itf"]), _p(o["g_fr"]), _p(o["g_ft"]), _p(o["pb_rw"]), _p(o["pb_rb"]),
+     _p(o["pb_tw"]), _p(o["pb_tb"]), _p(o["pb_rrw"]), _p(o["pb_rrb"]), _p(o["pb_rtw"]), _p(o["pb_rtb"]), _stream())
         red = lambda t, like: col_sum(t).view_as(like)              # per-pair partials -> the parameter's gradient (fixed order)
         return (o["g_sf_rot"], o["g_sf_trans"], red(o["pb_rrw"], reg_rot_w), red(o["pb_rrb"], reg_rot_b), red(o["pb_rtw"], reg_trans_w),
                 red(o["pb_rtb"], reg_trans_b), o["g_irf"], o["g_itf"], o["g_fr"], o["g_ft"], red(o["pb_rw"], rots_w), red(o["pb_rb"], rots_b),
@@ -212,9 +199,8 @@ class _Losses(torch.autograd.Function):
         f32 = dict(device=dev, dtype=torch.float32)
         o = [torch.empty(B, 4, **f32), torch.empty(B, 3, **f32), torch.empty(B, 4, **f32), torch.empty(B, 3, **f32), torch.empty(B, NH, **f32),
              torch.empty(B, NH, **f32), torch.empty(ctx.l2_shape, **f32)]
-        rc = _L().nopesac_refine_losses_backward(_p(pr), _p(pt), _p(ar), _p(at), _p(rots_all), _p(trans_all), _p(sr), _p(st), _p(m), _p(gt),
-                                                 _p(g.contiguous()), B, NH - 1, ctx.weight, *[_p(t) for t in o], _st())
-        _lib.check(rc, "nopesac_refine_losses_backward")
+        _C.nopesac_refine_losses_backward(_p(pr), _p(pt), _p(ar), _p(at), _p(rots_all), _p(trans_all), _p(sr), _p(st), _p(m), _p(gt),
+                                          _p(g.contiguous()), B, NH - 1, ctx.weight, *[_p(t) for t in o], _stream())
         return o[0], o[1], o[2], o[3], o[4], o[5], o[6], None, None, None, None, None
 
 
@@ -231,8 +217,7 @@ class _Normalize(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         out = torch.empty_like(x)
         D = x.shape[-1]
-        rc = _L().nopesac_normalize_rows_backward(_p(x), _p(g.contiguous()), x.numel() // D, D, int(ctx.canonical), _p(out), _st())
-        _lib.check(rc, "nopesac_normalize_rows_backward")
+        _C.nopesac_normalize_rows_backward(_p(x), _p(g.contiguous()), x.numel() // D, D, int(ctx.canonical), _p(out), _stream())
         return out, None
 
 
@@ -251,9 +236,8 @@ class _PoseLoss(torch.autograd.Function):
         est_t, est_q, gt_t, gt_q = ctx.saved_tensors
         B = est_t.shape[0]
         o = [torch.empty_like(est_t), torch.empty_like(est_q), torch.empty_like(gt_t), torch.empty_like(gt_q)]
-        rc = _L().nopesac_camera_pose_loss_backward(_p(est_t), _p(est_q), _p(gt_t), 3, _p(gt_q), 4, B, ctx.eps, ctx.weight, _p(g.contiguous()),
-                                                    *[_p(t) for t in o], _st())
-        _lib.check(rc, "nopesac_camera_pose_loss_backward")
+        _C.nopesac_camera_pose_loss_backward(_p(est_t), _p(est_q), _p(gt_t), 3, _p(gt_q), 4, B, ctx.eps, ctx.weight, _p(g.contiguous()),
+                                             *[_p(t) for t in o], _stream())
         return o[0], o[1], o[2], o[3], None, None
 
 
@@ -397,10 +381,9 @@ class _Attention(torch.autograd.Function):
         B, Lq, Lk, heads, scale = ctx.conf
         g = g.contiguous()
         dq, dk, dv = (torch.empty(t.shape[0], heads * 32, device=q.device, dtype=torch.float32) for t in (q, k, v))
-        rc = _L().nopesac_attention_small_backward(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(g), g.stride(0), B, Lq, Lk,
-                                                   heads, scale, _p(qlen), _p(klen), _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv),
-                                                   dv.stride(0), _st())
-        _lib.check(rc, "nopesac_attention_small_backward")
+        _C.nopesac_attention_small_backward(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(g), g.stride(0), B, Lq, Lk,
+                                            heads, scale, _p(qlen), _p(klen), _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv),
+                                            dv.stride(0), _stream())
         return dq, dk, dv, None, None, None, None, None, None, None
 
 
@@ -438,10 +421,9 @@ class _AttentionFused(torch.autograd.Function):
             dq = torch.empty_like(q)
             qv, kv, vv = q, packed[:, :W], packed[:, W:]
             gq, gk, gv = dq, dpacked[:, :W], dpacked[:, W:]
-        rc = _L().nopesac_attention_small_backward(_p(qv), qv.stride(0), _p(kv), kv.stride(0), _p(vv), vv.stride(0), _p(g), g.stride(0), B, Lq, Lk,
-                                                   heads, scale, _p(qlen), _p(klen), _p(gq), gq.stride(0), _p(gk), gk.stride(0), _p(gv),
-                                                   gv.stride(0), _st())
-        _lib.check(rc, "nopesac_attention_small_backward")
+        _C.nopesac_attention_small_backward(_p(qv), qv.stride(0), _p(kv), kv.stride(0), _p(vv), vv.stride(0), _p(g), g.stride(0), B, Lq, Lk,
+                                            heads, scale, _p(qlen), _p(klen), _p(gq), gq.stride(0), _p(gk), gk.stride(0), _p(gv),
+                                            gv.stride(0), _stream())
         return dq, dpacked, None, None, None, None, None, None, None
 
 
@@ -465,7 +447,7 @@ class _LinearSplit(torch.autograd.Function):
         a, b, w, y = ctx.saved_tensors
         g = g.contiguous()
         gm = torch.empty_like(g)
-        _lib.check(_L().nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(gm), _st()), "nopesac_relu_backward_f32")
+        _C.nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(gm), _stream())
         ga = gb = gw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gx = ops.linear(gm, transpose(w))
@@ -493,10 +475,9 @@ class _LayerNorm(torch.autograd.Function):
         D = x.shape[-1]
         rows = x.numel() // D
         dx, dgamma, dbeta = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
-        n_ws = _L().nopesac_layernorm_backward_workspace_floats(rows)
+        n_ws = _C.nopesac_layernorm_backward_workspace_floats(rows)
         ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
-        rc = _L().nopesac_layernorm_backward(_p(x), _p(gamma), _p(g), rows, D, LN_EPS, _p(dx), _p(dgamma), _p(dbeta), _p(ws), n_ws, _st())
-        _lib.check(rc, "nopesac_layernorm_backward")
+        _C.nopesac_layernorm_backward(_p(x), _p(gamma), _p(g), rows, D, LN_EPS, _p(dx), _p(dgamma), _p(dbeta), _p(ws), n_ws, _stream())
         return dx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None)
 
 
@@ -518,8 +499,7 @@ class _DescDot(torch.autograd.Function):
         B, nq, D = d0.shape
         g = g.contiguous()
         dd0, dd1 = torch.empty_like(d0), torch.empty_like(d1)
-        rc = _L().nopesac_desc_dot_backward(_p(g), _p(d0), _p(d1), _p(n1), _p(n2), B, nq, D, _p(dd0), _p(dd1), _st())
-        _lib.check(rc, "nopesac_desc_dot_backward")
+        _C.nopesac_desc_dot_backward(_p(g), _p(d0), _p(d1), _p(n1), _p(n2), B, nq, D, _p(dd0), _p(dd1), _stream())
         return dd0, dd1, None, None
 
 
@@ -539,8 +519,7 @@ class _SinkhornEmbLoss(torch.autograd.Function):
         log_scores, _assignment = ops.matcher_sinkhorn(dots, planes1, planes2, cam7, n1, n2, bin_score, float(offset_mult), float(normal_mult),
                                                        int(iters), 0.0)
         stats, loss = torch.empty(B, 2, **f32), torch.empty(2, **f32)
-        rc = _L().nopesac_matcher_emb_loss(_p(log_scores), _p(gt_corr), _p(n1), _p(n2), B, nq, _p(stats), _p(loss), _st())
-        _lib.check(rc, "nopesac_matcher_emb_loss")
+        _C.nopesac_matcher_emb_loss(_p(log_scores), _p(gt_corr), _p(n1), _p(n2), B, nq, _p(stats), _p(loss), _stream())
         ctx.conf = (float(offset_mult), float(normal_mult), int(iters))
         ctx.save_for_backward(dots, bin_score, planes1, planes2, cam7, n1, n2, gt_corr)
         ctx.loss = loss
@@ -556,16 +535,14 @@ class _SinkhornEmbLoss(torch.autograd.Function):
         g = g.contiguous().view(1)
         uv = torch.empty(B, iters, 2, nq + 1, **f32)
         scratch = (torch.empty(B, nq + 1, nq + 1, **f32), torch.empty(B, 2, **f32), torch.empty(2, **f32))
-        rc = _L().nopesac_matcher_sinkhorn_train(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
-                                                 normal_mult, iters, _p(gt_corr), B, nq, _p(scratch[0]), _p(uv), _p(scratch[1]), _p(scratch[2]),
-                                                 _st())
-        _lib.check(rc, "nopesac_matcher_sinkhorn_train")
+        _C.nopesac_matcher_sinkhorn_train(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
+                                          normal_mult, iters, _p(gt_corr), B, nq, _p(scratch[0]), _p(uv), _p(scratch[1]), _p(scratch[2]),
+                                          _stream())
         d_dots = torch.empty_like(dots)
         d_bin = torch.empty(B, 1, **f32)
-        rc = _L().nopesac_matcher_sinkhorn_train_backward(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
-                                                          normal_mult, iters, _p(gt_corr), _p(uv), _p(ctx.loss), _p(g), B, nq, _p(d_dots),
-                                                          _p(d_bin), _st())
-        _lib.check(rc, "nopesac_matcher_sinkhorn_train_backward")
+        _C.nopesac_matcher_sinkhorn_train_backward(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
+                                                   normal_mult, iters, _p(gt_corr), _p(uv), _p(ctx.loss), _p(g), B, nq, _p(d_dots),
+                                                   _p(d_bin), _stream())
         return d_dots, col_sum(d_bin).view_as(bin_score), None, None, None, None, None, None, None, None, None
 
 
@@ -686,15 +663,13 @@ class RefineTrainer:
                 if optimizer.upper() == "ADAMW":
                     if not st:
                         st["m1"], st["m2"] = torch.zeros_like(p), torch.zeros_like(p)
-                    rc = _L().nopesac_adamw_step(_p(p), _p(g), _p(st["m1"]), _p(st["m2"]), p.numel(), float(lr), float(betas[0]), float(betas[1]),
-                                                 float(eps), float(wd), self.steps, _st())
-                    _lib.check(rc, "nopesac_adamw_step")
+                    _C.nopesac_adamw_step(_p(p), _p(g), _p(st["m1"]), _p(st["m2"]), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+                                          float(eps), float(wd), self.steps, _stream())
                 elif optimizer.upper() == "SGD":
                     first = "mom" not in st
                     if first:
                         st["mom"] = torch.zeros_like(p)
-                    rc = _L().nopesac_sgd_step(_p(p), _p(g), _p(st["mom"]), p.numel(), float(lr), float(momentum), float(wd), int(first), _st())
-                    _lib.check(rc, "nopesac_sgd_step")
+                    _C.nopesac_sgd_step(_p(p), _p(g), _p(st["mom"]), p.numel(), float(lr), float(momentum), float(wd), int(first), _stream())
                 else:
                     raise NotImplementedError(f"no optimizer type {optimizer}")           # train_NopeSAC.py:158
 
@@ -705,13 +680,13 @@ class RefineTrainer:
         acc = torch.zeros(1, device=grads[0].device, dtype=torch.float32)
         coef = torch.empty(1, device=grads[0].device, dtype=torch.float32)
         for g in grads:
-            _lib.check(_L().nopesac_sumsq_accumulate_f32(_p(g.contiguous()), g.numel(), _p(acc), _st()), "nopesac_sumsq_accumulate_f32")
-        _lib.check(_L().nopesac_clip_coefficient(_p(acc), float(max_norm), _p(coef), _st()), "nopesac_clip_coefficient")
+            _C.nopesac_sumsq_accumulate_f32(_p(g.contiguous()), g.numel(), _p(acc), _stream())
+        _C.nopesac_clip_coefficient(_p(acc), float(max_norm), _p(coef), _stream())
         for p in self.params.values():
             if p.grad is not None:
                 if not p.grad.is_contiguous():
                     p.grad = p.grad.contiguous()
-                _lib.check(_L().nopesac_scale_by_f32(_p(p.grad), p.grad.numel(), _p(coef), _st()), "nopesac_scale_by_f32")
+                _C.nopesac_scale_by_f32(_p(p.grad), p.grad.numel(), _p(coef), _stream())
         return coef
 
     def step_from_cfg(self, cfg):

@@ -71,18 +71,18 @@ def test_header_reader_follows_the_text_and_refuses_what_it_does_not_know():
         return text.replace(old, new)
     row = good.signatures["nopesac_count_nonfinite"]
     assert row[1] is c_int64
-    narrowed = _lib.read_header(planted("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x, int n,"))
+    narrowed = _lib.read_header(planted("nps_status nopesac_count_nonfinite(const float* x, int64_t n,", "nps_status nopesac_count_nonfinite(const float* x, int n,"))
     assert narrowed.signatures["nopesac_count_nonfinite"] == [row[0], c_int, row[2], row[3]]
-    dropped = _lib.read_header(planted("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x,"))
+    dropped = _lib.read_header(planted("nps_status nopesac_count_nonfinite(const float* x, int64_t n,", "nps_status nopesac_count_nonfinite(const float* x,"))
     assert dropped.signatures["nopesac_count_nonfinite"] == [row[0], row[2], row[3]]
     for other in (narrowed, dropped):
         assert {k: v for k, v in other.signatures.items() if k != "nopesac_count_nonfinite"} == {
             k: v for k, v in good.signatures.items() if k != "nopesac_count_nonfinite"}
     for old, new, names in (
-            ("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x, size_t n,", "nopesac_count_nonfinite.*size_t"),
-            ("int nopesac_count_nonfinite(const float* x, int64_t n,", "int nopesac_count_nonfinite(const float* x, int64_t,", "nopesac_count_nonfinite"),
-            ("int nopesac_tape_destroy(void* tape);", "unsigned nopesac_tape_destroy(void* tape);", "nopesac_tape_destroy.*unsigned"),
-            ("int nopesac_tape_destroy(void* tape);", "int nopesac_tape_destroy(void* tape);\nstatic int counter;", "static int counter"),
+            ("nps_status nopesac_count_nonfinite(const float* x, int64_t n,", "nps_status nopesac_count_nonfinite(const float* x, size_t n,", "nopesac_count_nonfinite.*size_t"),
+            ("nps_status nopesac_count_nonfinite(const float* x, int64_t n,", "nps_status nopesac_count_nonfinite(const float* x, int64_t,", "nopesac_count_nonfinite"),
+            ("nps_status nopesac_tape_destroy(void* tape);", "unsigned nopesac_tape_destroy(void* tape);", "nopesac_tape_destroy.*unsigned"),
+            ("nps_status nopesac_tape_destroy(void* tape);", "nps_status nopesac_tape_destroy(void* tape);\nstatic int counter;", "static int counter"),
             ("    int64_t out_ld;", "    size_t out_ld;", "nopesac_mlp_layer.out_ld.*size_t"),
             ("#define NOPESAC_GATHER_MAX_SEGMENTS 32", "#define NOPESAC_GATHER_MAX_SEGMENTS (1 << 5)", "NOPESAC_GATHER_MAX_SEGMENTS")):
         with pytest.raises(_lib.HeaderError, match=names):
@@ -136,6 +136,77 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert rc == -1 and b"null pointer" in lib.nopesac_last_error()
     with pytest.raises(_lib.HipKernelError):
         _lib.check(rc, "nopesac_conv2d_nhwc")
+
+
+def test_header_states_which_results_are_statuses():
+    """include/nopesac_hip.h declares an entry point `nps_status` when its int result is 0 / NPS_E_* / hipError_t; every other result is a
+    value.  The reader's status set and the rest partition the prototypes, the value side is the list written here by hand from the
+    definitions in csrc/, and the reader follows the text: a planted nps_status prototype is a status, a value prototype turned into
+    nps_status becomes one, an unknown return type raises."""
+    from ctypes import c_int
+    from nopesac_amd import _lib
+    values = set(_lib.SIGNATURES) - _lib.STATUS
+    assert _lib.STATUS <= set(_lib.SIGNATURES) and _lib.STATUS and values
+    assert all(_lib.RESTYPES[name] is c_int for name in _lib.STATUS)
+    assert values == {
+        "nopesac_version", "nopesac_last_error", "nopesac_conv2d_p8_sk_workspace_bytes", "nopesac_conv2d_nhwc_forms", "nopesac_mlp_padded_k",
+        "nopesac_mlp_packed_elems", "nopesac_bottleneck_tail_forms", "nopesac_transformer_tail_forms", "nopesac_jpeg_prepare_scan",
+        "nopesac_jpeg_batch_scan_host", "nopesac_jpeg_batch_fill_host", "nopesac_jpeg_batch_free_host", "nopesac_rle_compress_host",
+        "nopesac_rle_compress_batch_host", "nopesac_conv2d_wgrad_workspace_bytes", "nopesac_bn_act_backward_workspace_floats",
+        "nopesac_layernorm_backward_workspace_floats", "nopesac_plane_criterion_workspace_floats", "nopesac_png_info_host",
+        "nopesac_png_decode_host", "nopesac_png_decode_files_host", "nopesac_inflate_zlib_host"}
+    text = open(_lib.HEADER_PATH).read()
+    assert _lib.read_header(text).status == _lib.STATUS
+
+    def planted(old, new):
+        assert text.count(old) == 1, old
+        return _lib.read_header(text.replace(old, new))
+    more = planted("int nopesac_version(void);", "int nopesac_version(void);\nnps_status nopesac_x(const float* a, int n, void* stream);")
+    assert more.status == _lib.STATUS | {"nopesac_x"} and more.restypes["nopesac_x"] is c_int and len(more.signatures["nopesac_x"]) == 3
+    assert planted("int nopesac_version(void);", "nps_status nopesac_version(void);").status == _lib.STATUS | {"nopesac_version"}
+    assert planted("nps_status nopesac_tape_destroy(void* tape);", "int nopesac_tape_destroy(void* tape);").status == _lib.STATUS - {"nopesac_tape_destroy"}
+    for ret in ("nps_result", "hipError_t", "unsigned nps_status"):
+        with pytest.raises(_lib.HeaderError, match="nopesac_x.*" + ret):
+            planted("int nopesac_version(void);", "int nopesac_version(void);\n%s nopesac_x(const float* a, int n, void* stream);" % ret)
+
+
+def test_checked_layer_raises_on_a_status_and_hands_values_through():
+    """_lib.C, the namespace the wrappers call: the refused conv call of test_argument_errors_are_reported_without_a_gpu raises
+    HipKernelError by itself, with the entry point's own name, its status and the library's message; value entry points are the raw
+    functions."""
+    from nopesac_amd import _lib, ops
+    lib = _lib.load()
+    with pytest.raises(_lib.HipKernelError) as e:
+        _lib.C.nopesac_conv2d_nhwc(None, None, None, None, None, None, 1, 1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 0, 0, 0, 0, 0, None)
+    assert str(e.value).startswith("nopesac_conv2d_nhwc failed (rc=-1): ") and "null pointer" in str(e.value)
+    assert str(e.value) == "nopesac_conv2d_nhwc failed (rc=-1): " + lib.nopesac_last_error().decode()
+    assert _lib.C.nopesac_version() == lib.nopesac_version() >= 100
+    for N, K in ((32, 16), (64, 300), (1024, 1280), (0, 5)):
+        assert _lib.C.nopesac_mlp_padded_k(N, K) == lib.nopesac_mlp_padded_k(N, K)
+    assert _lib.C.nopesac_mlp_padded_k(64, 300) >= 300
+    for name in _lib.SIGNATURES:                          # every entry point is there; a value one is the library's function itself
+        assert callable(getattr(_lib.C, name)), name
+        if name not in _lib.STATUS:
+            assert vars(_lib.C)[name].restype is _lib.RESTYPES[name] and vars(_lib.C)[name].argtypes == _lib.SIGNATURES[name], name
+    with pytest.raises(AttributeError, match="nopesac_no_such_entry"):
+        _lib.C.nopesac_no_such_entry
+    assert ops._L() is lib and ops._C is _lib.C           # the raw library stays what tests and scripts read statuses from
+
+
+def test_training_wrappers_refuse_cpu_tensors(monkeypatch):
+    """The training-side wrappers share ops' pointer helper: a CPU tensor raises OpsArgumentError before the library is called (its
+    host address must never reach a kernel)."""
+    from nopesac_amd import _lib, ops, training
+    assert training._p is ops._p and training._stream is ops._stream
+
+    def reached(*args):
+        raise AssertionError("the library was called with a host address")
+    for name in ("nopesac_col_sum_f32", "nopesac_transpose_f32"):
+        monkeypatch.setattr(_lib.C, name, reached)
+    with pytest.raises(ops.OpsArgumentError, match="no CPU path"):
+        training.col_sum(torch.zeros(4, 8))
+    with pytest.raises(ops.OpsArgumentError, match="no CPU path"):
+        training.transpose(torch.zeros(4, 8))
 
 
 def test_no_cpu_fallback():
