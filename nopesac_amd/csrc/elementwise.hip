@@ -455,6 +455,8 @@ extern "C" int nopesac_preprocess_nchw_to_nhwc(const float* x, void* y, const fl
 extern "C" int nopesac_maxpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int K, int stride, int pad,
                                     int dt, void* stream) {
     NPS_CHECK_ARG(x && y && B > 0 && H > 0 && W > 0 && C > 0 && K > 0 && stride > 0, "maxpool: bad args");
+    // (C++ division truncates: with H + 2 pad < K the output size below would come out as 1, not 0, and a pixel would be written)
+    NPS_CHECK_ARG(pad >= 0 && H + 2 * pad >= K && W + 2 * pad >= K, "maxpool: window %d larger than the %d x %d input padded by %d", K, H, W, pad);
     const int OH = (H + 2 * pad - K) / stride + 1, OW = (W + 2 * pad - K) / stride + 1;
     hipStream_t st = (hipStream_t)stream;
     if (dt == NPS_DT_BF16) {
@@ -529,8 +531,7 @@ extern "C" int nopesac_groupnorm_nhwc(const void* x, const float* gamma, const f
     NPS_CHECK_ARG(cpg <= 256 && 256 % cpg == 0, "groupnorm: channels/group %d must divide 256", cpg);
     int gpb = 256 / cpg / 16;  // 16 pixel rows per block
     if (gpb < 1) gpb = 1;
-    while (G % gpb) --gpb;
-    while (256 % (cpg * gpb)) --gpb;
+    while (gpb > 1 && (G % gpb || 256 % (cpg * gpb))) --gpb;     // both at once: the largest gpb that divides G with cpg * gpb dividing 256
     NPS_CHECK_ARG(gpb >= 1 && gpb <= 32, "groupnorm: cannot tile groups");
     dim3 grid(G / gpb, B);
     if (dt == NPS_DT_BF16)
