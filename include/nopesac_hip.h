@@ -795,6 +795,42 @@ nps_status nopesac_rle_compress_device_capped(const uint32_t* positions, const i
 long long nopesac_rle_compress_batch_host(const uint32_t* positions, const long long* offsets, const int* counts, int n_masks,
                                           int H, int W, char* out, long long cap, long long* out_off, double* bbox4);
 
+/* ---- plane AP evaluator (evaluation/mp3d_evaluation.py:467-743 `evaluate_for_planes` and the pycocotools.mask.iou it calls) ----
+ * Ragged quantities use exclusive-offset arrays, int64 [n + 1], so that one launch serves every view of a batch.  Pixel order is
+ * COCO's column-major scan p = x H + y; bit p of a mask is bit (p & 31) of word (p >> 5); a mask has ceil(H W / 32) words and the
+ * unused high bits of its last word are zero.  All four are deterministic (integer counts, no atomics); n_masks = 0 / V = 0 is a
+ * valid call that enqueues nothing.
+ * string_runs: compressed COCO `counts` strings (cocoapi rleFrString), concatenated in `bytes`, string i = bytes[str_off[i] ..
+ *   str_off[i + 1]) -> run lengths.  A mask has at most as many runs as bytes: mask i's runs go to runs + str_off[i] (runs: int32
+ *   [str_off[n_masks]]) and their count to n_runs[i]. */
+nps_status nopesac_rle_string_runs(const uint8_t* bytes, const int64_t* str_off, int n_masks, int32_t* runs, int32_t* n_runs, void* stream);
+/* runs_to_bits: mask i owns runs[run_off[i] .. run_off[i] + n_runs[i]) (n_runs[i] <= run_off[i + 1] - run_off[i]); odd-indexed runs
+ *   are ones.  bits uint32 [n_masks, ceil(H W / 32)], area int32 [n_masks] (number of ones), bad int32 [n_masks]: 1 when a run is
+ *   negative, the running sum passes H W, the runs do not sum to H W, or n_runs[i] does not fit its slice - the mask's words are then
+ *   zero and its area 0.  starts: int32 scratch laid out like runs (the first pixel of every run).  H W < 2^31 - 32. */
+nps_status nopesac_rle_runs_to_bits(const int32_t* runs, const int64_t* run_off, const int32_t* n_runs, int n_masks, int H, int W,
+                                    int32_t* starts, uint32_t* bits, int32_t* area, int32_t* bad, void* stream);
+/* mask_iou_bits: for view v, predictions = rows dt_off[v] .. dt_off[v + 1] of dt_bits (areas in dt_area), GT masks = rows gt_off[v] ..
+ *   gt_off[v + 1] of gt_bits (gt_area; iscrowd uint8 per GT mask, NULL = none).  inter = popcount(dt & gt), union = area_dt + area_gt -
+ *   inter (area_dt for a crowd GT), iou = union > 0 ? (double)inter / (double)union : 0, written at iou_off[v] + i n_gt(v) + j of
+ *   `iou` and `inter`.  max_dt / max_gt: upper bounds of a view's counts; they size the grid only (any count is computed). */
+nps_status nopesac_mask_iou_bits(const uint32_t* dt_bits, const int32_t* dt_area, const int64_t* dt_off, const uint32_t* gt_bits,
+                                 const int32_t* gt_area, const int64_t* gt_off, const uint8_t* iscrowd, const int64_t* iou_off, int V,
+                                 int words, int max_dt, int max_gt, double* iou, int32_t* inter, void* stream);
+#define NPS_PLANE_AP_COLS 10 /* doubles per prediction row of nopesac_plane_ap_assign */
+/* plane_ap_assign: the per-view loop of mp3d_evaluation.py:570-649.  Per view: the IoU block (layout of mask_iou_bits), score f32,
+ *   pred_label int32 (already the dataset category id), pred_plane f32 [.,3]; gt_label int32, gt_plane f32 [.,3].  rows: NPS_PLANE_AP_COLS doubles
+ *   per prediction, in the predictions' own order: score, label, tp_mask, tp_plane, tp_normal, tp_offset, normal_err_deg,
+ *   offset_err, best_iou, gt_id.  Predictions are taken in descending score order (ties: lower index first); gt_id = first maximum
+ *   of the IoU row; true positive for a criterion = equal labels, iou > iou_thresh, normal_err < normal_thresh and / or offset_err <
+ *   offset_thresh, and gt_id not yet taken for THAT criterion.  Errors (utils/metrics.py:6-24) in float64 from the f32 planes.  A view
+ *   without GT: gt_id = -1, best_iou = 0, flags 0, NaN errors.  max_dt <= NPS_PLANE_MAX_QUERIES, max_gt <= 255 (upper bounds of a
+ *   view's counts; a view beyond them is left unwritten), else NPS_E_ARG. */
+nps_status nopesac_plane_ap_assign(const double* iou, const int64_t* iou_off, const int64_t* dt_off, const int64_t* gt_off, const float* score,
+                                   const int32_t* pred_label, const float* pred_plane, const int32_t* gt_label, const float* gt_plane, int V,
+                                   int max_dt, int max_gt, double iou_thresh, double normal_thresh, double offset_thresh, double* rows,
+                                   void* stream);
+
 
 /* Layers 1..5 of both branches of the pixel pose net (camera_net/camera_modules.py `convs_trans` / `convs_rots`: Conv3x3 + BatchNorm +
  * LeakyReLU(0.01), strides 2,1,2,1,2 behind the stride-1 first layer; call site camera_head.py:642-735) in one launch, one workgroup per

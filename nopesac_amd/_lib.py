@@ -10,7 +10,7 @@ import ctypes
 import os
 import re
 from collections import namedtuple
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 from types import SimpleNamespace
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,7 +23,7 @@ class HeaderError(RuntimeError):
 
 
 Header = namedtuple("Header", "signatures restypes constants structs status")
-_SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "float": c_float}
+_SCALARS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "float": c_float, "double": c_double}
 _RETURNS = {"int": c_int, "int64_t": c_int64, "long long": c_int64, "const char*": c_char_p, "void*": c_void_p, "void": None,
             "nps_status": c_int}      # nps_status: the header's `typedef int`, 0 = enqueued, < 0 = NPS_E_*, > 0 = hipError_t
 

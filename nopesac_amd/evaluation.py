@@ -11,7 +11,12 @@ that consumes the hot path's outputs: per-pair pose errors and their summary tab
     :852-860) - the two files the reference's offline eval.py / vis tools read.
   * evaluate_for_matchings()  ~ :746-849: plane-matching precision / recall / F-score from the predictions' RLE instances, the
     GT annotations' RLE masks and `gt_corrs` (mask IoU from nopesac_amd/rle.py instead of pycocotools.mask.iou).
-Plane AP (COCO tooling, pycocotools.cocoeval) stays out of scope.
+  * evaluate_for_planes() / PlaneEvaluator / plane_table()  ~ :467-743: the plane detection table - mask AP, the three plane APs
+    and the normal / offset error statistics, key for key.  RLE decoding, pairwise mask IoU and the score-ordered true-positive
+    assignment run on the device (csrc/plane_eval.hip) for all views of a batch at once; the final reduction (AP over a few thousand
+    rows, once per run) is plain numpy.
+Out of scope: polygon annotations (cocoapi's rasteriser frPyObjects - GT masks must be RLE dicts) and the depth metrics
+(:438-460).
 """
 from __future__ import annotations
 
@@ -121,7 +126,7 @@ class PoseEvaluator:
         return res
 
 
-def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict], iou_thresh: float = 0.5) -> Dict[str, dict]:
+def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict], iou_thresh: float = 0.5, device=None) -> Dict[str, dict]:
     """Plane-matching precision / recall / F-score (mp3d_evaluation.py:746-849).  For every pair: each predicted plane of a view
     is assigned the GT plane with the highest mask IoU (instances[k]["segmentation"] vs the GT annotations' RLE masks); a
     predicted correspondence (i, j) counts as correct when both IoUs reach `iou_thresh` and [gt_i, gt_j] is one of the pair's
@@ -129,8 +134,20 @@ def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict
     predictions.  Returns {assignment key: {"precision", "recall", "F-score", "TP", "Pred. Num.", "GT Num."}} - the reference logs
     one table per key and returns only the last one; it also ignores its iou_thresh argument (0.5 is hard-coded, :830) and divides by
     zero when nothing was matched (here: 0.0).  GT masks must be RLE dicts (compressed or not); polygon annotations need
-    cocoapi's rasteriser (frPyObjects), which is not part of this package."""
+    cocoapi's rasteriser (frPyObjects), which is not part of this package.  device: a GPU - the IoU matrices of all views then come
+    from rle.iou_device_views in one set of launches (the same float64 numbers, bit for bit); None: rle.iou on the host, per view."""
     from . import rle
+    jobs = []
+    for pred in predictions:
+        pair = dataset_dict[pred["0"]["image_id"] + "__" + pred["1"]["image_id"]]
+        for v in ("0", "1"):
+            for ann in pair[v]["annotations"]:
+                if not isinstance(ann["segmentation"], dict):
+                    raise TypeError("evaluate_for_matchings: GT segmentation must be an RLE dict (polygons need cocoapi frPyObjects)")
+            gt_rles = [ann["segmentation"] for ann in pair[v]["annotations"]]
+            jobs.append(([ins["segmentation"] for ins in pred[v]["instances"]], gt_rles, [0] * len(gt_rles)))
+    # device: every view of every pair in one set of launches; host: view by view
+    ious = iter(rle.iou_device_views(jobs, device) if device is not None else (rle.iou(*j) for j in jobs))
     keys = [k for k in predictions[0] if "assignment" in k] if predictions else []
     stats = {k: {"tp": 0, "pred": 0} for k in keys}
     gt_total = 0
@@ -140,13 +157,7 @@ def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict
         gt_total += len(pair["gt_corrs"])
         best_iou, best_gt = [], []
         for v in ("0", "1"):
-            gt_rles = []
-            for ann in pair[v]["annotations"]:
-                seg = ann["segmentation"]
-                if not isinstance(seg, dict):
-                    raise TypeError("evaluate_for_matchings: GT segmentation must be an RLE dict (polygons need cocoapi frPyObjects)")
-                gt_rles.append(seg)
-            m = rle.iou([ins["segmentation"] for ins in pred[v]["instances"]], gt_rles, [0] * len(gt_rles))
+            m = next(ious)
             if m.shape[1] == 0:
                 best_iou.append(np.zeros(m.shape[0])); best_gt.append(np.full(m.shape[0], -1))
             else:
@@ -167,6 +178,251 @@ def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict
         out[k] = {"precision": prec, "recall": rec, "F-score": 2 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0,
                   "TP": tp, "Pred. Num.": npred, "GT Num.": gt_total}
     return out
+
+
+# ---- plane detection table (mp3d_evaluation.py:467-743) -------------------------------------------------------------------------
+from .ops import PLANE_AP_COLS as PLANE_ROW_COLS  # noqa: E402  (the row nopesac_plane_ap_assign writes, named once, in ops.py)
+
+
+def average_precision(scores: np.ndarray, tp: np.ndarray, npos: float) -> float:
+    """utils/VOCap.py compute_ap + xVOCap in float64 without a loop over elements: descending sort (stable: tied scores keep their
+    row order), cumulative TP / FP, precision envelope (reversed cumulative maximum), sum over the recall steps.  No rows: 0."""
+    scores, tp = np.asarray(scores, np.float64).reshape(-1), np.asarray(tp, np.float64).reshape(-1)
+    if scores.size == 0:
+        return 0.0
+    order = np.argsort(-scores, kind="stable")
+    ctp = np.cumsum(tp[order] == 1)
+    cfp = np.cumsum(tp[order] == 0)
+    mrec = np.concatenate([[0.0], ctp / float(npos), [1.0]])
+    mpre = np.concatenate([[0.0], ctp / (cfp + ctp), [0.0]])
+    mpre = np.maximum.accumulate(mpre[::-1])[::-1]
+    i = np.flatnonzero(mrec[1:] != mrec[:-1]) + 1
+    return float(np.sum((mrec[i] - mrec[i - 1]) * mpre[i]))
+
+
+def plane_table(rows: np.ndarray, npos_by_cat: Dict[int, float], iou_thresh: float = 0.5, normal_threshold: float = 30,
+                offset_threshold: float = 0.3, cat_names: Optional[Dict[int, str]] = None) -> Dict[str, float]:
+    """The reference's final reduction (mp3d_evaluation.py:651-743) with exactly its keys.  rows: float64 [n, >= 8], columns
+    PLANE_ROW_COLS (one row per prediction, any order); npos_by_cat: {dataset category id: number of GT planes}.  First the eight
+    error statistics over all predictions (rows with NaN errors - views without GT - are left out; no row at all: percentages 0,
+    means / medians NaN), then per category with npos > 0 the four APs "<metric> - <category name>", then their means over those
+    categories (0 when there is none).  The last mean keeps the reference's key: it formats the NORMAL threshold into
+    "plane_ap@iou0.5offset30.0" (:713-716), while the per-category key carries the offset threshold."""
+    rows = np.asarray(rows, np.float64)
+    rows = rows if rows.ndim == 2 else rows.reshape(-1, len(PLANE_ROW_COLS))
+    names = {1: "plane", **(cat_names or {})}
+    nerr, oerr = rows[:, 6], rows[:, 7]
+    nerr, oerr = nerr[~np.isnan(nerr)], oerr[~np.isnan(oerr)]
+    out: Dict[str, float] = {}
+    for key, e, t in (("%normal<10", nerr, 10), ("%normal<30", nerr, 30), ("%offset<0.5", oerr, 0.5), ("%offset<0.3", oerr, 0.3)):
+        out[key] = float((e < t).sum()) / len(e) * 100 if len(e) else 0.0
+    out["mean_normal"] = float(nerr.mean()) if len(nerr) else float("nan")
+    out["median_normal"] = float(np.median(nerr)) if len(nerr) else float("nan")
+    out["mean_offset"] = float(oerr.mean()) if len(oerr) else float("nan")
+    out["median_offset"] = float(np.median(oerr)) if len(oerr) else float("nan")
+    heads = ("mask_ap@%.1f" % iou_thresh,
+             "plane_ap@iou%.1fnormal%.1foffset%.1f" % (iou_thresh, normal_threshold, offset_threshold),
+             "plane_ap@iou%.1fnormal%.1f" % (iou_thresh, normal_threshold),
+             "plane_ap@iou%.1foffset%.1f" % (iou_thresh, offset_threshold))
+    sums, valid = [0.0] * 4, 0
+    for cat in sorted(npos_by_cat):
+        if npos_by_cat[cat] == 0:
+            continue                                     # no plane of this category in the dataset
+        valid += 1
+        mine = rows[rows[:, 1] == cat]
+        for c, head in enumerate(heads):
+            ap = average_precision(mine[:, 0], mine[:, 2 + c], npos_by_cat[cat])
+            sums[c] += ap
+            out["%s - %s" % (head, names.get(cat, str(cat)))] = ap
+    mean_heads = heads[:3] + ("plane_ap@iou%.1foffset%.1f" % (iou_thresh, normal_threshold),)      # the reference's quirk (:713-716)
+    for c, head in enumerate(mean_heads):
+        out[head] = sums[c] / valid if valid else 0.0
+    return out
+
+
+def _rle_of(seg, who: str) -> dict:
+    if not isinstance(seg, dict):
+        raise TypeError(f"{who}: GT segmentation must be an RLE dict (polygons need cocoapi frPyObjects)")
+    return seg
+
+
+def plane_rows(views: List[dict], device, iou_thresh: float = 0.5, normal_threshold: float = 30, offset_threshold: float = 0.3,
+               id_map: Optional[Dict[int, int]] = None) -> np.ndarray:
+    """The per-prediction part of the reference's evaluator (mp3d_evaluation.py:512-649) for a list of views in ONE set of launches:
+    every mask of every view is decoded into bit-packed form (rle.decode_bits), one launch takes all IoU blocks, one the assignment.
+    views: [{"instances": [{"segmentation", "score", "category_id"}], "pred_plane": [n, 3], "annotations": [{"segmentation", "plane",
+    "category_id"}]}]; id_map: contiguous prediction label -> dataset category id (default {0: 1}).  Returns float64
+    [number of predictions, 10] (PLANE_ROW_COLS), view after view, each view's predictions in their own order.
+    A view with predictions but no annotation gets gt_id = -1, best_iou = 0, no true positive and NaN errors (the reference raises
+    there: argmax of an empty IoU row); plane_table leaves such rows out of the error statistics."""
+    from . import ops, rle
+    id_map = {0: 1} if id_map is None else id_map
+    device = torch.device(device)
+    n_dt = [len(v["instances"]) for v in views]
+    n_gt = [len(v["annotations"]) for v in views]
+    total = int(sum(n_dt))
+    if total == 0:
+        return np.zeros((0, len(PLANE_ROW_COLS)), np.float64)
+    dt_rles = [ins["segmentation"] for v in views for ins in v["instances"]]
+    gt_rles = [_rle_of(a["segmentation"], "plane_rows") for v in views for a in v["annotations"]]
+    bits, area = rle.decode_bits(dt_rles + gt_rles, device)
+    offs = np.zeros((3, len(views) + 1), np.int64)
+    np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
+    planes = [np.asarray(v["pred_plane"].detach().cpu() if torch.is_tensor(v["pred_plane"]) else v["pred_plane"], np.float32).reshape(-1, 3)
+              for v in views]
+    for v, p, k in zip(views, planes, n_dt):
+        if p.shape[0] != k:
+            raise ValueError(f"plane_rows: {k} instances but {p.shape[0]} pred_plane rows")
+    f32 = np.concatenate([np.asarray([ins["score"] for v in views for ins in v["instances"]], np.float32),
+                          np.concatenate(planes).reshape(-1),
+                          np.asarray([a["plane"] for v in views for a in v["annotations"]], np.float32).reshape(-1)])
+    i32 = np.asarray([id_map[int(ins["category_id"])] for v in views for ins in v["instances"]]
+                     + [int(a["category_id"]) for v in views for a in v["annotations"]], np.int32)
+    d_off = torch.from_numpy(offs).to(device)
+    d_f32, d_i32 = torch.from_numpy(f32).to(device), torch.from_numpy(i32).to(device)
+    n_g = int(sum(n_gt))
+    score, pred_plane, gt_plane = d_f32[:total], d_f32[total:4 * total], d_f32[4 * total:]
+    iou, _ = ops.mask_iou_bits(bits[:total], area[:total], d_off[0], bits[total:], area[total:], d_off[1], None, d_off[2],
+                               int(offs[2, -1]), max(n_dt), max(n_gt))
+    rows = ops.plane_ap_assign(iou, d_off[2], d_off[0], d_off[1], score, d_i32[:total], pred_plane, d_i32[total:total + n_g], gt_plane,
+                               max(n_dt), max(n_gt), iou_thresh, normal_threshold, offset_threshold)
+    return rows.cpu().numpy()
+
+
+def _unique_views(records: List[dict], seen: set):
+    """The reference's _siamese_to_single / _siamese_to_coco de-duplication: every image once, first occurrence wins."""
+    for rec in records:
+        for v in ("0", "1"):
+            image_id = rec[v]["image_id"]
+            if image_id not in seen:
+                seen.add(image_id)
+                yield image_id, rec[v]
+
+
+def evaluate_for_planes(predictions: List[dict], dataset_dict: Dict[str, dict], device, iou_thresh: float = 0.5,
+                        normal_threshold: float = 30, offset_threshold: float = 0.3, id_map: Optional[Dict[int, int]] = None,
+                        categories: Optional[List[dict]] = None) -> Dict[str, float]:
+    """Plane detection table (mp3d_evaluation.py:467-743) over kept prediction records, the offline form: predictions = per pair
+    {"0" / "1": {"image_id", "instances", "pred_plane"}}, dataset_dict = {"<id0>__<id1>": {"0" / "1": {"image_id"?, "annotations"}}}
+    (the shape evaluate_for_matchings takes).  Every image counts once (first occurrence wins, in the predictions and in the dataset);
+    a view without instances is skipped; npos counts the annotations of every image of dataset_dict.  categories: the dataset json's
+    `categories` ([{"id", "name"}]) for the key names; id 1 is "plane".  GT masks must be RLE dicts (TypeError otherwise)."""
+    gt_of, npos = {}, {}
+    for key, pair in dataset_dict.items():
+        ids = key.split("__") if "__" in key else (None, None)
+        for v, fallback in zip(("0", "1"), ids):
+            image_id = pair[v].get("image_id", fallback)
+            if image_id in gt_of:
+                continue
+            gt_of[image_id] = pair[v]["annotations"]
+            for a in pair[v]["annotations"]:
+                _rle_of(a["segmentation"], "evaluate_for_planes")
+                npos[int(a["category_id"])] = npos.get(int(a["category_id"]), 0.0) + 1.0
+    views = [{"instances": view["instances"], "pred_plane": view["pred_plane"], "annotations": gt_of[image_id]}
+             for image_id, view in _unique_views(predictions, set()) if len(view.get("instances") or []) and image_id in gt_of]
+    rows = plane_rows(views, device, iou_thresh, normal_threshold, offset_threshold, id_map)
+    names = {int(c["id"]): c["name"] for c in (categories or [])}
+    return plane_table(rows, npos or {1: 0.0}, iou_thresh, normal_threshold, offset_threshold, names)
+
+
+class PlaneEvaluator:
+    """DatasetEvaluator-style plane detection evaluator: reset() / process(inputs, outputs) / evaluate() -> plane_table's dict.
+    process() takes each view of each pair once, by image_id (first occurrence wins; a view without instances is skipped but its
+    annotations still count in npos), and runs decode, IoU and assignment for the whole batch in one set of launches (plane_rows).
+    Ranks see disjoint pairs but may see the same image: every row carries its image's number (image_index[image_id] - the
+    image's index in the dataset json - when given, else the id itself when it is an integer), evaluate() gathers rows and
+    per-image GT counts from all ranks and keeps, per image, the lowest rank's copy, so the table does not depend on the world size.
+    A single process may leave image_index out with any ids (images are numbered as they come); several ranks with string ids
+    need it (ValueError)."""
+
+    def __init__(self, device, iou_thresh: float = 0.5, normal_threshold: float = 30, offset_threshold: float = 0.3,
+                 id_map: Optional[Dict[int, int]] = None, image_index: Optional[Dict[str, int]] = None,
+                 categories: Optional[List[dict]] = None):
+        self.device = torch.device(device)
+        self.iou_thresh, self.normal_threshold, self.offset_threshold = iou_thresh, normal_threshold, offset_threshold
+        self.id_map = {0: 1} if id_map is None else dict(id_map)
+        self.image_index = image_index
+        self.cat_names = {int(c["id"]): c["name"] for c in (categories or [])}
+        self.reset()
+
+    def reset(self):
+        self._seen: set = set()
+        self._numbers: Dict[object, float] = {}     # single process without image_index: images numbered as they come
+        self._rows: List[np.ndarray] = []           # [n, 11]: PLANE_ROW_COLS + image number
+        self._gt: List[np.ndarray] = []             # [m, 3]: image number, category id, count
+
+    def _number(self, image_id) -> float:
+        if self.image_index is not None:
+            return float(self.image_index[image_id])
+        if isinstance(image_id, (int, np.integer)):
+            return float(image_id)
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError(f"PlaneEvaluator: image id {image_id!r} is no integer; with several ranks pass image_index "
+                             "(image id -> index in the dataset json), the same on every rank")
+        return self._numbers.setdefault(image_id, float(len(self._numbers)))
+
+    def _register(self, number: float, cats: Dict[int, int]):
+        """An image this rank has seen, with its GT count per category: one row per category and always at least one (count 0 for
+        an image without annotations) - evaluate() learns from these rows which rank owns an image."""
+        self._gt += [np.array([[number, c, k]], np.float64) for c, k in (cats or {0: 0}).items()]
+
+    def process(self, inputs: List[dict], outputs: List[dict]):
+        views, numbers = [], []
+        for inp, out in zip(inputs, outputs):
+            for v in ("0", "1"):
+                image_id = inp[v].get("image_id")
+                if image_id in self._seen or "annotations" not in inp[v]:
+                    continue
+                self._seen.add(image_id)
+                num, anns = self._number(image_id), inp[v]["annotations"]
+                cats: Dict[int, int] = {}
+                for a in anns:
+                    _rle_of(a["segmentation"], "PlaneEvaluator")
+                    cats[int(a["category_id"])] = cats.get(int(a["category_id"]), 0) + 1
+                self._register(num, cats)
+                o = out[v] if out.get(v) is not None else {}
+                if len(o.get("instances") or []):
+                    views.append({"instances": o["instances"], "pred_plane": o["pred_plane"], "annotations": anns})
+                    numbers.append(num)
+        if views:
+            rows = plane_rows(views, self.device, self.iou_thresh, self.normal_threshold, self.offset_threshold, self.id_map)
+            num = np.repeat(np.asarray(numbers, np.float64), [len(v["instances"]) for v in views])
+            self._rows.append(np.concatenate([rows, num[:, None]], 1))
+
+    @staticmethod
+    def _gather(local: np.ndarray, device) -> List[np.ndarray]:
+        """Per-rank blocks of a [n, w] float64 table, rank order (PoseEvaluator.evaluate's pad / gather / drop)."""
+        dist = torch.distributed
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return [local]
+        dev = device if dist.get_backend() == "nccl" else torch.device("cpu")
+        n = torch.tensor([local.shape[0]], device=dev)
+        counts = [torch.zeros_like(n) for _ in range(dist.get_world_size())]
+        dist.all_gather(counts, n)
+        nmax = int(max(c.item() for c in counts))
+        padded = torch.zeros(max(nmax, 1), local.shape[1], device=dev, dtype=torch.float64)
+        padded[: local.shape[0]] = torch.from_numpy(local).to(dev)
+        allrows = runner.gather_metrics(padded).cpu().numpy()
+        return [allrows[r * max(nmax, 1): r * max(nmax, 1) + int(c.item())] for r, c in enumerate(counts)]
+
+    def evaluate(self) -> Dict[str, float]:
+        rows = np.concatenate(self._rows) if self._rows else np.zeros((0, len(PLANE_ROW_COLS) + 1), np.float64)
+        gts = np.concatenate(self._gt) if self._gt else np.zeros((0, 3), np.float64)
+        owner: Dict[float, int] = {}                 # image number -> the lowest rank that saw it
+        gt_parts = self._gather(gts, self.device)
+        for r, part in enumerate(gt_parts):
+            for num in part[:, 0]:
+                owner.setdefault(float(num), r)
+        npos: Dict[int, float] = {}
+        for r, part in enumerate(gt_parts):
+            for num, cat, k in part:
+                if owner[float(num)] == r and k > 0:
+                    npos[int(cat)] = npos.get(int(cat), 0.0) + float(k)
+        kept = [part[[owner[float(num)] == r for num in part[:, -1]]] if len(part) else part
+                for r, part in enumerate(self._gather(rows, self.device))]
+        return plane_table(np.concatenate(kept)[:, :len(PLANE_ROW_COLS)], npos or {1: 0.0}, self.iou_thresh, self.normal_threshold,
+                           self.offset_threshold, self.cat_names)
 
 
 def optimized_dict(predictions: List[dict]) -> Dict[int, dict]:

@@ -1103,6 +1103,86 @@ def rle_compress_capped(positions: torch.Tensor, offsets: torch.Tensor, counts: 
     return out, out_off, lens, bbox, ends[-1:]
 
 
+# ---- plane AP evaluator (csrc/plane_eval.hip): RLE strings -> runs -> bit masks -> IoU -> true-positive assignment
+PLANE_AP_COLS = ("score", "label", "tp_mask", "tp_plane", "tp_normal", "tp_offset", "normal_err_deg", "offset_err", "best_iou", "gt_id")
+assert len(PLANE_AP_COLS) == _H.NPS_PLANE_AP_COLS       # the names of the row the header sizes
+
+
+def rle_string_runs(data: torch.Tensor, str_off: torch.Tensor):
+    """Compressed COCO counts strings, concatenated (data uint8 [total], str_off int64 [n+1]) -> (runs int32 [total], n_runs int32 [n]):
+    mask i's run lengths are runs[str_off[i] : str_off[i] + n_runs[i]] (a mask never has more runs than bytes)."""
+    _chk(data, torch.uint8); _chk(str_off, torch.int64)
+    n = str_off.numel() - 1
+    _require(n >= 0, "rle_string_runs: str_off holds n + 1 offsets")
+    if data.numel() == 0:                       # only 0-byte strings: the library still wants a buffer to point at
+        data = torch.zeros(1, device=data.device, dtype=torch.uint8)
+    runs = torch.empty(max(data.numel(), 1), device=data.device, dtype=torch.int32)
+    n_runs = torch.empty(n, device=data.device, dtype=torch.int32)
+    _C.nopesac_rle_string_runs(_p(data), _p(str_off), n, _p(runs), _p(n_runs), _stream())
+    return runs, n_runs
+
+
+def rle_runs_to_bits(runs: torch.Tensor, run_off: torch.Tensor, n_runs: torch.Tensor, H: int, W: int, bits: torch.Tensor = None):
+    """Run lengths (runs int32, run_off int64 [n+1], n_runs int32 [n]) -> (bits uint32-as-int32 [n, ceil(H W / 32)], area int32 [n],
+    bad int32 [n]).  bad[i] = 1 (words zero): a negative run, or runs that do not cover exactly H W pixels.  bits: a caller's buffer
+    of at least n rows."""
+    _chk(runs, torch.int32); _chk(run_off, torch.int64); _chk(n_runs, torch.int32)
+    n, words = n_runs.numel(), (H * W + 31) // 32
+    _require(run_off.numel() == n + 1, "rle_runs_to_bits: run_off holds n + 1 offsets")
+    dev = runs.device
+    if runs.numel() == 0:                       # only masks without a run (all bad): the library still wants a buffer to point at
+        runs = torch.zeros(1, device=dev, dtype=torch.int32)
+    if bits is None:
+        bits = torch.empty((max(n, 1), words), device=dev, dtype=torch.int32)[:n]
+    else:
+        _chk(bits, torch.int32)
+        _require(bits.numel() >= n * words, "rle_runs_to_bits: bits buffer too small")
+    starts = torch.empty(max(runs.numel(), 1), device=dev, dtype=torch.int32)
+    area = torch.empty(n, device=dev, dtype=torch.int32)
+    bad = torch.empty(n, device=dev, dtype=torch.int32)
+    _C.nopesac_rle_runs_to_bits(_p(runs), _p(run_off), _p(n_runs), n, H, W, _p(starts), _p(bits), _p(area), _p(bad), _stream())
+    return bits, area, bad
+
+
+def mask_iou_bits(dt_bits, dt_area, dt_off, gt_bits, gt_area, gt_off, iscrowd, iou_off, total: int, max_dt: int, max_gt: int):
+    """Pairwise mask IoU of V views in one launch: view v's predictions are rows dt_off[v]:dt_off[v+1] of dt_bits, its GT masks rows
+    gt_off[v]:gt_off[v+1] of gt_bits (iscrowd uint8 per GT mask or None) -> (iou float64 [total], inter int32 [total]), view v's
+    [n_dt, n_gt] block at iou_off[v].  total = iou_off[V]; max_dt / max_gt: the largest per-view counts (the caller has them)."""
+    for t in (dt_bits, dt_area, gt_bits, gt_area):
+        _chk(t, torch.int32)
+    for t in (dt_off, gt_off, iou_off):
+        _chk(t, torch.int64)
+    if iscrowd is not None:
+        _chk(iscrowd, torch.uint8)
+    V = dt_off.numel() - 1
+    _require(gt_off.numel() == V + 1 and iou_off.numel() == V + 1 and dt_bits.dim() == 2 and gt_bits.dim() == 2
+             and dt_bits.shape[1] == gt_bits.shape[1], "mask_iou_bits: shapes")
+    dev = dt_bits.device
+    iou = torch.zeros(max(total, 1), device=dev, dtype=torch.float64)
+    inter = torch.zeros(max(total, 1), device=dev, dtype=torch.int32)
+    _C.nopesac_mask_iou_bits(_p(dt_bits), _p(dt_area), _p(dt_off), _p(gt_bits), _p(gt_area), _p(gt_off), _p(iscrowd), _p(iou_off), V,
+                             max(dt_bits.shape[1], 1), max_dt, max_gt, _p(iou), _p(inter), _stream())
+    return iou[:total], inter[:total]
+
+
+def plane_ap_assign(iou, iou_off, dt_off, gt_off, score, pred_label, pred_plane, gt_label, gt_plane, max_dt: int, max_gt: int,
+                    iou_thresh: float, normal_thresh: float, offset_thresh: float) -> torch.Tensor:
+    """The reference's score-ordered true-positive assignment (mp3d_evaluation.py:570-649) for V views in one launch ->
+    rows float64 [n_pred, 10] (PLANE_AP_COLS), in the predictions' own order."""
+    _chk(iou, torch.float64); _chk(score, torch.float32); _chk(pred_label, torch.int32); _chk(pred_plane, torch.float32)
+    _chk(gt_label, torch.int32); _chk(gt_plane, torch.float32)
+    for t in (iou_off, dt_off, gt_off):
+        _chk(t, torch.int64)
+    V, n = dt_off.numel() - 1, score.numel()
+    _require(gt_off.numel() == V + 1 and iou_off.numel() == V + 1 and pred_label.numel() == n and pred_plane.numel() == 3 * n
+             and gt_plane.numel() == 3 * gt_label.numel(), "plane_ap_assign: shapes")
+    rows = torch.full((n, len(PLANE_AP_COLS)), float("nan"), device=score.device, dtype=torch.float64)
+    _C.nopesac_plane_ap_assign(_p(iou), _p(iou_off), _p(dt_off), _p(gt_off), _p(score), _p(pred_label), _p(pred_plane), _p(gt_label),
+                               _p(gt_plane), V, max_dt, max_gt, float(iou_thresh), float(normal_thresh), float(offset_thresh), _p(rows),
+                               _stream())
+    return rows
+
+
 GNN_PREFETCH = os.environ.get("NOPESAC_GNN_PREFETCH", "1") != "0"
 
 

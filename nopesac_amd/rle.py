@@ -6,6 +6,9 @@ positions where the plane's mask flips along the column-major scan; no [n,H,W] m
 nopesac_rle_compress_device (a workgroup per mask) turns the flips into the compressed counts strings and the [x, y, w, h]
 boxes, still on the device; the host receives finished byte strings.  Host syncs: two size reads (positions buffer, byte buffer).
 nopesac_rle_compress_host / _batch_host (same library, plain C) are the host forms of the same encoder.
+
+Reading side (evaluation): counts_of / decode / iou on the host; decode_bits / iou_device on the device (csrc/plane_eval.hip:
+nopesac_rle_string_runs -> nopesac_rle_runs_to_bits -> nopesac_mask_iou_bits), bit-packed masks and IoU by popcount.
 """
 from __future__ import annotations
 
@@ -195,3 +198,98 @@ def iou(dt: List[dict], gt: List[dict], iscrowd=None) -> np.ndarray:
     crowd = np.zeros(len(gt), bool) if iscrowd is None else np.asarray(iscrowd, bool)
     union = np.where(crowd[None, :], ad, ad + ag - inter)
     return np.where(union > 0, inter / np.maximum(union, 1e-300), 0.0)
+
+
+# ---- the same on the device (csrc/plane_eval.hip): strings -> runs -> bit-packed masks -> IoU by popcount
+def decode_bits(rles: List[dict], device):
+    """COCO RLE dicts (all of one `size`) -> (bits int32 [n, ceil(H W / 32)], area int32 [n]) on `device`: bit p & 31 of word p >> 5
+    is pixel p = x H + y of the column-major scan.  Compressed `counts` (bytes / str) are parsed by nopesac_rle_string_runs,
+    uncompressed lists are uploaded as runs; one upload and one launch per kind, whatever the number of masks.  One host sync (the
+    `bad` flags).  Raises ValueError when the masks differ in size or a mask's runs do not cover exactly H W pixels (what decode()
+    asserts on the host)."""
+    device = torch.device(device)
+    n = len(rles)
+    sizes = {tuple(int(s) for s in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"decode_bits: masks of different sizes in one call: {sorted(sizes)}")
+    if n == 0:
+        return torch.empty((0, 0), device=device, dtype=torch.int32), torch.empty(0, device=device, dtype=torch.int32)
+    H, W = next(iter(sizes))
+    kinds = {True: [], False: []}                                       # compressed?
+    for i, r in enumerate(rles):
+        kinds[isinstance(r["counts"], (bytes, str))].append(i)
+    parts = []
+    if kinds[True]:
+        strs = [rles[i]["counts"] for i in kinds[True]]
+        strs = [s.encode("ascii") if isinstance(s, str) else bytes(s) for s in strs]
+        off = np.zeros(len(strs) + 1, np.int64)
+        np.cumsum([len(s) for s in strs], out=off[1:])
+        blob = b"".join(strs)
+        host = torch.from_numpy(np.concatenate([np.frombuffer(blob + bytes(-len(blob) % 8), np.uint8), off.view(np.uint8)]))
+        dev = host.to(device)                                           # one upload: the bytes (padded to 8) and their offsets
+        nb = host.numel() - off.nbytes
+        data, str_off = dev[:int(off[-1])], dev[nb:].view(torch.int64)
+        runs, n_runs = ops.rle_string_runs(data, str_off)
+        parts.append((kinds[True], ops.rle_runs_to_bits(runs, str_off, n_runs, H, W)))
+    if kinds[False]:
+        lists = [np.asarray(rles[i]["counts"], dtype=np.int64).reshape(-1) for i in kinds[False]]
+        off = np.zeros(len(lists) + 1, np.int64)
+        np.cumsum([len(c) for c in lists], out=off[1:])
+        allc = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        if allc.size and (allc.min() < -2**31 or allc.max() >= 2**31):
+            raise ValueError("decode_bits: a run length does not fit 32 bits")
+        lens = np.diff(off)
+        tail = np.concatenate([allc, lens, np.zeros((allc.size + lens.size) % 2, np.int64)]).astype(np.int32)
+        dev = torch.from_numpy(np.concatenate([off, tail.view(np.int64)])).to(device)      # one upload: offsets, runs, counts
+        run_off, tail = dev[:off.size], dev[off.size:].view(torch.int32)
+        runs, n_runs = tail[:allc.size], tail[allc.size:allc.size + lens.size]
+        parts.append((kinds[False], ops.rle_runs_to_bits(runs, run_off, n_runs, H, W)))
+    if len(parts) == 1:
+        bits, area, bad = parts[0][1]
+    else:
+        words = (H * W + 31) // 32
+        bits = torch.empty((n, words), device=device, dtype=torch.int32)
+        area = torch.empty(n, device=device, dtype=torch.int32)
+        bad = torch.empty(n, device=device, dtype=torch.int32)
+        for idx, (b, a, d) in parts:
+            where = torch.as_tensor(idx, device=device)
+            bits[where], area[where], bad[where] = b, a, d
+    if bool(bad.any().item()):                                          # host sync
+        which = torch.nonzero(bad).view(-1).tolist()
+        raise ValueError(f"decode_bits: RLE run lengths do not cover the image (masks {which[:8]} of {n})")
+    return bits, area
+
+
+def iou_device_views(views, device) -> List[np.ndarray]:
+    """rle.iou for many views at once: views = [(dt RLEs, gt RLEs, iscrowd or None)] -> [len(dt), len(gt)] float64 matrices, bit
+    for bit those of iou().  All masks of one image size go through ONE upload per kind, one decode and one nopesac_mask_iou_bits
+    launch, whatever the number of views; one copy back."""
+    device = torch.device(device)
+    out = [np.zeros((len(v[0]), len(v[1])), np.float64) for v in views]
+    by_size = {}
+    for k, (dt, gt, _) in enumerate(views):
+        if len(dt) and len(gt):
+            by_size.setdefault(tuple(int(s) for s in dt[0]["size"]), []).append(k)
+    for ks in by_size.values():
+        n_dt, n_gt = [len(views[k][0]) for k in ks], [len(views[k][1]) for k in ks]
+        bits, area = decode_bits([r for k in ks for r in views[k][0]] + [r for k in ks for r in views[k][1]], device)
+        offs = np.zeros((3, len(ks) + 1), np.int64)
+        np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
+        crowd = np.concatenate([np.zeros(len(views[k][1]), np.uint8) if views[k][2] is None else np.asarray(views[k][2], bool).astype(np.uint8)
+                                for k in ks])
+        packed = np.concatenate([offs.reshape(-1), np.concatenate([crowd, np.zeros(-crowd.size % 8, np.uint8)]).view(np.int64)])
+        dev = torch.from_numpy(packed).to(device)                        # one upload: the three offset rows and the crowd flags
+        d_off, d_crowd = dev[:offs.size].view(3, -1), dev[offs.size:].view(torch.uint8)[:crowd.size]
+        nd = int(offs[0, -1])
+        m, _ = ops.mask_iou_bits(bits[:nd], area[:nd], d_off[0], bits[nd:], area[nd:], d_off[1], d_crowd, d_off[2], int(offs[2, -1]),
+                                 max(n_dt), max(n_gt))
+        m = m.cpu().numpy()
+        for j, k in enumerate(ks):
+            out[k] = m[offs[2, j]:offs[2, j + 1]].reshape(n_dt[j], n_gt[j])
+    return out
+
+
+def iou_device(dt: List[dict], gt: List[dict], iscrowd=None, device="cuda") -> np.ndarray:
+    """rle.iou on the device: the same [len(dt), len(gt)] float64 matrix, bit for bit (the counts are exact integers and the
+    quotient is the float64 quotient of the same two integers)."""
+    return iou_device_views([(dt, gt, iscrowd)], device)[0]

@@ -23,7 +23,7 @@ import torch
 
 from . import runner
 from .config import get_cfg
-from .evaluation import PoseEvaluator, create_small_table, dump_predictions, evaluate_for_matchings
+from .evaluation import PlaneEvaluator, PoseEvaluator, create_small_table, dump_predictions, evaluate_for_matchings
 from .registry import build_model
 from .synth import synth_pair, synth_state_dict
 
@@ -52,6 +52,9 @@ def default_argument_parser():
     ap.add_argument("--output", default="", help="write the result summary JSON here")
     ap.add_argument("--eval-matchings", action="store_true", help="plane-matching precision / recall / F-score (mp3d_evaluation.py:746-849): "
                     "needs pairs with `gt_corrs` and RLE `annotations` (the dataset json's own fields)")
+    ap.add_argument("--eval-planes", action="store_true", help="plane detection table (mp3d_evaluation.py:467-743): mask AP, the three plane APs and "
+                    "the normal / offset error statistics; RLE decoding, mask IoU and the true-positive assignment run on the GPU (csrc/plane_eval.hip), "
+                    "so the model must be on one.  Needs pairs whose views carry RLE `annotations` with `plane` and `category_id`")
     ap.add_argument("--dump-dir", default="", help="write NopeSAC_instances_predictions.pth + continuous.pkl here (eval_full_scene)")
     ap.add_argument("--stub-model", action="store_true", help="TEST ONLY (results are marked invalid): the CLI's sharding, batch loop, evaluator "
                     "gather and dumps around a stub that fabricates result dicts instead of running the model - what the gloo CPU tests drive at "
@@ -104,12 +107,15 @@ def load_pairs(args, cfg=None):
     return pairs
 
 
-def inference_on_dataset(model, pairs, evaluator, pairs_per_batch: int, keep_outputs: list = None, inflight: int = 1):
+def inference_on_dataset(model, pairs, evaluator, pairs_per_batch: int, keep_outputs: list = None, inflight: int = 1, also=()):
     """Batch loop of detectron2's inference_on_dataset (eval mode, no_grad, timing log).
     inflight > 1 (GPU only): that many batches are in flight on their own HIP streams - batch i's host-to-device copies and forward
     are enqueued before the results of batch i - inflight + 1 are fetched, packaged and handed to the evaluator (in order); the
-    head stages of one batch then run under the convolutions of the next (2-3x the strictly serial rate)."""
+    head stages of one batch then run under the convolutions of the next (2-3x the strictly serial rate).
+    also: further evaluators fed from the same (batch, outputs) stream, e.g. the PlaneEvaluator."""
     evaluator.reset()
+    for ev in also:
+        ev.reset()
     model.eval()
     t0, n_done, t_compute = time.perf_counter(), 0, 0.0
     on_gpu = torch.cuda.is_available() and next(model.parameters()).is_cuda
@@ -128,6 +134,8 @@ def inference_on_dataset(model, pairs, evaluator, pairs_per_batch: int, keep_out
     def consume(batch, outputs):
         nonlocal n_done
         evaluator.process(batch, outputs)
+        for ev in also:
+            ev.process(batch, outputs)
         if keep_outputs is not None:         # what evaluate_for_matchings reads: ids, RLE instances, assignment matrices
             for out in outputs:
                 keep_outputs.append({**{v: {"image_id": out[v]["image_id"], "instances": out[v]["instances"]} for v in "01"},
@@ -247,7 +255,11 @@ def tune_kernels(model, cfg, pairs_per_batch: int, rank: int = 0) -> int:
 
 def main(argv=None):
     """Entry point (test_NopeSAC.py:207-216): `--num-gpus N` outside a torchrun environment starts N ranks itself."""
-    args = default_argument_parser().parse_args(argv)
+    parser = default_argument_parser()
+    args = parser.parse_args(argv)
+    if args.eval_planes and args.stub_model:
+        parser.error("--eval-planes cannot run with --stub-model: the plane evaluator's kernels need a GPU and real plane instances, "
+                     "the stub fabricates results without either")
     if args.num_gpus > 1 and "WORLD_SIZE" not in os.environ:
         return runner.launch(_main_rank, args.num_gpus, (args,))
     return _main_rank(args)
@@ -283,21 +295,43 @@ def _main_rank(args):
     logger.info("rank %d/%d: weights=%s pairs [%d,%d) of %d", rank, world, src, lo, hi, len(pairs))
     evaluator = PoseEvaluator(keep_predictions=bool(args.dump_dir))
     kept = [] if args.eval_matchings else None
+    on_gpu = next(model.parameters()).is_cuda
+    annotated = pairs.entries if hasattr(pairs, "entries") else pairs           # (a LazyPairs keeps the json entries: no pixels needed here)
+    plane_evaluator = None
+    if args.eval_planes:
+        if not on_gpu:
+            raise RuntimeError("--eval-planes needs the model on a GPU (MODEL.DEVICE cuda): RLE decoding, mask IoU and the true-positive "
+                               "assignment are HIP kernels, there is no host path")
+        image_index = {}                         # an image's number = its first position in the dataset, the same on every rank
+        for p in annotated:
+            for v in "01":
+                if "annotations" in p[v]:
+                    image_index.setdefault(p[v].get("image_id"), len(image_index))
+        if image_index:
+            plane_evaluator = PlaneEvaluator(next(model.parameters()).device, image_index=image_index)
+        elif rank == 0:
+            logger.warning("--eval-planes: no pair carries annotations; nothing to evaluate")
     try:
-        timing = inference_on_dataset(model, pairs[lo:hi], evaluator, args.pairs_per_batch, kept, inflight=args.inflight)
+        timing = inference_on_dataset(model, pairs[lo:hi], evaluator, args.pairs_per_batch, kept, inflight=args.inflight,
+                                      also=(plane_evaluator,) if plane_evaluator is not None else ())
     finally:
         gc.unfreeze()
     results = evaluator.evaluate()
+    if plane_evaluator is not None:
+        table = plane_evaluator.evaluate()       # (a collective: every rank calls it)
+        results["plane"] = table
+        if rank == 0:
+            logger.info("Detection metrics: \n%s", create_small_table({k: v for k, v in table.items() if "ap@" in k}))
+            logger.info("Plane metrics: \n%s", create_small_table({k: v for k, v in table.items() if "ap@" not in k}))
     if args.eval_matchings:
         if world > 1:                            # comm.gather semantics: rank-ordered concatenation
             parts = [None] * world
             torch.distributed.all_gather_object(parts, kept)
             kept = [p for part in parts for p in part]
-        annotated = pairs.entries if hasattr(pairs, "entries") else pairs           # (a LazyPairs keeps the json entries: no pixels needed here)
         dataset_dict = {p["0"]["image_id"] + "__" + p["1"]["image_id"]: p for p in annotated if "gt_corrs" in p}
         if rank == 0 and dataset_dict:
             results["matching"] = evaluate_for_matchings([k for k in kept if k["0"]["image_id"] + "__" + k["1"]["image_id"] in dataset_dict],
-                                                         dataset_dict)
+                                                         dataset_dict, device=next(model.parameters()).device if on_gpu else None)
             for k, v in results["matching"].items():
                 logger.info("Plane metrics (%s):\n%s", k, create_small_table({kk: float(vv) for kk, vv in v.items()}))
         elif rank == 0:
@@ -312,7 +346,7 @@ def _main_rank(args):
             logger.info("wrote %s", files)
     if rank == 0:
         for k, v in results.items():
-            if isinstance(v, dict) and v and all(isinstance(x, (int, float)) for x in v.values()):
+            if k != "plane" and isinstance(v, dict) and v and all(isinstance(x, (int, float)) for x in v.values()):
                 logger.info("%s metrics (final output mode -> %s):\n%s", k, cfg.MODEL.CAMERA_HEAD.INFERENCE_OUT_CAM_TYPE,
                             create_small_table({kk: float(vv) for kk, vv in v.items()}))
         if args.output:
