@@ -830,6 +830,30 @@ nps_status nopesac_plane_ap_assign(const double* iou, const int64_t* iou_off, co
                                    const int32_t* pred_label, const float* pred_plane, const int32_t* gt_label, const float* gt_plane, int V,
                                    int max_dt, int max_gt, double iou_thresh, double normal_thresh, double offset_thresh, double* rows,
                                    void* stream);
+#define NPS_RECON_AP_COLS 8 /* doubles per predicted entry of nopesac_recon_ap_assign */
+/* recon_ap_assign: the per-pair part of the reference's offline `eval.py --evaluate AP` (evaluate_ap_by_idx :343-619, get_maskiou_merged
+ *   :657-779, evaluate_by_idx / inst_bench_image :830-913, get_plane_params_in_global utils/mesh_utils.py:89-105).  Pair i owns views
+ *   2 i and 2 i + 1 of dt_off / gt_off / iou_off (int64 [2 P + 1], the layout mask_iou_bits writes), the cameras pred_cam / gt_cam
+ *   (7 doubles per pair: position, then quaternion w x y z; it need not be a unit quaternion) and the correspondences
+ *   pred_corr[pred_corr_off[i] .. pred_corr_off[i + 1]) / gt_corr likewise: int32 pairs (plane of view 0, plane of view 1), the
+ *   predicted ones in row-major order of the assignment matrix.  Both views' planes go to view 1's frame (view 0 through the camera);
+ *   entries = view 0's unmatched planes in index order, view 1's, then one per correspondence (prediction: offset mean, score max,
+ *   normal = top eigenvector of the two unit normals' outer products; GT: view 0's plane).  Errors [predicted entries, GT entries] in
+ *   float64: |offset difference|, acos|normal dot| in degrees, merged mask IoU (single - single: the view's IoU or 0 across views;
+ *   merged - single: the IoU in the single's view; merged - merged: the mean of both views).  Criteria all, -offset, -normal, -mask,
+ *   -normal-offset: iou >= (.5 .5 .5 0 .5), normal <= (30 30 1000 30 1000), offset <= (1 1000 1 1 1000).  Entries are visited IN ENTRY
+ *   ORDER; each claims the first GT entry its criterion flags and is a true positive iff nobody claimed it before.
+ *   rows: NPS_RECON_AP_COLS doubles per predicted entry - score, the five flags, the entry's plane in view 0 and in view 1 (-1: none) -
+ *   pair i's entries from row dt_off[2 i] - pred_corr_off[i] on; n_rows = dt_off[2 P] - pred_corr_off[P] rows in all.
+ *   n_gt_entries int32 [P].  bad int32 [P]: 1 for a pair with a correspondence index out of range, a plane in two correspondences, or
+ *   counts beyond the limits / offsets that do not fit n_rows - none of its rows is written and n_gt_entries is 0.
+ *   errs (NULL: none): pair i's three matrices [3][predicted entries][GT entries] (offset, normal, IoU) at errs + err_off[i].
+ *   max_dt <= NPS_PLANE_MAX_QUERIES, max_gt <= 255 per VIEW, else NPS_E_ARG.  Deterministic, no atomics; P = 0 enqueues nothing. */
+nps_status nopesac_recon_ap_assign(const double* iou, const int64_t* iou_off, const int64_t* dt_off, const int64_t* gt_off, const float* score,
+                                   const float* pred_plane, const float* gt_plane, const double* pred_cam, const double* gt_cam,
+                                   const int32_t* pred_corr, const int64_t* pred_corr_off, const int32_t* gt_corr, const int64_t* gt_corr_off,
+                                   int P, int max_dt, int max_gt, int64_t n_rows, double* rows, int32_t* n_gt_entries, int32_t* bad,
+                                   double* errs, const int64_t* err_off, void* stream);
 
 
 /* Layers 1..5 of both branches of the pixel pose net (camera_net/camera_modules.py `convs_trans` / `convs_rots`: Conv3x3 + BatchNorm +

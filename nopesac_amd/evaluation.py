@@ -15,6 +15,10 @@ that consumes the hot path's outputs: per-pair pose errors and their summary tab
     and the normal / offset error statistics, key for key.  RLE decoding, pairwise mask IoU and the score-ordered true-positive
     assignment run on the device (csrc/plane_eval.hip) for all views of a batch at once; the final reduction (AP over a few thousand
     rows, once per run) is plain numpy.
+  * evaluate_for_reconstruction() / ReconEvaluator / recon_table()  ~ the offline eval.py --evaluate AP (:343-619, :657-779,
+    :830-1007): the AP of the planes of both views merged through the predicted camera and assignment, under five criteria.  The
+    per-pair work (global planes, merged entries, error matrices, the walk) runs on the device (csrc/recon_eval.hip), the
+    accumulation over all pairs is plain numpy.
 Out of scope: polygon annotations (cocoapi's rasteriser frPyObjects - GT masks must be RLE dicts) and the depth metrics
 (:438-460).
 """
@@ -423,6 +427,234 @@ class PlaneEvaluator:
                 for r, part in enumerate(self._gather(rows, self.device))]
         return plane_table(np.concatenate(kept)[:, :len(PLANE_ROW_COLS)], npos or {1: 0.0}, self.iou_thresh, self.normal_threshold,
                            self.offset_threshold, self.cat_names)
+
+
+# ---- two-view reconstruction AP (the reference's offline eval.py --evaluate AP, :343-619, :657-779, :830-1007) -----------------------
+from .ops import RECON_AP_COLS as RECON_ROW_COLS  # noqa: E402  (the row nopesac_recon_ap_assign writes, named once, in ops.py)
+
+RECON_CRITERIA = ("all", "-offset", "-normal", "-mask", "-normal-offset")       # eval.py's EP_ap_str, columns 1..5 of a row
+
+
+def recon_table(rows: np.ndarray, npos: float) -> Dict[str, float]:
+    """The reference's accumulation over all pairs (eval.py inst_bench :975-990 + VOCap :993-1007): per criterion the VOC area under
+    the monotone precision envelope, IN PERCENT as the reference prints it, plus "npos".  rows: float64 [n, >= 6] (RECON_ROW_COLS),
+    ordered by (pair, entry); npos: the sum of the pairs' GT entry counts.  Scores are sorted descending with a stable sort, so equal
+    scores keep the (pair, entry) order (the reference leaves them in whatever order np.argsort of the ascending scores yields).
+    npos = 0 (no GT entry anywhere): every AP is 0 (the reference divides by zero and prints nan)."""
+    rows = np.asarray(rows, np.float64)
+    rows = rows if rows.ndim == 2 else rows.reshape(-1, len(RECON_ROW_COLS))
+    out = {name: (100.0 * average_precision(rows[:, 0], rows[:, 1 + c], npos) if npos > 0 else 0.0)
+           for c, name in enumerate(RECON_CRITERIA)}
+    out["npos"] = float(npos)
+    return out
+
+
+def _f32_planes(p) -> np.ndarray:
+    return np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, np.float32).reshape(-1, 3)
+
+
+def _camera7(cam: dict, who: str) -> np.ndarray:
+    """{"position" | "tran", "rotation" | "rot"} -> float64 [7]: position, quaternion wxyz."""
+    t = cam["position"] if "position" in cam else cam["tran"]
+    q = cam["rotation"] if "rotation" in cam else cam["rot"]
+    t, q = (np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, np.float64).reshape(-1) for x in (t, q))
+    if t.size != 3 or q.size != 4:
+        raise ValueError(f"{who}: a camera is a position [3] and a quaternion [4] (got {t.size}, {q.size})")
+    return np.concatenate([t, q])
+
+
+def _corr_pairs(corrs) -> np.ndarray:
+    c = np.asarray(corrs.detach().cpu() if torch.is_tensor(corrs) else corrs)
+    return c.reshape(-1, 2).astype(np.int32)
+
+
+def assignment_corrs(assignment) -> np.ndarray:
+    """The correspondences of a 0 / 1 assignment matrix [n0, n1] in np.argwhere order (row-major), int32 [k, 2]."""
+    a = np.asarray(assignment.detach().cpu() if torch.is_tensor(assignment) else assignment)
+    return np.argwhere(a.reshape(a.shape[-2:]) if a.ndim > 2 else a).astype(np.int32).reshape(-1, 2)
+
+
+def recon_rows(pairs: List[dict], device, with_errors: bool = False):
+    """The per-pair part of the reconstruction AP (eval.py:343-619, :657-779, :830-913) for a list of pairs in ONE set of launches:
+    every mask of every view is decoded once (rle.decode_bits), one launch takes all IoU blocks, one the merge, the error matrices and
+    the walk (ops.recon_ap_assign).  pairs: [{"views": (view0, view1), "pred_camera", "gt_camera": {"position", "rotation" wxyz},
+    "pred_corrs": int [k, 2] in row-major order of the assignment (assignment_corrs), "gt_corrs": [[a, b], ...]}] with
+    view = {"instances": [{"segmentation", "score"}], "pred_plane": [n, 3], "annotations": [{"segmentation", "plane"}]}.
+    Returns (rows float64 [entries, 8] (RECON_ROW_COLS), pair after pair, n_entries int64 [P], n_gt_entries int64 [P]); with_errors: a
+    fourth result, per pair the float64 [3, entries, GT entries] offset / normal / IoU matrices.
+    Every instance counts: the reference's create_instances drops predictions with score <= 0.1 from the planes but not from the IoU
+    rows or the correspondence indices, so it is only defined when every score is above 0.1, and there both agree.
+    A correspondence that names a plane a view does not have, or a plane named twice, is a ValueError."""
+    from . import ops, rle
+    device = torch.device(device)
+    P = len(pairs)
+    if P == 0:
+        z = np.zeros(0, np.int64)
+        return (np.zeros((0, len(RECON_ROW_COLS)), np.float64), z, z) + (([],) if with_errors else ())
+    views = [v for p in pairs for v in p["views"]]
+    n_dt = [len(v["instances"]) for v in views]
+    n_gt = [len(v["annotations"]) for v in views]
+    total, n_g = int(sum(n_dt)), int(sum(n_gt))
+    planes = [_f32_planes(v["pred_plane"]) for v in views]
+    for p, k in zip(planes, n_dt):
+        if p.shape[0] != k:
+            raise ValueError(f"recon_rows: {k} instances but {p.shape[0]} pred_plane rows")
+    dt_rles = [ins["segmentation"] for v in views for ins in v["instances"]]
+    gt_rles = [_rle_of(a["segmentation"], "recon_rows") for v in views for a in v["annotations"]]
+    offs = np.zeros((3, 2 * P + 1), np.int64)
+    np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
+    pc = [_corr_pairs(p["pred_corrs"]) for p in pairs]
+    gc = [_corr_pairs(p["gt_corrs"]) for p in pairs]
+    coffs = np.zeros((2, P + 1), np.int64)
+    np.cumsum([len(c) for c in pc], out=coffs[0, 1:]); np.cumsum([len(c) for c in gc], out=coffs[1, 1:])
+    n_entries = np.asarray([n_dt[2 * i] + n_dt[2 * i + 1] - len(pc[i]) for i in range(P)], np.int64)
+    if (n_entries < 0).any():
+        raise ValueError(f"recon_rows: pair {int(np.argmax(n_entries < 0))} has more correspondences than planes")
+    n_rows = int(n_entries.sum())
+    f32 = np.concatenate([np.asarray([ins["score"] for v in views for ins in v["instances"]], np.float32),
+                          np.concatenate(planes).reshape(-1),
+                          np.asarray([a["plane"] for v in views for a in v["annotations"]], np.float32).reshape(-1)])
+    cams = np.stack([np.stack([_camera7(p["pred_camera"], "recon_rows") for p in pairs]),
+                     np.stack([_camera7(p["gt_camera"], "recon_rows") for p in pairs])])
+    i32 = np.concatenate(pc + gc).reshape(-1)
+    d_off, d_coff = torch.from_numpy(offs).to(device), torch.from_numpy(coffs).to(device)
+    d_f32, d_cam, d_i32 = torch.from_numpy(f32).to(device), torch.from_numpy(cams).to(device), torch.from_numpy(i32).to(device)
+    if total + n_g:
+        bits, area = rle.decode_bits(dt_rles + gt_rles, device)
+        iou, _ = ops.mask_iou_bits(bits[:total], area[:total], d_off[0], bits[total:], area[total:], d_off[1], None, d_off[2],
+                                   int(offs[2, -1]), max(n_dt), max(n_gt))
+    else:
+        iou = torch.zeros(0, device=device, dtype=torch.float64)
+    n_pc = 2 * int(coffs[0, -1])
+    err_off = None
+    if with_errors:
+        err_off = np.zeros(P + 1, np.int64)
+        n_ge = [n_gt[2 * i] + n_gt[2 * i + 1] - len(gc[i]) for i in range(P)]
+        np.cumsum([3 * int(a) * max(b, 0) for a, b in zip(n_entries, n_ge)], out=err_off[1:])
+    res = ops.recon_ap_assign(iou, d_off[2], d_off[0], d_off[1], d_f32[:total], d_f32[total:4 * total], d_f32[4 * total:], d_cam[0], d_cam[1],
+                              d_i32[:n_pc], d_coff[0], d_i32[n_pc:], d_coff[1], n_rows, max(n_dt), max(n_gt),
+                              err_off=torch.from_numpy(err_off).to(device) if with_errors else None,
+                              err_total=int(err_off[-1]) if with_errors else 0)
+    rows, n_gt_entries, bad = res[0].cpu().numpy(), res[1].cpu().numpy().astype(np.int64), res[2].cpu().numpy()
+    if bad.any():
+        raise ValueError(f"recon_rows: pair(s) {np.flatnonzero(bad).tolist()} of the batch have a correspondence that names a plane "
+                         "their view does not have, or name a plane twice")
+    if not with_errors:
+        return rows, n_entries, n_gt_entries
+    flat = res[3].cpu().numpy()
+    errs = [flat[err_off[i]:err_off[i + 1]].reshape(3, int(n_entries[i]), int(n_gt_entries[i])) for i in range(P)]
+    return rows, n_entries, n_gt_entries, errs
+
+
+def _recon_pair(views_pred, annotations, pred_camera, gt_camera, assignment, gt_corrs, who: str) -> dict:
+    for anns in annotations:
+        for a in anns:
+            _rle_of(a["segmentation"], who)
+    return {"views": tuple({"instances": vp.get("instances") or [], "pred_plane": vp["pred_plane"], "annotations": anns}
+                           for vp, anns in zip(views_pred, annotations)),
+            "pred_camera": pred_camera, "gt_camera": gt_camera, "pred_corrs": assignment_corrs(assignment), "gt_corrs": gt_corrs}
+
+
+def _recon_gt(entry: Optional[dict]):
+    """(annotations of both views, gt_corrs, GT camera or None) of a dataset pair, or None when it lacks one of the first two."""
+    if entry is None or "gt_corrs" not in entry or any("annotations" not in entry.get(v, {}) for v in "01"):
+        return None
+    return [entry["0"]["annotations"], entry["1"]["annotations"]], entry["gt_corrs"], entry.get("rel_pose")
+
+
+def evaluate_for_reconstruction(predictions: List[dict], dataset_dict: Dict[str, dict], device, camera_key: str = "camera",
+                                assignment_key: str = "pred_assignment", pairs_per_launch: int = 64) -> Dict[str, float]:
+    """The reconstruction AP table of the reference's offline `eval.py --evaluate AP` over kept prediction records: predictions = per
+    pair {"0" / "1": {"image_id", "instances", "pred_plane"}, camera_key: {"pred": {"tran", "rot"}, "gts": {"tran", "rot"}},
+    assignment_key: 0 / 1 matrix} (PoseEvaluator.prediction_record; the camera and assignment optimized_dict writes to continuous.pkl),
+    dataset_dict = {"<id0>__<id1>": {"0" / "1": {"annotations"}, "gt_corrs", "rel_pose"?}} (the shape evaluate_for_matchings takes).
+    The GT camera is the record's "gts" when it has one, else the dataset pair's `rel_pose`.  A pair without dataset entry, `gt_corrs`,
+    `annotations` or GT camera is skipped and counted.  pairs_per_launch bounds the bit masks resident on the device at once (a split
+    of a thousand pairs at 480 x 640 would be gigabytes in one piece); the rows do not depend on it.  Returns recon_table's dict plus
+    "pairs" and "skipped"."""
+    rows, npos, todo, skipped = [], 0, [], 0
+    for pred in predictions:
+        gt = _recon_gt(dataset_dict.get(pred["0"]["image_id"] + "__" + pred["1"]["image_id"]))
+        cam = pred.get(camera_key)
+        gts = (cam or {}).get("gts") or {}
+        gt_cam = {"tran": gts["tran"], "rot": gts["rot"]} if gts.get("tran") is not None and gts.get("rot") is not None else (gt[2] if gt else None)
+        if gt is None or cam is None or gt_cam is None or assignment_key not in pred:
+            skipped += 1
+            continue
+        todo.append(_recon_pair((pred["0"], pred["1"]), gt[0], cam["pred"], gt_cam, pred[assignment_key], gt[1], "evaluate_for_reconstruction"))
+    for i in range(0, len(todo), max(1, pairs_per_launch)):
+        r, _, n_ge = recon_rows(todo[i:i + pairs_per_launch], device)
+        rows.append(r)
+        npos += int(n_ge.sum())
+    table = recon_table(np.concatenate(rows) if rows else np.zeros((0, len(RECON_ROW_COLS))), npos)
+    table.update(pairs=len(todo), skipped=skipped)
+    return table
+
+
+class ReconEvaluator:
+    """DatasetEvaluator-style reconstruction AP: reset() / process(inputs, outputs) / evaluate() -> recon_table's dict plus "pairs" and
+    "skipped".  process() runs decode, IoU and the per-pair kernel for the whole batch in one set of launches (recon_rows); a pair
+    without `rel_pose`, `gt_corrs` or `annotations` in both views is skipped and counted.  Ranks hold disjoint pairs, so nothing is
+    de-duplicated: every row carries its pair's number (pair_index["<id0>__<id1>"] - the pair's index in the dataset - when given) and
+    its entry index, evaluate() gathers rows and per-pair GT entry counts from all ranks and orders the rows by (pair, entry), so
+    equal scores rank the same at every world size.  A single process may leave pair_index out (pairs are numbered as they come);
+    several ranks need it (ValueError)."""
+
+    def __init__(self, device, camera_key: str = "camera", assignment_key: str = "pred_assignment",
+                 pair_index: Optional[Dict[str, int]] = None):
+        self.device = torch.device(device)
+        self.camera_key, self.assignment_key, self.pair_index = camera_key, assignment_key, pair_index
+        self.reset()
+
+    def reset(self):
+        self._rows: List[np.ndarray] = []           # [n, 10]: RECON_ROW_COLS + pair number + entry index
+        self._gt: List[np.ndarray] = []             # [m, 2]: pair number, GT entry count
+        self._skipped = 0
+        self._count = 0
+
+    def _number(self, key: str) -> float:
+        if self.pair_index is not None:
+            return float(self.pair_index[key])
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("ReconEvaluator: with several ranks pass pair_index ('<id0>__<id1>' -> index in the dataset), the same on "
+                             "every rank")
+        self._count += 1
+        return float(self._count - 1)
+
+    def _add(self, numbers, rows: np.ndarray, n_entries, n_gt_entries):
+        """Rows of a batch (recon_rows' results) under their pairs' numbers."""
+        num = np.repeat(np.asarray(numbers, np.float64), n_entries)
+        ent = np.concatenate([np.arange(k, dtype=np.float64) for k in n_entries]) if len(n_entries) else np.zeros(0)
+        self._rows.append(np.concatenate([rows, num[:, None], ent[:, None]], 1))
+        self._gt.append(np.stack([np.asarray(numbers, np.float64), np.asarray(n_gt_entries, np.float64)], 1))
+
+    def process(self, inputs: List[dict], outputs: List[dict]):
+        todo, numbers = [], []
+        for inp, out in zip(inputs, outputs):
+            gt = _recon_gt(inp)
+            cam = out.get(self.camera_key)
+            if gt is None or gt[2] is None or cam is None or self.assignment_key not in out:
+                self._skipped += 1
+                continue
+            views = tuple(out[v] if out.get(v) is not None else {"instances": [], "pred_plane": np.zeros((0, 3), np.float32)} for v in "01")
+            todo.append(_recon_pair(views, gt[0], cam, gt[2], out[self.assignment_key], gt[1], "ReconEvaluator"))
+            numbers.append(self._number(str(inp["0"].get("image_id")) + "__" + str(inp["1"].get("image_id"))))
+        if todo:
+            self._add(numbers, *recon_rows(todo, self.device))
+
+    def evaluate(self) -> Dict[str, float]:
+        w = len(RECON_ROW_COLS) + 2
+        rows = np.concatenate(self._rows) if self._rows else np.zeros((0, w), np.float64)
+        gts = np.concatenate(self._gt) if self._gt else np.zeros((0, 2), np.float64)
+        gts = np.concatenate([gts, [[-1.0, float(self._skipped)]]])              # (the rank's skipped pairs ride along under number -1)
+        rows = np.concatenate(PlaneEvaluator._gather(rows, self.device))
+        gts = np.concatenate(PlaneEvaluator._gather(gts, self.device))
+        rows = rows[np.lexsort((rows[:, w - 1], rows[:, w - 2]))]
+        counted = gts[gts[:, 0] >= 0]
+        table = recon_table(rows[:, :len(RECON_ROW_COLS)], float(counted[:, 1].sum()))
+        table.update(pairs=int(len(counted)), skipped=int(gts[gts[:, 0] < 0, 1].sum()))
+        return table
 
 
 def optimized_dict(predictions: List[dict]) -> Dict[int, dict]:

@@ -1183,7 +1183,46 @@ def plane_ap_assign(iou, iou_off, dt_off, gt_off, score, pred_label, pred_plane,
     return rows
 
 
-GNN_PREFETCH = os.environ.get("NOPESAC_GNN_PREFETCH", "1") != "0"
+# ---- two-view reconstruction AP (csrc/recon_eval.hip): planes of both views in one frame, merged entries, errors, true positives
+RECON_AP_COLS = ("score", "tp_all", "tp_no_offset", "tp_no_normal", "tp_no_mask", "tp_no_normal_offset", "index0", "index1")
+assert len(RECON_AP_COLS) == _H.NPS_RECON_AP_COLS       # the names of the row the header sizes
+
+
+def recon_ap_assign(iou, iou_off, dt_off, gt_off, score, pred_plane, gt_plane, pred_cam, gt_cam, pred_corr, pred_corr_off, gt_corr,
+                    gt_corr_off, n_rows: int, max_dt: int, max_gt: int, err_off=None, err_total: int = 0):
+    """The per-pair part of the reference's `eval.py --evaluate AP` for P pairs in one launch (include/nopesac_hip.h states the
+    rules).  Views 2 i and 2 i + 1 of iou_off / dt_off / gt_off (int64 [2 P + 1]) are pair i's; pred_cam / gt_cam float64 [P, 7]
+    (position, quaternion wxyz); pred_corr / gt_corr int32 [., 2] with int64 offsets [P + 1].  n_rows = number of predictions - number
+    of predicted correspondences (the caller has both).  Returns (rows float64 [n_rows, 8] (RECON_AP_COLS), n_gt_entries int32 [P],
+    bad int32 [P]); a bad pair's rows stay zero.  err_off (int64 [P + 1]) with err_total: also the three error matrices of every
+    pair, flat float64 [err_total], pair i's [3, entries, GT entries] block at err_off[i] - a fourth result."""
+    _chk(iou, torch.float64); _chk(score, torch.float32); _chk(pred_plane, torch.float32); _chk(gt_plane, torch.float32)
+    _chk(pred_cam, torch.float64); _chk(gt_cam, torch.float64); _chk(pred_corr, torch.int32); _chk(gt_corr, torch.int32)
+    for t in (iou_off, dt_off, gt_off, pred_corr_off, gt_corr_off):
+        _chk(t, torch.int64)
+    P, n = pred_corr_off.numel() - 1, score.numel()
+    _require(P >= 0 and dt_off.numel() == 2 * P + 1 and gt_off.numel() == 2 * P + 1 and iou_off.numel() == 2 * P + 1
+             and gt_corr_off.numel() == P + 1 and pred_cam.numel() == 7 * P and gt_cam.numel() == 7 * P and pred_plane.numel() == 3 * n
+             and gt_plane.numel() % 3 == 0 and pred_corr.numel() % 2 == 0 and gt_corr.numel() % 2 == 0 and 0 <= n_rows <= n,
+             "recon_ap_assign: shapes")
+    dev = pred_cam.device
+    if iou.numel() == 0:                        # no view with both predictions and GT: the library still wants a buffer to point at
+        iou = torch.zeros(1, device=dev, dtype=torch.float64)
+    rows = torch.zeros((n_rows, len(RECON_AP_COLS)), device=dev, dtype=torch.float64)
+    n_gt_entries = torch.zeros(P, device=dev, dtype=torch.int32)
+    bad = torch.zeros(P, device=dev, dtype=torch.int32)
+    errs = None
+    if err_off is not None:
+        _chk(err_off, torch.int64)
+        _require(err_off.numel() == P + 1 and err_total >= 0, "recon_ap_assign: err_off holds P + 1 offsets")
+        errs = torch.zeros(max(err_total, 1), device=dev, dtype=torch.float64)
+    _C.nopesac_recon_ap_assign(_p(iou), _p(iou_off), _p(dt_off), _p(gt_off), _p(score), _p(pred_plane), _p(gt_plane), _p(pred_cam),
+                               _p(gt_cam), _p(pred_corr), _p(pred_corr_off), _p(gt_corr), _p(gt_corr_off), P, max_dt, max_gt, int(n_rows),
+                               _p(rows), _p(n_gt_entries), _p(bad), _p(errs), _p(err_off), _stream())
+    return (rows, n_gt_entries, bad) if errs is None else (rows, n_gt_entries, bad, errs[:err_total])
+
+
+GNN_PREFETCH =os.environ.get("NOPESAC_GNN_PREFETCH", "1") != "0"
 
 
 def gnn_layer(x: torch.Tensor, x_off: int, src: torch.Tensor, src_off: int, out: torch.Tensor, out_off: int, n_sets: int, lens, W: dict,

@@ -23,7 +23,7 @@ import torch
 
 from . import runner
 from .config import get_cfg
-from .evaluation import PlaneEvaluator, PoseEvaluator, create_small_table, dump_predictions, evaluate_for_matchings
+from .evaluation import RECON_CRITERIA, PlaneEvaluator, PoseEvaluator, ReconEvaluator, create_small_table, dump_predictions, evaluate_for_matchings
 from .registry import build_model
 from .synth import synth_pair, synth_state_dict
 
@@ -55,6 +55,10 @@ def default_argument_parser():
     ap.add_argument("--eval-planes", action="store_true", help="plane detection table (mp3d_evaluation.py:467-743): mask AP, the three plane APs and "
                     "the normal / offset error statistics; RLE decoding, mask IoU and the true-positive assignment run on the GPU (csrc/plane_eval.hip), "
                     "so the model must be on one.  Needs pairs whose views carry RLE `annotations` with `plane` and `category_id`")
+    ap.add_argument("--eval-recon", action="store_true", help="two-view reconstruction AP (the reference's offline eval.py --evaluate AP): both views' "
+                    "planes in one frame through the predicted camera, matched planes merged, AP under all / -offset / -normal / -mask / "
+                    "-normal-offset; computed on the GPU (csrc/recon_eval.hip), so the model must be on one.  Needs pairs with `rel_pose`, "
+                    "`gt_corrs` and RLE `annotations` with `plane`")
     ap.add_argument("--dump-dir", default="", help="write NopeSAC_instances_predictions.pth + continuous.pkl here (eval_full_scene)")
     ap.add_argument("--stub-model", action="store_true", help="TEST ONLY (results are marked invalid): the CLI's sharding, batch loop, evaluator "
                     "gather and dumps around a stub that fabricates result dicts instead of running the model - what the gloo CPU tests drive at "
@@ -260,6 +264,9 @@ def main(argv=None):
     if args.eval_planes and args.stub_model:
         parser.error("--eval-planes cannot run with --stub-model: the plane evaluator's kernels need a GPU and real plane instances, "
                      "the stub fabricates results without either")
+    if args.eval_recon and args.stub_model:
+        parser.error("--eval-recon cannot run with --stub-model: the reconstruction evaluator's kernels need a GPU and real plane "
+                     "instances, the stub fabricates results without either")
     if args.num_gpus > 1 and "WORLD_SIZE" not in os.environ:
         return runner.launch(_main_rank, args.num_gpus, (args,))
     return _main_rank(args)
@@ -311,9 +318,22 @@ def _main_rank(args):
             plane_evaluator = PlaneEvaluator(next(model.parameters()).device, image_index=image_index)
         elif rank == 0:
             logger.warning("--eval-planes: no pair carries annotations; nothing to evaluate")
+    recon_evaluator = None
+    if args.eval_recon:
+        if not on_gpu:
+            raise RuntimeError("--eval-recon needs the model on a GPU (MODEL.DEVICE cuda): RLE decoding, mask IoU and the per-pair merge, "
+                               "errors and true-positive walk are HIP kernels, there is no host path")
+        pair_index = {}                          # a pair's number = its first position in the dataset, the same on every rank
+        for i, p in enumerate(annotated):
+            if "rel_pose" in p and "gt_corrs" in p and all("annotations" in p[v] for v in "01"):
+                pair_index.setdefault(str(p["0"].get("image_id")) + "__" + str(p["1"].get("image_id")), i)
+        if pair_index:
+            recon_evaluator = ReconEvaluator(next(model.parameters()).device, pair_index=pair_index)
+        elif rank == 0:
+            logger.warning("--eval-recon: no pair carries rel_pose, gt_corrs and annotations; nothing to evaluate")
     try:
         timing = inference_on_dataset(model, pairs[lo:hi], evaluator, args.pairs_per_batch, kept, inflight=args.inflight,
-                                      also=(plane_evaluator,) if plane_evaluator is not None else ())
+                                      also=tuple(ev for ev in (plane_evaluator, recon_evaluator) if ev is not None))
     finally:
         gc.unfreeze()
     results = evaluator.evaluate()
@@ -323,6 +343,12 @@ def _main_rank(args):
         if rank == 0:
             logger.info("Detection metrics: \n%s", create_small_table({k: v for k, v in table.items() if "ap@" in k}))
             logger.info("Plane metrics: \n%s", create_small_table({k: v for k, v in table.items() if "ap@" not in k}))
+    if recon_evaluator is not None:
+        table = recon_evaluator.evaluate()       # (a collective: every rank calls it)
+        results["recon"] = table
+        if rank == 0:
+            logger.info("Reconstruction AP (%d pairs, %d skipped, %d GT entries):\n%s", table["pairs"], table["skipped"], int(table["npos"]),
+                        "\n".join("{:>20s}: {:5.3f}".format(k, table[k]) for k in RECON_CRITERIA))
     if args.eval_matchings:
         if world > 1:                            # comm.gather semantics: rank-ordered concatenation
             parts = [None] * world
@@ -346,7 +372,7 @@ def _main_rank(args):
             logger.info("wrote %s", files)
     if rank == 0:
         for k, v in results.items():
-            if k != "plane" and isinstance(v, dict) and v and all(isinstance(x, (int, float)) for x in v.values()):
+            if k not in ("plane", "recon") and isinstance(v, dict) and v and all(isinstance(x, (int, float)) for x in v.values()):
                 logger.info("%s metrics (final output mode -> %s):\n%s", k, cfg.MODEL.CAMERA_HEAD.INFERENCE_OUT_CAM_TYPE,
                             create_small_table({kk: float(vv) for kk, vv in v.items()}))
         if args.output:
