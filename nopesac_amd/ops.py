@@ -1,7 +1,9 @@
 """Thin typed wrappers: torch tensors (device memory + the current HIP stream) -> C-ABI calls.
 
 torch is plumbing here (allocation, streams); every computation below runs in libnopesac_hip.so.
-All wrappers enqueue on torch's current stream and never synchronise.
+All wrappers enqueue on torch's current stream and never synchronise.  This is the one module through which device pointers of
+caller-supplied tensors reach the library (inference, conv backward, the training path's backward kernels and optimiser): what the C side
+cannot see - device, dtype, strides, element counts - is checked here, with explicit raises that stay in force under `python -O`.
 """
 from __future__ import annotations
 
@@ -55,20 +57,47 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+_NO_CPU_PATH = "nopesac_amd ops need device tensors (there is no CPU path)"
+
+
 def _p(t: Optional[torch.Tensor]):
     if t is None:
         return None
-    _require(t.is_cuda, "nopesac_amd ops need device tensors (there is no CPU path)")
+    if not t.is_cuda:                           # (raised in place, not through _require: these two run for every tensor of every launch)
+        raise OpsArgumentError(_NO_CPU_PATH)
     return t.data_ptr()
 
 
 def _chk(t: torch.Tensor, dtype=None, contiguous=True):
-    _require(t.is_cuda, "nopesac_amd ops need device tensors (there is no CPU path)")
-    if dtype is not None:
-        _require(t.dtype == dtype, (t.dtype, dtype))
-    if contiguous:
-        _require(t.is_contiguous(), 'argument check failed: t.is_contiguous()')
+    if not t.is_cuda:
+        raise OpsArgumentError(_NO_CPU_PATH)
+    if dtype is not None and t.dtype != dtype:
+        raise OpsArgumentError(repr((t.dtype, dtype)))
+    if contiguous and not t.is_contiguous():
+        raise OpsArgumentError('argument check failed: t.is_contiguous()')
     return t
+
+
+def _sized(t: torch.Tensor, dtype, n: int, what: str) -> torch.Tensor:
+    """A contiguous device tensor of `dtype` with exactly n elements."""
+    _chk(t, dtype)
+    if t.numel() != n:
+        raise OpsArgumentError("%s: %d elements expected, got shape %s" % (what, n, tuple(t.shape)))
+    return t
+
+
+def _lengths(t: Optional[torch.Tensor], B: int, what: str) -> Optional[torch.Tensor]:
+    """The per-set lengths of a ragged batch (attention's qlen / klen): None, or int32 [B] on the device."""
+    return None if t is None else _sized(t, torch.int32, B, what)
+
+
+def _rows(t: torch.Tensor, rows: int, cols: int, what: str) -> int:
+    """f32 device matrix [rows, >= cols] with unit column stride (a column slice of a wider buffer is allowed) -> its row stride."""
+    _chk(t, torch.float32, contiguous=False)
+    if not (t.dim() == 2 and t.shape[0] == rows and t.shape[1] >= cols and t.stride(1) == 1):
+        raise OpsArgumentError("%s: [%d, >= %d] with unit column stride expected, got shape %s, strides %s"
+                               % (what, rows, cols, tuple(t.shape), tuple(t.stride())))
+    return t.stride(0)
 
 
 class ConvTuner:
@@ -732,6 +761,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, Lq: int
         _require(t.is_cuda and t.dtype == q.dtype and t.dim() == 2 and t.stride(1) == 1, 'argument check failed: t.is_cuda and t.dtype == q.dtype and t.dim() == 2 and t.stride(1) == 1')
     _require(q.dtype == torch.float32 or (io16 and mfma_bf16), 'argument check failed: q.dtype == torch.float32 or (io16 and mfma_bf16)')
     _require(q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk, 'argument check failed: q.shape[0] == B * Lq and k.shape[0] == B * Lk and v.shape[0] == B * Lk')
+    _lengths(qlen, B, "attention: qlen"); _lengths(klen, B, "attention: klen")
     o = torch.empty((B * Lq, heads * 32), device=q.device, dtype=q.dtype)
     fn = _C.nopesac_attention_small_bf16io if io16 else (_C.nopesac_attention_small_bf16 if mfma_bf16 else _C.nopesac_attention_small)
     fn(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), o.stride(0), B, Lq, Lk,
@@ -1619,6 +1649,282 @@ def corr_softmax_backward(a: torch.Tensor, da: torch.Tensor, x1: torch.Tensor, x
     dx2t = conv2d(ds_t.view(B, h, w, P), transpose_batched(x1.reshape(B, P, C)).view(B, C, 1, 1, P), batched_weights=True)
     dx2 = transpose_hw_rows(dx2t.reshape(B, P, C), w, h).view(B, h, w, C)
     return dx1, dx2
+
+
+# ---- backward kernels and optimiser of the training path (csrc/refine_bwd.hip, csrc/matcher_bwd.hip; nopesac_amd/training.py) --------------
+# The kernels index from the integer dimensions passed beside the pointers, so every wrapper checks what the C side cannot see: device,
+# dtype, density and that each tensor holds the element count those dimensions imply.  Ranges the entry points refuse themselves
+# (nq, Lq, Lk <= 128, D <= 4, step >= 1, ...) are not restated: they surface as HipKernelError.
+def transpose_rows(x: torch.Tensor) -> torch.Tensor:
+    """[rows, cols] f32 (rows may be strided) -> contiguous [cols, rows]."""
+    _require(x.dim() == 2, "transpose_rows: [rows, cols]")
+    ld = _rows(x, x.shape[0], x.shape[1], "transpose_rows: x")
+    y = torch.empty(x.shape[1], x.shape[0], device=x.device, dtype=torch.float32)
+    _C.nopesac_transpose_f32(_p(x), x.shape[0], x.shape[1], ld, _p(y), _stream())
+    return y
+
+
+def col_sum(x: torch.Tensor) -> torch.Tensor:
+    """Column sums [cols] of [rows, cols] f32 (rows may be strided), in a fixed order."""
+    _require(x.dim() == 2, "col_sum: [rows, cols]")
+    ld = _rows(x, x.shape[0], x.shape[1], "col_sum: x")
+    out = torch.empty(x.shape[1], device=x.device, dtype=torch.float32)
+    _C.nopesac_col_sum_f32(_p(x), x.shape[0], x.shape[1], ld, _p(out), _stream())
+    return out
+
+
+def relu_backward(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """y > 0 ? g : 0 for the output y of a ReLU and its gradient g."""
+    _chk(g, torch.float32)
+    _sized(y, torch.float32, g.numel(), "relu_backward: y")
+    out = torch.empty_like(g)
+    _C.nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(out), _stream())
+    return out
+
+
+def ransac_score_maps_backward(geo_local, rot_raw, trans_raw, init_rot, init_trans, m, g_normal_score, g_param_score, g_l2_dist):
+    """Backward of ransac_score_maps: the gradients of normal_score / param_score / l2_dist [B,nq+1,nq] ->
+    (g_rot_raw [B,nq,4], g_trans_raw [B,nq,3], g_init_rot [B,4], g_init_trans [B,3])."""
+    _chk(geo_local, torch.float32)
+    _require(geo_local.dim() == 3 and geo_local.shape[2] == 6, "ransac_score_maps_backward: geo_local [B,nq,6]")
+    B, nq, _ = geo_local.shape
+    _sized(rot_raw, torch.float32, B * nq * 4, "ransac_score_maps_backward: rot_raw")
+    _sized(trans_raw, torch.float32, B * nq * 3, "ransac_score_maps_backward: trans_raw")
+    _sized(init_rot, torch.float32, B * 4, "ransac_score_maps_backward: init_rot")
+    _sized(init_trans, torch.float32, B * 3, "ransac_score_maps_backward: init_trans")
+    _sized(m, torch.int32, B, "ransac_score_maps_backward: m")
+    for t in (g_normal_score, g_param_score, g_l2_dist):
+        _sized(t, torch.float32, B * (nq + 1) * nq, "ransac_score_maps_backward: score gradient [B,nq+1,nq]")
+    f32 = dict(device=geo_local.device, dtype=torch.float32)
+    out = (torch.empty(B, nq, 4, **f32), torch.empty(B, nq, 3, **f32), torch.empty(B, 4, **f32), torch.empty(B, 3, **f32))
+    _C.nopesac_refine_score_maps_backward(_p(geo_local), _p(rot_raw), _p(trans_raw), _p(init_rot), _p(init_trans), _p(m), B, nq,
+                                          _p(g_normal_score), _p(g_param_score), _p(g_l2_dist), *[_p(t) for t in out], _stream())
+    return out
+
+
+def ransac_soft_vote_backward(sf_rot, sf_trans, reg_rot_w, reg_rot_b, reg_trans_w, reg_trans_b, init_rot_feat, init_trans_feat, fused_rot,
+                              fused_trans, rots_w, rots_b, trans_w, trans_b, m, g_pred_rot, g_pred_trans, g_avg_rot, g_avg_trans, g_score_rot,
+                              g_score_trans) -> dict:
+    """Backward of ransac_soft_vote (mode | 16) -> the gradients of the score features g_sf_rot / g_sf_trans [B,nq+1,64], of the initial pose
+    features g_init_rot_feat / g_init_trans_feat [B,256], of the per-plane features g_fused_rot / g_fused_trans [B,nq,256] and the PER-PAIR
+    partials pb_<parameter> [B, size of the parameter] of the eight parameter gradients (sum them with col_sum)."""
+    _chk(sf_rot, torch.float32)
+    _require(sf_rot.dim() == 3 and sf_rot.shape[2] == 64, "ransac_soft_vote_backward: sf_rot [B,nq+1,64]")
+    B, NH, _ = sf_rot.shape
+    nq = NH - 1
+    inputs = (sf_trans, reg_rot_w, reg_rot_b, reg_trans_w, reg_trans_b, init_rot_feat, init_trans_feat, fused_rot, fused_trans, rots_w,
+              rots_b, trans_w, trans_b, g_pred_rot, g_pred_trans, g_avg_rot, g_avg_trans, g_score_rot, g_score_trans)
+    sizes = (B * NH * 64, 64, 1, 64, 1, B * 256, B * 256, B * nq * 256, B * nq * 256, 4 * 256, 4, 3 * 256, 3, B * 4, B * 3, B * 4, B * 3,
+             B * NH, B * NH)
+    for t, n in zip(inputs, sizes):
+        _sized(t, torch.float32, n, "ransac_soft_vote_backward: an argument behind sf_rot, in the entry point's order")
+    _sized(m, torch.int32, B, "ransac_soft_vote_backward: m")
+    f32 = dict(device=sf_rot.device, dtype=torch.float32)
+    out = {"g_sf_rot": torch.empty(B, NH, 64, **f32), "g_sf_trans": torch.empty(B, NH, 64, **f32), "g_init_rot_feat": torch.empty(B, 256, **f32),
+           "g_init_trans_feat": torch.empty(B, 256, **f32), "g_fused_rot": torch.empty(B, nq, 256, **f32),
+           "g_fused_trans": torch.empty(B, nq, 256, **f32), "pb_rots_w": torch.empty(B, 4 * 256, **f32), "pb_rots_b": torch.empty(B, 4, **f32),
+           "pb_trans_w": torch.empty(B, 3 * 256, **f32), "pb_trans_b": torch.empty(B, 3, **f32), "pb_reg_rot_w": torch.empty(B, 64, **f32),
+           "pb_reg_rot_b": torch.empty(B, 1, **f32), "pb_reg_trans_w": torch.empty(B, 64, **f32), "pb_reg_trans_b": torch.empty(B, 1, **f32)}
+    _C.nopesac_refine_vote_backward(_p(sf_rot), *[_p(t) for t in inputs[:13]], _p(m), B, nq, *[_p(t) for t in inputs[13:]],
+                                    *[_p(t) for t in out.values()], _stream())         # (out is in the entry point's argument order)
+    return out
+
+
+def plane_cam_ref_losses_backward(vote: dict, maps: dict, m, gt_pose, g_losses, weight: float = 1.0):
+    """Backward of plane_cam_ref_losses: g_losses f32[7] -> the gradients of (pred_rot [B,4], pred_trans [B,3], avg_rot, avg_trans,
+    score_rot [B,nq+1], score_trans, l2_dist [B,nq+1,nq]); `maps` needs rots_all / trans_all only (the hypothesis the index losses pick
+    is a constant)."""
+    _chk(gt_pose, torch.float32)
+    _require(gt_pose.dim() == 2 and gt_pose.shape[1] == 7, "plane_cam_ref_losses_backward: gt_pose [B,7]")
+    B = gt_pose.shape[0]
+    _chk(vote["score_rot"], torch.float32)
+    _require(vote["score_rot"].dim() == 2 and vote["score_rot"].shape[0] == B, "plane_cam_ref_losses_backward: score_rot [B,nq+1]")
+    NH = vote["score_rot"].shape[1]
+    args = ((vote["pred_rot"], B * 4), (vote["pred_trans"], B * 3), (vote["avg_rot"], B * 4), (vote["avg_trans"], B * 3),
+            (maps["rots_all"], B * NH * 4), (maps["trans_all"], B * NH * 3), (vote["score_rot"], B * NH), (vote["score_trans"], B * NH))
+    for t, n in args:
+        _sized(t, torch.float32, n, "plane_cam_ref_losses_backward: vote / maps")
+    _sized(m, torch.int32, B, "plane_cam_ref_losses_backward: m")
+    _sized(g_losses, torch.float32, 7, "plane_cam_ref_losses_backward: g_losses")
+    f32 = dict(device=gt_pose.device, dtype=torch.float32)
+    out = (torch.empty(B, 4, **f32), torch.empty(B, 3, **f32), torch.empty(B, 4, **f32), torch.empty(B, 3, **f32), torch.empty(B, NH, **f32),
+           torch.empty(B, NH, **f32), torch.empty(B, NH, NH - 1, **f32))
+    _C.nopesac_refine_losses_backward(*[_p(t) for t, _ in args], _p(m), _p(gt_pose), _p(g_losses), B, NH - 1, float(weight),
+                                      *[_p(t) for t in out], _stream())
+    return out
+
+
+def normalize_rows_backward(x: torch.Tensor, g: torch.Tensor, canonical_sign: bool = False) -> torch.Tensor:
+    """Backward of normalize_rows(x, canonical_sign) at its input x for the output gradient g."""
+    _chk(x, torch.float32)
+    _sized(g, torch.float32, x.numel(), "normalize_rows_backward: g")
+    D = x.shape[-1]
+    out = torch.empty_like(x)
+    _C.nopesac_normalize_rows_backward(_p(x), _p(g), x.numel() // D, D, int(canonical_sign), _p(out), _stream())
+    return out
+
+
+def camera_pose_loss_backward(est_trans, est_rot, gt_trans, gt_rot, g_out, weight: float = 1.0, trans_eps: float = 0.0):
+    """Backward of camera_pose_loss: g_out f32[2] -> the gradients of all four pose arguments ([B,3] / [B,4], dense).  `gt_trans` /
+    `gt_rot` may be column views of one [B,7] pose tensor, as in the forward (row strides are passed on)."""
+    _chk(est_trans, torch.float32)
+    _require(est_trans.dim() == 2 and est_trans.shape[1] == 3, "camera_pose_loss_backward: est_trans [B,3]")
+    B = est_trans.shape[0]
+    _sized(est_rot, torch.float32, B * 4, "camera_pose_loss_backward: est_rot")
+    st = _rows(gt_trans, B, 3, "camera_pose_loss_backward: gt_trans")
+    sq = _rows(gt_rot, B, 4, "camera_pose_loss_backward: gt_rot")
+    _require(gt_trans.shape[1] == 3 and gt_rot.shape[1] == 4, "camera_pose_loss_backward: gt_trans [B,3], gt_rot [B,4]")
+    _sized(g_out, torch.float32, 2, "camera_pose_loss_backward: g_out")
+    f32 = dict(device=est_trans.device, dtype=torch.float32)
+    out = (torch.empty(B, 3, **f32), torch.empty(B, 4, **f32), torch.empty(B, 3, **f32), torch.empty(B, 4, **f32))
+    _C.nopesac_camera_pose_loss_backward(_p(est_trans), _p(est_rot), _p(gt_trans), st, _p(gt_rot), sq, B, float(trans_eps), float(weight),
+                                         _p(g_out), *[_p(t) for t in out], _stream())
+    return out
+
+
+def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_out: torch.Tensor, B: int, Lq: int, Lk: int, heads: int,
+                       scale: float, qlen=None, klen=None, out=None):
+    """Backward of attention (f32, head dim 32) for the output gradient d_out [B*Lq, >= heads*32]: -> (dq, dk, dv), each [rows, heads*32];
+    the softmax is recomputed.  Like q / k / v, d_out and `out` = (dq, dk, dv) may be column slices of wider matrices."""
+    W = heads * 32
+    sq, sk, sv = _rows(q, B * Lq, W, "attention_backward: q"), _rows(k, B * Lk, W, "attention_backward: k"), _rows(v, B * Lk, W, "attention_backward: v")
+    sg = _rows(d_out, B * Lq, W, "attention_backward: d_out")
+    _lengths(qlen, B, "attention_backward: qlen"); _lengths(klen, B, "attention_backward: klen")
+    if out is None:
+        out = tuple(torch.empty(rows, W, device=q.device, dtype=torch.float32) for rows in (B * Lq, B * Lk, B * Lk))
+    dq, dk, dv = out
+    so = [_rows(t, rows, W, "attention_backward: out") for t, rows in ((dq, B * Lq), (dk, B * Lk), (dv, B * Lk))]
+    _C.nopesac_attention_small_backward(_p(q), sq, _p(k), sk, _p(v), sv, _p(d_out), sg, B, Lq, Lk, heads, float(scale), _p(qlen), _p(klen),
+                                        _p(dq), so[0], _p(dk), so[1], _p(dv), so[2], _stream())
+    return dq, dk, dv
+
+
+def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, eps: float = 1e-5):
+    """Backward of layernorm over D = 256: x [rows, 256] (the LayerNorm input), gamma [256], dy like x -> (dx, dgamma, dbeta)."""
+    _chk(x, torch.float32)
+    D = x.shape[-1]
+    rows = x.numel() // D
+    _sized(gamma, torch.float32, D, "layernorm_backward: gamma")
+    _sized(dy, torch.float32, rows * D, "layernorm_backward: dy")
+    dx, dgamma, dbeta = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
+    ws = torch.empty(int(_C.nopesac_layernorm_backward_workspace_floats(rows)), device=x.device, dtype=torch.float32)
+    _C.nopesac_layernorm_backward(_p(x), _p(gamma), _p(dy), rows, D, float(eps), _p(dx), _p(dgamma), _p(dbeta), _p(ws), ws.numel(), _stream())
+    return dx, dgamma, dbeta
+
+
+def desc_dot_backward(g: torch.Tensor, d0: torch.Tensor, d1: torch.Tensor, n1: torch.Tensor, n2: torch.Tensor):
+    """Backward of dots[b] = d0[b] d1[b]^T / 16: g [B,nq,nq], d0 / d1 [B,nq,256], n1 / n2 int32 [B] -> (dd0, dd1), zero rows beyond n1 / n2."""
+    _chk(d0, torch.float32)
+    _require(d0.dim() == 3, "desc_dot_backward: d0 [B,nq,D]")
+    B, nq, D = d0.shape
+    _sized(d1, torch.float32, B * nq * D, "desc_dot_backward: d1")
+    _sized(g, torch.float32, B * nq * nq, "desc_dot_backward: g")
+    _sized(n1, torch.int32, B, "desc_dot_backward: n1"); _sized(n2, torch.int32, B, "desc_dot_backward: n2")
+    dd0, dd1 = torch.empty_like(d0), torch.empty_like(d0)
+    _C.nopesac_desc_dot_backward(_p(g), _p(d0), _p(d1), _p(n1), _p(n2), B, nq, D, _p(dd0), _p(dd1), _stream())
+    return dd0, dd1
+
+
+def _matcher_pairs(n1, n2, gt_corr, B: int, nq: int):
+    """The operands every training entry point of the matcher takes: n1 / n2 int32 [B], gt_corr uint8 [B,nq+1,nq+1] (with the dustbin)."""
+    _sized(n1, torch.int32, B, "matcher training: n1"); _sized(n2, torch.int32, B, "matcher training: n2")
+    _sized(gt_corr, torch.uint8, B * (nq + 1) * (nq + 1), "matcher training: gt_corr [B,nq+1,nq+1] (dustbin row and column included)")
+
+
+def _matcher_inputs(desc_dot, planes1, planes2, cam7, n1, n2, bin_score, gt_corr):
+    """The inputs matcher_sinkhorn_train and its backward share -> (B, nq)."""
+    _chk(desc_dot, torch.float32)
+    _require(desc_dot.dim() == 3 and desc_dot.shape[1] == desc_dot.shape[2], "matcher training: desc_dot [B,nq,nq]")
+    B, nq, _ = desc_dot.shape
+    _sized(planes1, torch.float32, B * nq * 3, "matcher training: planes1"); _sized(planes2, torch.float32, B * nq * 3, "matcher training: planes2")
+    _sized(cam7, torch.float32, B * 7, "matcher training: cam7"); _sized(bin_score, torch.float32, 1, "matcher training: bin_score")
+    _matcher_pairs(n1, n2, gt_corr, B, nq)
+    return B, nq
+
+
+def matcher_emb_loss(log_scores: torch.Tensor, gt_corr: torch.Tensor, n1: torch.Tensor, n2: torch.Tensor):
+    """embedding_loss_forward (matching_head.py:135-139) on the log scores [B,nq+1,nq+1] of matcher_sinkhorn -> (pair_stats [B,2] = the
+    pair's sum of -min(score, 0) over the entries gt_corr selects and their count, loss [2] = (2 * sum / count over the batch, count))."""
+    _chk(log_scores, torch.float32)
+    _require(log_scores.dim() == 3 and log_scores.shape[1] == log_scores.shape[2], "matcher_emb_loss: log_scores [B,nq+1,nq+1]")
+    B, nq = log_scores.shape[0], log_scores.shape[1] - 1
+    _matcher_pairs(n1, n2, gt_corr, B, nq)
+    stats = torch.empty(B, 2, device=log_scores.device, dtype=torch.float32)
+    loss = torch.empty(2, device=log_scores.device, dtype=torch.float32)
+    _C.nopesac_matcher_emb_loss(_p(log_scores), _p(gt_corr), _p(n1), _p(n2), B, nq, _p(stats), _p(loss), _stream())
+    return stats, loss
+
+
+def matcher_sinkhorn_train(desc_dot, planes1, planes2, cam7, n1, n2, bin_score, offset_mult, normal_mult, iters: int, gt_corr):
+    """matcher_sinkhorn without the assignment, keeping every iteration's potentials for the backward pass ->
+    (log_scores [B,nq+1,nq+1], uv [B,iters,2,nq+1], pair_stats [B,2], loss [2]) (the last two as matcher_emb_loss)."""
+    B, nq = _matcher_inputs(desc_dot, planes1, planes2, cam7, n1, n2, bin_score, gt_corr)
+    f32 = dict(device=desc_dot.device, dtype=torch.float32)
+    iters = int(iters)
+    out = (torch.empty(B, nq + 1, nq + 1, **f32), torch.empty(B, max(iters, 0), 2, nq + 1, **f32), torch.empty(B, 2, **f32), torch.empty(2, **f32))
+    _C.nopesac_matcher_sinkhorn_train(_p(desc_dot), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), float(offset_mult),
+                                      float(normal_mult), iters, _p(gt_corr), B, nq, *[_p(t) for t in out], _stream())
+    return out
+
+
+def matcher_sinkhorn_train_backward(desc_dot, planes1, planes2, cam7, n1, n2, bin_score, offset_mult, normal_mult, iters: int, gt_corr, uv,
+                                    loss, g_loss):
+    """Gradient of loss[0] * g_loss[0] through the unrolled iterations: uv from matcher_sinkhorn_train, loss [2] from it or from
+    matcher_emb_loss, g_loss f32[1] -> (d_desc_dot [B,nq,nq], d_bin_pairs [B] = per-pair partials of d bin_score)."""
+    B, nq = _matcher_inputs(desc_dot, planes1, planes2, cam7, n1, n2, bin_score, gt_corr)
+    iters = int(iters)
+    _sized(uv, torch.float32, B * max(iters, 0) * 2 * (nq + 1), "matcher_sinkhorn_train_backward: uv [B,iters,2,nq+1]")
+    _sized(loss, torch.float32, 2, "matcher_sinkhorn_train_backward: loss"); _sized(g_loss, torch.float32, 1, "matcher_sinkhorn_train_backward: g_loss")
+    d_dots = torch.empty_like(desc_dot)
+    d_bin = torch.empty(B, device=desc_dot.device, dtype=torch.float32)
+    _C.nopesac_matcher_sinkhorn_train_backward(_p(desc_dot), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), float(offset_mult),
+                                               float(normal_mult), iters, _p(gt_corr), _p(uv), _p(loss), _p(g_loss), B, nq, _p(d_dots),
+                                               _p(d_bin), _stream())
+    return d_dots, d_bin
+
+
+def adamw_step(param, grad, exp_avg, exp_avg_sq, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int):
+    """One torch.optim.AdamW update of `param` and its two moment buffers in place (step counts from 1)."""
+    _chk(param, torch.float32)
+    n = param.numel()
+    _sized(grad, torch.float32, n, "adamw_step: grad"); _sized(exp_avg, torch.float32, n, "adamw_step: exp_avg")
+    _sized(exp_avg_sq, torch.float32, n, "adamw_step: exp_avg_sq")
+    _C.nopesac_adamw_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, float(lr), float(beta1), float(beta2), float(eps),
+                          float(weight_decay), int(step), _stream())
+
+
+def sgd_step(param, grad, momentum_buf, lr: float, momentum: float, weight_decay: float, first_step: bool):
+    """One torch.optim.SGD(momentum) update of `param` and its momentum buffer in place."""
+    _chk(param, torch.float32)
+    n = param.numel()
+    _sized(grad, torch.float32, n, "sgd_step: grad"); _sized(momentum_buf, torch.float32, n, "sgd_step: momentum_buf")
+    _C.nopesac_sgd_step(_p(param), _p(grad), _p(momentum_buf), n, float(lr), float(momentum), float(weight_decay), int(first_step), _stream())
+
+
+def sumsq_accumulate(x: torch.Tensor, acc: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """acc[0] += sum x^2 (one launch per tensor on the same accumulator, fixed order); a new zero accumulator without `acc`."""
+    _chk(x, torch.float32)
+    if acc is None:
+        acc = torch.zeros(1, device=x.device, dtype=torch.float32)
+    _sized(acc, torch.float32, 1, "sumsq_accumulate: acc")
+    _C.nopesac_sumsq_accumulate_f32(_p(x), x.numel(), _p(acc), _stream())
+    return acc
+
+
+def clip_coefficient(sumsq: torch.Tensor, max_norm: float) -> torch.Tensor:
+    """f32[1] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)): torch.nn.utils.clip_grad_norm_'s coefficient, on the device."""
+    _sized(sumsq, torch.float32, 1, "clip_coefficient: sumsq")
+    coef = torch.empty(1, device=sumsq.device, dtype=torch.float32)
+    _C.nopesac_clip_coefficient(_p(sumsq), float(max_norm), _p(coef), _stream())
+    return coef
+
+
+def scale_by(x: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """x *= coef[0] in place (coef: a device scalar, e.g. clip_coefficient's)."""
+    _chk(x, torch.float32)
+    _sized(coef, torch.float32, 1, "scale_by: coef")
+    _C.nopesac_scale_by_f32(_p(x), x.numel(), _p(coef), _stream())
+    return x
 
 
 # ---- set criterion of the plane head (csrc/plane_criterion.hip) --------------------------------------------------------------------------

@@ -39,7 +39,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
-from .ops import _C, _p, _stream
+from .ops import _require, col_sum, transpose_rows as transpose      # ([rows, cols] f32, rows may be strided: column sums / the transpose)
 
 PREFIX = "camera_head_list.0."
 CONV_STACKS = ("pixel_decoder", "convs_backbone", "convs_trans", "convs_rots")       # the pixel pose net's conv stacks (conv_stacks=True)
@@ -73,21 +73,6 @@ MLPS = ("geo_encoder", "geo_proj_s1", "decoder_rot", "geo_proj_s2", "decoder_tra
 LINEARS = ("rots", "trans", "rot_score_reg", "trans_score_reg")
 
 
-def transpose(x: torch.Tensor) -> torch.Tensor:
-    """[rows, cols] f32 (rows may be strided) -> contiguous [cols, rows]."""
-    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
-    y = torch.empty(x.shape[1], x.shape[0], device=x.device, dtype=torch.float32)
-    _C.nopesac_transpose_f32(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(y), _stream())
-    return y
-
-
-def col_sum(x: torch.Tensor) -> torch.Tensor:
-    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
-    out = torch.empty(x.shape[1], device=x.device, dtype=torch.float32)
-    _C.nopesac_col_sum_f32(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(out), _stream())
-    return out
-
-
 class _Linear(torch.autograd.Function):
     """y = act(x W^T + b) on the exact-f32 GEMM kernel; backward: dX = dY W, dW = dY^T X (the same kernel), db = column sums."""
 
@@ -104,9 +89,7 @@ class _Linear(torch.autograd.Function):
         x, w, y = ctx.saved_tensors
         g = g.contiguous()
         if ctx.relu:
-            gm = torch.empty_like(g)
-            _C.nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(gm), _stream())
-            g = gm
+            g = ops.relu_backward(g, y)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = ops.linear(g, transpose(w))                      # [rows, N] x [N, K]
@@ -133,10 +116,8 @@ class _ScoreMaps(torch.autograd.Function):
         z = lambda t, ref: torch.zeros_like(ref) if t is None else t.contiguous()
         ref = torch.empty(B, nq + 1, nq, device=geo_local.device, dtype=torch.float32)
         g_ns, g_ps, g_l2 = (z(t, ref) for t in (g_ns, g_ps, g_l2))
-        g_rot, g_tr = torch.empty_like(rot_raw), torch.empty_like(trans_raw)
-        g_ir, g_it = torch.empty_like(init_rot), torch.empty_like(init_trans)
-        _C.nopesac_refine_score_maps_backward(_p(geo_local), _p(rot_raw.contiguous()), _p(trans_raw.contiguous()), _p(init_rot), _p(init_trans),
-                                              _p(m), B, nq, _p(g_ns), _p(g_ps), _p(g_l2), _p(g_rot), _p(g_tr), _p(g_ir), _p(g_it), _stream())
+        g_rot, g_tr, g_ir, g_it = ops.ransac_score_maps_backward(geo_local, rot_raw.contiguous(), trans_raw.contiguous(), init_rot, init_trans, m,
+                                                                 g_ns, g_ps, g_l2)
         return None, g_rot, g_tr, g_ir, g_it, None
 
 
@@ -163,20 +144,13 @@ class _Vote(torch.autograd.Function):
         g_pr, g_ar = zl(g_pr, (B, 4)), zl(g_ar, (B, 4))
         g_pt, g_at = zl(g_pt, (B, 3)), zl(g_at, (B, 3))
         g_sr, g_st = zl(g_sr, (B, NH)), zl(g_st, (B, NH))
-        o = {"g_sf_rot": torch.empty_like(sf_rot), "g_sf_trans": torch.empty_like(sf_trans), "g_irf": torch.empty_like(init_rot_feat),
-             "g_itf": torch.empty_like(init_trans_feat), "g_fr": torch.empty_like(fused_rot), "g_ft": torch.empty_like(fused_trans),
-             "pb_rw": torch.empty(B, 4 * 256, **f32), "pb_rb": torch.empty(B, 4, **f32), "pb_tw": torch.empty(B, 3 * 256, **f32),
-             "pb_tb": torch.empty(B, 3, **f32), "pb_rrw": torch.empty(B, 64, **f32), "pb_rrb": torch.empty(B, 1, **f32),
-             "pb_rtw": torch.empty(B, 64, **f32), "pb_rtb": torch.empty(B, 1, **f32)}
-        _C.nopesac_refine_vote_backward(
-     _p(sf_rot), _p(sf_trans), _p(reg_rot_w), _p(reg_rot_b), _p(reg_trans_w), _p(reg_trans_b), _p(init_rot_feat), _p(init_trans_feat), _p(fused_rot),
-     _p(fused_trans), _p(rots_w), _p(rots_b), _p(trans_w), _p(trans_b), _p(m), B, nq, _p(g_pr), _p(g_pt), _p(g_ar), _p(g_at), _p(g_sr), _p(g_st),
-     _p(o["g_sf_rot"]), _p(o["g_sf_trans"]), _p(o["g_irf"]), _p(o["g_itf"]), _p(o["g_fr"]), _p(o["g_ft"]), _p(o["pb_rw"]), _p(o["pb_rb"]),
-     _p(o["pb_tw"]), _p(o["pb_tb"]), _p(o["pb_rrw"]), _p(o["pb_rrb"]), _p(o["pb_rtw"]), _p(o["pb_rtb"]), _stream())
+        o = ops.ransac_soft_vote_backward(sf_rot, sf_trans, reg_rot_w, reg_rot_b, reg_trans_w, reg_trans_b, init_rot_feat, init_trans_feat, fused_rot,
+                                          fused_trans, rots_w, rots_b, trans_w, trans_b, m, g_pr, g_pt, g_ar, g_at, g_sr, g_st)
         red = lambda t, like: col_sum(t).view_as(like)              # per-pair partials -> the parameter's gradient (fixed order)
-        return (o["g_sf_rot"], o["g_sf_trans"], red(o["pb_rrw"], reg_rot_w), red(o["pb_rrb"], reg_rot_b), red(o["pb_rtw"], reg_trans_w),
-                red(o["pb_rtb"], reg_trans_b), o["g_irf"], o["g_itf"], o["g_fr"], o["g_ft"], red(o["pb_rw"], rots_w), red(o["pb_rb"], rots_b),
-                red(o["pb_tw"], trans_w), red(o["pb_tb"], trans_b), None, None, None, None, None, None, None)
+        return (o["g_sf_rot"], o["g_sf_trans"], red(o["pb_reg_rot_w"], reg_rot_w), red(o["pb_reg_rot_b"], reg_rot_b),
+                red(o["pb_reg_trans_w"], reg_trans_w), red(o["pb_reg_trans_b"], reg_trans_b), o["g_init_rot_feat"], o["g_init_trans_feat"],
+                o["g_fused_rot"], o["g_fused_trans"], red(o["pb_rots_w"], rots_w), red(o["pb_rots_b"], rots_b), red(o["pb_trans_w"], trans_w),
+                red(o["pb_trans_b"], trans_b), None, None, None, None, None, None, None)
 
 
 class _Losses(torch.autograd.Function):
@@ -188,20 +162,14 @@ class _Losses(torch.autograd.Function):
         ctx.weight = float(weight)
         ctx.save_for_backward(vote["pred_rot"], vote["pred_trans"], vote["avg_rot"], vote["avg_trans"], vote["score_rot"], vote["score_trans"], rots_all,
                               trans_all, m, gt_pose)
-        ctx.l2_shape = tuple(l2_dist.shape)
         return ops.plane_cam_ref_losses(vote, maps, m, gt_pose, weight)
 
     @staticmethod
     def backward(ctx, g):
         pr, pt, ar, at, sr, st, rots_all, trans_all, m, gt = ctx.saved_tensors
-        B, NH = sr.shape
-        dev = sr.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        o = [torch.empty(B, 4, **f32), torch.empty(B, 3, **f32), torch.empty(B, 4, **f32), torch.empty(B, 3, **f32), torch.empty(B, NH, **f32),
-             torch.empty(B, NH, **f32), torch.empty(ctx.l2_shape, **f32)]
-        _C.nopesac_refine_losses_backward(_p(pr), _p(pt), _p(ar), _p(at), _p(rots_all), _p(trans_all), _p(sr), _p(st), _p(m), _p(gt),
-                                          _p(g.contiguous()), B, NH - 1, ctx.weight, *[_p(t) for t in o], _stream())
-        return o[0], o[1], o[2], o[3], o[4], o[5], o[6], None, None, None, None, None
+        vote = {"pred_rot": pr, "pred_trans": pt, "avg_rot": ar, "avg_trans": at, "score_rot": sr, "score_trans": st}
+        grads = ops.plane_cam_ref_losses_backward(vote, {"rots_all": rots_all, "trans_all": trans_all}, m, gt, g.contiguous(), ctx.weight)
+        return (*grads, None, None, None, None, None)
 
 
 class _Normalize(torch.autograd.Function):
@@ -215,10 +183,7 @@ class _Normalize(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
-        out = torch.empty_like(x)
-        D = x.shape[-1]
-        _C.nopesac_normalize_rows_backward(_p(x), _p(g.contiguous()), x.numel() // D, D, int(ctx.canonical), _p(out), _stream())
-        return out, None
+        return ops.normalize_rows_backward(x, g.contiguous(), ctx.canonical), None
 
 
 class _PoseLoss(torch.autograd.Function):
@@ -234,11 +199,7 @@ class _PoseLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         est_t, est_q, gt_t, gt_q = ctx.saved_tensors
-        B = est_t.shape[0]
-        o = [torch.empty_like(est_t), torch.empty_like(est_q), torch.empty_like(gt_t), torch.empty_like(gt_q)]
-        _C.nopesac_camera_pose_loss_backward(_p(est_t), _p(est_q), _p(gt_t), 3, _p(gt_q), 4, B, ctx.eps, ctx.weight, _p(g.contiguous()),
-                                             *[_p(t) for t in o], _stream())
-        return o[0], o[1], o[2], o[3], None, None
+        return (*ops.camera_pose_loss_backward(est_t, est_q, gt_t, gt_q, g.contiguous(), ctx.weight, ctx.eps), None, None)
 
 
 def _ohwi(w: torch.Tensor, cin: int) -> torch.Tensor:
@@ -366,7 +327,7 @@ class _CorrSoftmax(torch.autograd.Function):
 
 class _Attention(torch.autograd.Function):
     """ops.attention (f32, head dim 32, ragged by qlen / klen) on row-major q / k / v that may be column slices of a wider matrix;
-    backward: nopesac_attention_small_backward (softmax recomputed)."""
+    backward: ops.attention_backward (softmax recomputed)."""
 
     @staticmethod
     def forward(ctx, q, k, v, B: int, Lq: int, Lk: int, heads: int, scale: float, qlen, klen):
@@ -379,11 +340,7 @@ class _Attention(torch.autograd.Function):
     def backward(ctx, g):
         q, k, v, qlen, klen = ctx.saved_tensors
         B, Lq, Lk, heads, scale = ctx.conf
-        g = g.contiguous()
-        dq, dk, dv = (torch.empty(t.shape[0], heads * 32, device=q.device, dtype=torch.float32) for t in (q, k, v))
-        _C.nopesac_attention_small_backward(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(g), g.stride(0), B, Lq, Lk,
-                                            heads, scale, _p(qlen), _p(klen), _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv),
-                                            dv.stride(0), _stream())
+        dq, dk, dv = ops.attention_backward(q, k, v, g.contiguous(), B, Lq, Lk, heads, scale, qlen, klen)
         return dq, dk, dv, None, None, None, None, None, None, None
 
 
@@ -421,9 +378,7 @@ class _AttentionFused(torch.autograd.Function):
             dq = torch.empty_like(q)
             qv, kv, vv = q, packed[:, :W], packed[:, W:]
             gq, gk, gv = dq, dpacked[:, :W], dpacked[:, W:]
-        _C.nopesac_attention_small_backward(_p(qv), qv.stride(0), _p(kv), kv.stride(0), _p(vv), vv.stride(0), _p(g), g.stride(0), B, Lq, Lk,
-                                            heads, scale, _p(qlen), _p(klen), _p(gq), gq.stride(0), _p(gk), gk.stride(0), _p(gv),
-                                            gv.stride(0), _stream())
+        ops.attention_backward(qv, kv, vv, g, B, Lq, Lk, heads, scale, qlen, klen, out=(gq, gk, gv))
         return dq, dpacked, None, None, None, None, None, None, None
 
 
@@ -445,9 +400,7 @@ class _LinearSplit(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         a, b, w, y = ctx.saved_tensors
-        g = g.contiguous()
-        gm = torch.empty_like(g)
-        _C.nopesac_relu_backward_f32(_p(g), _p(y), g.numel(), _p(gm), _stream())
+        gm = ops.relu_backward(g.contiguous(), y)
         ga = gb = gw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             gx = ops.linear(gm, transpose(w))
@@ -472,18 +425,13 @@ class _LayerNorm(torch.autograd.Function):
     def backward(ctx, g):
         x, gamma = ctx.saved_tensors
         g = g.contiguous()
-        D = x.shape[-1]
-        rows = x.numel() // D
-        dx, dgamma, dbeta = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
-        n_ws = _C.nopesac_layernorm_backward_workspace_floats(rows)
-        ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
-        _C.nopesac_layernorm_backward(_p(x), _p(gamma), _p(g), rows, D, LN_EPS, _p(dx), _p(dgamma), _p(dbeta), _p(ws), n_ws, _stream())
+        dx, dgamma, dbeta = ops.layernorm_backward(x, gamma, g, LN_EPS)
         return dx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None)
 
 
 class _DescDot(torch.autograd.Function):
     """dots[b] = D0[b] D1[b]^T / sqrt(256) on the batched-weights f32 GEMM (as MatchingHead.forward); backward:
-    nopesac_desc_dot_backward over the live n1 x n2 block - padded descriptor rows get exactly zero."""
+    ops.desc_dot_backward over the live n1 x n2 block - padded descriptor rows get exactly zero."""
 
     @staticmethod
     def forward(ctx, d0, d1, n1, n2):
@@ -496,10 +444,7 @@ class _DescDot(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         d0, d1, n1, n2 = ctx.saved_tensors
-        B, nq, D = d0.shape
-        g = g.contiguous()
-        dd0, dd1 = torch.empty_like(d0), torch.empty_like(d1)
-        _C.nopesac_desc_dot_backward(_p(g), _p(d0), _p(d1), _p(n1), _p(n2), B, nq, D, _p(dd0), _p(dd1), _stream())
+        dd0, dd1 = ops.desc_dot_backward(g.contiguous(), d0, d1, n1, n2)
         return dd0, dd1, None, None
 
 
@@ -514,12 +459,9 @@ class _SinkhornEmbLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dots, bin_score, planes1, planes2, cam7, n1, n2, gt_corr, offset_mult: float, normal_mult: float, iters: int):
         dots, bin_score = dots.contiguous(), bin_score.contiguous()
-        B, nq, _ = dots.shape
-        f32 = dict(device=dots.device, dtype=torch.float32)
         log_scores, _assignment = ops.matcher_sinkhorn(dots, planes1, planes2, cam7, n1, n2, bin_score, float(offset_mult), float(normal_mult),
                                                        int(iters), 0.0)
-        stats, loss = torch.empty(B, 2, **f32), torch.empty(2, **f32)
-        _C.nopesac_matcher_emb_loss(_p(log_scores), _p(gt_corr), _p(n1), _p(n2), B, nq, _p(stats), _p(loss), _stream())
+        _stats, loss = ops.matcher_emb_loss(log_scores, gt_corr, n1, n2)
         ctx.conf = (float(offset_mult), float(normal_mult), int(iters))
         ctx.save_for_backward(dots, bin_score, planes1, planes2, cam7, n1, n2, gt_corr)
         ctx.loss = loss
@@ -530,20 +472,10 @@ class _SinkhornEmbLoss(torch.autograd.Function):
     def backward(ctx, g, _g_scores):
         dots, bin_score, planes1, planes2, cam7, n1, n2, gt_corr = ctx.saved_tensors
         offset_mult, normal_mult, iters = ctx.conf
-        B, nq, _ = dots.shape
-        f32 = dict(device=dots.device, dtype=torch.float32)
-        g = g.contiguous().view(1)
-        uv = torch.empty(B, iters, 2, nq + 1, **f32)
-        scratch = (torch.empty(B, nq + 1, nq + 1, **f32), torch.empty(B, 2, **f32), torch.empty(2, **f32))
-        _C.nopesac_matcher_sinkhorn_train(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
-                                          normal_mult, iters, _p(gt_corr), B, nq, _p(scratch[0]), _p(uv), _p(scratch[1]), _p(scratch[2]),
-                                          _stream())
-        d_dots = torch.empty_like(dots)
-        d_bin = torch.empty(B, 1, **f32)
-        _C.nopesac_matcher_sinkhorn_train_backward(_p(dots), _p(planes1), _p(planes2), _p(cam7), _p(n1), _p(n2), _p(bin_score), offset_mult,
-                                                   normal_mult, iters, _p(gt_corr), _p(uv), _p(ctx.loss), _p(g), B, nq, _p(d_dots),
-                                                   _p(d_bin), _stream())
-        return d_dots, col_sum(d_bin).view_as(bin_score), None, None, None, None, None, None, None, None, None
+        inputs = (dots, planes1, planes2, cam7, n1, n2, bin_score, offset_mult, normal_mult, iters, gt_corr)
+        _scores, uv, _stats, _loss = ops.matcher_sinkhorn_train(*inputs)
+        d_dots, d_bin = ops.matcher_sinkhorn_train_backward(*inputs, uv, ctx.loss, g.contiguous().view(1))
+        return d_dots, col_sum(d_bin.view(-1, 1)).view_as(bin_score), None, None, None, None, None, None, None, None, None
 
 
 class RefineTrainer:
@@ -663,13 +595,12 @@ class RefineTrainer:
                 if optimizer.upper() == "ADAMW":
                     if not st:
                         st["m1"], st["m2"] = torch.zeros_like(p), torch.zeros_like(p)
-                    _C.nopesac_adamw_step(_p(p), _p(g), _p(st["m1"]), _p(st["m2"]), p.numel(), float(lr), float(betas[0]), float(betas[1]),
-                                          float(eps), float(wd), self.steps, _stream())
+                    ops.adamw_step(p, g, st["m1"], st["m2"], lr, betas[0], betas[1], eps, wd, self.steps)
                 elif optimizer.upper() == "SGD":
                     first = "mom" not in st
                     if first:
                         st["mom"] = torch.zeros_like(p)
-                    _C.nopesac_sgd_step(_p(p), _p(g), _p(st["mom"]), p.numel(), float(lr), float(momentum), float(wd), int(first), _stream())
+                    ops.sgd_step(p, g, st["mom"], lr, momentum, wd, first)
                 else:
                     raise NotImplementedError(f"no optimizer type {optimizer}")           # train_NopeSAC.py:158
 
@@ -677,16 +608,15 @@ class RefineTrainer:
         """torch.nn.utils.clip_grad_norm_ over ALL parameters of this trainer (the reference's FullModelGradientClippingOptimizer,
         train_NopeSAC.py:139-148), on the device: returns the clip coefficient (f32[1]; 1 = not clipped) without a host sync."""
         grads = [p.grad for p in self.params.values() if p.grad is not None]
-        acc = torch.zeros(1, device=grads[0].device, dtype=torch.float32)
-        coef = torch.empty(1, device=grads[0].device, dtype=torch.float32)
+        acc = None
         for g in grads:
-            _C.nopesac_sumsq_accumulate_f32(_p(g.contiguous()), g.numel(), _p(acc), _stream())
-        _C.nopesac_clip_coefficient(_p(acc), float(max_norm), _p(coef), _stream())
+            acc = ops.sumsq_accumulate(g.contiguous(), acc)
+        coef = ops.clip_coefficient(acc, max_norm)
         for p in self.params.values():
             if p.grad is not None:
                 if not p.grad.is_contiguous():
                     p.grad = p.grad.contiguous()
-                _C.nopesac_scale_by_f32(_p(p.grad), p.grad.numel(), _p(coef), _stream())
+                ops.scale_by(p.grad, coef)
         return coef
 
     def step_from_cfg(self, cfg):
@@ -733,11 +663,11 @@ class CameraHeadTrainer(RefineTrainer):
                  conv_stacks: bool = False, feature_grads: bool = False):
         super().__init__(params, nq, warp_in_ref)
         self.conv_stacks, self.feature_grads = bool(conv_stacks), bool(feature_grads)
-        assert not self.feature_grads or self.conv_stacks, "feature_grads needs conv_stacks=True"
+        _require(not self.feature_grads or self.conv_stacks, "feature_grads needs conv_stacks=True")
         self.buffers = {k: v.detach().float().contiguous() for k, v in (buffers or {}).items()}
         if self.conv_stacks:
             missing = [k for k in self.parameter_names(list(self.params) + list(self.buffers), True) if k not in self.params]
-            assert not missing, missing
+            _require(not missing, "conv_stacks=True: missing parameters %s" % (missing,))
 
     @staticmethod
     def parameter_names(sd_keys, conv_stacks: bool = False) -> List[str]:
@@ -960,7 +890,8 @@ class MatchingHeadTrainer(RefineTrainer):
         n_all = n_all.contiguous()
         n1, n2 = n_all[:B].contiguous(), n_all[B:].contiguous()
         gt = gt_corr.to(torch.uint8).contiguous()
-        assert app.shape == (2 * B, nq, 256) and gt.shape == (B, nq + 1, nq + 1) and n_all.dtype == torch.int32, (app.shape, gt.shape)
+        _require(app.shape == (2 * B, nq, 256) and gt.shape == (B, nq + 1, nq + 1) and n_all.dtype == torch.int32,
+                 "matching_losses: app [2B,nq,256], gt_corr [B,nq+1,nq+1], n_all int32; got %s, %s, %s" % (tuple(app.shape), tuple(gt.shape), n_all.dtype))
         q = MATCHER_PREFIX
         f = _Linear.apply(app.reshape(2 * rows, 256), P[q + "planeApp_proj.weight"].view(256, 256), P[q + "planeApp_proj.bias"], False)
         for i in range(GNN_LAYERS):

@@ -194,19 +194,57 @@ def test_checked_layer_raises_on_a_status_and_hands_values_through():
 
 
 def test_training_wrappers_refuse_cpu_tensors(monkeypatch):
-    """The training-side wrappers share ops' pointer helper: a CPU tensor raises OpsArgumentError before the library is called (its
-    host address must never reach a kernel)."""
+    """The training path reaches the library through ops alone, and every wrapper of that path raises OpsArgumentError for a CPU tensor
+    before the library is called (a host address must never reach a kernel)."""
     from nopesac_amd import _lib, ops, training
-    assert training._p is ops._p and training._stream is ops._stream
+    assert not any(hasattr(training, name) for name in ("_C", "_p", "_stream"))
+    _lib.load()
 
     def reached(*args):
         raise AssertionError("the library was called with a host address")
-    for name in ("nopesac_col_sum_f32", "nopesac_transpose_f32"):
+    for name in _lib.STATUS:
         monkeypatch.setattr(_lib.C, name, reached)
     with pytest.raises(ops.OpsArgumentError, match="no CPU path"):
         training.col_sum(torch.zeros(4, 8))
     with pytest.raises(ops.OpsArgumentError, match="no CPU path"):
         training.transpose(torch.zeros(4, 8))
+
+    B, nq, iters, L, heads = 2, 3, 3, 4, 8
+    NH, W = nq + 1, heads * 32
+    f = lambda *shape: torch.zeros(*shape)
+    i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32)
+    gt_corr = torch.zeros(B, NH, NH, dtype=torch.uint8)
+    sinkhorn = (f(B, nq, nq), f(B, nq, 3), f(B, nq, 3), f(B, 7), i32(B), i32(B), f(1), 4.0, 8.0, iters, gt_corr)
+    vote = {"pred_rot": f(B, 4), "pred_trans": f(B, 3), "avg_rot": f(B, 4), "avg_trans": f(B, 3), "score_rot": f(B, NH), "score_trans": f(B, NH)}
+    calls = {
+        "transpose_rows": lambda: ops.transpose_rows(f(4, 8)),
+        "col_sum": lambda: ops.col_sum(f(4, 8)),
+        "relu_backward": lambda: ops.relu_backward(f(4, 8), f(4, 8)),
+        "ransac_score_maps_backward": lambda: ops.ransac_score_maps_backward(f(B, nq, 6), f(B, nq, 4), f(B, nq, 3), f(B, 4), f(B, 3), i32(B),
+                                                                             f(B, NH, nq), f(B, NH, nq), f(B, NH, nq)),
+        "ransac_soft_vote_backward": lambda: ops.ransac_soft_vote_backward(
+            f(B, NH, 64), f(B, NH, 64), f(64), f(1), f(64), f(1), f(B, 256), f(B, 256), f(B, nq, 256), f(B, nq, 256), f(4, 256), f(4), f(3, 256),
+            f(3), i32(B), f(B, 4), f(B, 3), f(B, 4), f(B, 3), f(B, NH), f(B, NH)),
+        "plane_cam_ref_losses_backward": lambda: ops.plane_cam_ref_losses_backward(vote, {"rots_all": f(B, NH, 4), "trans_all": f(B, NH, 3)}, i32(B),
+                                                                                   f(B, 7), f(7), 1.0),
+        "normalize_rows_backward": lambda: ops.normalize_rows_backward(f(B, 4), f(B, 4), True),
+        "camera_pose_loss_backward": lambda: ops.camera_pose_loss_backward(f(B, 3), f(B, 4), f(B, 3), f(B, 4), f(2)),
+        "attention_backward": lambda: ops.attention_backward(f(B * L, W), f(B * L, W), f(B * L, W), f(B * L, W), B, L, L, heads, 0.25, i32(B), i32(B)),
+        "layernorm_backward": lambda: ops.layernorm_backward(f(5, 256), f(256), f(5, 256)),
+        "desc_dot_backward": lambda: ops.desc_dot_backward(f(B, nq, nq), f(B, nq, 256), f(B, nq, 256), i32(B), i32(B)),
+        "matcher_emb_loss": lambda: ops.matcher_emb_loss(f(B, NH, NH), gt_corr, i32(B), i32(B)),
+        "matcher_sinkhorn_train": lambda: ops.matcher_sinkhorn_train(*sinkhorn),
+        "matcher_sinkhorn_train_backward": lambda: ops.matcher_sinkhorn_train_backward(*sinkhorn, f(B, iters, 2, NH), f(2), f(1)),
+        "adamw_step": lambda: ops.adamw_step(f(5), f(5), f(5), f(5), 1e-3, 0.9, 0.999, 1e-8, 0.01, 1),
+        "sgd_step": lambda: ops.sgd_step(f(5), f(5), f(5), 1e-3, 0.9, 0.01, True),
+        "sumsq_accumulate": lambda: ops.sumsq_accumulate(f(5), f(1)),
+        "clip_coefficient": lambda: ops.clip_coefficient(f(1), 1.0),
+        "scale_by": lambda: ops.scale_by(f(5), f(1)),
+    }
+    for name, call in calls.items():
+        with pytest.raises(ops.OpsArgumentError, match="no CPU path"):
+            call()
+            pytest.fail(name + " accepted CPU tensors")
 
 
 def test_no_cpu_fallback():
