@@ -810,6 +810,22 @@ nps_status nopesac_rle_string_runs(const uint8_t* bytes, const int64_t* str_off,
  *   zero and its area 0.  starts: int32 scratch laid out like runs (the first pixel of every run).  H W < 2^31 - 32. */
 nps_status nopesac_rle_runs_to_bits(const int32_t* runs, const int64_t* run_off, const int32_t* n_runs, int n_masks, int H, int W,
                                     int32_t* starts, uint32_t* bits, int32_t* area, int32_t* bad, void* stream);
+#define NPS_POLY_COORD_MAX 536870912  /* poly_to_bits: |5 x + 0.5| of every coordinate must stay below this (2^29) */
+#define NPS_POLY_POINT_FACTOR 16      /* poly_to_bits: a polygon may have at most NPS_POLY_POINT_FACTOR (H W + H + W) + */
+#define NPS_POLY_POINT_FLOOR 1048576  /*   NPS_POLY_POINT_FLOOR upsampled boundary points */
+/* poly_to_bits: COCO polygon lists -> masks in the layout of runs_to_bits (csrc/plane_eval.hip): cocoapi's rleFrPoly per polygon
+ *   (upsampling by 5, truncating casts, crossings at x H + y, y clamped to [0, H]) and rleMerge(intersect = 0) across a mask's
+ *   polygons, bit for bit.  xy: double [2 n_points], all polygons concatenated, x first; polygon j owns points poly_off[j] ..
+ *   poly_off[j + 1] (int64 [n_polys + 1]); mask i owns polygons mask_off[i] .. mask_off[i + 1] (int64 [n_masks + 1]).
+ *   bits uint32 [n_masks, ceil(H W / 32)], area int32 [n_masks], bad int32 [n_masks]: 1 when the mask has no polygon, an offset lies
+ *   outside [0, n_polys] / [0, n_points], a polygon has fewer than 3 (or more than 2^30) points, a coordinate is not finite or
+ *   reaches NPS_POLY_COORD_MAX after upsampling, or a polygon's upsampled point count sum(max(dx, dy) + 1) exceeds the cap above -
+ *   all checked before a point is generated; the mask's words are then zero and its area 0.  toggles: uint32 scratch of the size of
+ *   `bits` (the kernel clears it itself and leaves it zero).  One launch for all masks, a workgroup per mask.  Deterministic: integer
+ *   results, and its only atomics are XOR / exchange on scratch words, which do not depend on order.  H W < 2^31 - 32; n_masks = 0
+ *   enqueues nothing. */
+nps_status nopesac_poly_to_bits(const double* xy, const int64_t* poly_off, const int64_t* mask_off, int64_t n_points, int64_t n_polys,
+                                int n_masks, int H, int W, uint32_t* toggles, uint32_t* bits, int32_t* area, int32_t* bad, void* stream);
 /* mask_iou_bits: for view v, predictions = rows dt_off[v] .. dt_off[v + 1] of dt_bits (areas in dt_area), GT masks = rows gt_off[v] ..
  *   gt_off[v + 1] of gt_bits (gt_area; iscrowd uint8 per GT mask, NULL = none).  inter = popcount(dt & gt), union = area_dt + area_gt -
  *   inter (area_dt for a crowd GT), iou = union > 0 ? (double)inter / (double)union : 0, written at iou_off[v] + i n_gt(v) + j of

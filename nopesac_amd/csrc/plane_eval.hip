@@ -5,6 +5,7 @@
 // Ragged quantities use exclusive-offset arrays (int64 [n + 1]), so one launch serves every view of a batch.  Pixel order is COCO's
 // column-major scan p = x H + y; bit p of a mask is bit (p & 31) of word (p >> 5); a mask has ceil(H W / 32) words and the unused
 // high bits of its last word are zero.  Every kernel is deterministic: integer counts, no atomics, each output written once.
+// Polygon annotations reach the same bit-packed form through poly_to_bits_kernel (below; deterministic too, its atomics are XOR on words).
 #include "common.h"
 
 namespace nps {
@@ -334,6 +335,197 @@ __global__ __launch_bounds__(64) void plane_ap_assign_kernel(const double* __res
     }
 }
 
+// ---- COCO polygon lists -> bit-packed masks: one workgroup per mask ---------------------------------------------------------------
+// cocoapi's rleFrPoly (maskApi.c) followed by rleMerge(intersect = 0), written in the layout of rle_runs_to_bits_kernel, so that GT
+// masks annotated as polygons feed mask_iou_bits_kernel directly (the reference: mask_util.frPyObjects + merge, mp3d_evaluation.py:544-554).
+// cocoapi upsamples a polygon by 5, walks every edge one upsampled unit at a time, turns every change of the upsampled x between
+// two consecutive boundary points into a "crossing" at a flat position p = x H + y, SORTS the positions and differences them into
+// runs.  The runs say: pixel q is set iff an odd number of crossings lie at or before q.  This kernel never sorts: it XORs every
+// crossing into a toggle bitmap and takes the prefix parity of that bitmap along the flat bit order (shift-XOR inside a word, a
+// scan of the words' popcount parities across words), then ORs the polygon into the mask.  Every per-point operation (the
+// truncating casts, the separate multiply and add, the division by 5.0) is cocoapi's, one IEEE double operation at a time
+// (-ffp-contract=off).  Integer results only; the atomics are XOR on words, which does not depend on order: two runs give the same bytes.
+//
+// One workgroup per mask.  Pass 0 checks the mask (offsets, vertex counts, finite and bounded coordinates, the point cap) before
+// any point is generated.  Then per polygon: 256 edges at a time, the per-edge point counts are scanned so that threads take POINTS
+// (not edges: a contour has hundreds of 6-point edges, a box four edges of thousands), each point forms the pair with its
+// predecessor - across an edge junction the previous edge's last point, computed from the same formula, which is not always the
+// vertex - and toggles its crossing; after a barrier one pass reads and clears the toggles, 256 words per step, and writes the words.
+constexpr int PM_MAX_VERTS = 1 << 30;          // vertices of one polygon (the chunk loop counts in int)
+
+// X = (int)(5 x + 0.5), cocoapi's upsampling (the cast truncates toward zero).  false: not finite, or beyond NPS_POLY_COORD_MAX.
+__device__ __forceinline__ bool pm_upsample(double c, int& C) {
+    const double r = 5.0 * c + 0.5;
+    const bool ok = fabs(r) < (double)NPS_POLY_COORD_MAX;      // (false for NaN)
+    C = (int)(ok ? r : 0.0);
+    return ok;
+}
+
+__device__ __forceinline__ int pm_edge_len(int xs, int ys, int xe, int ye) { return max(abs(xe - xs), abs(ye - ys)); }
+
+// The edge's slope along its longer axis, after cocoapi's flip; 0 for an edge of length 0 (cocoapi's 0 / 0 is never used).
+__device__ __forceinline__ double pm_slope(int xs, int ys, int xe, int ye) {
+    const int dx = abs(xe - xs), dy = abs(ye - ys);
+    const bool wide = dx >= dy;
+    const bool flip = wide ? xs > xe : ys > ye;
+    const int num = wide ? (flip ? ys - ye : ye - ys) : (flip ? xs - xe : xe - xs), den = wide ? dx : dy;
+    return den ? (double)num / (double)den : 0.0;
+}
+
+// Point d (0 .. length) of the edge (xs, ys) -> (xe, ye), counted in the edge's own direction.
+__device__ __forceinline__ void pm_point(int xs, int ys, int xe, int ye, double s, int d, int& u, int& v) {
+    const int dx = abs(xe - xs), dy = abs(ye - ys);
+    const bool wide = dx >= dy;
+    const bool flip = wide ? xs > xe : ys > ye;
+    const int x0 = flip ? xe : xs, y0 = flip ? ye : ys, n = wide ? dx : dy;
+    const int t = flip ? n - d : d;
+    const double st = s * (double)t;
+    const int c = (int)((double)(wide ? y0 : x0) + st + 0.5);
+    u = n == 0 ? xs : (wide ? x0 + t : c);
+    v = n == 0 ? ys : (wide ? c : y0 + t);
+}
+
+// Flat position of the crossing between a boundary point and its predecessor, or -1 when there is none.
+__device__ __forceinline__ long long pm_crossing(int u, int v, int pu, int pv, int H, int W) {
+    if (u == pu) return -1;
+    double xd = (double)(u < pu ? u : u - 1);
+    xd = (xd + 0.5) / 5.0 - 0.5;
+    if (floor(xd) != xd || xd < 0.0 || xd > (double)(W - 1)) return -1;
+    double yd = (double)(v < pv ? v : pv);
+    yd = (yd + 0.5) / 5.0 - 0.5;
+    yd = yd < 0.0 ? 0.0 : (yd > (double)H ? (double)H : yd);
+    yd = ceil(yd);
+    return (long long)(int)xd * H + (int)yd;
+}
+
+__global__ __launch_bounds__(PE_T) void poly_to_bits_kernel(const double* __restrict__ xy, const long long* __restrict__ poly_off,
+                                                            const long long* __restrict__ mask_off, long long n_points, long long n_polys,
+                                                            int H, int W, int N, int words, long long cap, uint32_t* __restrict__ toggles,
+                                                            uint32_t* __restrict__ bits, int* __restrict__ area, int* __restrict__ bad) {
+    // a chunk's vertices: slot s holds vertex j0 - 1 + s of the polygon; edge slot e joins vertex slots e and e + 1 (edge j0 - 1 + e)
+    __shared__ int sX[PE_T + 2], sY[PE_T + 2];
+    __shared__ double sS[PE_T + 1];
+    __shared__ long long sStart[PE_T];
+    __shared__ long long wave_ll[PE_T / 64];
+    __shared__ int wave_i[2][PE_T / 64];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t* tg = toggles + (long long)i * words;
+    uint32_t* bw = bits + (long long)i * words;
+    const long long m0 = mask_off[i], m1 = mask_off[i + 1];
+    int is_bad = (m0 < 0 || m1 > n_polys || m1 <= m0) ? 1 : 0;            // (a mask without polygons is bad)
+    const long long n_mine = is_bad ? 0 : m1 - m0;
+
+    // ---- pass 0: nothing is generated for a mask that fails any check
+    for (long long q = 0; q < n_mine; ++q) {
+        const long long a = poly_off[m0 + q], b = poly_off[m0 + q + 1];
+        if (a < 0 || b > n_points || b - a < 3 || b - a > PM_MAX_VERTS) {   // (the same for every thread)
+            is_bad = 1;
+            continue;
+        }
+        const int k = (int)(b - a);
+        const double* p = xy + 2 * a;
+        long long mine = 0;
+        for (int j0 = 0; j0 < k; j0 += PE_T) {
+            const int j = min(j0 + tid, k - 1), jn = j + 1 == k ? 0 : j + 1;
+            const double x0 = p[2 * j], y0 = p[2 * j + 1], x1 = p[2 * jn], y1 = p[2 * jn + 1];
+            int X0, Y0, X1, Y1;
+            const bool ok0 = pm_upsample(x0, X0), ok1 = pm_upsample(y0, Y0), ok2 = pm_upsample(x1, X1), ok3 = pm_upsample(y1, Y1);
+            if (!(ok0 && ok1 && ok2 && ok3)) is_bad = 1;
+            mine += j0 + tid < k ? (long long)pm_edge_len(X0, Y0, X1, Y1) + 1 : 0;
+        }
+        long long total;
+        pe_block_excl(mine, wave_ll, total);
+        if (total > cap) is_bad = 1;
+    }
+    {
+        const int any = __ballot(is_bad) != 0ull ? 1 : 0;
+        __syncthreads();                       // wave_i is free
+        if (lane == 0) wave_i[0][wave] = any;
+        __syncthreads();
+        is_bad = wave_i[0][0] | wave_i[0][1] | wave_i[0][2] | wave_i[0][3];
+    }
+    if (is_bad) {
+        for (int w = tid; w < words; w += PE_T) bw[w] = 0u;
+        if (tid == 0) { bad[i] = 1; area[i] = 0; }
+        return;
+    }
+    for (int w = tid; w < words; w += PE_T) tg[w] = 0u;
+    __threadfence();                           // the zeros have reached memory before another wave's XOR on the same word can
+
+    int ones = 0;
+    for (long long q = 0; q < n_mine; ++q) {
+        const long long a = poly_off[m0 + q];
+        const int k = (int)(poly_off[m0 + q + 1] - a);
+        const double* p = xy + 2 * a;
+        // ---- crossings of polygon q -> toggles
+        for (int j0 = 0; j0 < k; j0 += PE_T) {
+            __syncthreads();                   // the previous chunk's slots have been read; the toggle words are zero for everybody
+            for (int s = tid; s < PE_T + 2; s += PE_T) {
+                const int j = j0 - 1 + s, jj = (j < 0 || j >= k) ? 0 : j;      // vertex k is vertex 0; slots beyond it are not used
+                pm_upsample(p[2 * jj], sX[s]);
+                pm_upsample(p[2 * jj + 1], sY[s]);
+            }
+            __syncthreads();
+            const int n_edges = min(PE_T, k - j0);
+            for (int e = tid; e < PE_T + 1; e += PE_T) sS[e] = pm_slope(sX[e], sY[e], sX[e + 1], sY[e + 1]);
+            const long long cnt = tid < n_edges ? (long long)pm_edge_len(sX[tid + 1], sY[tid + 1], sX[tid + 2], sY[tid + 2]) + 1 : 0;
+            long long total;
+            sStart[tid] = pe_block_excl(cnt, wave_ll, total);
+            __syncthreads();
+            for (long long f = tid; f < total; f += PE_T) {
+                int lo = 0, hi = n_edges;                                  // the last edge that starts at or before point f
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (sStart[mid] <= f) lo = mid; else hi = mid;
+                }
+                const int d = (int)(f - sStart[lo]), e = lo + 1;
+                if (d == 0 && lo == 0 && j0 == 0) continue;                // the polygon's first point has no predecessor
+                int u, v, pu, pv;
+                pm_point(sX[e], sY[e], sX[e + 1], sY[e + 1], sS[e], d, u, v);
+                const int pe = d == 0 ? e - 1 : e;                         // across a junction: the previous edge's last point
+                const int pxs = sX[pe], pys = sY[pe], pxe = sX[pe + 1], pye = sY[pe + 1];
+                pm_point(pxs, pys, pxe, pye, sS[pe], d == 0 ? pm_edge_len(pxs, pys, pxe, pye) : d - 1, pu, pv);
+                const long long pos = pm_crossing(u, v, pu, pv, H, W);
+                if (pos >= 0 && pos < N) atomicXor(&tg[pos >> 5], 1u << (int)(pos & 31));
+            }
+        }
+        __threadfence();
+        __syncthreads();                       // every toggle of the polygon has been made, and has reached memory
+        // ---- prefix parity of the toggles (read and cleared), OR into the mask
+        int carry = 0;
+        for (int w0 = 0; w0 < words; w0 += PE_T) {
+            const int w = w0 + tid, buf = (w0 / PE_T) & 1;
+            const bool in = w < words;
+            const uint32_t t = in ? atomicExch(&tg[w], 0u) : 0u;
+            uint32_t x = t;                    // bit b of x = parity of bits 0 .. b of t
+            x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16;
+            const unsigned long long odd = __ballot(__popc(t) & 1);
+            if (lane == 0) wave_i[buf][wave] = __popcll(odd) & 1;
+            __syncthreads();                   // (two buffers: the step after the next one writes this one again, a barrier later)
+            int cin = carry ^ (__popcll(odd & ((1ull << lane) - 1ull)) & 1);
+#pragma unroll
+            for (int ww = 0; ww < PE_T / 64; ++ww) {
+                const int tp = wave_i[buf][ww];
+                if (ww < wave) cin ^= tp;
+                carry ^= tp;
+            }
+            if (cin) x = ~x;
+            if (in) {
+                if (w == words - 1 && (N & 31)) x &= (1u << (N & 31)) - 1u;
+                const uint32_t o = q == 0 ? x : (bw[w] | x);
+                bw[w] = o;
+                if (q == n_mine - 1) ones += __popc(o);
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) ones += __shfl_xor(ones, d, 64);
+    __syncthreads();                           // wave_i is free
+    if (lane == 0) wave_i[0][wave] = ones;
+    __syncthreads();
+    if (tid == 0) { bad[i] = 0; area[i] = wave_i[0][0] + wave_i[0][1] + wave_i[0][2] + wave_i[0][3]; }
+}
+
 }  // namespace nps
 
 extern "C" nps_status nopesac_rle_string_runs(const uint8_t* bytes, const int64_t* str_off, int n_masks, int32_t* runs, int32_t* n_runs,
@@ -386,5 +578,20 @@ extern "C" nps_status nopesac_plane_ap_assign(const double* iou, const int64_t* 
     NPS_CHECK_ARG(max_gt == 0 || (iou && gt_label && gt_plane), "plane_ap_assign: null pointer (GT)");
     hipLaunchKernelGGL(plane_ap_assign_kernel, dim3(V), dim3(64), 0, (hipStream_t)stream, iou, (const long long*)iou_off, (const long long*)dt_off,
                        (const long long*)gt_off, score, pred_label, pred_plane, gt_label, gt_plane, iou_thresh, normal_thresh, offset_thresh, rows);
+    NPS_LAUNCH_RET();
+}
+
+extern "C" nps_status nopesac_poly_to_bits(const double* xy, const int64_t* poly_off, const int64_t* mask_off, int64_t n_points,
+                                           int64_t n_polys, int n_masks, int H, int W, uint32_t* toggles, uint32_t* bits, int32_t* area,
+                                           int32_t* bad, void* stream) {
+    using namespace nps;
+    NPS_CHECK_ARG(n_masks >= 0 && n_points >= 0 && n_polys >= 0, "poly_to_bits: n_masks, n_points or n_polys < 0");
+    NPS_CHECK_ARG(H > 0 && W > 0 && (long long)H * W <= 0x7fffffdfLL, "poly_to_bits: H, W > 0 and H W < 2^31 - 32");
+    if (n_masks == 0) return 0;
+    NPS_CHECK_ARG(xy && poly_off && mask_off && toggles && bits && area && bad, "poly_to_bits: null pointer");
+    const int N = H * W;
+    const long long cap = (long long)NPS_POLY_POINT_FACTOR * ((long long)N + H + W) + NPS_POLY_POINT_FLOOR;
+    hipLaunchKernelGGL(poly_to_bits_kernel, dim3(n_masks), dim3(PE_T), 0, (hipStream_t)stream, xy, (const long long*)poly_off,
+                       (const long long*)mask_off, (long long)n_points, (long long)n_polys, H, W, N, (N + 31) / 32, cap, toggles, bits, area, bad);
     NPS_LAUNCH_RET();
 }

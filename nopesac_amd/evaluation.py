@@ -19,8 +19,9 @@ that consumes the hot path's outputs: per-pair pose errors and their summary tab
     :830-1007): the AP of the planes of both views merged through the predicted camera and assignment, under five criteria.  The
     per-pair work (global planes, merged entries, error matrices, the walk) runs on the device (csrc/recon_eval.hip), the
     accumulation over all pairs is plain numpy.
-Out of scope: polygon annotations (cocoapi's rasteriser frPyObjects - GT masks must be RLE dicts) and the depth metrics
-(:438-460).
+GT masks are RLE dicts; with gt_polygons=True the matching, plane and reconstruction evaluators also take the polygon lists the
+datasets are distributed with (the reference's mask_util.frPyObjects + merge, :544-554), rasterised on the device by
+csrc/plane_eval.hip (rle.polygon_bits).  Out of scope: the depth metrics (:438-460).
 """
 from __future__ import annotations
 
@@ -130,24 +131,28 @@ class PoseEvaluator:
         return res
 
 
-def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict], iou_thresh: float = 0.5, device=None) -> Dict[str, dict]:
+def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict], iou_thresh: float = 0.5, device=None,
+                           gt_polygons: bool = False) -> Dict[str, dict]:
     """Plane-matching precision / recall / F-score (mp3d_evaluation.py:746-849).  For every pair: each predicted plane of a view
     is assigned the GT plane with the highest mask IoU (instances[k]["segmentation"] vs the GT annotations' RLE masks); a
     predicted correspondence (i, j) counts as correct when both IoUs reach `iou_thresh` and [gt_i, gt_j] is one of the pair's
     `gt_corrs`.  precision = TP / #predicted, recall = TP / #GT, over all pairs, separately for every "*assignment*" key of the
     predictions.  Returns {assignment key: {"precision", "recall", "F-score", "TP", "Pred. Num.", "GT Num."}} - the reference logs
     one table per key and returns only the last one; it also ignores its iou_thresh argument (0.5 is hard-coded, :830) and divides by
-    zero when nothing was matched (here: 0.0).  GT masks must be RLE dicts (compressed or not); polygon annotations need
-    cocoapi's rasteriser (frPyObjects), which is not part of this package.  device: a GPU - the IoU matrices of all views then come
-    from rle.iou_device_views in one set of launches (the same float64 numbers, bit for bit); None: rle.iou on the host, per view."""
+    zero when nothing was matched (here: 0.0).  By default GT masks must be RLE dicts (compressed or not;
+    TypeError for anything else).  device: a GPU - the IoU matrices of all views then come
+    from rle.iou_device_views in one set of launches (the same float64 numbers, bit for bit); None: rle.iou on the host, per view.
+    gt_polygons=True: a GT segmentation may also be a list of polygons (rasterised on the device like cocoapi's frPyObjects + merge, at
+    the size of the view's predictions); that needs a device (ValueError with device=None: there is no host rasteriser)."""
     from . import rle
+    if gt_polygons and device is None:
+        raise ValueError("evaluate_for_matchings: gt_polygons=True needs a device (polygons are rasterised on the GPU only)")
     jobs = []
     for pred in predictions:
         pair = dataset_dict[pred["0"]["image_id"] + "__" + pred["1"]["image_id"]]
         for v in ("0", "1"):
             for ann in pair[v]["annotations"]:
-                if not isinstance(ann["segmentation"], dict):
-                    raise TypeError("evaluate_for_matchings: GT segmentation must be an RLE dict (polygons need cocoapi frPyObjects)")
+                _rle_of(ann["segmentation"], "evaluate_for_matchings", gt_polygons)
             gt_rles = [ann["segmentation"] for ann in pair[v]["annotations"]]
             jobs.append(([ins["segmentation"] for ins in pred[v]["instances"]], gt_rles, [0] * len(gt_rles)))
     # device: every view of every pair in one set of launches; host: view by view
@@ -244,21 +249,26 @@ def plane_table(rows: np.ndarray, npos_by_cat: Dict[int, float], iou_thresh: flo
     return out
 
 
-def _rle_of(seg, who: str) -> dict:
-    if not isinstance(seg, dict):
-        raise TypeError(f"{who}: GT segmentation must be an RLE dict (polygons need cocoapi frPyObjects)")
-    return seg
+def _rle_of(seg, who: str, polygons: bool = False):
+    """A GT segmentation as the evaluators take it: an RLE dict, or with polygons=True (the evaluators' gt_polygons) a polygon list."""
+    if isinstance(seg, dict) or (polygons and isinstance(seg, (list, tuple))):
+        return seg
+    if polygons:
+        raise TypeError(f"{who}: GT segmentation must be an RLE dict or a list of polygons")
+    raise TypeError(f"{who}: GT segmentation must be an RLE dict (polygons need cocoapi frPyObjects)")
 
 
 def plane_rows(views: List[dict], device, iou_thresh: float = 0.5, normal_threshold: float = 30, offset_threshold: float = 0.3,
-               id_map: Optional[Dict[int, int]] = None) -> np.ndarray:
+               id_map: Optional[Dict[int, int]] = None, gt_polygons: bool = False) -> np.ndarray:
     """The per-prediction part of the reference's evaluator (mp3d_evaluation.py:512-649) for a list of views in ONE set of launches:
     every mask of every view is decoded into bit-packed form (rle.decode_bits), one launch takes all IoU blocks, one the assignment.
     views: [{"instances": [{"segmentation", "score", "category_id"}], "pred_plane": [n, 3], "annotations": [{"segmentation", "plane",
     "category_id"}]}]; id_map: contiguous prediction label -> dataset category id (default {0: 1}).  Returns float64
     [number of predictions, 10] (PLANE_ROW_COLS), view after view, each view's predictions in their own order.
     A view with predictions but no annotation gets gt_id = -1, best_iou = 0, no true positive and NaN errors (the reference raises
-    there: argmax of an empty IoU row); plane_table leaves such rows out of the error statistics."""
+    there: argmax of an empty IoU row); plane_table leaves such rows out of the error statistics.
+    gt_polygons=True: an annotation's segmentation may also be a list of polygons (rle.segmentation_bits; the image size is the one
+    of the predictions' RLE dicts)."""
     from . import ops, rle
     id_map = {0: 1} if id_map is None else id_map
     device = torch.device(device)
@@ -268,8 +278,8 @@ def plane_rows(views: List[dict], device, iou_thresh: float = 0.5, normal_thresh
     if total == 0:
         return np.zeros((0, len(PLANE_ROW_COLS)), np.float64)
     dt_rles = [ins["segmentation"] for v in views for ins in v["instances"]]
-    gt_rles = [_rle_of(a["segmentation"], "plane_rows") for v in views for a in v["annotations"]]
-    bits, area = rle.decode_bits(dt_rles + gt_rles, device)
+    gt_rles = [_rle_of(a["segmentation"], "plane_rows", gt_polygons) for v in views for a in v["annotations"]]
+    bits, area = rle.segmentation_bits(dt_rles + gt_rles, device) if gt_polygons else rle.decode_bits(dt_rles + gt_rles, device)
     offs = np.zeros((3, len(views) + 1), np.int64)
     np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
     planes = [np.asarray(v["pred_plane"].detach().cpu() if torch.is_tensor(v["pred_plane"]) else v["pred_plane"], np.float32).reshape(-1, 3)
@@ -305,12 +315,13 @@ def _unique_views(records: List[dict], seen: set):
 
 def evaluate_for_planes(predictions: List[dict], dataset_dict: Dict[str, dict], device, iou_thresh: float = 0.5,
                         normal_threshold: float = 30, offset_threshold: float = 0.3, id_map: Optional[Dict[int, int]] = None,
-                        categories: Optional[List[dict]] = None) -> Dict[str, float]:
+                        categories: Optional[List[dict]] = None, gt_polygons: bool = False) -> Dict[str, float]:
     """Plane detection table (mp3d_evaluation.py:467-743) over kept prediction records, the offline form: predictions = per pair
     {"0" / "1": {"image_id", "instances", "pred_plane"}}, dataset_dict = {"<id0>__<id1>": {"0" / "1": {"image_id"?, "annotations"}}}
     (the shape evaluate_for_matchings takes).  Every image counts once (first occurrence wins, in the predictions and in the dataset);
     a view without instances is skipped; npos counts the annotations of every image of dataset_dict.  categories: the dataset json's
-    `categories` ([{"id", "name"}]) for the key names; id 1 is "plane".  GT masks must be RLE dicts (TypeError otherwise)."""
+    `categories` ([{"id", "name"}]) for the key names; id 1 is "plane".  GT masks must be RLE dicts (TypeError otherwise), or with
+    gt_polygons=True RLE dicts or polygon lists."""
     gt_of, npos = {}, {}
     for key, pair in dataset_dict.items():
         ids = key.split("__") if "__" in key else (None, None)
@@ -320,11 +331,11 @@ def evaluate_for_planes(predictions: List[dict], dataset_dict: Dict[str, dict], 
                 continue
             gt_of[image_id] = pair[v]["annotations"]
             for a in pair[v]["annotations"]:
-                _rle_of(a["segmentation"], "evaluate_for_planes")
+                _rle_of(a["segmentation"], "evaluate_for_planes", gt_polygons)
                 npos[int(a["category_id"])] = npos.get(int(a["category_id"]), 0.0) + 1.0
     views = [{"instances": view["instances"], "pred_plane": view["pred_plane"], "annotations": gt_of[image_id]}
              for image_id, view in _unique_views(predictions, set()) if len(view.get("instances") or []) and image_id in gt_of]
-    rows = plane_rows(views, device, iou_thresh, normal_threshold, offset_threshold, id_map)
+    rows = plane_rows(views, device, iou_thresh, normal_threshold, offset_threshold, id_map, gt_polygons)
     names = {int(c["id"]): c["name"] for c in (categories or [])}
     return plane_table(rows, npos or {1: 0.0}, iou_thresh, normal_threshold, offset_threshold, names)
 
@@ -337,12 +348,13 @@ class PlaneEvaluator:
     image's index in the dataset json - when given, else the id itself when it is an integer), evaluate() gathers rows and
     per-image GT counts from all ranks and keeps, per image, the lowest rank's copy, so the table does not depend on the world size.
     A single process may leave image_index out with any ids (images are numbered as they come); several ranks with string ids
-    need it (ValueError)."""
+    need it (ValueError).  gt_polygons=True: annotations may carry polygon lists instead of RLE dicts (plane_rows)."""
 
     def __init__(self, device, iou_thresh: float = 0.5, normal_threshold: float = 30, offset_threshold: float = 0.3,
                  id_map: Optional[Dict[int, int]] = None, image_index: Optional[Dict[str, int]] = None,
-                 categories: Optional[List[dict]] = None):
+                 categories: Optional[List[dict]] = None, gt_polygons: bool = False):
         self.device = torch.device(device)
+        self.gt_polygons = bool(gt_polygons)
         self.iou_thresh, self.normal_threshold, self.offset_threshold = iou_thresh, normal_threshold, offset_threshold
         self.id_map = {0: 1} if id_map is None else dict(id_map)
         self.image_index = image_index
@@ -382,7 +394,7 @@ class PlaneEvaluator:
                 num, anns = self._number(image_id), inp[v]["annotations"]
                 cats: Dict[int, int] = {}
                 for a in anns:
-                    _rle_of(a["segmentation"], "PlaneEvaluator")
+                    _rle_of(a["segmentation"], "PlaneEvaluator", self.gt_polygons)
                     cats[int(a["category_id"])] = cats.get(int(a["category_id"]), 0) + 1
                 self._register(num, cats)
                 o = out[v] if out.get(v) is not None else {}
@@ -390,7 +402,8 @@ class PlaneEvaluator:
                     views.append({"instances": o["instances"], "pred_plane": o["pred_plane"], "annotations": anns})
                     numbers.append(num)
         if views:
-            rows = plane_rows(views, self.device, self.iou_thresh, self.normal_threshold, self.offset_threshold, self.id_map)
+            rows = plane_rows(views, self.device, self.iou_thresh, self.normal_threshold, self.offset_threshold, self.id_map,
+                              self.gt_polygons)
             num = np.repeat(np.asarray(numbers, np.float64), [len(v["instances"]) for v in views])
             self._rows.append(np.concatenate([rows, num[:, None]], 1))
 
@@ -474,7 +487,7 @@ def assignment_corrs(assignment) -> np.ndarray:
     return np.argwhere(a.reshape(a.shape[-2:]) if a.ndim > 2 else a).astype(np.int32).reshape(-1, 2)
 
 
-def recon_rows(pairs: List[dict], device, with_errors: bool = False):
+def recon_rows(pairs: List[dict], device, with_errors: bool = False, gt_polygons: bool = False):
     """The per-pair part of the reconstruction AP (eval.py:343-619, :657-779, :830-913) for a list of pairs in ONE set of launches:
     every mask of every view is decoded once (rle.decode_bits), one launch takes all IoU blocks, one the merge, the error matrices and
     the walk (ops.recon_ap_assign).  pairs: [{"views": (view0, view1), "pred_camera", "gt_camera": {"position", "rotation" wxyz},
@@ -484,7 +497,9 @@ def recon_rows(pairs: List[dict], device, with_errors: bool = False):
     fourth result, per pair the float64 [3, entries, GT entries] offset / normal / IoU matrices.
     Every instance counts: the reference's create_instances drops predictions with score <= 0.1 from the planes but not from the IoU
     rows or the correspondence indices, so it is only defined when every score is above 0.1, and there both agree.
-    A correspondence that names a plane a view does not have, or a plane named twice, is a ValueError."""
+    A correspondence that names a plane a view does not have, or a plane named twice, is a ValueError.
+    gt_polygons=True: an annotation's segmentation may also be a list of polygons (rle.segmentation_bits; the image size is the one
+    of the predictions' RLE dicts, and a batch without any prediction, whose IoU blocks are all empty, rasterises nothing)."""
     from . import ops, rle
     device = torch.device(device)
     P = len(pairs)
@@ -500,7 +515,7 @@ def recon_rows(pairs: List[dict], device, with_errors: bool = False):
         if p.shape[0] != k:
             raise ValueError(f"recon_rows: {k} instances but {p.shape[0]} pred_plane rows")
     dt_rles = [ins["segmentation"] for v in views for ins in v["instances"]]
-    gt_rles = [_rle_of(a["segmentation"], "recon_rows") for v in views for a in v["annotations"]]
+    gt_rles = [_rle_of(a["segmentation"], "recon_rows", gt_polygons) for v in views for a in v["annotations"]]
     offs = np.zeros((3, 2 * P + 1), np.int64)
     np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
     pc = [_corr_pairs(p["pred_corrs"]) for p in pairs]
@@ -519,8 +534,8 @@ def recon_rows(pairs: List[dict], device, with_errors: bool = False):
     i32 = np.concatenate(pc + gc).reshape(-1)
     d_off, d_coff = torch.from_numpy(offs).to(device), torch.from_numpy(coffs).to(device)
     d_f32, d_cam, d_i32 = torch.from_numpy(f32).to(device), torch.from_numpy(cams).to(device), torch.from_numpy(i32).to(device)
-    if total + n_g:
-        bits, area = rle.decode_bits(dt_rles + gt_rles, device)
+    if total + n_g and not (gt_polygons and total == 0):
+        bits, area = rle.segmentation_bits(dt_rles + gt_rles, device) if gt_polygons else rle.decode_bits(dt_rles + gt_rles, device)
         iou, _ = ops.mask_iou_bits(bits[:total], area[:total], d_off[0], bits[total:], area[total:], d_off[1], None, d_off[2],
                                    int(offs[2, -1]), max(n_dt), max(n_gt))
     else:
@@ -546,10 +561,10 @@ def recon_rows(pairs: List[dict], device, with_errors: bool = False):
     return rows, n_entries, n_gt_entries, errs
 
 
-def _recon_pair(views_pred, annotations, pred_camera, gt_camera, assignment, gt_corrs, who: str) -> dict:
+def _recon_pair(views_pred, annotations, pred_camera, gt_camera, assignment, gt_corrs, who: str, gt_polygons: bool = False) -> dict:
     for anns in annotations:
         for a in anns:
-            _rle_of(a["segmentation"], who)
+            _rle_of(a["segmentation"], who, gt_polygons)
     return {"views": tuple({"instances": vp.get("instances") or [], "pred_plane": vp["pred_plane"], "annotations": anns}
                            for vp, anns in zip(views_pred, annotations)),
             "pred_camera": pred_camera, "gt_camera": gt_camera, "pred_corrs": assignment_corrs(assignment), "gt_corrs": gt_corrs}
@@ -563,15 +578,16 @@ def _recon_gt(entry: Optional[dict]):
 
 
 def evaluate_for_reconstruction(predictions: List[dict], dataset_dict: Dict[str, dict], device, camera_key: str = "camera",
-                                assignment_key: str = "pred_assignment", pairs_per_launch: int = 64) -> Dict[str, float]:
+                                assignment_key: str = "pred_assignment", pairs_per_launch: int = 64,
+                                gt_polygons: bool = False) -> Dict[str, float]:
     """The reconstruction AP table of the reference's offline `eval.py --evaluate AP` over kept prediction records: predictions = per
     pair {"0" / "1": {"image_id", "instances", "pred_plane"}, camera_key: {"pred": {"tran", "rot"}, "gts": {"tran", "rot"}},
     assignment_key: 0 / 1 matrix} (PoseEvaluator.prediction_record; the camera and assignment optimized_dict writes to continuous.pkl),
     dataset_dict = {"<id0>__<id1>": {"0" / "1": {"annotations"}, "gt_corrs", "rel_pose"?}} (the shape evaluate_for_matchings takes).
     The GT camera is the record's "gts" when it has one, else the dataset pair's `rel_pose`.  A pair without dataset entry, `gt_corrs`,
     `annotations` or GT camera is skipped and counted.  pairs_per_launch bounds the bit masks resident on the device at once (a split
-    of a thousand pairs at 480 x 640 would be gigabytes in one piece); the rows do not depend on it.  Returns recon_table's dict plus
-    "pairs" and "skipped"."""
+    of a thousand pairs at 480 x 640 would be gigabytes in one piece); the rows do not depend on it.  gt_polygons=True: annotations may
+    carry polygon lists instead of RLE dicts (recon_rows).  Returns recon_table's dict plus "pairs" and "skipped"."""
     rows, npos, todo, skipped = [], 0, [], 0
     for pred in predictions:
         gt = _recon_gt(dataset_dict.get(pred["0"]["image_id"] + "__" + pred["1"]["image_id"]))
@@ -581,9 +597,10 @@ def evaluate_for_reconstruction(predictions: List[dict], dataset_dict: Dict[str,
         if gt is None or cam is None or gt_cam is None or assignment_key not in pred:
             skipped += 1
             continue
-        todo.append(_recon_pair((pred["0"], pred["1"]), gt[0], cam["pred"], gt_cam, pred[assignment_key], gt[1], "evaluate_for_reconstruction"))
+        todo.append(_recon_pair((pred["0"], pred["1"]), gt[0], cam["pred"], gt_cam, pred[assignment_key], gt[1], "evaluate_for_reconstruction",
+                                gt_polygons))
     for i in range(0, len(todo), max(1, pairs_per_launch)):
-        r, _, n_ge = recon_rows(todo[i:i + pairs_per_launch], device)
+        r, _, n_ge = recon_rows(todo[i:i + pairs_per_launch], device, gt_polygons=gt_polygons)
         rows.append(r)
         npos += int(n_ge.sum())
     table = recon_table(np.concatenate(rows) if rows else np.zeros((0, len(RECON_ROW_COLS))), npos)
@@ -598,11 +615,12 @@ class ReconEvaluator:
     de-duplicated: every row carries its pair's number (pair_index["<id0>__<id1>"] - the pair's index in the dataset - when given) and
     its entry index, evaluate() gathers rows and per-pair GT entry counts from all ranks and orders the rows by (pair, entry), so
     equal scores rank the same at every world size.  A single process may leave pair_index out (pairs are numbered as they come);
-    several ranks need it (ValueError)."""
+    several ranks need it (ValueError).  gt_polygons=True: annotations may carry polygon lists instead of RLE dicts (recon_rows)."""
 
     def __init__(self, device, camera_key: str = "camera", assignment_key: str = "pred_assignment",
-                 pair_index: Optional[Dict[str, int]] = None):
+                 pair_index: Optional[Dict[str, int]] = None, gt_polygons: bool = False):
         self.device = torch.device(device)
+        self.gt_polygons = bool(gt_polygons)
         self.camera_key, self.assignment_key, self.pair_index = camera_key, assignment_key, pair_index
         self.reset()
 
@@ -638,10 +656,10 @@ class ReconEvaluator:
                 self._skipped += 1
                 continue
             views = tuple(out[v] if out.get(v) is not None else {"instances": [], "pred_plane": np.zeros((0, 3), np.float32)} for v in "01")
-            todo.append(_recon_pair(views, gt[0], cam, gt[2], out[self.assignment_key], gt[1], "ReconEvaluator"))
+            todo.append(_recon_pair(views, gt[0], cam, gt[2], out[self.assignment_key], gt[1], "ReconEvaluator", self.gt_polygons))
             numbers.append(self._number(str(inp["0"].get("image_id")) + "__" + str(inp["1"].get("image_id"))))
         if todo:
-            self._add(numbers, *recon_rows(todo, self.device))
+            self._add(numbers, *recon_rows(todo, self.device, gt_polygons=self.gt_polygons))
 
     def evaluate(self) -> Dict[str, float]:
         w = len(RECON_ROW_COLS) + 2

@@ -1174,6 +1174,33 @@ def rle_runs_to_bits(runs: torch.Tensor, run_off: torch.Tensor, n_runs: torch.Te
     return bits, area, bad
 
 
+def poly_to_bits(xy: torch.Tensor, poly_off: torch.Tensor, mask_off: torch.Tensor, H: int, W: int, bits: torch.Tensor = None):
+    """COCO polygons (xy float64 [2 * points], x first; poly_off int64 [polygons + 1] in points; mask_off int64 [n + 1] in polygons)
+    -> (bits uint32-as-int32 [n, ceil(H W / 32)], area int32 [n], bad int32 [n]), the layout of rle_runs_to_bits: cocoapi's
+    rleFrPoly + merge, bit for bit.  bad[i] = 1 (words zero): no polygon, a polygon of fewer than 3 points, a coordinate that is not
+    finite or too large, more boundary points than the header's cap.  bits: a caller's buffer of at least n rows."""
+    _chk(xy, torch.float64); _chk(poly_off, torch.int64); _chk(mask_off, torch.int64)
+    n, n_polys, words = mask_off.numel() - 1, poly_off.numel() - 1, (H * W + 31) // 32
+    _require(n >= 0 and n_polys >= 0 and xy.numel() % 2 == 0, "poly_to_bits: mask_off / poly_off hold n + 1 offsets, xy holds pairs")
+    dev = mask_off.device
+    if xy.numel() == 0:                         # only masks without a point (all bad): the library still wants a buffer to point at
+        xy = torch.zeros(2, device=dev, dtype=torch.float64)
+        n_points = 0
+    else:
+        n_points = xy.numel() // 2
+    if bits is None:
+        bits = torch.empty((max(n, 1), words), device=dev, dtype=torch.int32)[:n]
+    else:
+        _chk(bits, torch.int32)
+        _require(bits.numel() >= n * words, "poly_to_bits: bits buffer too small")
+    toggles = torch.empty((max(n, 1), words), device=dev, dtype=torch.int32)
+    area = torch.empty(n, device=dev, dtype=torch.int32)
+    bad = torch.empty(n, device=dev, dtype=torch.int32)
+    _C.nopesac_poly_to_bits(_p(xy), _p(poly_off), _p(mask_off), n_points, n_polys, n, H, W, _p(toggles), _p(bits), _p(area), _p(bad),
+                            _stream())
+    return bits, area, bad
+
+
 def mask_iou_bits(dt_bits, dt_area, dt_off, gt_bits, gt_area, gt_off, iscrowd, iou_off, total: int, max_dt: int, max_gt: int):
     """Pairwise mask IoU of V views in one launch: view v's predictions are rows dt_off[v]:dt_off[v+1] of dt_bits, its GT masks rows
     gt_off[v]:gt_off[v+1] of gt_bits (iscrowd uint8 per GT mask or None) -> (iou float64 [total], inter int32 [total]), view v's

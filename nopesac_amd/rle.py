@@ -8,7 +8,9 @@ boxes, still on the device; the host receives finished byte strings.  Host syncs
 nopesac_rle_compress_host / _batch_host (same library, plain C) are the host forms of the same encoder.
 
 Reading side (evaluation): counts_of / decode / iou on the host; decode_bits / iou_device on the device (csrc/plane_eval.hip:
-nopesac_rle_string_runs -> nopesac_rle_runs_to_bits -> nopesac_mask_iou_bits), bit-packed masks and IoU by popcount.
+nopesac_rle_string_runs -> nopesac_rle_runs_to_bits -> nopesac_mask_iou_bits), bit-packed masks and IoU by popcount.  Polygon
+annotations (what pycocotools.mask.frPyObjects + merge do for the evaluators) become the same bit-packed masks on the device:
+polygon_bits (csrc/plane_eval.hip: nopesac_poly_to_bits); segmentation_bits takes RLE dicts and polygon lists mixed.
 """
 from __future__ import annotations
 
@@ -260,10 +262,82 @@ def decode_bits(rles: List[dict], device):
     return bits, area
 
 
+def polygon_bits(segmentations, H: int, W: int, device):
+    """COCO polygon annotations -> (bits int32 [n, ceil(H W / 32)], area int32 [n]) on `device`, the layout of decode_bits.
+    segmentations: per mask a list of polygons, each a flat [x0, y0, x1, y1, ...]; a mask is the union of its polygons.  What
+    pycocotools.mask.frPyObjects(polygons, H, W) + merge compute (cocoapi rleFrPoly), bit for bit, by nopesac_poly_to_bits: one upload
+    (coordinates and both offset tables), one launch whatever the number of masks, one host sync (the `bad` flags).  Raises ValueError
+    before anything is uploaded for a polygon of odd length or of fewer than 6 numbers, and after the launch, naming the masks, when
+    a mask has no polygon, a coordinate that is not finite or too large, or more boundary points than the library's cap.
+    Departure from cocoapi: frPyObjects reads a whole list whose first element has exactly 4 numbers as bounding boxes; here every
+    element is a polygon (4 numbers: ValueError)."""
+    device = torch.device(device)
+    H, W = int(H), int(W)
+    n, words = len(segmentations), (H * W + 31) // 32
+    polys = []
+    for i, seg in enumerate(segmentations):
+        for poly in seg:
+            xy = np.asarray(poly, dtype=np.float64).reshape(-1)
+            if xy.size % 2 or xy.size < 6:
+                raise ValueError(f"polygon_bits: a polygon of mask {i} has {xy.size} numbers (an even count of at least 6 is needed)")
+            polys.append(xy)
+    if n == 0:
+        return torch.empty((0, words), device=device, dtype=torch.int32), torch.empty(0, device=device, dtype=torch.int32)
+    off = np.zeros(len(polys) + 1 + n + 1, np.int64)
+    poly_off, mask_off = off[:len(polys) + 1], off[len(polys) + 1:]
+    np.cumsum([xy.size // 2 for xy in polys], out=poly_off[1:])
+    np.cumsum([len(seg) for seg in segmentations], out=mask_off[1:])
+    xy = np.concatenate(polys) if polys else np.zeros(0, np.float64)
+    dev = torch.from_numpy(np.concatenate([xy.view(np.int64), off])).to(device)      # one upload: coordinates, polygon and mask offsets
+    d_xy, d_off = dev[:xy.size].view(torch.float64), dev[xy.size:]
+    bits, area, bad = ops.poly_to_bits(d_xy, d_off[:poly_off.size], d_off[poly_off.size:], H, W)
+    if bool(bad.any().item()):                                          # host sync
+        which = torch.nonzero(bad).view(-1).tolist()
+        raise ValueError(f"polygon_bits: no polygon, a coordinate that is not finite or too large, or too many boundary points "
+                         f"(masks {which[:8]} of {n})")
+    return bits, area
+
+
+def segmentation_bits(segs, device, size=None):
+    """decode_bits for COCO `segmentation` entries of either kind: every seg is an RLE dict (compressed or not) or a list of polygons.
+    RLE dicts go through decode_bits, polygon lists through polygon_bits, the results come back in input order.  The image size is the
+    common size of the RLE dicts of the call, else `size` = (H, W); ValueError when polygons come with neither, or when both are there
+    and differ."""
+    device = torch.device(device)
+    n = len(segs)
+    is_rle = [isinstance(s, dict) for s in segs]
+    for s, r in zip(segs, is_rle):
+        if not r and not isinstance(s, (list, tuple)):
+            raise TypeError(f"segmentation_bits: a segmentation is an RLE dict or a list of polygons, not {type(s).__name__}")
+    rles = [s for s, r in zip(segs, is_rle) if r]
+    if len(rles) == n:
+        return decode_bits(rles, device)
+    sizes = {tuple(int(x) for x in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"segmentation_bits: masks of different sizes in one call: {sorted(sizes)}")
+    given = None if size is None else tuple(int(x) for x in size)
+    if sizes and given is not None and given not in sizes:
+        raise ValueError(f"segmentation_bits: size {given} but the RLE masks of the call are {sorted(sizes)[0]}")
+    if not sizes and given is None:
+        raise ValueError("segmentation_bits: polygons need an image size - the call holds no RLE dict and no `size`")
+    H, W = next(iter(sizes)) if sizes else given
+    p_bits, p_area = polygon_bits([s for s, r in zip(segs, is_rle) if not r], H, W, device)
+    if not rles:
+        return p_bits, p_area
+    r_bits, r_area = decode_bits(rles, device)
+    bits = torch.empty((n, (H * W + 31) // 32), device=device, dtype=torch.int32)
+    area = torch.empty(n, device=device, dtype=torch.int32)
+    for want, b, a in ((True, r_bits, r_area), (False, p_bits, p_area)):
+        where = torch.as_tensor([i for i, r in enumerate(is_rle) if r == want], device=device)
+        bits[where], area[where] = b, a
+    return bits, area
+
+
 def iou_device_views(views, device) -> List[np.ndarray]:
     """rle.iou for many views at once: views = [(dt RLEs, gt RLEs, iscrowd or None)] -> [len(dt), len(gt)] float64 matrices, bit
     for bit those of iou().  All masks of one image size go through ONE upload per kind, one decode and one nopesac_mask_iou_bits
-    launch, whatever the number of views; one copy back."""
+    launch, whatever the number of views; one copy back.  A GT entry may also be a polygon list (segmentation_bits; the size is the
+    predictions'); a view without predictions or without GT is never decoded."""
     device = torch.device(device)
     out = [np.zeros((len(v[0]), len(v[1])), np.float64) for v in views]
     by_size = {}
@@ -272,7 +346,7 @@ def iou_device_views(views, device) -> List[np.ndarray]:
             by_size.setdefault(tuple(int(s) for s in dt[0]["size"]), []).append(k)
     for ks in by_size.values():
         n_dt, n_gt = [len(views[k][0]) for k in ks], [len(views[k][1]) for k in ks]
-        bits, area = decode_bits([r for k in ks for r in views[k][0]] + [r for k in ks for r in views[k][1]], device)
+        bits, area = segmentation_bits([r for k in ks for r in views[k][0]] + [r for k in ks for r in views[k][1]], device)
         offs = np.zeros((3, len(ks) + 1), np.int64)
         np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
         crowd = np.concatenate([np.zeros(len(views[k][1]), np.uint8) if views[k][2] is None else np.asarray(views[k][2], bool).astype(np.uint8)

@@ -51,14 +51,14 @@ def default_argument_parser():
     ap.add_argument("--synthetic-weights", action="store_true", help="name-seeded checkpoint instead of cfg.MODEL.WEIGHTS")
     ap.add_argument("--output", default="", help="write the result summary JSON here")
     ap.add_argument("--eval-matchings", action="store_true", help="plane-matching precision / recall / F-score (mp3d_evaluation.py:746-849): "
-                    "needs pairs with `gt_corrs` and RLE `annotations` (the dataset json's own fields)")
+                    "needs pairs with `gt_corrs` and `annotations` (the dataset json's own fields; polygon masks need the model on a GPU)")
     ap.add_argument("--eval-planes", action="store_true", help="plane detection table (mp3d_evaluation.py:467-743): mask AP, the three plane APs and "
                     "the normal / offset error statistics; RLE decoding, mask IoU and the true-positive assignment run on the GPU (csrc/plane_eval.hip), "
-                    "so the model must be on one.  Needs pairs whose views carry RLE `annotations` with `plane` and `category_id`")
+                    "so the model must be on one.  Needs pairs whose views carry `annotations` (RLE or polygon masks) with `plane` and `category_id`")
     ap.add_argument("--eval-recon", action="store_true", help="two-view reconstruction AP (the reference's offline eval.py --evaluate AP): both views' "
                     "planes in one frame through the predicted camera, matched planes merged, AP under all / -offset / -normal / -mask / "
                     "-normal-offset; computed on the GPU (csrc/recon_eval.hip), so the model must be on one.  Needs pairs with `rel_pose`, "
-                    "`gt_corrs` and RLE `annotations` with `plane`")
+                    "`gt_corrs` and `annotations` (RLE or polygon masks) with `plane`")
     ap.add_argument("--dump-dir", default="", help="write NopeSAC_instances_predictions.pth + continuous.pkl here (eval_full_scene)")
     ap.add_argument("--stub-model", action="store_true", help="TEST ONLY (results are marked invalid): the CLI's sharding, batch loop, evaluator "
                     "gather and dumps around a stub that fabricates result dicts instead of running the model - what the gloo CPU tests drive at "
@@ -315,7 +315,7 @@ def _main_rank(args):
                 if "annotations" in p[v]:
                     image_index.setdefault(p[v].get("image_id"), len(image_index))
         if image_index:
-            plane_evaluator = PlaneEvaluator(next(model.parameters()).device, image_index=image_index)
+            plane_evaluator = PlaneEvaluator(next(model.parameters()).device, image_index=image_index, gt_polygons=True)
         elif rank == 0:
             logger.warning("--eval-planes: no pair carries annotations; nothing to evaluate")
     recon_evaluator = None
@@ -328,7 +328,7 @@ def _main_rank(args):
             if "rel_pose" in p and "gt_corrs" in p and all("annotations" in p[v] for v in "01"):
                 pair_index.setdefault(str(p["0"].get("image_id")) + "__" + str(p["1"].get("image_id")), i)
         if pair_index:
-            recon_evaluator = ReconEvaluator(next(model.parameters()).device, pair_index=pair_index)
+            recon_evaluator = ReconEvaluator(next(model.parameters()).device, pair_index=pair_index, gt_polygons=True)
         elif rank == 0:
             logger.warning("--eval-recon: no pair carries rel_pose, gt_corrs and annotations; nothing to evaluate")
     try:
@@ -357,7 +357,8 @@ def _main_rank(args):
         dataset_dict = {p["0"]["image_id"] + "__" + p["1"]["image_id"]: p for p in annotated if "gt_corrs" in p}
         if rank == 0 and dataset_dict:
             results["matching"] = evaluate_for_matchings([k for k in kept if k["0"]["image_id"] + "__" + k["1"]["image_id"] in dataset_dict],
-                                                         dataset_dict, device=next(model.parameters()).device if on_gpu else None)
+                                                         dataset_dict, device=next(model.parameters()).device if on_gpu else None,
+                                                         gt_polygons=on_gpu)      # (polygon GT is rasterised on the GPU only)
             for k, v in results["matching"].items():
                 logger.info("Plane metrics (%s):\n%s", k, create_small_table({kk: float(vv) for kk, vv in v.items()}))
         elif rank == 0:
