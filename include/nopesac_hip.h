@@ -487,7 +487,7 @@ nps_status nopesac_ransac_soft_vote(const float* score_feat_rot, const float* sc
  * nopesac_ransac_soft_vote in mode 16 (pred_* = soft pose, avg_*, score_*); gt_pose f32[B,7] = trans | quaternion (normalised
  * inside), m int32[B] (>= 1 each, as in the reference: the parameter loss divides by it).
  * losses f32[7] = { tran_planeAvgReg, rot_planeAvgReg, tran_planeSoftReg, rot_planeSoftReg, rotIdx * 0.01, transIdx * 0.02,
- * paramL2_dist * 0.1 } * weight.  Forward only: no gradient kernels exist for this path. */
+ * paramL2_dist * 0.1 } * weight.  Its vector-Jacobian product is nopesac_refine_losses_backward. */
 nps_status nopesac_plane_cam_ref_losses(const float* pred_rot, const float* pred_trans, const float* avg_rot,
                                         const float* avg_trans, const float* rots_all, const float* trans_all,
                                         const float* score_rot, const float* score_trans, const float* l2_dist,
@@ -498,7 +498,7 @@ nps_status nopesac_plane_cam_ref_losses(const float* pred_rot, const float* pred
  * (camera_head.py:700-705, :725-731, with trans_eps = 1e-10 as the reference adds it to the re-embedded translation):
  *   out[0] = mean_b |gt_trans[b] + trans_eps - est_trans[b]|_2 * weight, out[1] = mean_b |n(gt_rot[b]) - n(est_rot[b])|_2 * weight.
  * est_trans f32[B,3], est_rot f32[B,4]; gt_trans / gt_rot are rows of `stride` floats (7 and 7 for a [B,7] pose tensor with
- * gt_rot = gt_pose + 3).  Forward only. */
+ * gt_rot = gt_pose + 3).  Its vector-Jacobian product (both pose arguments) is nopesac_camera_pose_loss_backward. */
 nps_status nopesac_camera_pose_loss(const float* est_trans, const float* est_rot, const float* gt_trans, int gt_trans_stride,
                                     const float* gt_rot, int gt_rot_stride, int B, float trans_eps, float weight, float* out,
                                     void* stream);
@@ -893,7 +893,13 @@ nps_status nopesac_posenet_branch_tail_bf16(const void* x_trans, const void* x_r
  *  vote_backward:       -> gradients of the score features [B,nq+1,64] x 2, the initial pose features [B,256] x 2, the per-plane features
  *                       [B,nq,256] x 2 and, per pair, of rots / trans weights + biases and of the two score regressors.
  *  score_maps_backward: gradients of normal_score / param_score / l2_dist [B,nq+1,nq] -> rot_raw [B,nq,4] (through its normalisation),
- *                       trans_raw [B,nq,3], init_rot [B,4], init_trans [B,3]. */
+ *                       trans_raw [B,nq,3], init_rot [B,4], init_trans [B,3].
+ * m int32[B]: losses_backward and vote_backward REQUIRE m >= 1 for every pair, as their forwards do (the parameter loss and the average
+ * pose divide by m: a pair with m = 0 is 0 / 0 by the reference's own definition and what is written for THAT pair is unspecified; the
+ * other pairs of the launch are not affected by it).  score_maps_backward is defined at m = 0: both scores are masked out there, so
+ * only g_l2_dist (which is never masked) reaches the gradients, for every hypothesis and every plane of the pair.
+ * Every element of every output is written by each call (exact zeros: g_score_* off the picked hypothesis, g_l2_dist off the
+ * diagonal [b, 1 + j, j], g_sf_* rows h > m, g_fused_* rows k >= m).  Held per element to float64 VJPs by tests/test_refine_bwd_forms_gpu.py. */
 nps_status nopesac_refine_losses_backward(const float* pred_rot, const float* pred_trans, const float* avg_rot, const float* avg_trans,
                                           const float* rots_all, const float* trans_all, const float* score_rot, const float* score_trans,
                                           const int32_t* m, const float* gt_pose, const float* g_loss, int B, int nq, float weight,

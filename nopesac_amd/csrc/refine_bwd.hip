@@ -5,7 +5,8 @@
 // with the library's f32 GEMM kernel (dgrad = dY W, wgrad = dY^T X: nopesac_amd/training.py) plus the small kernels at the end of this file
 // (transpose, column sums, ReLU mask, row-normalisation backward, AdamW / SGD step).  Everything is f32 and deterministic: per-pair
 // partial sums of the parameter gradients are written per pair and reduced by nopesac_col_sum_f32 in a fixed order - no atomics.
-// Gated against torch.autograd on the oracle (tests/test_training_gpu.py).
+// Gated against torch.autograd on the oracle (tests/test_training_gpu.py); the four geometry kernels (1), (1b), (2), (3) per element against
+// float64 vector-Jacobian products at nq = 1 .. 128 (tests/test_refine_bwd_forms_gpu.py).
 #include "common.h"
 
 namespace nps {
