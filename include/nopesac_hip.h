@@ -870,6 +870,39 @@ nps_status nopesac_recon_ap_assign(const double* iou, const int64_t* iou_off, co
                                    const int32_t* pred_corr, const int64_t* pred_corr_off, const int32_t* gt_corr, const int64_t* gt_corr_off,
                                    int P, int max_dt, int max_gt, int64_t n_rows, double* rows, int32_t* n_gt_entries, int32_t* bad,
                                    double* errs, const int64_t* err_off, void* stream);
+#define NPS_MESH_LDS_WORDS 15360 /* recon_mesh_count / _fill: a mask at its stride must fit this many 32-bit LDS words (60 KiB), see below */
+/* The two-view reconstruction as textured meshes (csrc/recon_mesh.hip; the reference's vis_NopeSAC.py save_pair_objects on the dense
+ * route of utils/vis.py get_single_image_mesh(reduce_size=False)).  Deterministic, no atomics, every output written once; P = 0 / n = 0
+ * enqueues nothing.
+ * recon_mesh_merge: merge_plane_params_from_local_params for P pairs, float64, a workgroup per pair.  Pair i owns views 2 i and 2 i + 1
+ *   of view_off (int64 [2 P + 1], rows of planes f32 [total, 3]), the camera cams + 7 i (position, then quaternion w x y z; it need
+ *   not be a unit quaternion) and the correspondences corr[corr_off[i] .. corr_off[i + 1]): int32 pairs (plane of view 0, plane of
+ *   view 1).  A pair without correspondences keeps its planes (widened to double).  Otherwise every plane of the pair goes to view 1's
+ *   frame (get_plane_params_in_global, offset = max(|.|, 1e-5); view 0 through the camera), a correspondence replaces both its planes by
+ *   normalize(n0 + n1) times the mean offset, and every plane comes back through get_plane_params_in_local -> merged double [total, 3].
+ *   For n0 . n1 < 0 the reference's sign is a rounding accident; here the merged normal is then normalize(n0 - n1), the orientation
+ *   of view 0's plane.  bad int32 [P]: 1 for a pair with a correspondence index out of range, a plane in two correspondences, more
+ *   than max_n planes in a view or offsets outside [0, total] - none of its planes is written.  max_n <= NPS_PLANE_MAX_QUERIES.
+ * recon_mesh_count: per instance (bits: the layout of runs_to_bits, uint32 [n, ceil(H W / 32)]) the vertex and face counts of the
+ *   mask m[::stride, ::stride]: one vertex per set pixel; per vertex (y, x) a triangle when (y, x + 1) and (y + 1, x + 1) are set and
+ *   one when (y + 1, x) and (y + 1, x + 1) are set.  A workgroup per instance holds the strided mask row-major in LDS:
+ *   Hs (RW | 1) + 2 (Hs + 1) words with Hs = ceil(H / stride), RW = ceil(ceil(W / stride) / 32) must not exceed NPS_MESH_LDS_WORDS
+ *   (480 x 640 at stride 1: 11042), else NPS_E_ARG; so do stride < 1 and H W >= 2^31 - 32.
+ * recon_mesh_fill: instance i writes rows vert_off[i] .. vert_off[i + 1] of verts f32 [n_verts, 3] and uvs f32 [n_verts, 2] and rows
+ *   face_off[i] .. face_off[i + 1] of faces int32 [n_faces, 3] (int64 [n + 1] exclusive scans of the counts).  Vertices in row-major
+ *   order of the strided mask, pixel (x, y) = stride (xs, ys): ray = kinv [x, y, 1], depth = |p| / ((p / |p|) . ray) with p = planes
+ *   + 3 i (double, the plane in its view's frame), v = depth ray in plain IEEE arithmetic; then v [1, -1, -1] turned by the quaternion
+ *   of cams + 7 view (q v q^-1, divided by |q|^2) plus its position; uv = (x / W, 1 - y / H).  view = inst_view[i] indexes kinv (double
+ *   [n_views, 9], row-major K^-1) and cams (double [n_views, 7]; an identity row for the view that is the common frame).  Faces in
+ *   vertex order, ids local to the instance from 0: [id(y, x), id(y + 1, x + 1), id(y, x + 1)], then [id(y, x), id(y + 1, x),
+ *   id(y + 1, x + 1)].  Float64 arithmetic, f32 stores.  bad int32 [n]: 1 for an instance whose counts differ from its offset ranges,
+ *   whose ranges leave [0, n_verts] / [0, n_faces] or whose view is outside [0, n_views) - nothing else of it is written. */
+nps_status nopesac_recon_mesh_merge(const float* planes, const int64_t* view_off, const double* cams, const int32_t* corr,
+                                    const int64_t* corr_off, int P, int max_n, int64_t total, double* merged, int32_t* bad, void* stream);
+nps_status nopesac_recon_mesh_count(const uint32_t* bits, int n, int H, int W, int stride, int32_t* n_vert, int32_t* n_face, void* stream);
+nps_status nopesac_recon_mesh_fill(const uint32_t* bits, int n, int H, int W, int stride, const double* planes, const int32_t* inst_view,
+                                   int n_views, const double* kinv, const double* cams, const int64_t* vert_off, const int64_t* face_off,
+                                   int64_t n_verts, int64_t n_faces, float* verts, float* uvs, int32_t* faces, int32_t* bad, void* stream);
 
 
 /* Layers 1..5 of both branches of the pixel pose net (camera_net/camera_modules.py `convs_trans` / `convs_rots`: Conv3x3 + BatchNorm +

@@ -1279,6 +1279,79 @@ def recon_ap_assign(iou, iou_off, dt_off, gt_off, score, pred_plane, gt_plane, p
     return (rows, n_gt_entries, bad) if errs is None else (rows, n_gt_entries, bad, errs[:err_total])
 
 
+# ---- the reconstruction as meshes (csrc/recon_mesh.hip): merged plane parameters, vertex / face counts, the fill
+MESH_LDS_WORDS = _H.NPS_MESH_LDS_WORDS
+
+
+def mesh_lds_words(H: int, W: int, stride: int) -> int:
+    """LDS words a workgroup of recon_mesh_count / _fill needs for an H x W mask at `stride` (the header states the formula)."""
+    hs, ws = -(-H // stride), -(-W // stride)
+    return hs * (-(-ws // 32) | 1) + 2 * (hs + 1)
+
+
+def _mesh_mask_args(who: str, bits, H: int, W: int, stride: int) -> int:
+    _require(H > 0 and W > 0 and H * W <= 0x7fffffdf, f"{who}: H, W > 0 and H W < 2^31 - 32")
+    _require(stride >= 1, f"{who}: stride >= 1 (got {stride})")
+    _require(mesh_lds_words(H, W, stride) <= MESH_LDS_WORDS,
+             f"{who}: a {H} x {W} mask at stride {stride} needs {mesh_lds_words(H, W, stride)} LDS words, NPS_MESH_LDS_WORDS is {MESH_LDS_WORDS}")
+    _chk(bits, torch.int32)
+    words = (H * W + 31) // 32
+    _require(bits.dim() == 2 and (bits.shape[0] == 0 or bits.shape[1] == words), f"{who}: bits is int32 [n, ceil(H W / 32)]")
+    return bits.shape[0]
+
+
+def recon_mesh_merge(planes, view_off, cams, corr, corr_off, max_n: int):
+    """merge_plane_params_from_local_params for P pairs in one launch (include/nopesac_hip.h states the rules): planes f32 [total, 3],
+    view_off int64 [2 P + 1] (pair i owns views 2 i and 2 i + 1), cams float64 [P, 7] (position, quaternion wxyz), corr int32 [., 2]
+    with corr_off int64 [P + 1]; max_n: the largest per-view plane count (the caller has it).  Returns (merged float64 [total, 3],
+    bad int32 [P]); a bad pair's planes stay zero."""
+    _require(0 <= max_n <= PLANE_MAX_QUERIES, f"recon_mesh_merge: at most {PLANE_MAX_QUERIES} planes per view (got {max_n})")
+    _chk(planes, torch.float32); _chk(view_off, torch.int64); _chk(cams, torch.float64); _chk(corr, torch.int32); _chk(corr_off, torch.int64)
+    P, total = corr_off.numel() - 1, planes.numel() // 3
+    _require(P >= 0 and view_off.numel() == 2 * P + 1 and cams.numel() == 7 * P and planes.numel() == 3 * total and corr.numel() % 2 == 0,
+             "recon_mesh_merge: shapes")
+    dev = cams.device
+    merged = torch.zeros((total, 3), device=dev, dtype=torch.float64)
+    bad = torch.zeros(P, device=dev, dtype=torch.int32)
+    if corr.numel() == 0:                       # no correspondence at all: the library still wants a buffer to point at
+        corr = torch.zeros(2, device=dev, dtype=torch.int32)
+    _C.nopesac_recon_mesh_merge(_p(planes) if total else None, _p(view_off), _p(cams), _p(corr), _p(corr_off), P, int(max_n), total,
+                                _p(merged) if total else None, _p(bad), _stream())
+    return merged, bad
+
+
+def recon_mesh_count(bits, H: int, W: int, stride: int = 1):
+    """Per instance (bits int32 [n, ceil(H W / 32)], the layout of rle_runs_to_bits) -> (n_vert int32 [n], n_face int32 [n]) of the
+    dense mesh of the mask m[::stride, ::stride]."""
+    n = _mesh_mask_args("recon_mesh_count", bits, H, W, stride)
+    n_vert = torch.empty(n, device=bits.device, dtype=torch.int32)
+    n_face = torch.empty(n, device=bits.device, dtype=torch.int32)
+    _C.nopesac_recon_mesh_count(_p(bits), n, H, W, stride, _p(n_vert), _p(n_face), _stream())
+    return n_vert, n_face
+
+
+def recon_mesh_fill(bits, H: int, W: int, stride: int, planes, inst_view, kinv, cams, vert_off, face_off, n_verts: int, n_faces: int):
+    """The dense meshes of n instances in one launch: planes float64 [n, 3] (each in its view's frame), inst_view int32 [n] indexing
+    kinv float64 [V, 9] and cams float64 [V, 7], vert_off / face_off int64 [n + 1] (exclusive scans of recon_mesh_count's counts) with
+    their totals n_verts / n_faces.  Returns (verts f32 [n_verts, 3], uvs f32 [n_verts, 2], faces int32 [n_faces, 3], bad int32 [n])."""
+    n = _mesh_mask_args("recon_mesh_fill", bits, H, W, stride)
+    _require(n_verts >= 0 and n_faces >= 0, "recon_mesh_fill: n_verts, n_faces >= 0")
+    _chk(planes, torch.float64); _chk(inst_view, torch.int32); _chk(kinv, torch.float64); _chk(cams, torch.float64)
+    _chk(vert_off, torch.int64); _chk(face_off, torch.int64)
+    V = kinv.numel() // 9
+    _require(planes.numel() == 3 * n and inst_view.numel() == n and kinv.numel() == 9 * V and cams.numel() == 7 * V
+             and vert_off.numel() == n + 1 and face_off.numel() == n + 1, "recon_mesh_fill: shapes")
+    dev = bits.device
+    verts = torch.empty((n_verts, 3), device=dev, dtype=torch.float32)
+    uvs = torch.empty((n_verts, 2), device=dev, dtype=torch.float32)
+    faces = torch.empty((n_faces, 3), device=dev, dtype=torch.int32)
+    bad = torch.zeros(n, device=dev, dtype=torch.int32)
+    _C.nopesac_recon_mesh_fill(_p(bits), n, H, W, stride, _p(planes), _p(inst_view), V, _p(kinv), _p(cams), _p(vert_off), _p(face_off),
+                               int(n_verts), int(n_faces), _p(verts) if n_verts else None, _p(uvs) if n_verts else None,
+                               _p(faces) if n_faces else None, _p(bad), _stream())
+    return verts, uvs, faces, bad
+
+
 GNN_PREFETCH =os.environ.get("NOPESAC_GNN_PREFETCH", "1") != "0"
 
 

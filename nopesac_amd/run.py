@@ -60,6 +60,13 @@ def default_argument_parser():
                     "-normal-offset; computed on the GPU (csrc/recon_eval.hip), so the model must be on one.  Needs pairs with `rel_pose`, "
                     "`gt_corrs` and `annotations` (RLE or polygon masks) with `plane`")
     ap.add_argument("--dump-dir", default="", help="write NopeSAC_instances_predictions.pth + continuous.pkl here (eval_full_scene)")
+    ap.add_argument("--export-meshes", default="", metavar="DIR", help="write the two-view reconstruction of the first --mesh-limit pairs as textured "
+                    "meshes, <id0>__<id1>.obj / .mtl (the reference's vis_NopeSAC.py on its dense route; nopesac_amd/mesh.py): matched planes "
+                    "merged, every mask lifted onto its plane, both views in view 1's frame through the predicted camera; built on the GPU "
+                    "(csrc/recon_mesh.hip)")
+    ap.add_argument("--mesh-stride", type=int, default=4, help="take every N-th pixel of a mask in both directions (1 = the reference's mesh, "
+                    "tens of megabytes of text per pair)")
+    ap.add_argument("--mesh-limit", type=int, default=16, help="export the first N pairs of each rank (0 = all)")
     ap.add_argument("--stub-model", action="store_true", help="TEST ONLY (results are marked invalid): the CLI's sharding, batch loop, evaluator "
                     "gather and dumps around a stub that fabricates result dicts instead of running the model - what the gloo CPU tests drive at "
                     "world sizes no box offers")
@@ -331,9 +338,16 @@ def _main_rank(args):
             recon_evaluator = ReconEvaluator(next(model.parameters()).device, pair_index=pair_index, gt_polygons=True)
         elif rank == 0:
             logger.warning("--eval-recon: no pair carries rel_pose, gt_corrs and annotations; nothing to evaluate")
+    mesh_exporter = None
+    if args.export_meshes:
+        from .mesh import MeshExporter
+        if not on_gpu and not args.stub_model:
+            raise RuntimeError("--export-meshes needs the model on a GPU (MODEL.DEVICE cuda): mask decoding, the plane merge and the mesh "
+                               "fill are HIP kernels, there is no host path")
+        mesh_exporter = MeshExporter(next(model.parameters()).device, args.export_meshes, stride=args.mesh_stride, limit=args.mesh_limit)
     try:
         timing = inference_on_dataset(model, pairs[lo:hi], evaluator, args.pairs_per_batch, kept, inflight=args.inflight,
-                                      also=tuple(ev for ev in (plane_evaluator, recon_evaluator) if ev is not None))
+                                      also=tuple(ev for ev in (plane_evaluator, recon_evaluator, mesh_exporter) if ev is not None))
     finally:
         gc.unfreeze()
     results = evaluator.evaluate()
@@ -349,6 +363,9 @@ def _main_rank(args):
         if rank == 0:
             logger.info("Reconstruction AP (%d pairs, %d skipped, %d GT entries):\n%s", table["pairs"], table["skipped"], int(table["npos"]),
                         "\n".join("{:>20s}: {:5.3f}".format(k, table[k]) for k in RECON_CRITERIA))
+    if mesh_exporter is not None:
+        results["meshes"] = mesh_exporter.evaluate()
+        logger.info("rank %d wrote %d meshes to %s", rank, len(mesh_exporter.written), args.export_meshes)
     if args.eval_matchings:
         if world > 1:                            # comm.gather semantics: rank-ordered concatenation
             parts = [None] * world
@@ -373,7 +390,7 @@ def _main_rank(args):
             logger.info("wrote %s", files)
     if rank == 0:
         for k, v in results.items():
-            if k not in ("plane", "recon") and isinstance(v, dict) and v and all(isinstance(x, (int, float)) for x in v.values()):
+            if k not in ("plane", "recon", "meshes") and isinstance(v, dict) and v and all(isinstance(x, (int, float)) for x in v.values()):
                 logger.info("%s metrics (final output mode -> %s):\n%s", k, cfg.MODEL.CAMERA_HEAD.INFERENCE_OUT_CAM_TYPE,
                             create_small_table({kk: float(vv) for kk, vv in v.items()}))
         if args.output:
