@@ -880,8 +880,8 @@ nps_status nopesac_recon_ap_assign(const double* iou, const int64_t* iou_off, co
  *   view 1).  A pair without correspondences keeps its planes (widened to double).  Otherwise every plane of the pair goes to view 1's
  *   frame (get_plane_params_in_global, offset = max(|.|, 1e-5); view 0 through the camera), a correspondence replaces both its planes by
  *   normalize(n0 + n1) times the mean offset, and every plane comes back through get_plane_params_in_local -> merged double [total, 3].
- *   For n0 . n1 < 0 the reference's sign is a rounding accident; here the merged normal is then normalize(n0 - n1), the orientation
- *   of view 0's plane.  bad int32 [P]: 1 for a pair with a correspondence index out of range, a plane in two correspondences, more
+ *   For n0 . n1 < 0 the merged normal is normalize(n0 - n1), the orientation of view 0's plane (csrc/two_view.h has the rule, shared
+ *   with recon_ap_assign).  bad int32 [P]: 1 for a pair with a correspondence index out of range, a plane in two correspondences, more
  *   than max_n planes in a view or offsets outside [0, total] - none of its planes is written.  max_n <= NPS_PLANE_MAX_QUERIES.
  * recon_mesh_count: per instance (bits: the layout of runs_to_bits, uint32 [n, ceil(H W / 32)]) the vertex and face counts of the
  *   mask m[::stride, ::stride]: one vertex per set pixel; per vertex (y, x) a triangle when (y, x + 1) and (y + 1, x + 1) are set and

@@ -2,48 +2,20 @@
 // get_maskiou_merged / get_single2merge :657-779, evaluate_by_idx / inst_bench_image :830-913, and get_plane_params_in_global,
 // utils/mesh_utils.py:89-105).  Per pair of views: both views' planes in one frame through the camera, the planes a correspondence
 // pairs merged into one entry, the three error matrices [predicted entries, GT entries], the five overlap criteria and the walk that
-// turns them into true positives.  What is left for the host is the AP over all pairs (evaluation.recon_table).
+// turns them into true positives.  What is left for the host is the AP over all pairs (evaluation.recon_table).  The global plane,
+// the merged normal and the match tables are two_view.h's, shared with recon_mesh.hip.
 //
 // Ragged quantities use exclusive-offset arrays (int64 [n + 1]) as in plane_eval.hip; pair i owns views 2 i and 2 i + 1 of the view
 // arrays.  Everything is float64 (the reference is float64 numpy), deterministic, without atomics, each output written once.
-#include "common.h"
+#include "two_view.h"
 
 namespace nps {
 
-constexpr int RE_MAXD = NPS_PLANE_MAX_QUERIES;     // predictions of one view
 constexpr int RE_MAXG = 255;                       // GT planes of one view
-constexpr int RE_MAXPE = 2 * RE_MAXD;              // predicted entries of a pair (no correspondence at all)
+constexpr int RE_MAXPE = 2 * TV_MAXN;              // predicted entries of a pair (no correspondence at all)
 constexpr int RE_MAXGE = 2 * RE_MAXG;              // GT entries of a pair
 constexpr int RE_CRIT = 5;                         // all, -offset, -normal, -mask, -normal-offset
 constexpr int RE_T = 64 * RE_CRIT;                 // one wave per criterion in the walk
-
-// A plane p = normal * offset of a camera's frame in the frame of the second view (get_plane_params_in_global): flip y and z,
-// rotate by q = [w, x, y, z] as q v q^-1 (a non-unit q divides by |q|^2, like numpy-quaternion's as_rotation_matrix), shift by
-// t; the plane through `end` with normal b = end - start is then named by the foot point of the origin, (a . b / |b|^2) b.
-// Out: offset = max(|plane|, 1e-5), n = plane / offset.
-__device__ __forceinline__ void re_global_plane(const float* __restrict__ p, const double* __restrict__ cam, bool identity, double& off,
-                                                double n[3]) {
-    const double vx = (double)p[0], vy = -(double)p[1], vz = -(double)p[2];
-    double tx = 0.0, ty = 0.0, tz = 0.0, ex = vx, ey = vy, ez = vz;
-    if (!identity) {
-        tx = cam[0]; ty = cam[1]; tz = cam[2];
-        const double w = cam[3], x = cam[4], y = cam[5], z = cam[6];
-        const double nq = w * w + x * x + y * y + z * z;
-        // v' = v + (w c + u x c) / |q|^2 with c = 2 u x v
-        const double cx = 2.0 * (y * vz - z * vy), cy = 2.0 * (z * vx - x * vz), cz = 2.0 * (x * vy - y * vx);
-        ex = vx + (w * cx + (y * cz - z * cy)) / nq;
-        ey = vy + (w * cy + (z * cx - x * cz)) / nq;
-        ez = vz + (w * cz + (x * cy - y * cx)) / nq;
-    }
-    const double ax = ex + tx, ay = ey + ty, az = ez + tz;                    // end
-    const double bx = ax - tx, by = ay - ty, bz = az - tz;                    // end - start, rounded as the reference rounds it
-    const double nb = sqrt(bx * bx + by * by + bz * bz);
-    const double s = (ax * bx + ay * by + az * bz) / (nb * nb);
-    const double gx = s * bx, gy = s * by, gz = s * bz;
-    const double len = sqrt(gx * gx + gy * gy + gz * gz);
-    off = len < 1e-5 ? 1e-5 : len;                                              // (a NaN stays one, as in np.maximum)
-    n[0] = gx / off; n[1] = gy / off; n[2] = gz / off;
-}
 
 // Entry tables of one side (predictions or GT) by one wave: the planes of view 0 no correspondence names, in index order, then those
 // of view 1, then one entry per correspondence in the order given.  match[v][k] >= 0: plane k of view v is in a correspondence.
@@ -70,11 +42,10 @@ __device__ __forceinline__ void re_entries(int lane, int n0, int n1, int nc, con
 }
 
 // One workgroup per pair, five waves.
-//  1. the correspondence lists become per-plane match tables in LDS; an index out of range or a plane named twice makes the pair
-//     `bad` (a thread's own write must still be there after the barrier): nothing of it is written but the flag.
+//  1. the correspondence lists become per-plane match tables in LDS (tv_match_mark / _verify); a `bad` pair writes nothing but the flag.
 //  2. wave 0 lays out the predicted entries, wave 1 the GT entries (ballot prefix count over the unmatched planes).
 //  3. every thread takes entries: global planes through the camera, the merged plane of a correspondence (offset mean, score max,
-//     normal = normalize(n0 + sign(n0 . n1) n1), the top eigenvector of n0 n0^T + n1 n1^T up to its sign, which |dot| ignores).
+//     tv_merged_normal, whose sign |dot| ignores).
 //  4. a wave takes a predicted entry, its lanes the GT entries, 64 at a time: the three errors once, the five overlap flags, and
 //     per criterion a ballot whose lowest set bit is the first flagged GT entry of this chunk.
 //  5. the walk (inst_bench_image with a 0 / 1 overlap) visits the entries in entry order; each claims the FIRST flagged GT entry
@@ -90,7 +61,7 @@ __global__ __launch_bounds__(RE_T) void recon_ap_assign_kernel(const double* __r
                                                                const long long* __restrict__ gt_corr_off, long long n_rows,
                                                                double* __restrict__ rows, int* __restrict__ n_gt_entries, int* __restrict__ bad,
                                                                double* __restrict__ errs, const long long* __restrict__ err_off) {
-    __shared__ int s_pm[2][RE_MAXD], s_gm[2][RE_MAXG];
+    __shared__ int s_pm[2][TV_MAXN], s_gm[2][RE_MAXG];
     __shared__ short s_pe[2][RE_MAXPE], s_ge[2][RE_MAXGE];
     __shared__ double s_po[RE_MAXPE], s_pn[RE_MAXPE][3], s_go[RE_MAXGE], s_gn[RE_MAXGE][3];
     __shared__ int s_first[RE_CRIT][RE_MAXPE];
@@ -100,7 +71,7 @@ __global__ __launch_bounds__(RE_T) void recon_ap_assign_kernel(const double* __r
     const long long n0l = d1 - d0, n1l = dt_off[2 * i + 2] - d1, m0l = g1 - g0, m1l = gt_off[2 * i + 2] - g1;
     const long long pc0 = pred_corr_off[i], npcl = pred_corr_off[i + 1] - pc0, gc0 = gt_corr_off[i], ngcl = gt_corr_off[i + 1] - gc0;
     const long long row0 = d0 - pc0;                                            // entries before this pair = planes - correspondences
-    const bool fits = n0l >= 0 && n0l <= RE_MAXD && n1l >= 0 && n1l <= RE_MAXD && m0l >= 0 && m0l <= RE_MAXG && m1l >= 0 && m1l <= RE_MAXG &&
+    const bool fits = n0l >= 0 && n0l <= TV_MAXN && n1l >= 0 && n1l <= TV_MAXN && m0l >= 0 && m0l <= RE_MAXG && m1l >= 0 && m1l <= RE_MAXG &&
                       npcl >= 0 && npcl <= (n0l < n1l ? n0l : n1l) && ngcl >= 0 && ngcl <= (m0l < m1l ? m0l : m1l) && row0 >= 0 &&
                       row0 + n0l + n1l - npcl <= n_rows;
     if (!fits) {                                                                // (uniform: before any barrier)
@@ -112,34 +83,22 @@ __global__ __launch_bounds__(RE_T) void recon_ap_assign_kernel(const double* __r
     const int* pc = pred_corr + 2 * pc0;
     const int* gc = gt_corr + 2 * gc0;
     // ---- 1. match tables
-    for (int k = tid; k < 2 * RE_MAXD; k += RE_T) (&s_pm[0][0])[k] = -1;
+    for (int k = tid; k < 2 * TV_MAXN; k += RE_T) (&s_pm[0][0])[k] = -1;
     for (int k = tid; k < 2 * RE_MAXG; k += RE_T) (&s_gm[0][0])[k] = -1;
     if (tid == 0) s_bad = 0;
     __syncthreads();
-    for (int c = tid; c < npc; c += RE_T) {
-        const int a = pc[2 * c], b = pc[2 * c + 1];
-        if (a >= 0 && a < n0 && b >= 0 && b < n1) { s_pm[0][a] = c; s_pm[1][b] = c; } else s_bad = 1;
-    }
-    for (int c = tid; c < ngc; c += RE_T) {
-        const int a = gc[2 * c], b = gc[2 * c + 1];
-        if (a >= 0 && a < m0 && b >= 0 && b < m1) { s_gm[0][a] = c; s_gm[1][b] = c; } else s_bad = 1;
-    }
+    tv_match_mark<TV_MAXN>(tid, RE_T, pc, npc, n0, n1, s_pm, s_bad);
+    tv_match_mark<RE_MAXG>(tid, RE_T, gc, ngc, m0, m1, s_gm, s_bad);
     __syncthreads();
-    for (int c = tid; c < npc; c += RE_T) {
-        const int a = pc[2 * c], b = pc[2 * c + 1];
-        if (a >= 0 && a < n0 && b >= 0 && b < n1 && (s_pm[0][a] != c || s_pm[1][b] != c)) s_bad = 1;
-    }
-    for (int c = tid; c < ngc; c += RE_T) {
-        const int a = gc[2 * c], b = gc[2 * c + 1];
-        if (a >= 0 && a < m0 && b >= 0 && b < m1 && (s_gm[0][a] != c || s_gm[1][b] != c)) s_bad = 1;
-    }
+    tv_match_verify<TV_MAXN>(tid, RE_T, pc, npc, n0, n1, s_pm, s_bad);
+    tv_match_verify<RE_MAXG>(tid, RE_T, gc, ngc, m0, m1, s_gm, s_bad);
     __syncthreads();
     if (s_bad) {                                                                // (uniform)
         if (tid == 0) { bad[i] = 1; n_gt_entries[i] = 0; }
         return;
     }
     // ---- 2. entry tables
-    if (wave == 0) re_entries<RE_MAXD>(lane, n0, n1, npc, pc, s_pm, s_pe);
+    if (wave == 0) re_entries<TV_MAXN>(lane, n0, n1, npc, pc, s_pm, s_pe);
     if (wave == 1) re_entries<RE_MAXG>(lane, m0, m1, ngc, gc, s_gm, s_ge);
     __syncthreads();
     // ---- 3. the entries' planes
@@ -152,18 +111,15 @@ __global__ __launch_bounds__(RE_T) void recon_ap_assign_kernel(const double* __r
         const float* planes = is_gt ? gt_plane : pred_plane;
         const long long b0 = is_gt ? g0 : d0, b1 = is_gt ? g1 : d1;
         const double* cam = is_gt ? gcam : pcam;
-        double off = 0.0, n[3] = {0.0, 0.0, 0.0};
-        if (k0 >= 0) re_global_plane(planes + 3 * (b0 + k0), cam, false, off, n);
+        double g[3], off = 0.0, n[3] = {0.0, 0.0, 0.0};
+        if (k0 >= 0) tv_global_plane(planes + 3 * (b0 + k0), cam, false, g, off, n);
         if (k1 >= 0 && (k0 < 0 || !is_gt)) {                                     // a merged GT entry keeps view 0's plane
             double o1, n1v[3];
-            re_global_plane(planes + 3 * (b1 + k1), cam, true, o1, n1v);
+            tv_global_plane(planes + 3 * (b1 + k1), cam, true, g, o1, n1v);
             if (k0 < 0) {
                 off = o1; n[0] = n1v[0]; n[1] = n1v[1]; n[2] = n1v[2];
             } else {
-                const double sg = n[0] * n1v[0] + n[1] * n1v[1] + n[2] * n1v[2] < 0.0 ? -1.0 : 1.0;
-                const double sx = n[0] + sg * n1v[0], sy = n[1] + sg * n1v[1], sz = n[2] + sg * n1v[2];
-                const double len = sqrt(sx * sx + sy * sy + sz * sz);
-                n[0] = sx / len; n[1] = sy / len; n[2] = sz / len;
+                tv_merged_normal(n, n1v, n);
                 off = (off + o1) / 2.0;
             }
         }
@@ -243,8 +199,8 @@ extern "C" nps_status nopesac_recon_ap_assign(const double* iou, const int64_t* 
     using namespace nps;
     static_assert(NPS_RECON_AP_COLS == 3 + RE_CRIT, "score, one flag per criterion, the entry's two plane indices");
     NPS_CHECK_ARG(P >= 0 && n_rows >= 0, "recon_ap_assign: P < 0 or n_rows < 0");
-    NPS_CHECK_ARG(max_dt >= 0 && max_dt <= RE_MAXD && max_gt >= 0 && max_gt <= RE_MAXG,
-                  "recon_ap_assign: at most %d predictions and %d GT planes per view (got %d, %d)", RE_MAXD, RE_MAXG, max_dt, max_gt);
+    NPS_CHECK_ARG(max_dt >= 0 && max_dt <= TV_MAXN && max_gt >= 0 && max_gt <= RE_MAXG,
+                  "recon_ap_assign: at most %d predictions and %d GT planes per view (got %d, %d)", TV_MAXN, RE_MAXG, max_dt, max_gt);
     if (P == 0) return 0;
     NPS_CHECK_ARG(iou_off && dt_off && gt_off && pred_cam && gt_cam && pred_corr_off && gt_corr_off && n_gt_entries && bad,
                   "recon_ap_assign: null pointer");

@@ -1,44 +1,18 @@
 // The two-view reconstruction as textured meshes (the reference's vis_NopeSAC.py save_pair_objects: merge_plane_params_from_local_params,
 // the dense route of utils/vis.py get_single_image_mesh(reduce_size=False) + get_pcd, utils/mesh_utils.py transform_meshes).  Three
-// kernels: the merged plane parameters of a pair (float64, a workgroup per pair), the vertex / face counts of every instance, and the
-// fill that writes vertices, texture coordinates and triangles at offsets the host scanned from the counts.
+// kernels: the merged plane parameters of a pair (float64, a workgroup per pair, on the rules of two_view.h, shared with
+// recon_eval.hip), the vertex / face counts of every instance, and the fill that writes vertices, texture coordinates and triangles
+// at offsets the host scanned from the counts.
 //
 // Ragged quantities use exclusive-offset arrays (int64 [n + 1]) as in plane_eval.hip; pair i owns views 2 i and 2 i + 1 of the view
 // arrays.  Masks come bit-packed in the layout of nopesac_rle_runs_to_bits (column-major: bit p & 31 of word p >> 5, p = x H + y).
 // Deterministic, without atomics, each output written once.
-#include "common.h"
+#include "two_view.h"
 
 namespace nps {
 
-constexpr int RM_MAXN = NPS_PLANE_MAX_QUERIES;     // instances of one view
 constexpr int RM_T = 256;                          // threads of the count and fill workgroups
 constexpr int RM_WAVES = RM_T / 64;
-
-// v -> q v q^-1 for q = [w, x, y, z] (a non-unit q divides by |q|^2, like numpy-quaternion's as_rotation_matrix):
-// v' = v + (w c + u x c) / |q|^2 with c = 2 u x v, the form of recon_eval.hip's re_global_plane.
-__device__ __forceinline__ void rm_rotate(const double q[4], double vx, double vy, double vz, double r[3]) {
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double nq = w * w + x * x + y * y + z * z;
-    const double cx = 2.0 * (y * vz - z * vy), cy = 2.0 * (z * vx - x * vz), cz = 2.0 * (x * vy - y * vx);
-    r[0] = vx + (w * cx + (y * cz - z * cy)) / nq;
-    r[1] = vy + (w * cy + (z * cx - x * cz)) / nq;
-    r[2] = vz + (w * cz + (x * cy - y * cx)) / nq;
-}
-
-// get_plane_params_in_global: flip y and z, rotate, shift by t; the plane through `end` with normal b = end - start is named by the
-// foot point of the origin, g = (a . b / |b|^2) b.  Out: g, offset = max(|g|, 1e-5), n = g / offset.
-__device__ __forceinline__ void rm_global(const float* __restrict__ p, const double cam[7], double g[3], double& off, double n[3]) {
-    double e[3];
-    rm_rotate(cam + 3, (double)p[0], -(double)p[1], -(double)p[2], e);
-    const double ax = e[0] + cam[0], ay = e[1] + cam[1], az = e[2] + cam[2];   // end
-    const double bx = ax - cam[0], by = ay - cam[1], bz = az - cam[2];         // end - start, rounded as the reference rounds it
-    const double nb = sqrt(bx * bx + by * by + bz * bz);
-    const double s = (ax * bx + ay * by + az * bz) / (nb * nb);
-    g[0] = s * bx; g[1] = s * by; g[2] = s * bz;
-    const double len = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-    off = len < 1e-5 ? 1e-5 : len;
-    n[0] = g[0] / off; n[1] = g[1] / off; n[2] = g[2] / off;
-}
 
 // get_plane_params_in_local: the point a + b - (a . b / |b|^2) b of the plane b seen from the camera at a, turned back by q^-1 and
 // flipped.
@@ -49,28 +23,25 @@ __device__ __forceinline__ void rm_local(const double b[3], const double cam[7],
     const double wx = ax + b[0] - s * b[0], wy = ay + b[1] - s * b[1], wz = az + b[2] - s * b[2];
     const double qi[4] = {cam[3], -cam[4], -cam[5], -cam[6]};                  // the inverse turns the other way; |q|^2 drops out
     double r[3];
-    rm_rotate(qi, wx - ax, wy - ay, wz - az, r);
+    tv_rotate(qi, wx - ax, wy - ay, wz - az, r);
     out[0] = r[0]; out[1] = -r[1]; out[2] = -r[2];
 }
 
-// One workgroup (a wave) per pair.  The correspondence list becomes per-plane match tables in LDS; an index out of range or a plane
-// named twice makes the pair `bad` and nothing of it is written but the flag.  A pair without correspondences keeps its planes as
-// they are (the reference merges only when the list is not empty).  Otherwise every plane goes to the common frame
-// (get_plane_params_in_global: view 0 through the camera, view 1 through the identity), a correspondence (a, b) replaces both planes
-// by normalize(n0 + n1) times the mean offset, and every plane, matched or not, comes back through get_plane_params_in_local.
-// The reference takes the top eigenvector of n0 n0^T + n1 n1^T, which is n0 + sign(n0 . n1) n1 up to its sign, and picks the sign by
-// v . n0 + v . n1; for n0 . n1 < 0 that sum is a rounding residue, so the case is DEFINED here: n0 . n1 < 0 gives normalize(n0 - n1),
-// the orientation of view 0's plane.
+// One workgroup (a wave) per pair.  The correspondence list becomes per-plane match tables in LDS (tv_match_mark / _verify); a `bad`
+// pair writes nothing but the flag.  A pair without correspondences keeps its planes as they are (the reference merges only when the
+// list is not empty).  Otherwise every plane goes to the common frame (tv_global_plane: view 0 through the camera, view 1 through the
+// identity), a correspondence (a, b) replaces both planes by tv_merged_normal times the mean offset, and every plane, matched or not,
+// comes back through get_plane_params_in_local.
 __global__ __launch_bounds__(64) void recon_mesh_merge_kernel(const float* __restrict__ planes, const long long* __restrict__ view_off,
                                                               const double* __restrict__ cams, const int* __restrict__ corr,
                                                               const long long* __restrict__ corr_off, long long total,
                                                               double* __restrict__ out, int* __restrict__ bad) {
-    __shared__ int s_m[2][RM_MAXN];
+    __shared__ int s_m[2][TV_MAXN];
     __shared__ int s_bad;
     const int i = blockIdx.x, tid = threadIdx.x;
     const long long v0 = view_off[2 * i], v1 = view_off[2 * i + 1], n0l = v1 - v0, n1l = view_off[2 * i + 2] - v1;
     const long long c0 = corr_off[i], ncl = corr_off[i + 1] - c0;
-    const bool fits = v0 >= 0 && n0l >= 0 && n0l <= RM_MAXN && n1l >= 0 && n1l <= RM_MAXN && v1 + n1l <= total && c0 >= 0 && ncl >= 0 &&
+    const bool fits = v0 >= 0 && n0l >= 0 && n0l <= TV_MAXN && n1l >= 0 && n1l <= TV_MAXN && v1 + n1l <= total && c0 >= 0 && ncl >= 0 &&
                       ncl <= (n0l < n1l ? n0l : n1l);
     if (!fits) {                                                                // (uniform: before any barrier)
         if (tid == 0) bad[i] = 1;
@@ -78,18 +49,12 @@ __global__ __launch_bounds__(64) void recon_mesh_merge_kernel(const float* __res
     }
     const int n0 = (int)n0l, n1 = (int)n1l, nc = (int)ncl;
     const int* pc = corr + 2 * c0;
-    for (int k = tid; k < 2 * RM_MAXN; k += 64) (&s_m[0][0])[k] = -1;
+    for (int k = tid; k < 2 * TV_MAXN; k += 64) (&s_m[0][0])[k] = -1;
     if (tid == 0) s_bad = 0;
     __syncthreads();
-    for (int c = tid; c < nc; c += 64) {
-        const int a = pc[2 * c], b = pc[2 * c + 1];
-        if (a >= 0 && a < n0 && b >= 0 && b < n1) { s_m[0][a] = c; s_m[1][b] = c; } else s_bad = 1;
-    }
+    tv_match_mark<TV_MAXN>(tid, 64, pc, nc, n0, n1, s_m, s_bad);
     __syncthreads();
-    for (int c = tid; c < nc; c += 64) {                                        // a thread's own write must still be there
-        const int a = pc[2 * c], b = pc[2 * c + 1];
-        if (a >= 0 && a < n0 && b >= 0 && b < n1 && (s_m[0][a] != c || s_m[1][b] != c)) s_bad = 1;
-    }
+    tv_match_verify<TV_MAXN>(tid, 64, pc, nc, n0, n1, s_m, s_bad);
     __syncthreads();
     if (s_bad) {                                                                // (uniform)
         if (tid == 0) bad[i] = 1;
@@ -107,19 +72,15 @@ __global__ __launch_bounds__(64) void recon_mesh_merge_kernel(const float* __res
             continue;
         }
         double g[3], off, n[3];
-        rm_global(p, v ? ident : cam0, g, off, n);
+        tv_global_plane(p, cam0, v == 1, g, off, n);
         const int c = s_m[v][k];
         if (c >= 0) {                                                           // both sides compute the same merged plane
             const int other = v ? pc[2 * c] : pc[2 * c + 1];
-            double g2[3], off2, n2[3];
-            rm_global(planes + 3 * ((v ? v0 : v1) + other), v ? cam0 : ident, g2, off2, n2);
-            const double* a0 = v ? n2 : n;                                      // view 0's normal, view 1's
-            const double* a1 = v ? n : n2;
-            const double sg = a0[0] * a1[0] + a0[1] * a1[1] + a0[2] * a1[2] < 0.0 ? -1.0 : 1.0;
-            const double sx = a0[0] + sg * a1[0], sy = a0[1] + sg * a1[1], sz = a0[2] + sg * a1[2];
-            const double len = sqrt(sx * sx + sy * sy + sz * sz);
+            double g2[3], off2, n2[3], m[3];
+            tv_global_plane(planes + 3 * ((v ? v0 : v1) + other), cam0, v == 0, g2, off2, n2);
+            tv_merged_normal(v ? n2 : n, v ? n : n2, m);                        // view 0's normal, view 1's
             const double mean = ((v ? off2 : off) + (v ? off : off2)) / 2.0;
-            g[0] = sx / len * mean; g[1] = sy / len * mean; g[2] = sz / len * mean;
+            g[0] = m[0] * mean; g[1] = m[1] * mean; g[2] = m[2] * mean;
         }
         rm_local(g, v ? ident : cam0, o);
     }
@@ -272,7 +233,7 @@ __global__ __launch_bounds__(RM_T) void recon_mesh_fill_kernel(const unsigned* _
                 const double rx = ki[0] * x + ki[1] * y + ki[2], ry = ki[3] * x + ki[4] * y + ki[5], rz = ki[6] * x + ki[7] * y + ki[8];
                 const double depth = off / (nx * rx + ny * ry + nz * rz);
                 double r[3];
-                rm_rotate(cam + 3, depth * rx, -(depth * ry), -(depth * rz), r);
+                tv_rotate(cam + 3, depth * rx, -(depth * ry), -(depth * rz), r);
                 vout[3 * (long long)id] = (float)(r[0] + cam[0]);
                 vout[3 * (long long)id + 1] = (float)(r[1] + cam[1]);
                 vout[3 * (long long)id + 2] = (float)(r[2] + cam[2]);
@@ -312,7 +273,7 @@ extern "C" nps_status nopesac_recon_mesh_merge(const float* planes, const int64_
                                                void* stream) {
     using namespace nps;
     NPS_CHECK_ARG(P >= 0 && total >= 0, "recon_mesh_merge: P < 0 or total < 0");
-    NPS_CHECK_ARG(max_n >= 0 && max_n <= RM_MAXN, "recon_mesh_merge: at most %d planes per view (got %d)", RM_MAXN, max_n);
+    NPS_CHECK_ARG(max_n >= 0 && max_n <= TV_MAXN, "recon_mesh_merge: at most %d planes per view (got %d)", TV_MAXN, max_n);
     if (P == 0) return 0;
     NPS_CHECK_ARG(view_off && cams && corr_off && bad, "recon_mesh_merge: null pointer");
     NPS_CHECK_ARG(total == 0 || (planes && merged), "recon_mesh_merge: null pointer (planes)");

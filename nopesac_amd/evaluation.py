@@ -35,6 +35,36 @@ import torch
 from . import runner
 
 
+def to_numpy(x) -> np.ndarray:
+    """A tensor (any device) or anything numpy takes, as a numpy array."""
+    return np.asarray(x.detach().cpu() if torch.is_tensor(x) else x)
+
+
+def _world() -> int:
+    dist = torch.distributed
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def _nccl() -> bool:
+    return _world() > 1 and torch.distributed.get_backend() == "nccl"
+
+
+def gather_rows(local: np.ndarray, device) -> List[np.ndarray]:
+    """Per-rank blocks of a [n, w] table, in rank order, in the table's dtype.  Ranks may hold different row counts (ceil sharding):
+    pad to the max (at least one row), one all_gather of the padded blocks on `device`, drop the padding."""
+    if _world() == 1:
+        return [local]
+    n = torch.tensor([local.shape[0]], device=device)
+    counts = [torch.zeros_like(n) for _ in range(_world())]
+    torch.distributed.all_gather(counts, n)
+    nmax = max(int(max(c.item() for c in counts)), 1)
+    rows = torch.from_numpy(local)
+    padded = torch.zeros(nmax, local.shape[1], device=device, dtype=rows.dtype)
+    padded[: local.shape[0]] = rows.to(device)
+    allrows = runner.gather_metrics(padded).cpu().numpy()
+    return [allrows[r * nmax: r * nmax + int(c.item())] for r, c in enumerate(counts)]
+
+
 def camera_metrics(pred_tran: np.ndarray, pred_rot: np.ndarray, gt_tran: np.ndarray, gt_rot: np.ndarray) -> Dict[str, float]:
     """The reference's camera table (mp3d_evaluation.py:382-418), same keys."""
     t_err = runner.translation_error(pred_tran, gt_tran)
@@ -107,20 +137,8 @@ class PoseEvaluator:
 
     def evaluate(self) -> Dict[str, dict]:
         local = np.stack(self._rows) if self._rows else np.zeros((0, self.row_width), np.float32)
-        rows = torch.from_numpy(local)
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            dev = self.device or (torch.device("cuda", torch.cuda.current_device()) if torch.distributed.get_backend() == "nccl"
-                                  else torch.device("cpu"))
-            # ranks may hold different pair counts (ceil sharding): pad to the max, gather, drop the padding
-            n = torch.tensor([rows.shape[0]], device=dev)
-            counts = [torch.zeros_like(n) for _ in range(torch.distributed.get_world_size())]
-            torch.distributed.all_gather(counts, n)
-            nmax = int(max(c.item() for c in counts))
-            padded = torch.zeros(nmax, self.row_width, device=dev)
-            padded[: rows.shape[0]] = rows.to(dev)
-            allrows = runner.gather_metrics(padded).cpu()
-            rows = torch.cat([allrows[r * nmax: r * nmax + int(c.item())] for r, c in enumerate(counts)], 0)
-        r = rows.numpy()
+        dev = self.device or (torch.device("cuda", torch.cuda.current_device()) if _nccl() else torch.device("cpu"))
+        r = np.concatenate(gather_rows(local, dev))
         res: Dict[str, dict] = {"pairs": {"count": int(r.shape[0]), "mean planes/view": float(r[:, 8:10].mean()) if len(r) else 0.0,
                                           "mean matches": float(r[:, 10].mean()) if len(r) else 0.0}}
         has_gt = r[:, 7] > 0 if len(r) else np.zeros(0, bool)
@@ -173,8 +191,7 @@ def evaluate_for_matchings(predictions: List[dict], dataset_dict: Dict[str, dict
                 best_iou.append(m.max(-1)); best_gt.append(m.argmax(-1))       # first maximum, like torch.max
         for k in keys:
             A = pred[k]
-            A = A.detach().cpu().numpy() if torch.is_tensor(A) else np.asarray(A)
-            idx = np.argwhere(A != 0)
+            idx = np.argwhere(to_numpy(A) != 0)
             stats[k]["pred"] += int(idx.shape[0])
             for i, j in idx:
                 if best_iou[0][i] >= iou_thresh and best_iou[1][j] >= iou_thresh and (int(best_gt[0][i]), int(best_gt[1][j])) in gt_corr:
@@ -277,27 +294,18 @@ def plane_rows(views: List[dict], device, iou_thresh: float = 0.5, normal_thresh
     total = int(sum(n_dt))
     if total == 0:
         return np.zeros((0, len(PLANE_ROW_COLS)), np.float64)
-    dt_rles = [ins["segmentation"] for v in views for ins in v["instances"]]
-    gt_rles = [_rle_of(a["segmentation"], "plane_rows", gt_polygons) for v in views for a in v["annotations"]]
-    bits, area = rle.segmentation_bits(dt_rles + gt_rles, device) if gt_polygons else rle.decode_bits(dt_rles + gt_rles, device)
-    offs = np.zeros((3, len(views) + 1), np.int64)
-    np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
-    planes = [np.asarray(v["pred_plane"].detach().cpu() if torch.is_tensor(v["pred_plane"]) else v["pred_plane"], np.float32).reshape(-1, 3)
-              for v in views]
-    for v, p, k in zip(views, planes, n_dt):
-        if p.shape[0] != k:
-            raise ValueError(f"plane_rows: {k} instances but {p.shape[0]} pred_plane rows")
+    dt_segs = [[ins["segmentation"] for ins in v["instances"]] for v in views]
+    gt_segs = [[_rle_of(a["segmentation"], "plane_rows", gt_polygons) for a in v["annotations"]] for v in views]
+    iou, d_off, _, _ = rle.iou_views(dt_segs, gt_segs, device, polygons=gt_polygons)
+    planes = checked_planes(views, n_dt, lambda k, n, rows: f"plane_rows: {n} instances but {rows} pred_plane rows")
     f32 = np.concatenate([np.asarray([ins["score"] for v in views for ins in v["instances"]], np.float32),
                           np.concatenate(planes).reshape(-1),
                           np.asarray([a["plane"] for v in views for a in v["annotations"]], np.float32).reshape(-1)])
     i32 = np.asarray([id_map[int(ins["category_id"])] for v in views for ins in v["instances"]]
                      + [int(a["category_id"]) for v in views for a in v["annotations"]], np.int32)
-    d_off = torch.from_numpy(offs).to(device)
     d_f32, d_i32 = torch.from_numpy(f32).to(device), torch.from_numpy(i32).to(device)
     n_g = int(sum(n_gt))
     score, pred_plane, gt_plane = d_f32[:total], d_f32[total:4 * total], d_f32[4 * total:]
-    iou, _ = ops.mask_iou_bits(bits[:total], area[:total], d_off[0], bits[total:], area[total:], d_off[1], None, d_off[2],
-                               int(offs[2, -1]), max(n_dt), max(n_gt))
     rows = ops.plane_ap_assign(iou, d_off[2], d_off[0], d_off[1], score, d_i32[:total], pred_plane, d_i32[total:total + n_g], gt_plane,
                                max(n_dt), max(n_gt), iou_thresh, normal_threshold, offset_threshold)
     return rows.cpu().numpy()
@@ -372,8 +380,7 @@ class PlaneEvaluator:
             return float(self.image_index[image_id])
         if isinstance(image_id, (int, np.integer)):
             return float(image_id)
-        dist = torch.distributed
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if _world() > 1:
             raise ValueError(f"PlaneEvaluator: image id {image_id!r} is no integer; with several ranks pass image_index "
                              "(image id -> index in the dataset json), the same on every rank")
         return self._numbers.setdefault(image_id, float(len(self._numbers)))
@@ -407,27 +414,12 @@ class PlaneEvaluator:
             num = np.repeat(np.asarray(numbers, np.float64), [len(v["instances"]) for v in views])
             self._rows.append(np.concatenate([rows, num[:, None]], 1))
 
-    @staticmethod
-    def _gather(local: np.ndarray, device) -> List[np.ndarray]:
-        """Per-rank blocks of a [n, w] float64 table, rank order (PoseEvaluator.evaluate's pad / gather / drop)."""
-        dist = torch.distributed
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-            return [local]
-        dev = device if dist.get_backend() == "nccl" else torch.device("cpu")
-        n = torch.tensor([local.shape[0]], device=dev)
-        counts = [torch.zeros_like(n) for _ in range(dist.get_world_size())]
-        dist.all_gather(counts, n)
-        nmax = int(max(c.item() for c in counts))
-        padded = torch.zeros(max(nmax, 1), local.shape[1], device=dev, dtype=torch.float64)
-        padded[: local.shape[0]] = torch.from_numpy(local).to(dev)
-        allrows = runner.gather_metrics(padded).cpu().numpy()
-        return [allrows[r * max(nmax, 1): r * max(nmax, 1) + int(c.item())] for r, c in enumerate(counts)]
-
     def evaluate(self) -> Dict[str, float]:
         rows = np.concatenate(self._rows) if self._rows else np.zeros((0, len(PLANE_ROW_COLS) + 1), np.float64)
         gts = np.concatenate(self._gt) if self._gt else np.zeros((0, 3), np.float64)
         owner: Dict[float, int] = {}                 # image number -> the lowest rank that saw it
-        gt_parts = self._gather(gts, self.device)
+        dev = self.device if _nccl() else torch.device("cpu")
+        gt_parts = gather_rows(gts, dev)
         for r, part in enumerate(gt_parts):
             for num in part[:, 0]:
                 owner.setdefault(float(num), r)
@@ -437,7 +429,7 @@ class PlaneEvaluator:
                 if owner[float(num)] == r and k > 0:
                     npos[int(cat)] = npos.get(int(cat), 0.0) + float(k)
         kept = [part[[owner[float(num)] == r for num in part[:, -1]]] if len(part) else part
-                for r, part in enumerate(self._gather(rows, self.device))]
+                for r, part in enumerate(gather_rows(rows, dev))]
         return plane_table(np.concatenate(kept)[:, :len(PLANE_ROW_COLS)], npos or {1: 0.0}, self.iou_thresh, self.normal_threshold,
                            self.offset_threshold, self.cat_names)
 
@@ -462,28 +454,37 @@ def recon_table(rows: np.ndarray, npos: float) -> Dict[str, float]:
     return out
 
 
-def _f32_planes(p) -> np.ndarray:
-    return np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, np.float32).reshape(-1, 3)
+def f32_planes(p) -> np.ndarray:
+    return np.asarray(to_numpy(p), np.float32).reshape(-1, 3)
 
 
-def _camera7(cam: dict, who: str) -> np.ndarray:
+def checked_planes(views: List[dict], n_inst: List[int], message) -> List[np.ndarray]:
+    """Every view's `pred_plane` as f32 [n, 3]; a view whose row count is not its instance count n_inst[k] is a
+    ValueError(message(k, instances, rows)) - the caller's own words."""
+    planes = [f32_planes(v["pred_plane"]) for v in views]
+    for k, (p, n) in enumerate(zip(planes, n_inst)):
+        if p.shape[0] != n:
+            raise ValueError(message(k, n, p.shape[0]))
+    return planes
+
+
+def camera7(cam: dict, who: str) -> np.ndarray:
     """{"position" | "tran", "rotation" | "rot"} -> float64 [7]: position, quaternion wxyz."""
     t = cam["position"] if "position" in cam else cam["tran"]
     q = cam["rotation"] if "rotation" in cam else cam["rot"]
-    t, q = (np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, np.float64).reshape(-1) for x in (t, q))
+    t, q = (np.asarray(to_numpy(x), np.float64).reshape(-1) for x in (t, q))
     if t.size != 3 or q.size != 4:
         raise ValueError(f"{who}: a camera is a position [3] and a quaternion [4] (got {t.size}, {q.size})")
     return np.concatenate([t, q])
 
 
-def _corr_pairs(corrs) -> np.ndarray:
-    c = np.asarray(corrs.detach().cpu() if torch.is_tensor(corrs) else corrs)
-    return c.reshape(-1, 2).astype(np.int32)
+def corr_pairs(corrs) -> np.ndarray:
+    return to_numpy(corrs).reshape(-1, 2).astype(np.int32)
 
 
 def assignment_corrs(assignment) -> np.ndarray:
     """The correspondences of a 0 / 1 assignment matrix [n0, n1] in np.argwhere order (row-major), int32 [k, 2]."""
-    a = np.asarray(assignment.detach().cpu() if torch.is_tensor(assignment) else assignment)
+    a = to_numpy(assignment)
     return np.argwhere(a.reshape(a.shape[-2:]) if a.ndim > 2 else a).astype(np.int32).reshape(-1, 2)
 
 
@@ -510,18 +511,12 @@ def recon_rows(pairs: List[dict], device, with_errors: bool = False, gt_polygons
     n_dt = [len(v["instances"]) for v in views]
     n_gt = [len(v["annotations"]) for v in views]
     total, n_g = int(sum(n_dt)), int(sum(n_gt))
-    planes = [_f32_planes(v["pred_plane"]) for v in views]
-    for p, k in zip(planes, n_dt):
-        if p.shape[0] != k:
-            raise ValueError(f"recon_rows: {k} instances but {p.shape[0]} pred_plane rows")
-    dt_rles = [ins["segmentation"] for v in views for ins in v["instances"]]
-    gt_rles = [_rle_of(a["segmentation"], "recon_rows", gt_polygons) for v in views for a in v["annotations"]]
-    offs = np.zeros((3, 2 * P + 1), np.int64)
-    np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
-    pc = [_corr_pairs(p["pred_corrs"]) for p in pairs]
-    gc = [_corr_pairs(p["gt_corrs"]) for p in pairs]
-    coffs = np.zeros((2, P + 1), np.int64)
-    np.cumsum([len(c) for c in pc], out=coffs[0, 1:]); np.cumsum([len(c) for c in gc], out=coffs[1, 1:])
+    planes = checked_planes(views, n_dt, lambda k, n, rows: f"recon_rows: {n} instances but {rows} pred_plane rows")
+    dt_segs = [[ins["segmentation"] for ins in v["instances"]] for v in views]
+    gt_segs = [[_rle_of(a["segmentation"], "recon_rows", gt_polygons) for a in v["annotations"]] for v in views]
+    pc = [corr_pairs(p["pred_corrs"]) for p in pairs]
+    gc = [corr_pairs(p["gt_corrs"]) for p in pairs]
+    coffs = np.stack([rle.exclusive_offsets([len(c) for c in pc]), rle.exclusive_offsets([len(c) for c in gc])])
     n_entries = np.asarray([n_dt[2 * i] + n_dt[2 * i + 1] - len(pc[i]) for i in range(P)], np.int64)
     if (n_entries < 0).any():
         raise ValueError(f"recon_rows: pair {int(np.argmax(n_entries < 0))} has more correspondences than planes")
@@ -529,23 +524,19 @@ def recon_rows(pairs: List[dict], device, with_errors: bool = False, gt_polygons
     f32 = np.concatenate([np.asarray([ins["score"] for v in views for ins in v["instances"]], np.float32),
                           np.concatenate(planes).reshape(-1),
                           np.asarray([a["plane"] for v in views for a in v["annotations"]], np.float32).reshape(-1)])
-    cams = np.stack([np.stack([_camera7(p["pred_camera"], "recon_rows") for p in pairs]),
-                     np.stack([_camera7(p["gt_camera"], "recon_rows") for p in pairs])])
+    cams = np.stack([np.stack([camera7(p["pred_camera"], "recon_rows") for p in pairs]),
+                     np.stack([camera7(p["gt_camera"], "recon_rows") for p in pairs])])
     i32 = np.concatenate(pc + gc).reshape(-1)
-    d_off, d_coff = torch.from_numpy(offs).to(device), torch.from_numpy(coffs).to(device)
+    d_coff = torch.from_numpy(coffs).to(device)
     d_f32, d_cam, d_i32 = torch.from_numpy(f32).to(device), torch.from_numpy(cams).to(device), torch.from_numpy(i32).to(device)
-    if total + n_g and not (gt_polygons and total == 0):
-        bits, area = rle.segmentation_bits(dt_rles + gt_rles, device) if gt_polygons else rle.decode_bits(dt_rles + gt_rles, device)
-        iou, _ = ops.mask_iou_bits(bits[:total], area[:total], d_off[0], bits[total:], area[total:], d_off[1], None, d_off[2],
-                                   int(offs[2, -1]), max(n_dt), max(n_gt))
-    else:
-        iou = torch.zeros(0, device=device, dtype=torch.float64)
+    # nothing to decode: no mask at all, or polygons only (no prediction names the image size) - then every IoU block is empty
+    iou, d_off, _, _ = rle.iou_views(dt_segs, gt_segs, device, polygons=gt_polygons,
+                                     decode=bool(total + n_g) and not (gt_polygons and total == 0))
     n_pc = 2 * int(coffs[0, -1])
     err_off = None
     if with_errors:
-        err_off = np.zeros(P + 1, np.int64)
         n_ge = [n_gt[2 * i] + n_gt[2 * i + 1] - len(gc[i]) for i in range(P)]
-        np.cumsum([3 * int(a) * max(b, 0) for a, b in zip(n_entries, n_ge)], out=err_off[1:])
+        err_off = rle.exclusive_offsets([3 * int(a) * max(b, 0) for a, b in zip(n_entries, n_ge)])
     res = ops.recon_ap_assign(iou, d_off[2], d_off[0], d_off[1], d_f32[:total], d_f32[total:4 * total], d_f32[4 * total:], d_cam[0], d_cam[1],
                               d_i32[:n_pc], d_coff[0], d_i32[n_pc:], d_coff[1], n_rows, max(n_dt), max(n_gt),
                               err_off=torch.from_numpy(err_off).to(device) if with_errors else None,
@@ -633,8 +624,7 @@ class ReconEvaluator:
     def _number(self, key: str) -> float:
         if self.pair_index is not None:
             return float(self.pair_index[key])
-        dist = torch.distributed
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if _world() > 1:
             raise ValueError("ReconEvaluator: with several ranks pass pair_index ('<id0>__<id1>' -> index in the dataset), the same on "
                              "every rank")
         self._count += 1
@@ -666,8 +656,8 @@ class ReconEvaluator:
         rows = np.concatenate(self._rows) if self._rows else np.zeros((0, w), np.float64)
         gts = np.concatenate(self._gt) if self._gt else np.zeros((0, 2), np.float64)
         gts = np.concatenate([gts, [[-1.0, float(self._skipped)]]])              # (the rank's skipped pairs ride along under number -1)
-        rows = np.concatenate(PlaneEvaluator._gather(rows, self.device))
-        gts = np.concatenate(PlaneEvaluator._gather(gts, self.device))
+        dev = self.device if _nccl() else torch.device("cpu")
+        rows, gts = np.concatenate(gather_rows(rows, dev)), np.concatenate(gather_rows(gts, dev))
         rows = rows[np.lexsort((rows[:, w - 1], rows[:, w - 2]))]
         counted = gts[gts[:, 0] >= 0]
         table = recon_table(rows[:, :len(RECON_ROW_COLS)], float(counted[:, 1].sum()))
@@ -695,11 +685,10 @@ def optimized_dict(predictions: List[dict]) -> Dict[int, dict]:
 def dump_predictions(predictions: List[dict], output_dir: str) -> Dict[str, str]:
     """Rank-0 side of `eval_full_scene` (mp3d_evaluation.py:330-341).  With a process group the per-rank lists are
     concatenated in rank order first (comm.gather semantics, :317-319); non-zero ranks return {}."""
-    dist = torch.distributed
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        parts = [None] * dist.get_world_size()
-        dist.all_gather_object(parts, predictions)
-        if dist.get_rank() != 0:
+    if _world() > 1:
+        parts = [None] * _world()
+        torch.distributed.all_gather_object(parts, predictions)
+        if torch.distributed.get_rank() != 0:
             return {}
         predictions = [p for part in parts for p in part]
     os.makedirs(output_dir, exist_ok=True)

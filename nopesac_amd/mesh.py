@@ -10,11 +10,9 @@ reference exactly.  Everything per pixel runs on the device (csrc/recon_mesh.hip
 from rle.segmentation_bits); the host scans the per-instance counts and writes the text.
 
 Merged plane parameters (merge=True, `merge_plane_params_from_local_params`): both views' planes go to the common frame
-(`get_plane_params_in_global`), a correspondence (a, b) replaces both planes by normalize(n0 + n1) times the mean offset, and every
-plane - matched or not - comes back through `get_plane_params_in_local`; a pair without correspondences keeps its planes untouched,
-as in the reference.  The reference picks the sign of the top eigenvector of n0 n0^T + n1 n1^T by the sign of v . n0 + v . n1, which
-for n0 . n1 < 0 is a rounding residue; that case is DEFINED here: for n0 . n1 < 0 the merged normal is normalize(n0 - n1), the
-orientation of view 0's plane.
+(`get_plane_params_in_global`), a correspondence (a, b) replaces both planes by the merged normal (csrc/two_view.h states the rule
+and its sign) times the mean offset, and every plane - matched or not - comes back through `get_plane_params_in_local`; a pair
+without correspondences keeps its planes untouched, as in the reference.
 
 Out of scope: the contour / earcut meshes of `get_single_image_mesh_plane` and their per-plane rectified texture maps, camera frusta
 (`get_camera_meshes`), `rotate_mesh_for_webview`, the matching figure and blended segmentations, depth-map meshes.
@@ -29,7 +27,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .evaluation import _camera7, _corr_pairs, _f32_planes, assignment_corrs
+from .evaluation import assignment_corrs, camera7, checked_planes, corr_pairs
+from .rle import exclusive_offsets
 
 DEFAULT_FOCAL = 517.97              # the reference's intrinsics when a pair has no K: this focal length, principal point (W / 2, H / 2)
 _IDENTITY7 = np.array([0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0])
@@ -83,19 +82,15 @@ def pair_meshes(pairs: List[dict], device, stride: int = 1, merge: bool = True, 
     if len(views) != 2 * P:
         raise ValueError("pair_meshes: a pair has two views")
     n_inst = [len(v.get("instances") or []) for v in views]
-    planes = [_f32_planes(v["pred_plane"]) for v in views]
-    for k, (p, n) in enumerate(zip(planes, n_inst)):
-        if p.shape[0] != n:
-            raise ValueError(f"pair_meshes: view {k % 2} of pair {k // 2} has {n} instances but {p.shape[0]} pred_plane rows")
+    planes = checked_planes(views, n_inst, lambda k, n, rows: f"pair_meshes: view {k % 2} of pair {k // 2} has {n} instances but {rows} "
+                                                              "pred_plane rows")
     if max(n_inst) > ops.PLANE_MAX_QUERIES:
         raise ValueError(f"pair_meshes: at most {ops.PLANE_MAX_QUERIES} instances per view (got {max(n_inst)})")
     total = int(sum(n_inst))
-    view_off = np.zeros(2 * P + 1, np.int64)
-    np.cumsum(n_inst, out=view_off[1:])
-    corrs = [_corr_pairs(p.get("corrs", ())) if merge else np.zeros((0, 2), np.int32) for p in pairs]
-    corr_off = np.zeros(P + 1, np.int64)
-    np.cumsum([len(c) for c in corrs], out=corr_off[1:])
-    pair_cam = np.stack([_camera7(p["camera"], "pair_meshes") for p in pairs])
+    view_off = exclusive_offsets(n_inst)
+    corrs = [corr_pairs(p.get("corrs", ())) if merge else np.zeros((0, 2), np.int32) for p in pairs]
+    corr_off = exclusive_offsets([len(c) for c in corrs])
+    pair_cam = np.stack([camera7(p["camera"], "pair_meshes") for p in pairs])
     view_of = np.concatenate([np.full(n, k % 2, np.int32) for k, n in enumerate(n_inst)]) if total else np.zeros(0, np.int32)
     inst_view = np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(n_inst)]) if total else np.zeros(0, np.int32)
     d_view_of = torch.from_numpy(view_of).to(device)

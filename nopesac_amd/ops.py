@@ -1138,14 +1138,18 @@ PLANE_AP_COLS = ("score", "label", "tp_mask", "tp_plane", "tp_normal", "tp_offse
 assert len(PLANE_AP_COLS) == _H.NPS_PLANE_AP_COLS       # the names of the row the header sizes
 
 
+def _or_dummy(t: torch.Tensor, n: int = 1) -> torch.Tensor:
+    """t, or n zeros in its place when it is empty: the library still wants a buffer to point at."""
+    return t if t.numel() else torch.zeros(n, device=t.device, dtype=t.dtype)
+
+
 def rle_string_runs(data: torch.Tensor, str_off: torch.Tensor):
     """Compressed COCO counts strings, concatenated (data uint8 [total], str_off int64 [n+1]) -> (runs int32 [total], n_runs int32 [n]):
     mask i's run lengths are runs[str_off[i] : str_off[i] + n_runs[i]] (a mask never has more runs than bytes)."""
     _chk(data, torch.uint8); _chk(str_off, torch.int64)
     n = str_off.numel() - 1
     _require(n >= 0, "rle_string_runs: str_off holds n + 1 offsets")
-    if data.numel() == 0:                       # only 0-byte strings: the library still wants a buffer to point at
-        data = torch.zeros(1, device=data.device, dtype=torch.uint8)
+    data = _or_dummy(data)                      # only 0-byte strings
     runs = torch.empty(max(data.numel(), 1), device=data.device, dtype=torch.int32)
     n_runs = torch.empty(n, device=data.device, dtype=torch.int32)
     _C.nopesac_rle_string_runs(_p(data), _p(str_off), n, _p(runs), _p(n_runs), _stream())
@@ -1160,8 +1164,7 @@ def rle_runs_to_bits(runs: torch.Tensor, run_off: torch.Tensor, n_runs: torch.Te
     n, words = n_runs.numel(), (H * W + 31) // 32
     _require(run_off.numel() == n + 1, "rle_runs_to_bits: run_off holds n + 1 offsets")
     dev = runs.device
-    if runs.numel() == 0:                       # only masks without a run (all bad): the library still wants a buffer to point at
-        runs = torch.zeros(1, device=dev, dtype=torch.int32)
+    runs = _or_dummy(runs)                      # only masks without a run (all bad)
     if bits is None:
         bits = torch.empty((max(n, 1), words), device=dev, dtype=torch.int32)[:n]
     else:
@@ -1183,11 +1186,8 @@ def poly_to_bits(xy: torch.Tensor, poly_off: torch.Tensor, mask_off: torch.Tenso
     n, n_polys, words = mask_off.numel() - 1, poly_off.numel() - 1, (H * W + 31) // 32
     _require(n >= 0 and n_polys >= 0 and xy.numel() % 2 == 0, "poly_to_bits: mask_off / poly_off hold n + 1 offsets, xy holds pairs")
     dev = mask_off.device
-    if xy.numel() == 0:                         # only masks without a point (all bad): the library still wants a buffer to point at
-        xy = torch.zeros(2, device=dev, dtype=torch.float64)
-        n_points = 0
-    else:
-        n_points = xy.numel() // 2
+    n_points = xy.numel() // 2
+    xy = _or_dummy(xy, 2)                       # only masks without a point (all bad)
     if bits is None:
         bits = torch.empty((max(n, 1), words), device=dev, dtype=torch.int32)[:n]
     else:
@@ -1263,8 +1263,7 @@ def recon_ap_assign(iou, iou_off, dt_off, gt_off, score, pred_plane, gt_plane, p
              and gt_plane.numel() % 3 == 0 and pred_corr.numel() % 2 == 0 and gt_corr.numel() % 2 == 0 and 0 <= n_rows <= n,
              "recon_ap_assign: shapes")
     dev = pred_cam.device
-    if iou.numel() == 0:                        # no view with both predictions and GT: the library still wants a buffer to point at
-        iou = torch.zeros(1, device=dev, dtype=torch.float64)
+    iou = _or_dummy(iou)                        # no view with both predictions and GT
     rows = torch.zeros((n_rows, len(RECON_AP_COLS)), device=dev, dtype=torch.float64)
     n_gt_entries = torch.zeros(P, device=dev, dtype=torch.int32)
     bad = torch.zeros(P, device=dev, dtype=torch.int32)
@@ -1313,8 +1312,7 @@ def recon_mesh_merge(planes, view_off, cams, corr, corr_off, max_n: int):
     dev = cams.device
     merged = torch.zeros((total, 3), device=dev, dtype=torch.float64)
     bad = torch.zeros(P, device=dev, dtype=torch.int32)
-    if corr.numel() == 0:                       # no correspondence at all: the library still wants a buffer to point at
-        corr = torch.zeros(2, device=dev, dtype=torch.int32)
+    corr = _or_dummy(corr, 2)                   # no correspondence at all
     _C.nopesac_recon_mesh_merge(_p(planes) if total else None, _p(view_off), _p(cams), _p(corr), _p(corr_off), P, int(max_n), total,
                                 _p(merged) if total else None, _p(bad), _stream())
     return merged, bad

@@ -24,6 +24,13 @@ from . import _lib, ops
 from .ops import _C
 
 
+def exclusive_offsets(counts) -> np.ndarray:
+    """Exclusive offsets of a list of counts: int64 [n + 1], the ragged layout every kernel of the evaluators takes."""
+    off = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(counts, out=off[1:])
+    return off
+
+
 def flip_positions(winner: torch.Tensor, kept_idx: torch.Tensor, n_kept: torch.Tensor, flags: torch.Tensor):
     """winner uint8 [V,H,W], kept_idx int32 [V,nq], n_kept int32 [V], flags int32 [V] (device) ->
     (counts int32 [V,nq] cpu, offsets int64 [V,nq] cpu, positions uint32 numpy [total])."""
@@ -224,8 +231,7 @@ def decode_bits(rles: List[dict], device):
     if kinds[True]:
         strs = [rles[i]["counts"] for i in kinds[True]]
         strs = [s.encode("ascii") if isinstance(s, str) else bytes(s) for s in strs]
-        off = np.zeros(len(strs) + 1, np.int64)
-        np.cumsum([len(s) for s in strs], out=off[1:])
+        off = exclusive_offsets([len(s) for s in strs])
         blob = b"".join(strs)
         host = torch.from_numpy(np.concatenate([np.frombuffer(blob + bytes(-len(blob) % 8), np.uint8), off.view(np.uint8)]))
         dev = host.to(device)                                           # one upload: the bytes (padded to 8) and their offsets
@@ -235,8 +241,7 @@ def decode_bits(rles: List[dict], device):
         parts.append((kinds[True], ops.rle_runs_to_bits(runs, str_off, n_runs, H, W)))
     if kinds[False]:
         lists = [np.asarray(rles[i]["counts"], dtype=np.int64).reshape(-1) for i in kinds[False]]
-        off = np.zeros(len(lists) + 1, np.int64)
-        np.cumsum([len(c) for c in lists], out=off[1:])
+        off = exclusive_offsets([len(c) for c in lists])
         allc = np.concatenate(lists) if lists else np.zeros(0, np.int64)
         if allc.size and (allc.min() < -2**31 or allc.max() >= 2**31):
             raise ValueError("decode_bits: a run length does not fit 32 bits")
@@ -283,10 +288,8 @@ def polygon_bits(segmentations, H: int, W: int, device):
             polys.append(xy)
     if n == 0:
         return torch.empty((0, words), device=device, dtype=torch.int32), torch.empty(0, device=device, dtype=torch.int32)
-    off = np.zeros(len(polys) + 1 + n + 1, np.int64)
-    poly_off, mask_off = off[:len(polys) + 1], off[len(polys) + 1:]
-    np.cumsum([xy.size // 2 for xy in polys], out=poly_off[1:])
-    np.cumsum([len(seg) for seg in segmentations], out=mask_off[1:])
+    poly_off, mask_off = exclusive_offsets([xy.size // 2 for xy in polys]), exclusive_offsets([len(seg) for seg in segmentations])
+    off = np.concatenate([poly_off, mask_off])
     xy = np.concatenate(polys) if polys else np.zeros(0, np.float64)
     dev = torch.from_numpy(np.concatenate([xy.view(np.int64), off])).to(device)      # one upload: coordinates, polygon and mask offsets
     d_xy, d_off = dev[:xy.size].view(torch.float64), dev[xy.size:]
@@ -333,33 +336,47 @@ def segmentation_bits(segs, device, size=None):
     return bits, area
 
 
+def iou_views(dt_views, gt_views, device, crowd=None, polygons: bool = False, size=None, decode: bool = True):
+    """Decode and IoU for V views in one set of launches: dt_views / gt_views are per view the lists of prediction and GT
+    segmentations (all of one image size), crowd per view the GT iscrowd flags or None (crowd=None: no crowd anywhere).  All masks are
+    decoded once (decode_bits, or with polygons=True segmentation_bits at `size`), the three rows of exclusive offsets - predictions,
+    GT, IoU blocks - travel in one upload (the crowd flags with them), one nopesac_mask_iou_bits launch takes every block.  Returns
+    (iou float64 [sum n_dt n_gt] on the device, the offsets int64 [3, V + 1] on the device, the same on the host, the bits with the
+    predictions' rows first).  decode=False: only the offsets; iou is empty and bits None.  No host sync besides the decode's."""
+    device = torch.device(device)
+    n_dt, n_gt = [len(d) for d in dt_views], [len(g) for g in gt_views]
+    offs = np.stack([exclusive_offsets(n_dt), exclusive_offsets(n_gt), exclusive_offsets(np.multiply(n_dt, n_gt))])
+    flags = np.zeros(0, np.uint8) if crowd is None else np.concatenate([np.zeros(k, np.uint8) if c is None else np.asarray(c, bool).astype(np.uint8)
+                                                                        for c, k in zip(crowd, n_gt)])
+    packed = np.concatenate([offs.reshape(-1), np.concatenate([flags, np.zeros(-flags.size % 8, np.uint8)]).view(np.int64)])
+    dev = torch.from_numpy(packed).to(device)                            # one upload: the three offset rows and the crowd flags
+    d_off, d_crowd = dev[:offs.size].view(3, -1), None if crowd is None else dev[offs.size:].view(torch.uint8)[:flags.size]
+    if not decode:
+        return torch.zeros(0, device=device, dtype=torch.float64), d_off, offs, None
+    segs = [s for d in dt_views for s in d] + [s for g in gt_views for s in g]
+    bits, area = segmentation_bits(segs, device, size=size) if polygons else decode_bits(segs, device)
+    nd = int(offs[0, -1])
+    iou, _ = ops.mask_iou_bits(bits[:nd], area[:nd], d_off[0], bits[nd:], area[nd:], d_off[1], d_crowd, d_off[2], int(offs[2, -1]),
+                               max(n_dt), max(n_gt))
+    return iou, d_off, offs, bits
+
+
 def iou_device_views(views, device) -> List[np.ndarray]:
     """rle.iou for many views at once: views = [(dt RLEs, gt RLEs, iscrowd or None)] -> [len(dt), len(gt)] float64 matrices, bit
     for bit those of iou().  All masks of one image size go through ONE upload per kind, one decode and one nopesac_mask_iou_bits
-    launch, whatever the number of views; one copy back.  A GT entry may also be a polygon list (segmentation_bits; the size is the
-    predictions'); a view without predictions or without GT is never decoded."""
-    device = torch.device(device)
+    launch, whatever the number of views (iou_views); one copy back.  A GT entry may also be a polygon list (segmentation_bits; the
+    size is the predictions'); a view without predictions or without GT is never decoded."""
     out = [np.zeros((len(v[0]), len(v[1])), np.float64) for v in views]
     by_size = {}
     for k, (dt, gt, _) in enumerate(views):
         if len(dt) and len(gt):
             by_size.setdefault(tuple(int(s) for s in dt[0]["size"]), []).append(k)
     for ks in by_size.values():
-        n_dt, n_gt = [len(views[k][0]) for k in ks], [len(views[k][1]) for k in ks]
-        bits, area = segmentation_bits([r for k in ks for r in views[k][0]] + [r for k in ks for r in views[k][1]], device)
-        offs = np.zeros((3, len(ks) + 1), np.int64)
-        np.cumsum(n_dt, out=offs[0, 1:]); np.cumsum(n_gt, out=offs[1, 1:]); np.cumsum(np.multiply(n_dt, n_gt), out=offs[2, 1:])
-        crowd = np.concatenate([np.zeros(len(views[k][1]), np.uint8) if views[k][2] is None else np.asarray(views[k][2], bool).astype(np.uint8)
-                                for k in ks])
-        packed = np.concatenate([offs.reshape(-1), np.concatenate([crowd, np.zeros(-crowd.size % 8, np.uint8)]).view(np.int64)])
-        dev = torch.from_numpy(packed).to(device)                        # one upload: the three offset rows and the crowd flags
-        d_off, d_crowd = dev[:offs.size].view(3, -1), dev[offs.size:].view(torch.uint8)[:crowd.size]
-        nd = int(offs[0, -1])
-        m, _ = ops.mask_iou_bits(bits[:nd], area[:nd], d_off[0], bits[nd:], area[nd:], d_off[1], d_crowd, d_off[2], int(offs[2, -1]),
-                                 max(n_dt), max(n_gt))
+        dts, gts, crowds = zip(*(views[k] for k in ks))
+        m, _, offs, _ = iou_views(dts, gts, device, crowd=crowds, polygons=True)
         m = m.cpu().numpy()
         for j, k in enumerate(ks):
-            out[k] = m[offs[2, j]:offs[2, j + 1]].reshape(n_dt[j], n_gt[j])
+            out[k] = m[offs[2, j]:offs[2, j + 1]].reshape(len(views[k][0]), len(views[k][1]))
     return out
 
 

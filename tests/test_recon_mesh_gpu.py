@@ -17,6 +17,8 @@ from oracle import rle_oracle as R
 from tests import poly_reference as PR
 from tests import recon_mesh_inputs as MI
 from tests import recon_mesh_ref as REF
+from tests.plane_eval_inputs import _rotate
+from tests.recon_eval_inputs import FLIP, _camera, _local_in_view0
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +86,34 @@ def test_negdot_follows_the_stated_rule(device):
         g0, g1 = REF.global_params(got["planes"][:n0], p["camera"]), REF.global_params(got["planes"][n0:], REF.IDENTITY)
         before0, before1 = REF.global_params(p["views"][0]["planes"], p["camera"]), REF.global_params(p["views"][1]["planes"], REF.IDENTITY)
         assert np.abs(g0[a] - g1[b]).max() <= 1e-9 and g0[a] @ before0[a] > 0 and g1[b] @ before1[b] < 0
+
+
+@pytest.mark.parametrize("seed,qscale", ((41, 1.0), (42, 1.0), (43, 1.0), (44, 1.0), (41, 1.7)))
+def test_merge_axis_aligned_planes_and_zero_components(device, seed, qscale):
+    """Floors and walls seen from an upright camera: view 1's planes have components that are exactly zero (one of them -0.0), which
+    no seeded case has; the identity view takes them without a rotation.  ops.recon_mesh_merge alone, no masks.  View 0's planes
+    0..2 are view 1's seen from the camera, turned by 1 to 8 degrees (n0 . n1 >= 0.99, far from DOT_MARGIN) and shifted by at most 0.1."""
+    from nopesac_amd import ops
+    rng = np.random.default_rng(seed)
+    cam = _camera(rng)
+    p1 = np.array([[0, 0, 2], [1.5, 0, 0], [0, -2.5, 0], [0, 3, -0.0]], np.float32)
+    p0 = []
+    for k in range(3):
+        p, _ = _local_in_view0(p1[k].astype(np.float64) * FLIP, cam)
+        off = np.linalg.norm(p)
+        p0.append(_rotate(p / off, rng.uniform(1.0, 8.0), rng) * (off + rng.uniform(-0.1, 0.1)))
+    p0 = np.asarray(p0 + [[0.0, 0.0, 1.25]], np.float32)
+    camera = {"position": cam["position"], "rotation": cam["rotation"] * qscale}
+    corrs = np.array([[0, 0], [1, 1], [2, 2]], np.int32)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731
+    merged, bad = ops.recon_mesh_merge(dev(np.concatenate([p0, p1])), dev(np.array([0, 4, 8], np.int64)),
+                                       dev(np.concatenate([camera["position"], camera["rotation"]])[None]), dev(corrs.reshape(-1)),
+                                       dev(np.array([0, 3], np.int64)), 4)
+    assert bad.tolist() == [0]
+    err = np.abs(merged.cpu().numpy() - np.concatenate(REF.merged_local_planes(p0, p1, camera, corrs))).max(1)
+    print(f"seed {seed}, qscale {qscale}: merged planes within {err[[0, 1, 2, 4, 5, 6]].max():.3g}, unmatched within {err[[3, 7]].max():.3g}")
+    assert err[[0, 1, 2, 4, 5, 6]].max() <= 1e-9                              # the merged planes, both views
+    assert err[[3, 7]].max() <= 1e-9                                          # the unmatched ones come back
 
 
 def _special_masks(h, w):
