@@ -1019,6 +1019,9 @@ nps_status nopesac_transpose_batched_f32(const float* x, int B, int rows, int co
  * nopesac_attention_small_backward: gradient of nopesac_attention_small (head dim 32, Lq, Lk <= 128) at q / k / v for the output gradient
  *   d_out; every matrix is row-major with its own row stride (elements), so column slices of a [rows, 768] q|k|v buffer are taken as
  *   they are.  The softmax is recomputed.  Rows >= qlen[b] get zero dq; keys >= klen[b] get zero dk / dv and take no part in the softmax.
+ *   qlen / klen may be null (every row / key is live) and are clamped to [0, Lq] / [0, Lk].  A set with klen[b] == 0 gets zero dq on every
+ *   row, a set with qlen[b] == 0 zero dk / dv on every key.  All Lq (Lk) rows of every set are written, heads * 32 values each: with a
+ *   row stride above heads * 32 the rest of a row is left as it was.
  * nopesac_layernorm_backward: y = LayerNorm(x) gamma + beta over D = 256 -> dx [rows, D], dgamma [D], dbeta [D]; ws holds per-block
  *   partials of the two column reductions (nopesac_layernorm_backward_workspace_floats(rows) floats), reduced in a fixed order.
  * nopesac_matcher_sinkhorn_train: the couplings and the iters log-Sinkhorn iterations of nopesac_matcher_sinkhorn without the
@@ -1026,12 +1029,17 @@ nps_status nopesac_transpose_batched_f32(const float* x, int B, int rows, int co
  *   (< n1, nq) x columns (< n2, nq) are ignored).  Outputs: log_scores; uv [B, iters, 2, nq+1] = every iteration's potentials (compact
  *   indices, dustbin at n1 / n2) for the backward pass; pair_stats [B, 2] = (sum of -min(score, 0) over the pair's selected entries,
  *   their count); loss [2] = (2 * sum / count over the WHOLE batch - 0 when nothing is selected -, count).  Pairs with n1 == 0 or
- *   n2 == 0 select nothing and get log_scores = -1e30 everywhere.
+ *   n2 == 0 select nothing and get log_scores = -1e30 everywhere.  The dustbin corner (nq, nq) is a live entry: a gt_corr bit there is
+ *   counted.  uv is written at the compact indices 0 .. n1 (u) and 0 .. n2 (v) only: entries beyond them, and every entry of a pair with
+ *   n1 == 0 or n2 == 0, are left as they were.  iters == 0: log_scores = couplings - norm, uv has no element and may be null.
  * nopesac_matcher_emb_loss: pair_stats and loss as above from log scores that already exist (the output of nopesac_matcher_sinkhorn):
  *   the training forward runs the inference kernel itself, so its scores are the inference head's bit for bit, and the potentials
  *   are produced by nopesac_matcher_sinkhorn_train as a replay when the backward pass starts.
  * nopesac_matcher_sinkhorn_train_backward: gradient of loss[0] (times g_loss[0], a device scalar) through the UNROLLED iterations ->
  *   d_desc_dot [B, nq, nq] (zero outside the live block) and d_bin_pairs [B] (per-pair partials of d bin_score; sum them in order).
+ *   Every element of both is written.  They are exactly zero for a pair with n1 == 0 or n2 == 0, for a pair none of whose selected
+ *   scores is <= 0, and for every pair when loss[1] (the batch's count) is 0.  iters == 0: d_desc_dot = -2 g_loss / count on the
+ *   selected entries with a score <= 0.
  * nopesac_desc_dot_backward: dots = D0 D1^T / 16 per pair (D = 256) -> dD0 = G D1 / 16, dD1 = G^T D0 / 16 over the live block, zero rows
  *   beyond n1 / n2.
  * nopesac_layernorm_backward_workspace_floats returns a size (a value; 0 for rows <= 0, never negative). */

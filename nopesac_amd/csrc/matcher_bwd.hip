@@ -9,7 +9,8 @@
 //       runs as a replay when the backward pass starts;
 //   (4) descriptor dot backward (dots = D0 D1^T / 16 per pair).
 // Everything is f32 and deterministic: no atomics, every reduction has a fixed order (wave shuffles, LDS partials summed by index, per-pair
-// partials reduced by nopesac_col_sum_f32).  Gated against float64 torch.autograd on the oracle (tests/test_matcher_training_gpu.py).
+// partials reduced by nopesac_col_sum_f32).  Gated per element against float64 VJPs (tests/matcher_bwd_forms.py, docs/kernels.md) and, as a
+// whole head, against float64 torch.autograd on the oracle (tests/test_matcher_training_gpu.py).
 #include "common.h"
 
 namespace nps {
@@ -20,9 +21,11 @@ constexpr float MB_NEG_PAD = -1e30f;
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (1) attention backward.  One workgroup per (set, head), 256 threads; L, S <= 128.  q (pre-scaled), k, v, dO of the (set, head) are staged
-// in LDS once.  Phase 1: threads (2 i, 2 i + 1) own query row i and split the keys by parity - row max, row sum and O (to form
-// delta_i = dO_i . O_i), then dq_i = scale * sum_j dS_ij k_j with dS_ij = P_ij (dO_i . v_j - delta_i); the two halves meet in one
-// shuffle.  Phase 2: threads (2 j, 2 j + 1) own key j and split the queries by parity: dv_j = sum_i P_ij dO_i, dk_j = sum_i dS_ij
+// in LDS once.  Phase 1: threads (2 i, 2 i + 1) own query row i and split the keys by parity - row max, row sum and
+// delta_i = sum_j P_ij (dO_i . v_j), then dq_i = scale * sum_j dS_ij k_j with dS_ij = P_ij (dO_i . v_j - delta_i); the two halves meet in
+// one shuffle.  (delta_i is formed from the same dO_i . v_j that dS_ij subtracts it from, not as dO_i . O_i: on a peaked row
+// dS_ij = P_ij (dp_ij - delta_i) cancels, and the rounding of dO_i . O_i - two sums of 32 products that need not be small where their
+// difference is - was up to 1.9 x the sweep's per-element bound on dq; a single live key gives dS = 0 exactly.)  Phase 2: threads (2 j, 2 j + 1) own key j and split the queries by parity: dv_j = sum_i P_ij dO_i, dk_j = sum_i dS_ij
 // (scale q_i), P_ij recomputed from the row statistics of phase 1 (same operations in the same order: the same bits).  The sums over
 // queries run inside this one workgroup in index order.
 __global__ __launch_bounds__(256) void attention_small_bwd_kernel(
@@ -76,25 +79,21 @@ __global__ __launch_bounds__(256) void attention_small_bwd_kernel(
         }
         m = fmaxf(m, __shfl_xor(m, 1, 64));
         if (!(m > -INFINITY)) m = 0.f;                   // nk == 0 (or one key and the empty half): keep the arithmetic finite
-        float l = 0.f;
+        float l = 0.f, dsum = 0.f;
         for (int j = half; j < nk; j += 2) {
-            float s = 0.f;
+            float s = 0.f, dp = 0.f;
 #pragma unroll
-            for (int d = 0; d < MB_HD; ++d) s = fmaf(qr[d], Ks[j * MB_LS + d], s);
+            for (int d = 0; d < MB_HD; ++d) {
+                s = fmaf(qr[d], Ks[j * MB_LS + d], s);
+                dp = fmaf(gr[d], Vs[j * MB_LS + d], dp);
+            }
             const float p = expf(s - m);
             l += p;
-#pragma unroll
-            for (int d = 0; d < MB_HD; ++d) acc[d] = fmaf(p, Vs[j * MB_LS + d], acc[d]);
+            dsum = fmaf(p, dp, dsum);
         }
         l += __shfl_xor(l, 1, 64);
         const float il = l > 0.f ? 1.f / l : 0.f;
-        float delta = 0.f;
-#pragma unroll
-        for (int d = 0; d < MB_HD; ++d) {
-            const float o = (acc[d] + __shfl_xor(acc[d], 1, 64)) * il;
-            delta = fmaf(gr[d], o, delta);
-            acc[d] = 0.f;
-        }
+        const float delta = (dsum + __shfl_xor(dsum, 1, 64)) * il;
         for (int j = half; j < nk; j += 2) {
             float s = 0.f, dp = 0.f;
 #pragma unroll
