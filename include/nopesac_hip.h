@@ -1142,6 +1142,34 @@ nps_status nopesac_plane_losses_backward(const nopesac_plane_criterion* a, void*
 nps_status nopesac_plane_corr_matrix(const int32_t* gt_corrs, int K, const int32_t* match1, const int32_t* match2, int B, int nq, int nmax,
                                      uint8_t* out, void* stream);
 
+/* ---- backward of the plane head's instance heads (csrc/plane_head_bwd.hip; nopesac_amd/training.py::PlaneInstanceHeadsTrainer) ----------
+ * The folded mask logits M[l,b,q,p] = sum_k F[l,b,q,k] p1[b,p,k] + beta[l,b,q] of L <= 3 supervised decoder layers (F = E W_pe,
+ * beta = E . b_pe: the pixel-embedding map is never materialised) and, joined as two more rows per image whose weights the batch
+ * shares, the 256 -> 2 pixel-centre conv Z[b,c,p] = sum_k wc[c,k] p1[b,p,k] + bc[c].  All f32, exact-f32 MFMA, deterministic (no
+ * atomics); C must be 256, nq in [1, 128], L in [1, 3]; argument errors -> NPS_E_ARG before any launch.
+ *  d_logits  dM [L*B][nq][h*w], pixel-minor and dense (what nopesac_plane_losses_backward writes for a contiguous [L*B,nq,h,w] input);
+ *  d_center  dZ [B][2][h*w], the gradient at the centre map IN FRONT of its sigmoid (nopesac_sigmoid_backward_f32), or null: no centre rows
+ *            (then d_wc / d_bc / wc are null too);
+ *  p1 / d_p1 [B][h*w][256] NHWC, pixel-dense: batch stride = h*w * pixel stride, pixel stride >= 256 (a channel slice of a wider buffer);
+ *            p1 16-byte aligned with a pixel stride % 4 == 0;
+ *  fold      F rows [L*B*nq][256] with row stride fold_ld (% 4 == 0, 16-byte aligned), row order (l, b, q); wc [2][256] dense.
+ * mask_product_wgrad: d_fold[(l,b,q)][k] = sum_p dM p1 (row stride d_fold_ld), d_beta[(l,b,q)] = sum_p dM (element stride d_beta_stride),
+ *            d_wc[c][k] = sum_b sum_p dZ p1, d_bc[c] = sum_b sum_p dZ.  Per image a GEMM (M = L nq + 2, N = 256, K = h w) split into
+ *            `splits` pixel ranges (1..1024; ranges beyond the map are empty) whose partial tiles go to ws - at least
+ *            NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS(L, B, nq, center_rows = 0 or 2, splits) floats: per range, image and row 256
+ *            partial sums and the row's own sum - and are summed in split order, the shared rows over the images in order.
+ * mask_product_dgrad: d_p1[b][p][k] = sum_{l,q} dM F + sum_c dZ wc, written once (M = h w, N = 256, K = L nq + 2 per image).
+ * sigmoid_backward: out = g y (1 - y) for the output y of a sigmoid, n elements. */
+#define NPS_MASK_PRODUCT_WS_ROW_FLOATS 257
+#define NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS(L, B, nq, center_rows, splits) ((int64_t)(splits) * (B) * ((int64_t)(L) * (nq) + (center_rows)) * NPS_MASK_PRODUCT_WS_ROW_FLOATS)
+nps_status nopesac_mask_product_wgrad_f32(const float* d_logits, const float* d_center, const float* p1, float* d_fold, int64_t d_fold_ld,
+                                          float* d_beta, int64_t d_beta_stride, float* d_wc, float* d_bc, float* ws, int64_t ws_floats, int L,
+                                          int B, int nq, int h, int w, int C, int64_t p1_pstride, int64_t p1_bstride, int splits, void* stream);
+nps_status nopesac_mask_product_dgrad_f32(const float* d_logits, const float* d_center, const float* fold, int64_t fold_ld, const float* wc,
+                                          float* d_p1, int L, int B, int nq, int h, int w, int C, int64_t dp1_pstride, int64_t dp1_bstride,
+                                          void* stream);
+nps_status nopesac_sigmoid_backward_f32(const float* g, const float* y, int64_t n, float* out, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

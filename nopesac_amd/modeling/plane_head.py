@@ -4,7 +4,8 @@ transformer/position_encoding.py) + fused plane post-selection (meta_arch/siames
 Token matrices are batch-major [B*L, 256] fp32.  Per encoder layer: 4 GEMMs (fused q|k projection, v,
 out-proj with the residual in the epilogue, 2 FFN GEMMs with ReLU / residual epilogues), 1 attention
 launch, 2 LayerNorm launches (which also emit `x + pos` for the next layer's q/k).  Only the last decoder
-layer's heads are evaluated (the reference's deep-supervision outputs are training-only).
+layer's heads are evaluated (the reference's deep-supervision outputs are training-only: `training_inputs`
+hands the supervised decoder outputs and the pixel decoder's map to training.PlaneInstanceHeadsTrainer).
 """
 from __future__ import annotations
 
@@ -109,6 +110,7 @@ class PlaneTRHead(ParamModule):
         H = cfg.MODEL.SEM_SEG_HEAD
         self.num_queries = H.NUM_OBJECT_QUERIES
         self.nheads = H.NHEADS
+        self.deep_supervision = bool(H.DEEP_SUPERVISION)
         assert H.HIDDEN_DIM == 256 and H.MASK_DIM == 256 and H.NHEADS == 8 and H.ENC_LAYERS == 6 and H.DEC_LAYERS == 6, \
             "PlaneTRHead kernels are specialised to hidden 256 / 8 heads / 6+6 layers (config/config.py:46-51)"
         assert H.PARAM_ON and H.CENTER_ON and not cfg.MODEL.DEPTH_ON, "inference configs set PARAM_ON/CENTER_ON, no depth"
@@ -195,6 +197,15 @@ class PlaneTRHead(ParamModule):
             hs, memory = self._transformer_bf16(src, pos, B, L, nq, nh, scale, mark)
             mark("ph.decoder")
             return self._heads(features, hs, memory, B, hc, wc, nq, want_logits, mark)
+        hs, memory, _ = self._transformer_f32(src, pos, B, L, nq, nh, scale, mark)
+        return self._heads(features, hs, memory, B, hc, wc, nq, want_logits, mark)
+
+    def _transformer_f32(self, src, pos, B, L, nq, nh, scale, mark, gd=None, inter_from=6):
+        """The encoder / decoder with f32 activations (weights in `gd`, default the head's GEMM dtype) -> (hs [B*nq, 256], memory, inter):
+        inter = context2plane_decoder.norm of the outputs of the decoder layers inter_from .. 5 (transformer.py:114-153 with
+        return_intermediate), the last of which is hs itself."""
+        P, gd = self.packed, (self.gemm_dtype if gd is None else gd)
+        mf = gd == torch.bfloat16
         q_in = ops.add_rows(src, pos)
         # ---- encoder (post-norm; transformer.py:183-199)
         for i in range(6):
@@ -212,7 +223,8 @@ class PlaneTRHead(ParamModule):
         mark("ph.encoder")
         # ---- decoder (pre-norm; transformer.py:293-322), only hs[-1] is needed at inference
         qpos = self.raw("query_embed.weight")
-        tgt = torch.zeros(B * nq, 256, device=c4.device, dtype=torch.float32)
+        tgt = torch.zeros(B * nq, 256, device=src.device, dtype=torch.float32)
+        inter = []
         for i in range(6):
             p = f"context2plane_decoder.layers.{i}"
             W = P[p]
@@ -230,9 +242,11 @@ class PlaneTRHead(ParamModule):
             t2 = self._ln(tgt, p + ".norm3")
             hdn = ops.linear(t2, W["l1"].w2d(gd), W["l1"].bias, act=ops.ACT_RELU)
             tgt = ops.linear(hdn, W["l2"].w2d(gd), W["l2"].bias, residual=tgt)
+            if inter_from <= i < 5:
+                inter.append(self._ln(tgt, "context2plane_decoder.norm"))
         hs = self._ln(tgt, "context2plane_decoder.norm")             # [B*nq, 256]
         mark("ph.decoder")
-        return self._heads(features, hs, memory, B, hc, wc, nq, want_logits, mark)
+        return hs, memory, inter + [hs]
 
     def _enc_tail_weights(self, i: int) -> dict:
         cache = self.__dict__.setdefault("_enc_tail_w", {})
@@ -388,8 +402,9 @@ class PlaneTRHead(ParamModule):
                         "gn": f(next_norm + ".weight"), "ben": f(next_norm + ".bias")}
         return cache[i]
 
-    def _heads(self, features, hs, memory, B, hc, wc, nq, want_logits, mark):
-        P, gd = self.packed, self.gemm_dtype
+    def _pyramid(self, features, memory, B, hc, wc, gd):
+        """The top-down pyramid down to p2 (planeTR_head.py:241-249) -> (p2, cbr, up_stage): the two stage functions finish it (p1)."""
+        P = self.packed
         c1, c2, c3, c4 = features["res2"], features["res3"], features["res4"], features["res5"]
         cd = c4.dtype
         # ---- top-down pyramid (planeTR_head.py:241-252): lateral + relu(bn(conv(up(.))))
@@ -412,6 +427,34 @@ class PlaneTRHead(ParamModule):
 
         p3 = up_stage(p4, "up_conv3", cbr(c3, "c3_conv"))
         p2 = up_stage(p3, "up_conv2", cbr(c2, "c2_conv"))
+        return p2, cbr, up_stage
+
+    def training_inputs(self, features: dict):
+        """The two tensors where the head's trunk ends, for training.PlaneInstanceHeadsTrainer: (hs [L, B, nq, 256] f32, p1 [B, h, w, 256]
+        f32 NHWC at res2 resolution).  hs[i] = context2plane_decoder.norm of the output of decoder layer 3 + i with
+        SEM_SEG_HEAD.DEEP_SUPERVISION (L = 3: the reference's hs[-3:], planeTR_head.py:140), else the last layer alone (L = 1); p1 = the
+        pixel decoder's p_context.  Runs the f32 route (f32 weights and activations, whatever the head's inference dtypes) without autograd."""
+        f32 = torch.float32
+        with torch.no_grad():
+            feats = {k: features[k].float().contiguous() for k in ("res2", "res3", "res4", "res5")}
+            c4 = feats["res5"]
+            B, hc, wc, _ = c4.shape
+            L, nq = hc * wc, self.num_queries
+            mark = lambda name: None
+            ip = self.packed["input_proj"]
+            src = ops.conv2d(c4, ip.w(f32), None, ip.bias, out_dtype=f32).view(B * L, 256)
+            layers = 3 if self.deep_supervision else 1
+            _, memory, inter = self._transformer_f32(src, self._pos(hc, wc, c4.device), B, L, nq, self.nheads, 32 ** -0.5, mark, gd=f32,
+                                                     inter_from=6 - layers)
+            p2, cbr, up_stage = self._pyramid(feats, memory, B, hc, wc, f32)
+            p1 = up_stage(p2, "up_conv1", cbr(feats["res2"], "c1_conv"))
+            return torch.stack(inter[-layers:]).view(layers, B, nq, 256), p1
+
+    def _heads(self, features, hs, memory, B, hc, wc, nq, want_logits, mark):
+        P, gd = self.packed, self.gemm_dtype
+        c1, c2, c3, c4 = features["res2"], features["res3"], features["res4"], features["res5"]
+        cd = c4.dtype
+        p2, cbr, up_stage = self._pyramid(features, memory, B, hc, wc, gd)
         # plane embedding MLP [B*nq, 256] -> folded mask-head operands [B*nq, 264]: mask weights | bias | pad
         # ... and the three small heads on the same rows: five stacks, one launch in bf16 GEMM mode
         if gd == torch.bfloat16 and hs.dtype == torch.float32:

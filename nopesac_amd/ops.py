@@ -2135,3 +2135,82 @@ def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torc
     out = torch.empty(B, nq + 1, nq + 1, device=gt_corrs.device, dtype=torch.uint8)
     _C.nopesac_plane_corr_matrix(_p(gt_corrs), K, _p(match1), _p(match2), B, nq, match1.shape[1], _p(out), _stream())
     return out
+
+
+# ---------------------------------------------------------------- backward of the plane head's instance heads (csrc/plane_head_bwd.hip)
+def sigmoid_backward(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """g y (1 - y) for the output y of a sigmoid and its gradient g."""
+    _chk(g, torch.float32)
+    _sized(y, torch.float32, g.numel(), "sigmoid_backward: y")
+    out = torch.empty_like(g)
+    _C.nopesac_sigmoid_backward_f32(_p(g), _p(y), g.numel(), _p(out), _stream())
+    return out
+
+
+def mask_product_splits(L: int, B: int, nq: int, hw: int, center_rows: int = 0) -> int:
+    """Pixel-range count of mask_product_backward's wgrad launch: about 512 workgroups over the (128-row tile, image) pairs, at least
+    256 pixels per range."""
+    tiles = -(-(L * nq + center_rows) // 128) * B
+    return max(1, min(64, -(-512 // tiles), hw // 256))
+
+
+def mask_product_workspace_floats(L: int, B: int, nq: int, center_rows: int, splits: int) -> int:
+    """The header's NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS: the wgrad launch's partial tiles."""
+    return splits * B * (L * nq + center_rows) * _H.NPS_MASK_PRODUCT_WS_ROW_FLOATS
+
+
+def mask_product_backward(d_logits: torch.Tensor, fold: torch.Tensor, p1: torch.Tensor, d_center: Optional[torch.Tensor] = None,
+                          w_center: Optional[torch.Tensor] = None, *, splits: Optional[int] = None, d_fold: Optional[torch.Tensor] = None,
+                          d_beta: Optional[torch.Tensor] = None, which: str = "both"):
+    """Backward of the folded mask product M[l,b,q,p] = sum_k fold[l,b,q,k] p1[b,p,k] + beta[l,b,q] (+ the 256 -> 2 pixel-centre conv
+    Z = w_center p1 + b_center joined as two shared rows per image).  d_logits [L, B, nq, h, w] f32 contiguous (pixel-minor: what
+    plane_losses_backward returns for a contiguous input), fold = the L*B*nq rows [.., 256] (unit column stride, rows may be a column
+    slice of a wider matrix), p1 [B, h, w, 256] pixel-dense NHWC (may be a channel slice), d_center [B, 2, h, w] = the gradient in
+    front of the centre map's sigmoid with w_center [2, 256], or both None
+    -> (d_fold [L, B, nq, 256], d_beta [L, B, nq], d_p1 [B, h, w, 256]) and, with the centre rows, (+ d_w_center [2, 256], d_b_center [2]).
+    d_fold / d_beta: optional outputs (column slices of one wider gradient matrix).  which = "wgrad" / "dgrad": only that launch (the
+    other outputs are None).  Two launches + the fixed-order reduction; the partial tiles live in the cached per-device workspace."""
+    _chk(d_logits, torch.float32)
+    _chk(p1, torch.float32, contiguous=False)
+    _require(d_logits.dim() == 5 and p1.dim() == 4, "mask_product_backward: d_logits [L,B,nq,h,w], p1 [B,h,w,256]")
+    _require(which in ("both", "wgrad", "dgrad"), which)
+    L, B, nq, h, w = d_logits.shape
+    _require(p1.shape[:3] == (B, h, w) and p1.stride(3) == 1 and p1.stride(1) == w * p1.stride(2),
+             "mask_product_backward: p1 [B,h,w,C] with unit channel stride and dense rows; got %s, strides %s" % (tuple(p1.shape), tuple(p1.stride())))
+    C = p1.shape[3]
+    rows = L * B * nq
+    _chk(fold, torch.float32, contiguous=False)
+    fold2 = fold.reshape(rows, fold.shape[-1]) if fold.dim() != 2 else fold
+    fold_ld = _rows(fold2, rows, C, "mask_product_backward: fold")
+    _require(fold2.shape[1] == C, "mask_product_backward: fold must have %d columns" % C)
+    _require((d_center is None) == (w_center is None), "mask_product_backward: d_center and w_center go together")
+    extra = 0
+    if d_center is not None:
+        _sized(d_center, torch.float32, B * 2 * h * w, "mask_product_backward: d_center")
+        _sized(w_center, torch.float32, 2 * C, "mask_product_backward: w_center")
+        extra = 2
+    dev = p1.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    out_f = out_b = d_p1 = d_wc = d_bc = None
+    if which != "dgrad":
+        out_f = torch.empty(L, B, nq, C, **f32) if d_fold is None else d_fold
+        out_b = torch.empty(L, B, nq, **f32) if d_beta is None else d_beta
+        of2 = out_f.view(rows, C) if out_f.dim() != 2 else out_f
+        ob = out_b.view(rows) if out_b.dim() != 1 else out_b
+        of_ld = _rows(of2, rows, C, "mask_product_backward: d_fold")
+        _chk(ob, torch.float32, contiguous=False)
+        _require(ob.shape == (rows,) and ob.stride(0) >= 1, "mask_product_backward: d_beta")
+        if extra:
+            d_wc, d_bc = torch.empty(2, C, **f32), torch.empty(2, **f32)
+        S = int(splits or mask_product_splits(L, B, nq, h * w, extra))
+        n_ws = mask_product_workspace_floats(L, B, nq, extra, S)
+        ws = wgrad_workspace(dev, 4 * max(n_ws, 1))
+        _C.nopesac_mask_product_wgrad_f32(_p(d_logits), _p(d_center), _p(p1), _p(of2), of_ld, _p(ob), ob.stride(0), _p(d_wc), _p(d_bc), _p(ws),
+                                          ws.numel(), L, B, nq, h, w, C, p1.stride(2), p1.stride(0), S, _stream())
+    if which != "wgrad":
+        d_p1 = torch.empty(B, h, w, C, **f32)
+        _C.nopesac_mask_product_dgrad_f32(_p(d_logits), _p(d_center), _p(fold2), fold_ld, _p(w_center), _p(d_p1), L, B, nq, h, w, C,
+                                          d_p1.stride(2), d_p1.stride(0), _stream())
+    if extra:
+        return out_f, out_b, d_p1, d_wc, d_bc
+    return out_f, out_b, d_p1

@@ -26,12 +26,18 @@ decoder layer run on the device (csrc/plane_criterion.hip) with no host round tr
 outputs (class logits, low-resolution mask logits, centres, parameters, the pixel centre map) come back through one autograd Function.
 plane_corr_matrix turns the match of both views into the gt_corr MatchingHeadTrainer.matching_losses takes.
 
-What this is NOT: a trainer for the whole network.  The backbone and the plane head's transformer / mask head have no backward kernels here -
-the criterion's gradients stop at the head's outputs; the backbone maps, the plane sets and their appearance features are inputs of the
-other stages, as they are of the reference functions, and receive no gradient beyond `input_grads`; the assignment between the matcher and
-the camera head is discrete and carries none.  Gated against torch.autograd on the oracle (tests/test_training_gpu.py,
-tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py) and against a float64 restatement pinned to the reference
-(tests/test_plane_criterion_gpu.py)."""
+The plane head's instance heads (planeTR_head.py:146-192: plane_embedding, pixel_embedding, plane_prob, plane_param, plane_center,
+pixel_plane_center - 24 tensors) are trained against that criterion by PlaneInstanceHeadsTrainer, under deep supervision: its inputs are
+the two tensors where the head's trunk ends (PlaneTRHead.training_inputs: the supervised decoder outputs hs and the pixel decoder's map
+p1), its forward makes the inference head's f32 launches for every supervised layer (the mask logits in folded form: the pixel-embedding
+map is never materialised), and the backward of the mask product is the two MFMA launches of csrc/plane_head_bwd.hip.
+
+What this is NOT: a trainer for the whole network.  The backbone and the plane head's trunk (its transformer and top-down pyramid) have no
+backward kernels here - the instance heads' gradients stop at hs and p1 (`input_grads`, ready for a trunk backward to chain onto); the
+backbone maps, the plane sets and their appearance features are inputs of the other stages, as they are of the reference functions, and
+receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
+against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py)
+and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -623,16 +629,21 @@ class RefineTrainer:
         """One optimiser step with the reference's solver settings (Trainer.build_optimizer, train_NopeSAC.py:88-169): SOLVER.OPTIMIZER
         (ADAMW / SGD), BASE_LR, WEIGHT_DECAY, MOMENTUM, CLIP_GRADIENTS (CLIP_TYPE "full_model": global-norm clipping in front of the
         step).  GroupNorm / BatchNorm affine tensors (held with CameraHeadTrainer(conv_stacks=True)) use WEIGHT_DECAY_NORM, as the
-        reference's norm module types do; the per-module multipliers (BACKBONE / SEM_SEG_HEAD / PLANE_MATCHER_HEAD) and the embedding
-        weight decay apply to modules this trainer does not hold."""
+        reference's norm module types do; the learning rate carries `lr_multiplier(cfg)`, the per-module multiplier of the module a
+        trainer holds (SEM_SEG_HEAD for PlaneInstanceHeadsTrainer; BACKBONE / PLANE_MATCHER_HEAD and the embedding weight decay apply
+        to modules no trainer here holds)."""
         S = cfg.SOLVER
         cg = S.CLIP_GRADIENTS
         if cg.ENABLED and cg.CLIP_TYPE == "full_model" and cg.CLIP_VALUE > 0.0:
             self.clip_grad_norm(float(cg.CLIP_VALUE))
         elif cg.ENABLED:
             raise NotImplementedError("SOLVER.CLIP_GRADIENTS.CLIP_TYPE %r (the reference's configs use full_model)" % (cg.CLIP_TYPE,))
-        self.step(lr=float(S.BASE_LR), optimizer=str(S.OPTIMIZER), weight_decay=float(S.WEIGHT_DECAY), momentum=float(S.MOMENTUM),
-                  weight_decay_norm=float(S.WEIGHT_DECAY_NORM))
+        self.step(lr=float(S.BASE_LR) * self.lr_multiplier(cfg), optimizer=str(S.OPTIMIZER), weight_decay=float(S.WEIGHT_DECAY),
+                  momentum=float(S.MOMENTUM), weight_decay_norm=float(S.WEIGHT_DECAY_NORM))
+
+    def lr_multiplier(self, cfg) -> float:
+        """The reference's per-module learning-rate multiplier of the module this trainer holds (train_NopeSAC.py:122-129); 1 here."""
+        return 1.0
 
     def write_back(self, head):
         """Copy the trained parameters into the inference head (its packed / bf16 copies are rebuilt on the next forward)."""
@@ -1029,6 +1040,175 @@ class PlaneCriterion:
             src, order = torch.sort(mq[b, :nb])
             out.append((src, order))
         return out
+
+
+# ---- the plane head's instance heads -----------------------------------------------------------------------------------------------------
+PLANE_PREFIX = "sem_seg_head."
+PLANE_INSTANCE_HEADS = ("plane_embedding", "pixel_embedding", "plane_prob", "plane_param", "plane_center", "pixel_plane_center")
+FOLD_WIDTH = 264                       # the folded mask operand's row: 256 mask weights | the mask bias | 7 zero columns (PlaneTRHead.pack)
+
+
+class _LinearSigmoid(torch.autograd.Function):
+    """y = sigmoid(x W^T + b), the sigmoid in the GEMM's epilogue as the inference head has it; backward: that of _Linear behind
+    ops.sigmoid_backward."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x = x.contiguous()
+        y = ops.linear(x, w, b, act=ops.ACT_SIGMOID)
+        ctx.save_for_backward(x, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, y = ctx.saved_tensors
+        g = ops.sigmoid_backward(g.contiguous(), y)
+        gx = ops.linear(g, transpose(w)) if ctx.needs_input_grad[0] else None
+        gw = ops.linear(transpose(g), transpose(x)) if ctx.needs_input_grad[1] else None
+        gb = col_sum(g) if ctx.needs_input_grad[2] else None
+        return gx, gw, gb
+
+
+class _MaskProduct(torch.autograd.Function):
+    """(fold [L*B*nq, 264] = mask weights | mask bias | pad, rows in (l, b, q) order; p1 [B, h, w, 256]; the pixel-centre conv's weight
+    [2, 256, 1, 1] and bias) -> (mask logits [L, B, nq, h, w], pixel centres [B, 2, h, w]).  Forward: per layer the batched-weights f32
+    conv the inference head launches (PlaneTRHead._heads) and its 256 -> 2 sigmoid conv; the NHWC results are stacked into the
+    pixel-minor layout the criterion works in.  Backward: ops.mask_product_backward - one wgrad and one dgrad launch of
+    csrc/plane_head_bwd.hip, the centre conv joined to both as two more rows, so p1's gradient is written once."""
+
+    @staticmethod
+    def forward(ctx, fold, p1, wc, bc, L: int, B: int, nq: int):
+        fold = fold.contiguous()
+        per = []
+        for l in range(L):
+            blk = fold[l * B * nq:(l + 1) * B * nq]
+            mw = blk[:, :256].contiguous().view(B, nq, 1, 1, 256)
+            mb = blk[:, 256].contiguous().view(B, nq)
+            per.append(ops.conv2d(p1, mw, None, mb, batched_weights=True, out_dtype=torch.float32).permute(0, 3, 1, 2))
+        masks = torch.stack(per)
+        pc = ops.conv2d(p1, _ohwi(wc, 256), None, bc.detach().contiguous(), act=ops.ACT_SIGMOID, out_dtype=torch.float32)
+        pc = pc.permute(0, 3, 1, 2).contiguous()
+        ctx.dims = (L, B, nq, p1.shape[1], p1.shape[2])
+        ctx.save_for_backward(fold, p1, wc, pc)
+        return masks, pc
+
+    @staticmethod
+    def backward(ctx, g_masks, g_pc):
+        fold, p1, wc, pc = ctx.saved_tensors
+        L, B, nq, h, w = ctx.dims
+        g_masks = torch.zeros(L, B, nq, h, w, device=p1.device) if g_masks is None else g_masks.contiguous()
+        dz = ops.sigmoid_backward(torch.zeros_like(pc) if g_pc is None else g_pc.contiguous(), pc)
+        g_fold = torch.zeros_like(fold)
+        _, _, d_p1, d_wc, d_bc = ops.mask_product_backward(g_masks, fold[:, :256], p1, dz, wc.detach().view(2, 256), d_fold=g_fold[:, :256],
+                                                           d_beta=g_fold[:, 256], which="both" if ctx.needs_input_grad[1] else "wgrad")
+        return g_fold, d_p1, d_wc.view_as(wc), d_bc, None, None, None
+
+
+class PlaneInstanceHeadsTrainer(RefineTrainer):
+    """The plane head's instance heads in TRAINING mode (reference PlaneTRHead.forward, planeTR_head.py:146-192, under deep supervision):
+    the 24 tensors of plane_embedding, pixel_embedding, plane_prob, plane_param, plane_center and pixel_plane_center, held under their
+    state-dict keys (`sem_seg_head. ...`).  The head's trunk is frozen: its two outputs enter as inputs.
+
+        hs, p1 = model.sem_seg_head.training_inputs(features)           # [L, B, nq, 256], [B, h, w, 256] (no autograd)
+        tr = PlaneInstanceHeadsTrainer.from_head(model.sem_seg_head)    # or .from_state_dict(sd, nq, device)
+        losses, indices = tr.losses(hs, p1, targets)                    # PlaneCriterion.from_cfg on the deep-supervision outputs
+        grads = tr.backward(losses)                                     # the criterion's weights; tr.input_grads["hs" / "p1"] on request
+        tr.step_from_cfg(cfg); tr.write_back(model.sem_seg_head)
+
+    The mask logits are evaluated in the folded form of the inference head, M = (E W_pe) . p1 + E . b_pe: W_pe^T and b_pe enter the fold's
+    Linear as autograd views of the two pixel_embedding leaves, so their gradients come back as slices of one wgrad.  Every launch of
+    the last layer is the launch PlaneTRHead.forward makes on its f32 route, so the same parameters give the same bits.
+    Optimiser groups (train_NopeSAC.py:88-135): none of the 24 tensors is a norm or an embedding parameter; the learning rate carries
+    SOLVER.SEM_SEG_HEAD_MULTIPLIER."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], nq: int, cfg=None):
+        super().__init__(params, nq)
+        if cfg is None:
+            from .config import get_cfg
+            cfg = get_cfg()
+        self.criterion = PlaneCriterion.from_cfg(cfg)
+        self._inputs: Dict[str, torch.Tensor] = {}
+        _require(len(self.params) == 24, "PlaneInstanceHeadsTrainer: 24 tensors expected, got %d" % len(self.params))
+
+    @staticmethod
+    def parameter_names(sd_keys) -> List[str]:
+        return sorted(k for k in sd_keys if k.startswith(PLANE_PREFIX) and k[len(PLANE_PREFIX):].split(".")[0] in PLANE_INSTANCE_HEADS)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, nq: int, device, cfg=None) -> "PlaneInstanceHeadsTrainer":
+        return cls({k: sd[k].to(device) for k in cls.parameter_names(sd.keys())}, nq, cfg)
+
+    @classmethod
+    def from_head(cls, head, cfg=None) -> "PlaneInstanceHeadsTrainer":
+        names = cls.parameter_names(PLANE_PREFIX + k for k in head._spec_keys)
+        return cls({k: head.raw(k[len(PLANE_PREFIX):]) for k in names}, head.num_queries, cfg)
+
+    def lr_multiplier(self, cfg) -> float:
+        return float(cfg.SOLVER.SEM_SEG_HEAD_MULTIPLIER)                 # train_NopeSAC.py:126-127
+
+    def write_back(self, head):
+        """Copy the trained tensors into the inference PlaneTRHead and drop its packed copies (pe_fold, which is derived from
+        pixel_embedding, among them: they are rebuilt on the next forward)."""
+        with torch.no_grad():
+            for k, p in self.params.items():
+                head.raw(k[len(PLANE_PREFIX):]).copy_(p)
+        head.invalidate()
+
+    # ---- forward
+    def _stack(self, x, name: str, sigmoid: bool = False):
+        """MLP (planeTR_head.py:194-206): ReLU between the layers, optionally a sigmoid behind the last one."""
+        P, q, i = self.params, PLANE_PREFIX + name, 0
+        while f"{q}.layers.{i + 1}.weight" in P:
+            x = _Linear.apply(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"], True)
+            i += 1
+        if sigmoid:
+            return _LinearSigmoid.apply(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"])
+        return _Linear.apply(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"], False)
+
+    def forward(self, hs: torch.Tensor, p1: torch.Tensor) -> dict:
+        """hs [L, B, nq, 256] (hs[i] = the normed output of decoder layer 6 - L + i), p1 [B, h, w, 256] pixel-dense NHWC -> the reference's
+        training dict: the last layer's pred_logits [B, nq, 2], pred_mask_logits [B, nq, h, w], pred_centers [B, nq, 2], pred_params
+        [B, nq, 3] and pixel_centers [B, 2, h, w], and for L > 1 aux_outputs = the same four of the layers 0 .. L - 2 - the last layer
+        first, the form PlaneCriterion takes.  Autograd tape attached."""
+        P, nq = self.params, self.nq
+        _require(hs.dim() == 4 and hs.shape[2] == nq and hs.shape[3] == 256 and 1 <= hs.shape[0] <= 3 and hs.dtype == torch.float32,
+                 "PlaneInstanceHeadsTrainer: hs [L <= 3, B, %d, 256] f32 expected, got %s" % (nq, tuple(hs.shape)))
+        L, B = hs.shape[:2]
+        _require(p1.dim() == 4 and p1.shape[0] == B and p1.shape[3] == 256 and p1.dtype == torch.float32,
+                 "PlaneInstanceHeadsTrainer: p1 [%d, h, w, 256] f32 expected, got %s" % (B, tuple(p1.shape)))
+        q = PLANE_PREFIX
+        x = hs.reshape(L * B * nq, 256)
+        emb = self._stack(x, "plane_embedding")
+        w_pe = P[q + "pixel_embedding.weight"].view(256, 256)
+        w_fold = torch.cat([w_pe.t(), P[q + "pixel_embedding.bias"].view(1, 256), w_pe.new_zeros(FOLD_WIDTH - 257, 256)], 0)
+        fold = _Linear.apply(emb, w_fold, None, False)
+        logits = _Linear.apply(x, P[q + "plane_prob.weight"], P[q + "plane_prob.bias"], False).view(L, B, nq, -1)
+        params = self._stack(x, "plane_param").view(L, B, nq, 3)
+        centers = self._stack(x, "plane_center", sigmoid=True).view(L, B, nq, 2)
+        masks, pixel_centers = _MaskProduct.apply(fold, p1, P[q + "pixel_plane_center.weight"], P[q + "pixel_plane_center.bias"], L, B, nq)
+        layer = lambda l: {"pred_logits": logits[l], "pred_mask_logits": masks[l], "pred_centers": centers[l], "pred_params": params[l]}
+        out = layer(L - 1)
+        out["pixel_centers"] = pixel_centers
+        if L > 1:
+            out["aux_outputs"] = [layer(l) for l in range(L - 1)]
+        return out
+
+    def losses(self, hs: torch.Tensor, p1: torch.Tensor, targets: dict, num_masks: Optional[float] = None):
+        """-> (losses, indices) of PlaneCriterion.from_cfg on forward(hs, p1), the autograd tape attached; hs / p1 may require grad (their
+        gradients land in `input_grads` after backward())."""
+        out = self.forward(hs, p1)
+        self._inputs = {"hs": hs, "p1": p1}
+        for t in self._inputs.values():
+            if t.requires_grad and not t.is_leaf:
+                t.retain_grad()
+        self.last = out
+        return self.criterion(out, targets, num_masks)
+
+    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+        """d (sum of the losses under criterion.weighted's weights, or under `loss_weights`) / d parameters -> {state-dict key: gradient}."""
+        if loss_weights is None:
+            return super().backward(self.criterion.weighted(losses))
+        return super().backward(losses, loss_weights)
 
 
 def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torch.Tensor, nq: int) -> torch.Tensor:
