@@ -1078,10 +1078,13 @@ nps_status nopesac_desc_dot_backward(const float* d_desc_dot, const float* d0, c
  *                [L*B, nq] = target of query q (-1 if unmatched);
  *   losses       losses [6 L + 2] unweighted: per layer (loss_ce, loss_mask, loss_dice, loss_center_ins, loss_param_l1, loss_param_cos),
  *                then loss_center_pixel and loss_q of the last layer; num_masks <= 0 means max(sum n, 1).  Kept for the backward pass:
- *                mask_stats [L*B, nmax, 4], q_valid uint8 [B, H, W], q_stats [B, 2];
+ *                mask_stats [L*B, nmax, 4] = (focal sum, sum sigmoid * t, sum sigmoid, sum t) of each matched mask at H x W (0 at
+ *                j >= n[b]), q_valid uint8 [B, H, W], q_stats [B, 2] = (sum, count) over the valid pixels; every element is written;
  *   gradients    g_losses [6 L + 2] (device) = one upstream scalar per loss; d_logits, d_centers, d_params in the shapes of the inputs,
- *                d_mask_logits and d_pixel_centers with the STRIDES of pred_mask_logits / pixel_centers.  Unmatched queries get exactly 0 in
- *                d_mask_logits, d_centers and d_params;
+ *                d_mask_logits and d_pixel_centers with the STRIDES of pred_mask_logits / pixel_centers: the strides need not be dense,
+ *                the gaps are neither read nor written.  Unmatched queries get exactly 0 in d_mask_logits, d_centers and d_params; a
+ *                centre (or centre-map pixel) at distance exactly 0 from its target gets the subgradient 0; an image without a valid
+ *                pixel adds nothing to loss_q or d_params;
  *   ws           nopesac_plane_criterion_workspace_floats(L, B, nq, nmax, h, w) floats, shared by the three entries (the loss entry's
  *                content must survive until its backward entry has run); the count is a value, 0 for a non-positive dimension
  *                (never negative). */
@@ -1124,14 +1127,19 @@ typedef struct nopesac_plane_criterion {
     int64_t ws_floats;
 } nopesac_plane_criterion;
 int64_t nopesac_plane_criterion_workspace_floats(int L, int B, int nq, int nmax, int h, int w);
-/* plane_centers [B, nmax, 2] = centroid of (x / W, y / H) over each mask (0 at j >= n[b]); pixel_centers [B, 2, H, W] = sum over planes of
- * centre * mask (prepare_targets, siamese_planeTR.py:498-504) */
+/* plane_centers [B, nmax, 2] = centroid of (x / W, y / H) over each mask (0 at j >= n[b]), computed in f64 from the exact integer sums
+ * as sum / W / count (two rounded divisions) and then rounded to f32; pixel_centers [B, 2, H, W] = the f32 sum over planes j < n[b], in plane order, of centre * mask (prepare_targets,
+ * siamese_planeTR.py:498-504).  An empty mask gives a NaN centre (the reference's 0 / 0); it covers no pixel, so the centre map stays finite. */
 nps_status nopesac_plane_targets(const uint8_t* masks, const int32_t* n_host, const int32_t* n, int B, int nmax, int H, int W, float* plane_centers,
                                  float* pixel_centers, void* stream);
 /* the matcher's seven-term cost matrix (class probability, focal and dice against the NEAREST-downsampled masks, centre L2, parameter L1,
  * normal angle in degrees, offset) -> a->cost */
 nps_status nopesac_plane_match_costs(const nopesac_plane_criterion* a, void* stream);
-/* rectangular linear sum assignment per image on the device (n[b] <= nq <= 128): shortest augmenting paths, one wave per image */
+/* rectangular linear sum assignment per image on the device (n[b] <= nq <= 128): shortest augmenting paths, one wave per image, duals in
+ * f64 (integer-valued costs up to 2^20 + small are matched exactly); ties go to an unmatched query first, then to the lowest index.  Only
+ * cost[i][q][j < n[b]] is read.  A query whose costs are all +inf is avoided.  A target whose costs are all +inf or NaN cannot be placed:
+ * the image keeps the matches of the targets before it, every later target gets match_q = -1 (match_gt accordingly), and the call
+ * returns; other images of the launch are not affected.  The loss entries need every target j < n[b] matched. */
 nps_status nopesac_plane_assign(const float* cost, const int32_t* n_host, const int32_t* n, int L, int B, int nq, int nmax, int32_t* match_q,
                                 int32_t* match_gt, void* stream);
 nps_status nopesac_plane_losses(const nopesac_plane_criterion* a, void* stream);

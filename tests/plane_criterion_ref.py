@@ -114,11 +114,12 @@ def _layer_losses(out, targets, tgt_centers, tgt_pixel, indices, wts, num_masks,
     return losses
 
 
-def criterion(outputs, targets, wts=DEFAULT_WEIGHTS, indices=None, num_masks=None):
+def criterion(outputs, targets, wts=DEFAULT_WEIGHTS, indices=None, num_masks=None, prepared=None):
     """-> (losses: the reference's names with _0, _1 for the auxiliary layers, unweighted; indices of every layer, last layer first;
-    float cost matrices of every layer).  `indices` (per layer) replaces the Hungarian match."""
+    float cost matrices of every layer).  `indices` (per layer) replaces the Hungarian match, `prepared` = (plane_centers, pixel_centers)
+    replaces prepare_targets (the values a kernel was handed)."""
     dtype = outputs["pred_logits"].dtype
-    tgt_centers, tgt_pixel = prepare_targets(targets["masks"], targets["n"], dtype)
+    tgt_centers, tgt_pixel = prepare_targets(targets["masks"], targets["n"], dtype) if prepared is None else prepared
     layers = [outputs] + list(outputs.get("aux_outputs", []))
     costs = [layer_costs(o, targets, tgt_centers, wts) for o in layers]
     if indices is None:

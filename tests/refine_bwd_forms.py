@@ -389,11 +389,16 @@ def term_magnitudes(family, x, aux, cots):
     return dict(zip(fam["leaves"], (s.detach() for s in S)))
 
 
+def jiggle(t, g):
+    """t in float64 with every element multiplied by 1 + d, d = +- 2^-23 with signs drawn from the generator g."""
+    return t.double() * (1 + EPS23 * (2.0 * torch.randint(0, 2, t.shape, generator=g).double() - 1))
+
+
 def conditioning(family, x, aux, cots, ref):
     """C_k: the largest change of the float64 VJP over DRAWS draws that multiply every f32 input by 1 + d, |d| <= 2^-23."""
     g = _g(77)
     C = {k: torch.zeros_like(v) for k, v in ref.items()}
-    jig = lambda t: t.double() * (1 + EPS23 * (2.0 * torch.randint(0, 2, t.shape, generator=g).double() - 1))      # d = +- 2^-23
+    jig = lambda t: jiggle(t, g)
     for _ in range(DRAWS):
         got = vjp(family, {k: jig(v) for k, v in x.items()}, dict(aux), [jig(t) for t in cots], F64)
         for k in C:
