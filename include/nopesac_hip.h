@@ -1178,6 +1178,40 @@ nps_status nopesac_mask_product_dgrad_f32(const float* d_logits, const float* d_
                                           void* stream);
 nps_status nopesac_sigmoid_backward_f32(const float* g, const float* y, int64_t n, float* out, void* stream);
 
+/* ---- training kernels of the plane head's transformer decoder (csrc/decoder_train.hip; nopesac_amd/training.py::PlaneDecoderTrainer) ----
+ * Dropout is counter based (csrc/dropout.h, docs/kernels.md): element `index` of the dropout site `stream` under `seed` is KEPT when the
+ * high 32 bits of mix64(index + mix64(stream + mix64(seed))) are >= floor(p 2^32); nothing is stored, every kernel recomputes the
+ * decision.  index = the row-major index in the LOGICAL tensor ([B, heads, Lq, Lk] for attention probabilities, [rows, D] for a matrix):
+ * it does not depend on tiles, strides or the launch.  p in [0, 1), else NPS_E_ARG; p == 0 keeps everything and skips the hash.
+ * Kept values are multiplied by (float)(1 / (1 - p)).  All f32, deterministic (no atomics).
+ * nopesac_dropout_keep_mask: out[i] = 1 if element i (0 <= i < n) is kept, else 0.
+ * nopesac_dropout_f32: y[i] = keep(i) ? x[i] / (1 - p) : 0, plus residual[i] when residual is not null; n = rows * D elements, dense.
+ *   Without a residual it is its own backward (x = the gradient at y).
+ * nopesac_attention_train_forward: nopesac_attention_small's contract (head dim 32, row strides, optional qlen / klen clamped to
+ *   [0, Lq] / [0, Lk], rows >= qlen[b] and sets with klen[b] == 0 written as zeros) for ANY Lq, Lk >= 1, tiled over the keys
+ *   (NPS_ATT_TRAIN_TK per tile through LDS, NPS_ATT_TRAIN_TQ query rows per workgroup) with an online softmax, and dropout on the
+ *   probabilities: O = (keep o softmax(S)) V / (1 - p).
+ * nopesac_attention_train_backward: its gradient at q / k / v for d_out, with the contract of nopesac_attention_small_backward (zero dq on
+ *   rows >= qlen[b], zero dk / dv on keys >= klen[b], every row written, heads * 32 values each).  Nothing of a forward launch is read:
+ *   a statistics kernel recomputes row max, 1 / row sum and D_i = sum_j P_ij dP_ij into ws (at least
+ *   NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS(B, heads, Lq) floats), a dq kernel (one workgroup per query
+ *   tile) and a dk / dv kernel (one per key tile) recompute P from them; the mask is regenerated from the counter. */
+#define NPS_ATT_TRAIN_TQ 64
+#define NPS_ATT_TRAIN_TK 64
+#define NPS_ATT_TRAIN_WS_ROW_FLOATS 3
+#define NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS(B, heads, Lq) ((int64_t)(B) * (heads) * (Lq) * NPS_ATT_TRAIN_WS_ROW_FLOATS)
+nps_status nopesac_dropout_keep_mask(uint8_t* out, int64_t n, double p, int64_t seed, int64_t stream_id, void* stream);
+nps_status nopesac_dropout_f32(const float* x, const float* residual, float* y, int64_t n, double p, int64_t seed, int64_t stream_id,
+                               void* stream);
+nps_status nopesac_attention_train_forward(const float* q, int64_t q_stride, const float* k, int64_t k_stride, const float* v, int64_t v_stride,
+                                           float* o, int64_t o_stride, int B, int Lq, int Lk, int heads, float scale, const int32_t* qlen,
+                                           const int32_t* klen, double p, int64_t seed, int64_t stream_id, void* stream);
+nps_status nopesac_attention_train_backward(const float* q, int64_t q_stride, const float* k, int64_t k_stride, const float* v, int64_t v_stride,
+                                            const float* d_out, int64_t do_stride, int B, int Lq, int Lk, int heads, float scale,
+                                            const int32_t* qlen, const int32_t* klen, double p, int64_t seed, int64_t stream_id, float* dq,
+                                            int64_t dq_stride, float* dk, int64_t dk_stride, float* dv, int64_t dv_stride, float* ws,
+                                            int64_t ws_floats, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

@@ -206,20 +206,7 @@ class PlaneTRHead(ParamModule):
         return_intermediate), the last of which is hs itself."""
         P, gd = self.packed, (self.gemm_dtype if gd is None else gd)
         mf = gd == torch.bfloat16
-        q_in = ops.add_rows(src, pos)
-        # ---- encoder (post-norm; transformer.py:183-199)
-        for i in range(6):
-            p = f"context_SA.layers.{i}"
-            W = P[p]
-            qk = ops.linear(q_in, W["attn"]["qk"].w2d(gd), W["attn"]["qk"].bias)
-            v = ops.linear(src, W["attn"]["v"].w2d(gd), W["attn"]["v"].bias)
-            o = ops.attention(qk[:, :256], qk[:, 256:], v, B, L, L, nh, scale, mfma_bf16=mf)
-            s = ops.linear(o, W["attn"]["o"].w2d(gd), W["attn"]["o"].bias, residual=src)
-            src = self._ln(s, p + ".norm1")
-            hdn = ops.linear(src, W["l1"].w2d(gd), W["l1"].bias, act=ops.ACT_RELU)
-            s = ops.linear(hdn, W["l2"].w2d(gd), W["l2"].bias, residual=src)
-            src, q_in = self._ln(s, p + ".norm2", addend=pos)
-        memory, mem_k = self._ln(src, "context_SA.norm", addend=pos)
+        memory, mem_k = self._encoder_f32(src, pos, B, L, nh, scale, gd)
         mark("ph.encoder")
         # ---- decoder (pre-norm; transformer.py:293-322), only hs[-1] is needed at inference
         qpos = self.raw("query_embed.weight")
@@ -247,6 +234,25 @@ class PlaneTRHead(ParamModule):
         hs = self._ln(tgt, "context2plane_decoder.norm")             # [B*nq, 256]
         mark("ph.decoder")
         return hs, memory, inter + [hs]
+
+    def _encoder_f32(self, src, pos, B, L, nh, scale, gd):
+        """The encoder half of _transformer_f32 -> (memory [B*L, 256], memory + pos)."""
+        P = self.packed
+        mf = gd == torch.bfloat16
+        q_in = ops.add_rows(src, pos)
+        # ---- encoder (post-norm; transformer.py:183-199)
+        for i in range(6):
+            p = f"context_SA.layers.{i}"
+            W = P[p]
+            qk = ops.linear(q_in, W["attn"]["qk"].w2d(gd), W["attn"]["qk"].bias)
+            v = ops.linear(src, W["attn"]["v"].w2d(gd), W["attn"]["v"].bias)
+            o = ops.attention(qk[:, :256], qk[:, 256:], v, B, L, L, nh, scale, mfma_bf16=mf)
+            s = ops.linear(o, W["attn"]["o"].w2d(gd), W["attn"]["o"].bias, residual=src)
+            src = self._ln(s, p + ".norm1")
+            hdn = ops.linear(src, W["l1"].w2d(gd), W["l1"].bias, act=ops.ACT_RELU)
+            s = ops.linear(hdn, W["l2"].w2d(gd), W["l2"].bias, residual=src)
+            src, q_in = self._ln(s, p + ".norm2", addend=pos)
+        return self._ln(src, "context_SA.norm", addend=pos)
 
     def _enc_tail_weights(self, i: int) -> dict:
         cache = self.__dict__.setdefault("_enc_tail_w", {})
@@ -449,6 +455,23 @@ class PlaneTRHead(ParamModule):
             p2, cbr, up_stage = self._pyramid(feats, memory, B, hc, wc, f32)
             p1 = up_stage(p2, "up_conv1", cbr(feats["res2"], "c1_conv"))
             return torch.stack(inter[-layers:]).view(layers, B, nq, 256), p1
+
+    def decoder_training_inputs(self, features: dict):
+        """The tensors where the head's FROZEN part ends when the decoder trains (training.PlaneDecoderTrainer): (memory [B*Lm, 256] f32,
+        the encoder's output; pos [Lm, 256], the sine position embedding the cross attention adds to its keys; p1 as training_inputs).
+        The encoder half and the pyramid of training_inputs, launch for launch, without autograd."""
+        f32 = torch.float32
+        with torch.no_grad():
+            feats = {k: features[k].float().contiguous() for k in ("res2", "res3", "res4", "res5")}
+            c4 = feats["res5"]
+            B, hc, wc, _ = c4.shape
+            ip = self.packed["input_proj"]
+            src = ops.conv2d(c4, ip.w(f32), None, ip.bias, out_dtype=f32).view(B * hc * wc, 256)
+            pos = self._pos(hc, wc, c4.device)
+            memory, _ = self._encoder_f32(src, pos, B, hc * wc, self.nheads, 32 ** -0.5, f32)
+            p2, cbr, up_stage = self._pyramid(feats, memory, B, hc, wc, f32)
+            p1 = up_stage(p2, "up_conv1", cbr(feats["res2"], "c1_conv"))
+            return memory, pos, p1
 
     def _heads(self, features, hs, memory, B, hc, wc, nq, want_logits, mark):
         P, gd = self.packed, self.gemm_dtype

@@ -2214,3 +2214,68 @@ def mask_product_backward(d_logits: torch.Tensor, fold: torch.Tensor, p1: torch.
     if extra:
         return out_f, out_b, d_p1, d_wc, d_bc
     return out_f, out_b, d_p1
+
+
+# ---------------------------------------------------------------- training kernels of the plane head's decoder (csrc/decoder_train.hip)
+ATT_TRAIN_TQ, ATT_TRAIN_TK = _H.NPS_ATT_TRAIN_TQ, _H.NPS_ATT_TRAIN_TK        # query rows per workgroup / keys per LDS tile
+
+
+def dropout_stream(step: int, layer: int, site: int) -> int:
+    """The counter stream of one dropout site of the decoder: step * 64 + layer * 8 + site, site 0 .. 5 = self-attention probabilities,
+    dropout1, cross-attention probabilities, dropout2, FFN inner, dropout3."""
+    _require(0 <= site < 6 and 0 <= layer < 8 and step >= 0, "dropout_stream: step >= 0, layer 0..7, site 0..5")
+    return int(step) * 64 + int(layer) * 8 + int(site)
+
+
+def dropout_keep_mask(shape, p: float, seed: int, stream: int, device=None) -> torch.Tensor:
+    """uint8 tensor of `shape`: 1 where the counter-based dropout (csrc/dropout.h) keeps the element of that row-major index at rate p
+    under (seed, stream), else 0 - the decision every kernel here recomputes, materialised.  p outside [0, 1) raises HipKernelError."""
+    shape = tuple(int(s) for s in shape)
+    out = torch.empty(shape, device=device if device is not None else torch.device("cuda", torch.cuda.current_device()), dtype=torch.uint8)
+    _C.nopesac_dropout_keep_mask(_p(out), out.numel(), float(p), int(seed), int(stream), _stream())
+    return out
+
+
+def dropout(x: torch.Tensor, p: float, seed: int, stream: int, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """keep ? x / (1 - p) : 0 [+ residual] on a dense f32 tensor, the element's row-major index as the counter.  Without a residual the
+    same call on the gradient is the backward."""
+    _chk(x, torch.float32)
+    if residual is not None:
+        _sized(residual, torch.float32, x.numel(), "dropout: residual")
+    y = torch.empty_like(x)
+    _C.nopesac_dropout_f32(_p(x), _p(residual), _p(y), x.numel(), float(p), int(seed), int(stream), _stream())
+    return y
+
+
+def attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, Lq: int, Lk: int, heads: int, scale: float, qlen=None, klen=None,
+                    *, p: float = 0.0, seed: int = 0, stream: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attention (f32, head dim 32) for any Lq, Lk, tiled over the keys, with dropout on the probabilities:
+    o = (keep o softmax(s)) v / (1 - p), keep from the counter at the index in [B, heads, Lq, Lk].  q / k / v / out may be column slices."""
+    W = heads * 32
+    sq, sk, sv = _rows(q, B * Lq, W, "attention_train: q"), _rows(k, B * Lk, W, "attention_train: k"), _rows(v, B * Lk, W, "attention_train: v")
+    _lengths(qlen, B, "attention_train: qlen"); _lengths(klen, B, "attention_train: klen")
+    o = torch.empty(B * Lq, W, device=q.device, dtype=torch.float32) if out is None else out
+    so = _rows(o, B * Lq, W, "attention_train: out")
+    _C.nopesac_attention_train_forward(_p(q), sq, _p(k), sk, _p(v), sv, _p(o), so, B, Lq, Lk, heads, float(scale), _p(qlen), _p(klen), float(p),
+                                       int(seed), int(stream), _stream())
+    return o
+
+
+def attention_train_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_out: torch.Tensor, B: int, Lq: int, Lk: int, heads: int,
+                             scale: float, qlen=None, klen=None, *, p: float = 0.0, seed: int = 0, stream: int = 0, out=None):
+    """Backward of attention_train (and, at p = 0, of attention) for any Lq, Lk: -> (dq, dk, dv).  Softmax statistics and the dropout mask
+    are recomputed; nothing of the forward launch is needed.  Strides as attention_backward."""
+    W = heads * 32
+    sq, sk, sv = (_rows(q, B * Lq, W, "attention_train_backward: q"), _rows(k, B * Lk, W, "attention_train_backward: k"),
+                  _rows(v, B * Lk, W, "attention_train_backward: v"))
+    sg = _rows(d_out, B * Lq, W, "attention_train_backward: d_out")
+    _lengths(qlen, B, "attention_train_backward: qlen"); _lengths(klen, B, "attention_train_backward: klen")
+    if out is None:
+        out = tuple(torch.empty(rows, W, device=q.device, dtype=torch.float32) for rows in (B * Lq, B * Lk, B * Lk))
+    dq, dk, dv = out
+    so = [_rows(t, rows, W, "attention_train_backward: out") for t, rows in ((dq, B * Lq), (dk, B * Lk), (dv, B * Lk))]
+    ws = torch.empty(B * heads * Lq * _H.NPS_ATT_TRAIN_WS_ROW_FLOATS, device=q.device, dtype=torch.float32)     # the header's NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS
+    _C.nopesac_attention_train_backward(_p(q), sq, _p(k), sk, _p(v), sv, _p(d_out), sg, B, Lq, Lk, heads, float(scale), _p(qlen), _p(klen),
+                                        float(p), int(seed), int(stream), _p(dq), so[0], _p(dk), so[1], _p(dv), so[2], _p(ws), ws.numel(),
+                                        _stream())
+    return dq, dk, dv

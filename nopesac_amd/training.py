@@ -32,12 +32,18 @@ the two tensors where the head's trunk ends (PlaneTRHead.training_inputs: the su
 p1), its forward makes the inference head's f32 launches for every supervised layer (the mask logits in folded form: the pixel-embedding
 map is never materialised), and the backward of the mask product is the two MFMA launches of csrc/plane_head_bwd.hip.
 
-What this is NOT: a trainer for the whole network.  The backbone and the plane head's trunk (its transformer and top-down pyramid) have no
-backward kernels here - the instance heads' gradients stop at hs and p1 (`input_grads`, ready for a trunk backward to chain onto); the
+The plane head's transformer decoder (planeTR_head.py:88, transformer/transformer.py:114-153, 293-322: six pre-norm layers with
+dropout 0.1, the final norm, query_embed - 111 tensors) is trained by PlaneDecoderTrainer: it takes the instance heads' gradient at hs
+(backward_from, or chained through one graph by losses / backward), runs the inference head's own launches at p = 0 and, at p > 0, the
+kernels of csrc/decoder_train.hip - attention with dropout on the probabilities for any key count and its recomputing backward, and
+element-wise dropout whose mask is a counter-based function of (seed, step, layer, site, element index) that is never stored.
+
+What this is NOT: a trainer for the whole network.  The backbone, the plane head's encoder and its top-down pyramid have no backward
+kernels here - the gradients stop at the encoder memory and p1 (`input_grads`, ready for a trunk backward to chain onto); the
 backbone maps, the plane sets and their appearance features are inputs of the other stages, as they are of the reference functions, and
 receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
 against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py)
-and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py)."""
+and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -594,7 +600,7 @@ class RefineTrainer:
         for k, p in self.params.items():
             if p.grad is None:
                 continue
-            wd = weight_decay if weight_decay_norm is None or not is_norm_parameter(k) else weight_decay_norm
+            wd = self._weight_decay(k, weight_decay, weight_decay_norm)
             g = p.grad.contiguous()
             st = self.state.setdefault(k, {})
             with torch.no_grad():
@@ -609,6 +615,10 @@ class RefineTrainer:
                     ops.sgd_step(p, g, st["mom"], lr, momentum, wd, first)
                 else:
                     raise NotImplementedError(f"no optimizer type {optimizer}")           # train_NopeSAC.py:158
+
+    def _weight_decay(self, key: str, weight_decay: float, weight_decay_norm: Optional[float]) -> float:
+        """The decay of one tensor's optimiser group."""
+        return weight_decay if weight_decay_norm is None or not is_norm_parameter(key) else weight_decay_norm
 
     def clip_grad_norm(self, max_norm: float) -> torch.Tensor:
         """torch.nn.utils.clip_grad_norm_ over ALL parameters of this trainer (the reference's FullModelGradientClippingOptimizer,
@@ -1209,6 +1219,264 @@ class PlaneInstanceHeadsTrainer(RefineTrainer):
         if loss_weights is None:
             return super().backward(self.criterion.weighted(losses))
         return super().backward(losses, loss_weights)
+
+
+class _LinearRes(torch.autograd.Function):
+    """y = x W^T + b + residual with the residual in the GEMM's epilogue, as the inference head launches it; backward: that of _Linear,
+    and the residual's gradient is the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, residual):
+        x = x.contiguous()
+        y = ops.linear(x, w, b, residual=residual.contiguous())
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g = g.contiguous()
+        gx = ops.linear(g, transpose(w)) if ctx.needs_input_grad[0] else None
+        gw = ops.linear(transpose(g), transpose(x)) if ctx.needs_input_grad[1] else None
+        gb = col_sum(g) if ctx.needs_input_grad[2] else None
+        return gx, gw, gb, (g if ctx.needs_input_grad[3] else None)
+
+
+class _LayerNormPair(torch.autograd.Function):
+    """(y, y + addend) of one ops.layernorm launch, the addend [rows_a, 256] broadcast over the rows / rows_a sets (the decoder's query
+    embedding).  Backward: ops.layernorm_backward on the sum of the two incoming gradients; the addend's gradient is the second one summed
+    over the sets (ops.col_sum, fixed order)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, addend):
+        x, addend = x.contiguous(), addend.contiguous()
+        ctx.save_for_backward(x, gamma)
+        ctx.a_shape = tuple(addend.shape)
+        return ops.layernorm(x, gamma, beta, addend=addend, eps=LN_EPS)
+
+    @staticmethod
+    def backward(ctx, g_y, g_y2):
+        x, gamma = ctx.saved_tensors
+        dx, dgamma, dbeta = ops.layernorm_backward(x, gamma, (g_y + g_y2).contiguous(), LN_EPS)
+        d_add = None
+        if ctx.needs_input_grad[3]:
+            n = ctx.a_shape[0] * ctx.a_shape[1]
+            d_add = col_sum(g_y2.contiguous().view(-1, n)).view(ctx.a_shape)
+        return dx, dgamma, dbeta, d_add
+
+
+class _AddRows(torch.autograd.Function):
+    """a + b with b [rows_b, D] broadcast over blocks of rows_b rows and constant (the sine position embedding on the encoder memory)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        return ops.add_rows(a.contiguous(), b.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+class _DecoderAttention(torch.autograd.Function):
+    """Attention of the decoder (f32, head dim 32, any Lq / Lk).  Forward at p = 0: ops.attention, the inference head's own launch; at
+    p > 0: ops.attention_train, dropout on the probabilities.  Backward: ops.attention_train_backward either way - it recomputes the
+    softmax statistics and the mask, so it needs nothing from the forward launch."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, B: int, Lq: int, Lk: int, heads: int, scale: float, p: float, seed: int, stream: int):
+        if p == 0.0:
+            o = ops.attention(q, k, v, B, Lq, Lk, heads, scale)
+        else:
+            o = ops.attention_train(q, k, v, B, Lq, Lk, heads, scale, p=p, seed=seed, stream=stream)
+        ctx.conf = (B, Lq, Lk, heads, float(scale), float(p), int(seed), int(stream))
+        ctx.save_for_backward(q, k, v)
+        return o
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v = ctx.saved_tensors
+        B, Lq, Lk, heads, scale, p, seed, stream = ctx.conf
+        dq, dk, dv = ops.attention_train_backward(q, k, v, g.contiguous(), B, Lq, Lk, heads, scale, p=p, seed=seed, stream=stream)
+        return dq, dk, dv, None, None, None, None, None, None, None, None
+
+
+class _Dropout(torch.autograd.Function):
+    """keep ? x / (1 - p) : 0 [+ residual] (ops.dropout, the mask from the counter); backward: the same kernel on the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, residual, p: float, seed: int, stream: int):
+        ctx.conf = (float(p), int(seed), int(stream))
+        return ops.dropout(x.contiguous(), p, seed, stream, residual=None if residual is None else residual.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        gx = ops.dropout(g, *ctx.conf) if ctx.needs_input_grad[0] else None
+        return gx, (g if ctx.needs_input_grad[1] else None), None, None, None
+
+
+DECODER = "context2plane_decoder"
+DECODER_LAYERS, DECODER_HEADS = 6, 8
+DROP_SELF_ATTN, DROP_1, DROP_CROSS_ATTN, DROP_2, DROP_FFN, DROP_3 = range(6)         # the dropout sites of a layer (ops.dropout_stream)
+
+
+class PlaneDecoderTrainer(RefineTrainer):
+    """The plane head's transformer decoder in TRAINING mode (reference: transformer/transformer.py:114-153, 293-322 as planeTR_head.py:88
+    builds it - six pre-norm layers, dropout 0.1, return_intermediate): the 111 tensors of context2plane_decoder (per layer
+    self_attn / multihead_attn in_proj + out_proj, linear1, linear2, norm1-3; the final norm) and query_embed.weight, held under their
+    state-dict keys.  The encoder, the pyramid and the backbone stay frozen: the encoder's output enters as an input.
+
+        memory, pos, p1 = model.sem_seg_head.decoder_training_inputs(features)     # [B*Lm, 256], [Lm, 256], [B, h, w, 256] (no autograd)
+        dec = PlaneDecoderTrainer.from_head(model.sem_seg_head)                    # or .from_state_dict(sd, nq, device)
+        hs = dec.forward(memory, pos, B, p=0.1, seed=seed, step=it)                # [L, B, nq, 256], autograd tape attached
+        dec.backward_from(d_hs)                                                    # .grads, .input_grads["memory"]
+      or, chained in front of the instance heads and the criterion:
+        heads = PlaneInstanceHeadsTrainer.from_head(model.sem_seg_head)
+        losses, indices = dec.losses(heads, memory, pos, p1, targets, p=0.1, seed=seed, step=it)
+        dec.backward(losses); dec.step_from_cfg(cfg); heads.step_from_cfg(cfg)
+
+    At p = 0 every launch of the forward is the launch PlaneTRHead._transformer_f32 makes on its f32 route, so the same parameters give
+    PlaneTRHead.training_inputs' hs bit for bit.  At p > 0 the six dropout sites of every layer are active (attention probabilities
+    inside ops.attention_train, the three residual branches and the FFN's hidden layer through ops.dropout); the masks are functions of
+    (seed, step * 64 + layer * 8 + site, element index) and are recomputed by the backward kernels, never stored.  in_proj_weight / bias
+    are one leaf each: their q | k rows and v rows enter the Linears as autograd views.  query_embed is the broadcast addend of norm1 and
+    norm2; its gradient is summed over the batch.  Optimiser groups (train_NopeSAC.py:88-135): the LayerNorm tensors take
+    WEIGHT_DECAY_NORM, query_embed (an nn.Embedding) WEIGHT_DECAY_EMBED, and the learning rate carries SOLVER.SEM_SEG_HEAD_MULTIPLIER."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], nq: int, deep_supervision: bool = True):
+        super().__init__(params, nq)
+        self.layers_out = 3 if deep_supervision else 1
+        self.weight_decay_embed: Optional[float] = None
+        self.grads: Dict[str, torch.Tensor] = {}
+        self._inputs: Dict[str, torch.Tensor] = {}
+        self._hs = self._heads = None
+        _require(len(self.params) == 18 * DECODER_LAYERS + 3, "PlaneDecoderTrainer: 111 tensors expected, got %d" % len(self.params))
+        _require(self.params[PLANE_PREFIX + "query_embed.weight"].shape == (self.nq, 256), "PlaneDecoderTrainer: query_embed.weight [nq, 256]")
+
+    @staticmethod
+    def parameter_names(sd_keys) -> List[str]:
+        return sorted(k for k in sd_keys if k.startswith(PLANE_PREFIX + DECODER + ".") or k == PLANE_PREFIX + "query_embed.weight")
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, nq: int, device, deep_supervision: bool = True) -> "PlaneDecoderTrainer":
+        return cls({k: sd[k].to(device) for k in cls.parameter_names(sd.keys())}, nq, deep_supervision)
+
+    @classmethod
+    def from_head(cls, head) -> "PlaneDecoderTrainer":
+        names = cls.parameter_names(PLANE_PREFIX + k for k in head._spec_keys)
+        return cls({k: head.raw(k[len(PLANE_PREFIX):]) for k in names}, head.num_queries, head.deep_supervision)
+
+    def lr_multiplier(self, cfg) -> float:
+        return float(cfg.SOLVER.SEM_SEG_HEAD_MULTIPLIER)
+
+    def _weight_decay(self, key: str, weight_decay: float, weight_decay_norm: Optional[float]) -> float:
+        leaf = key.split(".")[-2]
+        if leaf == "query_embed":
+            return weight_decay if self.weight_decay_embed is None else self.weight_decay_embed
+        if leaf in ("norm", "norm1", "norm2", "norm3"):
+            return weight_decay if weight_decay_norm is None else weight_decay_norm
+        return weight_decay
+
+    def step_from_cfg(self, cfg):
+        self.weight_decay_embed = float(cfg.SOLVER.WEIGHT_DECAY_EMBED)
+        super().step_from_cfg(cfg)
+
+    def write_back(self, head):
+        """Copy the trained tensors into the inference PlaneTRHead and drop its packed copies (rebuilt on the next forward)."""
+        with torch.no_grad():
+            for k, p in self.params.items():
+                head.raw(k[len(PLANE_PREFIX):]).copy_(p)
+        head.invalidate()
+
+    # ---- forward
+    def forward(self, memory: torch.Tensor, pos: torch.Tensor, B: int, p: float = 0.0, seed: int = 0, step: int = 0) -> torch.Tensor:
+        """memory [B*Lm, 256] f32 (the encoder's output, rows in (b, token) order), pos [Lm, 256] -> hs [L, B, nq, 256]: the final norm of
+        the outputs of the last L decoder layers (L = 3 under deep supervision, else 1), autograd tape attached.  p: the dropout rate
+        (0 = the inference head's launches), seed / step: the counter's seed and the training step the masks are drawn for."""
+        P, nq, nh = self.params, self.nq, DECODER_HEADS
+        p = float(p)
+        _require(memory.dim() == 2 and memory.shape[1] == 256 and memory.dtype == torch.float32 and B > 0 and memory.shape[0] % B == 0,
+                 "PlaneDecoderTrainer: memory [B*Lm, 256] f32 expected, got %s" % (tuple(memory.shape),))
+        Lm = memory.shape[0] // B
+        _require(tuple(pos.shape) == (Lm, 256) and pos.dtype == torch.float32, "PlaneDecoderTrainer: pos [%d, 256] f32 expected, got %s" % (Lm, tuple(pos.shape)))
+        mem = memory if memory.requires_grad else memory.detach().requires_grad_(True)
+        if not mem.is_leaf:
+            mem.retain_grad()
+        self._inputs = {"memory": mem}
+        mem_k = _AddRows.apply(mem, pos.detach())
+        scale = 32 ** -0.5
+        qpos = P[PLANE_PREFIX + "query_embed.weight"]
+        site = lambda i, s: ops.dropout_stream(step, i, s)
+        att = lambda q, k, v, Lk, i, s: _DecoderAttention.apply(q, k, v, B, nq, Lk, nh, scale, p, int(seed), site(i, s))
+
+        def out_proj(o, w, b, tgt, i, s):              # tgt + dropout(o W^T + b)
+            if p == 0.0:
+                return _LinearRes.apply(o, w, b, tgt)
+            return _Dropout.apply(_Linear.apply(o, w, b, False), tgt, p, int(seed), site(i, s))
+
+        tgt = torch.zeros(B * nq, 256, device=memory.device, dtype=torch.float32)
+        norm = (P[f"{PLANE_PREFIX}{DECODER}.norm.weight"], P[f"{PLANE_PREFIX}{DECODER}.norm.bias"])
+        inter = []
+        for i in range(DECODER_LAYERS):
+            q = f"{PLANE_PREFIX}{DECODER}.layers.{i}."
+            w, b = P[q + "self_attn.in_proj_weight"], P[q + "self_attn.in_proj_bias"]
+            t2, q_in = _LayerNormPair.apply(tgt, P[q + "norm1.weight"], P[q + "norm1.bias"], qpos)
+            qk = _Linear.apply(q_in, w[:512], b[:512], False)
+            v = _Linear.apply(t2, w[512:], b[512:], False)
+            o = att(qk[:, :256], qk[:, 256:], v, nq, i, DROP_SELF_ATTN)
+            tgt = out_proj(o, P[q + "self_attn.out_proj.weight"], P[q + "self_attn.out_proj.bias"], tgt, i, DROP_1)
+            w, b = P[q + "multihead_attn.in_proj_weight"], P[q + "multihead_attn.in_proj_bias"]
+            t2, q_in = _LayerNormPair.apply(tgt, P[q + "norm2.weight"], P[q + "norm2.bias"], qpos)
+            qc = _Linear.apply(q_in, w[:256], b[:256], False)
+            kc = _Linear.apply(mem_k, w[256:512], b[256:512], False)
+            vc = _Linear.apply(mem, w[512:], b[512:], False)
+            o = att(qc, kc, vc, Lm, i, DROP_CROSS_ATTN)
+            tgt = out_proj(o, P[q + "multihead_attn.out_proj.weight"], P[q + "multihead_attn.out_proj.bias"], tgt, i, DROP_2)
+            t2 = _LayerNorm.apply(tgt, P[q + "norm3.weight"], P[q + "norm3.bias"], None)
+            hdn = _Linear.apply(t2, P[q + "linear1.weight"], P[q + "linear1.bias"], True)
+            if p != 0.0:
+                hdn = _Dropout.apply(hdn, None, p, int(seed), site(i, DROP_FFN))
+            tgt = out_proj(hdn, P[q + "linear2.weight"], P[q + "linear2.bias"], tgt, i, DROP_3)
+            if i >= DECODER_LAYERS - self.layers_out:
+                inter.append(_LayerNorm.apply(tgt, norm[0], norm[1], None))
+        self._hs = torch.stack(inter).view(self.layers_out, B, nq, 256)
+        return self._hs
+
+    # ---- backward
+    def _clear_grads(self):
+        for t in self.params.values():
+            t.grad = None
+        for t in self._inputs.values():
+            if t.is_leaf:
+                t.grad = None
+
+    def _collect(self) -> Dict[str, torch.Tensor]:
+        self.input_grads = {k: t.grad for k, t in self._inputs.items() if t.grad is not None}
+        self.grads = {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in self.params.items()}
+        return self.grads
+
+    def backward_from(self, d_hs: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The gradient at hs (what PlaneInstanceHeadsTrainer.input_grads["hs"] holds for the last forward's hs) -> {state-dict key:
+        gradient} of the 111 tensors (also `.grads`); `.input_grads["memory"]` = the gradient at the encoder memory, its value path and its
+        key path (mem_k = memory + pos, pos constant) summed."""
+        _require(self._hs is not None and tuple(d_hs.shape) == tuple(self._hs.shape), "PlaneDecoderTrainer.backward_from: d_hs like the last forward's hs")
+        self._clear_grads()
+        torch.autograd.backward(self._hs, d_hs.contiguous())
+        return self._collect()
+
+    def losses(self, heads: "PlaneInstanceHeadsTrainer", memory: torch.Tensor, pos: torch.Tensor, p1: torch.Tensor, targets: dict, p: float = 0.0,
+               seed: int = 0, step: int = 0, num_masks: Optional[float] = None):
+        """Decoder, then the instance heads, then their PlaneCriterion: -> (losses, indices) of heads.losses on this forward's hs."""
+        self._heads = heads
+        return heads.losses(self.forward(memory, pos, p1.shape[0], p, seed, step), p1, targets, num_masks)
+
+    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+        """The chain's backward: the instance heads' backward runs on through hs into the decoder.  -> the gradients of both trainers'
+        tensors by state-dict key (the heads' own stay readable as their parameters' .grad; `.grads` holds the decoder's)."""
+        _require(self._heads is not None, "PlaneDecoderTrainer.backward: call losses() first (backward_from takes a gradient at hs)")
+        self._clear_grads()
+        head_grads = self._heads.backward(losses, loss_weights)
+        return {**self._collect(), **head_grads}
 
 
 def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torch.Tensor, nq: int) -> torch.Tensor:
