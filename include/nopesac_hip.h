@@ -1212,6 +1212,38 @@ nps_status nopesac_attention_train_backward(const float* q, int64_t q_stride, co
                                             int64_t dq_stride, float* dk, int64_t dk_stride, float* dv, int64_t dv_stride, float* ws,
                                             int64_t ws_floats, void* stream);
 
+/* ---- training kernels of the plane head's top-down pyramid (csrc/pyramid_train.hip; training.PlanePyramidTrainer) ----------------------
+ * Training-mode BatchNorm (BATCH statistics, running-statistics update, backward) and the adjoint of the bilinear 2x upsampling.  f32,
+ * NHWC, deterministic (no atomics: per-block partials of NPS_BN_TRAIN_RPS rows in ws, finished in a fixed order).
+ * The three bn_train entry points take their input v in one of two forms: up = 0: v = src, [n = B H W][C] with channel stride
+ * src_cstride >= C (a matrix [rows][C] is B = rows, H = W = 1); up = 1: v = the bilinear 2x upsampling (align_corners = False, the
+ * values of nopesac_upsample2x_bilinear_nhwc bit for bit) of src [B][H][W][C], n = B 2H 2W rows, evaluated on the fly, never written.
+ * y, dy, addend and the plain form's dsrc are dense [n][C].  A thread works on four channels: C and src_cstride are multiples of 4 and
+ * every pointer is 16-byte aligned (else NPS_E_ARG; upsample2x_bilinear_backward too).  ws: at least NPS_BN_TRAIN_WORKSPACE_FLOATS(n, C) floats.
+ *  bn_train_stats:    mean, biased variance and rstd = 1 / sqrt(var + eps) per channel over the n values (per-block mean and centred
+ *                     sum of squares, merged by Chan's formula: never E[x^2] - E[x]^2).  running_mean / running_var (both or neither)
+ *                     are updated in place on the device: r <- (1 - momentum) r + momentum stat, the variance unbiased (n / (n - 1)).
+ *                     n < 2: NPS_E_ARG.
+ *  bn_train_apply:    y = act(gamma (v - mean) rstd + beta) (+ addend, AFTER the activation); act NPS_ACT_NONE or NPS_ACT_RELU.
+ *  bn_train_backward: dy, the same input, gamma, beta, mean, rstd -> dgamma = sum dz xhat, dbeta = sum dz (dz = dy where z > 0 under
+ *                     RELU) and dsrc: up = 0: dv = gamma rstd (dz - dbeta / n - xhat dgamma / n), [n][C]; up = 1: the gradient at src,
+ *                     up2^T(dv) [B][H][W][C] dense, dv evaluated inside the gather and never written.  batch_stats = 0: mean and rstd
+ *                     are stored statistics, constants of the backward: dv = gamma rstd dz (dgamma, dbeta as above).
+ *  upsample2x_bilinear_backward: du [B][2H][2W][C] -> dx [B][H][W][C] = up2^T(du), a gather over the at most 4 x 4 outputs an input
+ *                     feeds (per axis 0.25, 0.75, 0.75, 0.25; the clamped border taps folded back in). */
+#define NPS_BN_TRAIN_RPS 256
+#define NPS_BN_TRAIN_WORKSPACE_FLOATS(n, C) ((((int64_t)(n) + NPS_BN_TRAIN_RPS - 1) / NPS_BN_TRAIN_RPS) * 2 * (C))
+nps_status nopesac_bn_train_stats_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, float eps, float momentum,
+                                      float* mean, float* var, float* rstd, float* running_mean, float* running_var, float* ws,
+                                      int64_t ws_floats, void* stream);
+nps_status nopesac_bn_train_apply_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, const float* gamma,
+                                      const float* beta, const float* mean, const float* rstd, int act, const float* addend, float* y,
+                                      void* stream);
+nps_status nopesac_bn_train_backward_f32(const float* dy, const float* src, int up, int B, int H, int W, int C, int64_t src_cstride,
+                                         const float* gamma, const float* beta, const float* mean, const float* rstd, int act, int batch_stats,
+                                         float* dsrc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
+nps_status nopesac_upsample2x_bilinear_backward_f32(const float* du, float* dx, int B, int H, int W, int C, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

@@ -473,6 +473,20 @@ class PlaneTRHead(ParamModule):
             p1 = up_stage(p2, "up_conv1", cbr(feats["res2"], "c1_conv"))
             return memory, pos, p1
 
+    def pyramid_training_inputs(self, features: dict):
+        """The tensors where the head's FROZEN part ends when the top-down pyramid trains (training.PlanePyramidTrainer): (memory
+        [B*Lm, 256] f32, the encoder's output - the encoder half of decoder_training_inputs, launch for launch; feats: the four backbone
+        maps res2 .. res5 as f32 NHWC).  Without autograd."""
+        f32 = torch.float32
+        with torch.no_grad():
+            feats = {k: features[k].float().contiguous() for k in ("res2", "res3", "res4", "res5")}
+            c4 = feats["res5"]
+            B, hc, wc, _ = c4.shape
+            ip = self.packed["input_proj"]
+            src = ops.conv2d(c4, ip.w(f32), None, ip.bias, out_dtype=f32).view(B * hc * wc, 256)
+            memory, _ = self._encoder_f32(src, self._pos(hc, wc, c4.device), B, hc * wc, self.nheads, 32 ** -0.5, f32)
+            return memory, feats
+
     def _heads(self, features, hs, memory, B, hc, wc, nq, want_logits, mark):
         P, gd = self.packed, self.gemm_dtype
         c1, c2, c3, c4 = features["res2"], features["res3"], features["res4"], features["res5"]

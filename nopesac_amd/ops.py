@@ -1710,6 +1710,84 @@ def upsample2x_nearest_add_backward(dy: torch.Tensor):
     return dx, dy
 
 
+def _bn_train_src(src: torch.Tensor, up: bool):
+    """The input of a training-mode BatchNorm kernel -> (B, H, W, C, channel stride, n, shape of v): plain form [rows, C] (rows may be
+    strided) or pixel-dense NHWC (a channel slice of a wider buffer is allowed); upsampled form: NHWC, v = its bilinear 2x upsampling."""
+    _chk(src, torch.float32, contiguous=False)
+    if src.dim() == 2 and not up:
+        _require(src.stride(1) == 1 and src.stride(0) >= src.shape[1], "rows of unit channel stride expected")
+        rows, C = src.shape
+        _require(rows > 0 and C > 0 and C % 4 == 0 and src.stride(0) % 4 == 0, "rows of a multiple of 4 channels (and such a stride) expected")
+        return rows, 1, 1, C, src.stride(0), rows, (rows, C)
+    cs = _nhwc_cs(src)
+    B, H, W, C = src.shape
+    _require(B > 0 and H > 0 and W > 0 and C > 0 and C % 4 == 0 and cs % 4 == 0, "a multiple of 4 channels (and such a channel stride) expected")
+    return (B, H, W, C, cs, 4 * B * H * W, (B, 2 * H, 2 * W, C)) if up else (B, H, W, C, cs, B * H * W, (B, H, W, C))
+
+
+def bn_train_workspace_floats(n: int, C: int) -> int:
+    """The header's NPS_BN_TRAIN_WORKSPACE_FLOATS: per block of NPS_BN_TRAIN_RPS rows two partials per channel."""
+    return -(-int(n) // _H.NPS_BN_TRAIN_RPS) * 2 * int(C)
+
+
+def bn_train_stats(src: torch.Tensor, *, up: bool = False, eps: float = 1e-5, momentum: float = 0.1, running_mean=None, running_var=None):
+    """Batch statistics of a training-mode BatchNorm over v = src ([rows, C] or NHWC) or, with `up`, v = upsample2x_bilinear(src) evaluated
+    on the fly -> (mean, biased var, rstd = 1 / sqrt(var + eps)), [C] each.  running_mean / running_var (both or neither) are updated in
+    place on the device as torch.nn.BatchNorm2d does (momentum, unbiased variance); no host sync.  One value per channel is refused."""
+    B, H, W, C, cs, n, _ = _bn_train_src(src, up)
+    _require(n >= 2, "bn_train_stats: more than one value per channel expected")
+    _require((running_mean is None) == (running_var is None), "running_mean and running_var come together")
+    if running_mean is not None:
+        _bn_vecs(C, running_mean, running_var)
+    mean, var, rstd = (torch.empty(C, device=src.device, dtype=torch.float32) for _ in range(3))
+    ws = torch.empty(bn_train_workspace_floats(n, C), device=src.device, dtype=torch.float32)
+    _C.nopesac_bn_train_stats_f32(_p(src), int(up), B, H, W, C, cs, float(eps), float(momentum), _p(mean), _p(var), _p(rstd), _p(running_mean),
+                                  _p(running_var), _p(ws), ws.numel(), _stream())
+    return mean, var, rstd
+
+
+def bn_train_apply(src: torch.Tensor, gamma, beta, mean, rstd, act=ACT_RELU, addend: Optional[torch.Tensor] = None, *, up: bool = False) -> torch.Tensor:
+    """act(gamma (v - mean) rstd + beta) (+ addend, after the activation) for v as in bn_train_stats; act: NONE or RELU.  Dense output."""
+    B, H, W, C, cs, n, shape = _bn_train_src(src, up)
+    _require(act in (ACT_NONE, ACT_RELU), act)
+    _bn_vecs(C, gamma, beta, mean, rstd)
+    if addend is not None:
+        _chk(addend, torch.float32)
+        _require(tuple(addend.shape) == shape, (tuple(addend.shape), shape))
+    y = torch.empty(shape, device=src.device, dtype=torch.float32)
+    _C.nopesac_bn_train_apply_f32(_p(src), int(up), B, H, W, C, cs, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), _p(addend), _p(y), _stream())
+    return y
+
+
+def bn_train_backward(dy: torch.Tensor, src: torch.Tensor, gamma, beta, mean, rstd, act=ACT_RELU, *, up: bool = False, batch_stats: bool = True):
+    """Backward of bn_train_apply through the batch statistics, from the same input (v is recomputed) -> (dsrc, dgamma, dbeta): plain form
+    dsrc = dv, dense in v's shape; with `up` dsrc = the gradient at src [B, H, W, C], the bilinear adjoint of dv gathered in the same launch
+    (dv is never written).  batch_stats=False: mean / rstd are stored statistics, constants of the backward (dv = gamma rstd dz).  The
+    addend's gradient is dy itself."""
+    B, H, W, C, cs, n, shape = _bn_train_src(src, up)
+    _require(act in (ACT_NONE, ACT_RELU), act)
+    _chk(dy, torch.float32)
+    _require(tuple(dy.shape) == shape, (tuple(dy.shape), shape))
+    _bn_vecs(C, gamma, beta, mean, rstd)
+    dsrc = torch.empty(tuple(src.shape) if up else shape, device=src.device, dtype=torch.float32)
+    dg = torch.empty(C, device=src.device, dtype=torch.float32)
+    db = torch.empty(C, device=src.device, dtype=torch.float32)
+    ws = torch.empty(bn_train_workspace_floats(n, C), device=src.device, dtype=torch.float32)
+    _C.nopesac_bn_train_backward_f32(_p(dy), _p(src), int(up), B, H, W, C, cs, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), int(bool(batch_stats)), _p(dsrc), _p(dg),
+                                     _p(db), _p(ws), ws.numel(), _stream())
+    return dsrc, dg, db
+
+
+def upsample2x_bilinear_backward(du: torch.Tensor) -> torch.Tensor:
+    """The adjoint of upsample2x_bilinear: du [B, 2H, 2W, C] f32 -> dx [B, H, W, C]."""
+    _chk(du, torch.float32)
+    _require(du.dim() == 4 and du.shape[1] % 2 == 0 and du.shape[2] % 2 == 0 and du.numel() > 0 and du.shape[3] % 4 == 0, tuple(du.shape))
+    B, H2, W2, C = du.shape
+    dx = torch.empty((B, H2 // 2, W2 // 2, C), device=du.device, dtype=torch.float32)
+    _C.nopesac_upsample2x_bilinear_backward_f32(_p(du), _p(dx), B, H2 // 2, W2 // 2, C, _stream())
+    return dx
+
+
 def transpose_batched(x: torch.Tensor) -> torch.Tensor:
     """[B, rows, cols] f32 -> contiguous [B, cols, rows]."""
     _chk(x, torch.float32)

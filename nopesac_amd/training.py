@@ -38,12 +38,20 @@ dropout 0.1, the final norm, query_embed - 111 tensors) is trained by PlaneDecod
 kernels of csrc/decoder_train.hip - attention with dropout on the probabilities for any key count and its recomputing backward, and
 element-wise dropout whose mask is a counter-based function of (seed, step, layer, site, element index) that is never stored.
 
-What this is NOT: a trainer for the whole network.  The backbone, the plane head's encoder and its top-down pyramid have no backward
-kernels here - the gradients stop at the encoder memory and p1 (`input_grads`, ready for a trunk backward to chain onto); the
+The plane head's top-down pyramid (planeTR_head.py:209-252: eight conv1x1 + nn.BatchNorm2d + ReLU blocks, three of them behind a
+bilinear 2x upsampling - 24 parameters, 16 running-statistics buffers, eight counters) is trained by PlanePyramidTrainer as the reference
+trains it: BatchNorm on BATCH statistics with the running buffers updated on the device.  It takes the instance heads' gradient at p1
+(backward_from, or chained by losses / backward), and its kernels are csrc/pyramid_train.hip - statistics, apply and backward of a
+training-mode BatchNorm whose input is a matrix or the on-the-fly upsampling of a low-resolution map (the up convs stay at the low
+resolution, as in the inference head), with the bilinear adjoint gathered inside the backward's second launch.  The encoder memory is a
+shared input of this trainer and the decoder's: given the same leaf, autograd sums both paths.
+
+What this is NOT: a trainer for the whole network.  The backbone and the plane head's encoder have no backward kernels here - the
+gradients stop at the encoder memory and the backbone maps (`input_grads`, ready for an encoder / backbone backward to chain onto); the
 backbone maps, the plane sets and their appearance features are inputs of the other stages, as they are of the reference functions, and
 receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
 against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py)
-and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py)."""
+and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py, tests/test_plane_pyramid_training_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -1474,6 +1482,208 @@ class PlaneDecoderTrainer(RefineTrainer):
         """The chain's backward: the instance heads' backward runs on through hs into the decoder.  -> the gradients of both trainers'
         tensors by state-dict key (the heads' own stay readable as their parameters' .grad; `.grads` holds the decoder's)."""
         _require(self._heads is not None, "PlaneDecoderTrainer.backward: call losses() first (backward_from takes a gradient at hs)")
+        self._clear_grads()
+        head_grads = self._heads.backward(losses, loss_weights)
+        return {**self._collect(), **head_grads}
+
+
+TOP_DOWN = "top_down"
+PYRAMID_CONVS = ("up_conv3", "up_conv2", "up_conv1", "c4_conv", "c3_conv", "c2_conv", "c1_conv", "m_conv_dict.m4")
+PYRAMID_BN_EPS, PYRAMID_BN_MOMENTUM = 1e-5, 0.1                   # nn.BatchNorm2d's defaults (planeTR_head.py:212)
+
+
+def _bn_statistics(src, up: bool, run_mean, run_var, batch_stats: bool):
+    """(mean, rstd) of a pyramid BatchNorm: the batch's (the running buffers are updated in place), or the stored ones."""
+    if batch_stats:
+        mean, _var, rstd = ops.bn_train_stats(src, up=up, eps=PYRAMID_BN_EPS, momentum=PYRAMID_BN_MOMENTUM, running_mean=run_mean,
+                                              running_var=run_var)
+        return mean, rstd
+    return run_mean, torch.rsqrt(run_var + PYRAMID_BN_EPS)
+
+
+class _ConvBNTrain(torch.autograd.Function):
+    """A lateral of the top-down pyramid: relu(bn(conv1x1(x))) (+ addend) with a training-mode BatchNorm (batch statistics, the running
+    buffers updated in place) or, batch_stats=False, with the stored statistics as constants.  The raw conv output is saved."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, addend, run_mean, run_var, batch_stats: bool):
+        x = x.contiguous()
+        c = ops.conv2d(x, _ohwi(w, x.shape[3]))
+        mean, rstd = _bn_statistics(c, False, run_mean, run_var, batch_stats)
+        ctx.batch_stats = batch_stats
+        ctx.save_for_backward(x, w, c, gamma, beta, mean, rstd)
+        return ops.bn_train_apply(c, gamma, beta, mean, rstd, ops.ACT_RELU, None if addend is None else addend.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, c, gamma, beta, mean, rstd = ctx.saved_tensors
+        g = g.contiguous()
+        dc, dgamma, dbeta = ops.bn_train_backward(g, c, gamma, beta, mean, rstd, ops.ACT_RELU, batch_stats=ctx.batch_stats)
+        dx, dw = _conv_input_grads(ctx, x, w, dc, 1, 0)
+        return dx, dw, dgamma, dbeta, (g if ctx.needs_input_grad[4] else None), None, None, None
+
+
+class _UpStageTrain(torch.autograd.Function):
+    """An up stage of the top-down pyramid: relu(bn(conv1x1(up2(x)))) + lateral, evaluated as relu(bn(up2(t))) + lateral with
+    t = conv1x1(x) at the LOW resolution (the 1x1 conv commutes with the bilinear interpolation, PlaneTRHead._pyramid); the BatchNorm's
+    batch statistics are those of up2(t), which the kernels evaluate on the fly.  Backward: the BatchNorm backward and the bilinear adjoint
+    in one gather (ops.bn_train_backward with up=True), then the conv's dgrad / wgrad at the low resolution."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, lateral, run_mean, run_var, batch_stats: bool):
+        x = x.contiguous()
+        t = ops.conv2d(x, _ohwi(w, x.shape[3]))
+        mean, rstd = _bn_statistics(t, True, run_mean, run_var, batch_stats)
+        ctx.batch_stats = batch_stats
+        ctx.save_for_backward(x, w, t, gamma, beta, mean, rstd)
+        return ops.bn_train_apply(t, gamma, beta, mean, rstd, ops.ACT_RELU, lateral.contiguous(), up=True)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, t, gamma, beta, mean, rstd = ctx.saved_tensors
+        g = g.contiguous()
+        dt, dgamma, dbeta = ops.bn_train_backward(g, t, gamma, beta, mean, rstd, ops.ACT_RELU, up=True, batch_stats=ctx.batch_stats)
+        dx, dw = _conv_input_grads(ctx, x, w, dt, 1, 0)
+        return dx, dw, dgamma, dbeta, (g if ctx.needs_input_grad[4] else None), None, None, None
+
+
+class PlanePyramidTrainer(RefineTrainer):
+    """The plane head's top-down pyramid in TRAINING mode (reference top_down, planeTR_head.py:209-252, unfrozen: cfg.MODEL.FREEZE = []):
+    eight 1x1 convs without bias, each followed by an nn.BatchNorm2d on BATCH statistics and a ReLU - 24 parameters (conv weight, BN
+    weight, BN bias) under their state-dict keys, plus the 16 running-statistics buffers and the eight num_batches_tracked counters
+    (`buffers`), which a batch-statistics forward updates on the device as torch does (momentum 0.1, unbiased variance).
+
+        memory, feats = model.sem_seg_head.pyramid_training_inputs(features)       # [B*Lm, 256], {res2 .. res5: f32 NHWC} (no autograd)
+        pyr = PlanePyramidTrainer.from_head(model.sem_seg_head)                    # or .from_state_dict(sd, device)
+        p1 = pyr.forward(feats, memory, B)                                         # [B, h, w, 256], autograd tape attached
+        pyr.backward_from(d_p1)                                                    # .grads, .input_grads["memory"] (and "res2" .. "res5")
+      or, chained in front of the instance heads and the criterion:
+        losses, indices = pyr.losses(heads, feats, memory, hs, targets)
+        pyr.backward(losses); pyr.step_from_cfg(cfg); heads.step_from_cfg(cfg); pyr.write_back(model.sem_seg_head)
+
+    `memory` may be a leaf that requires grad and that PlaneDecoderTrainer.forward consumes too: then autograd sums both paths into the
+    total gradient at the encoder's output.  batch_stats=False runs on the stored statistics (the reference's FrozenBatchNorm2d regime:
+    the same kernels with mean / rstd as constants of the backward) and leaves the buffers untouched.  Up stages keep the inference
+    head's algebra (the conv at the low resolution).  Optimiser groups (train_NopeSAC.py:88-135): the 16 BatchNorm affine tensors take
+    WEIGHT_DECAY_NORM; the learning rate carries SOLVER.SEM_SEG_HEAD_MULTIPLIER."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], buffers: Dict[str, torch.Tensor], feature_grads: bool = False):
+        super().__init__(params, 0)
+        self.feature_grads = bool(feature_grads)
+        self.buffers = {k: (v.detach().clone().to(torch.int64) if k.endswith("num_batches_tracked") else v.detach().clone().float().contiguous())
+                        for k, v in buffers.items()}
+        self.grads: Dict[str, torch.Tensor] = {}
+        self._inputs: Dict[str, torch.Tensor] = {}
+        self._p1 = self._heads = None
+        _require(len(self.params) == 24 and len(self.buffers) == 24,
+                 "PlanePyramidTrainer: 24 parameters and 24 buffers expected, got %d and %d" % (len(self.params), len(self.buffers)))
+
+    @staticmethod
+    def _names(sd_keys, buffers: bool) -> List[str]:
+        q = PLANE_PREFIX + TOP_DOWN + "."
+        return sorted(k for k in sd_keys if k.startswith(q) and (k.split(".")[-1] in _BUFFER_LEAVES) == buffers)
+
+    @staticmethod
+    def parameter_names(sd_keys) -> List[str]:
+        return PlanePyramidTrainer._names(sd_keys, False)
+
+    @staticmethod
+    def buffer_names(sd_keys) -> List[str]:
+        return PlanePyramidTrainer._names(sd_keys, True)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device, feature_grads: bool = False) -> "PlanePyramidTrainer":
+        keys = list(sd.keys())
+        return cls({k: sd[k].to(device) for k in cls.parameter_names(keys)}, {k: sd[k].to(device) for k in cls.buffer_names(keys)}, feature_grads)
+
+    @classmethod
+    def from_head(cls, head, feature_grads: bool = False) -> "PlanePyramidTrainer":
+        keys = [PLANE_PREFIX + k for k in head._spec_keys]
+        raw = lambda k: head.raw(k[len(PLANE_PREFIX):])
+        return cls({k: raw(k) for k in cls.parameter_names(keys)}, {k: raw(k) for k in cls.buffer_names(keys)}, feature_grads)
+
+    def lr_multiplier(self, cfg) -> float:
+        return float(cfg.SOLVER.SEM_SEG_HEAD_MULTIPLIER)
+
+    def _weight_decay(self, key: str, weight_decay: float, weight_decay_norm: Optional[float]) -> float:
+        norm = key.split(".")[-2] == "1"                                           # conv_bn_relu: Sequential(0 = conv, 1 = BatchNorm2d, 2 = ReLU)
+        return weight_decay if weight_decay_norm is None or not norm else weight_decay_norm
+
+    def write_back(self, head):
+        """Copy the trained tensors AND the running statistics / counters into the inference PlaneTRHead and drop its packed copies (the
+        BatchNorm folds among them: rebuilt on the next forward)."""
+        with torch.no_grad():
+            for k, t in list(self.params.items()) + list(self.buffers.items()):
+                head.raw(k[len(PLANE_PREFIX):]).copy_(t)
+        head.invalidate()
+
+    # ---- forward
+    def forward(self, feats: dict, memory: torch.Tensor, B: int, batch_stats: bool = True) -> torch.Tensor:
+        """feats: res2 .. res5 f32 NHWC ([B, h, w, 256 / 512 / 1024 / 2048], each level twice the next one's size), memory [B*Lm, 256] f32 with
+        Lm = res5's pixels -> p1 [B, h2, w2, 256], the pixel decoder's map at res2's resolution, autograd tape attached."""
+        P, Bf = self.params, self.buffers
+        c = {}
+        for k in ("res2", "res3", "res4", "res5"):
+            t = feats[k]
+            _require(t.dim() == 4 and t.shape[0] == B and t.dtype == torch.float32, "PlanePyramidTrainer: %s [%d, h, w, C] f32 expected, got %s" % (k, B, tuple(t.shape)))
+            c[k] = t.detach().requires_grad_(True) if self.feature_grads and not t.requires_grad else t
+        hc, wc = c["res5"].shape[1:3]
+        for k, f in (("res4", 2), ("res3", 4), ("res2", 8)):
+            _require(tuple(c[k].shape[1:3]) == (f * hc, f * wc), "PlanePyramidTrainer: %s must be %d x res5's size" % (k, f))
+        _require(tuple(memory.shape) == (B * hc * wc, 256) and memory.dtype == torch.float32,
+                 "PlanePyramidTrainer: memory [%d, 256] f32 expected, got %s" % (B * hc * wc, tuple(memory.shape)))
+        mem = memory if memory.requires_grad else memory.detach().requires_grad_(True)
+        self._inputs = dict({"memory": mem}, **{k: t for k, t in c.items() if t.requires_grad})
+        for t in self._inputs.values():
+            if not t.is_leaf:
+                t.retain_grad()
+        bs = bool(batch_stats)
+
+        def stage(fn, x, nm, other):
+            q = f"{PLANE_PREFIX}{TOP_DOWN}.{nm}"
+            y = fn.apply(x, P[q + ".0.weight"], P[q + ".1.weight"], P[q + ".1.bias"], other, Bf[q + ".1.running_mean"], Bf[q + ".1.running_var"], bs)
+            if bs:
+                Bf[q + ".1.num_batches_tracked"] += 1
+            return y
+        p4 = stage(_ConvBNTrain, mem.view(B, hc, wc, 256), "m_conv_dict.m4", stage(_ConvBNTrain, c["res5"], "c4_conv", None))
+        p3 = stage(_UpStageTrain, p4, "up_conv3", stage(_ConvBNTrain, c["res4"], "c3_conv", None))
+        p2 = stage(_UpStageTrain, p3, "up_conv2", stage(_ConvBNTrain, c["res3"], "c2_conv", None))
+        self._p1 = stage(_UpStageTrain, p2, "up_conv1", stage(_ConvBNTrain, c["res2"], "c1_conv", None))
+        return self._p1
+
+    # ---- backward
+    def _clear_grads(self):
+        for t in self.params.values():
+            t.grad = None
+        for t in self._inputs.values():
+            if t.is_leaf:
+                t.grad = None
+
+    def _collect(self) -> Dict[str, torch.Tensor]:
+        self.input_grads = {k: t.grad for k, t in self._inputs.items() if t.grad is not None}
+        self.grads = {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in self.params.items()}
+        return self.grads
+
+    def backward_from(self, d_p1: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The gradient at p1 (what PlaneInstanceHeadsTrainer.input_grads["p1"] holds for the last forward's p1) -> {state-dict key:
+        gradient} of the 24 parameters (also `.grads`); `.input_grads["memory"]` = the gradient at the encoder memory through m_conv_dict.m4
+        and, with feature_grads, `.input_grads["res2" .. "res5"]` = the gradients at the backbone maps."""
+        _require(self._p1 is not None and tuple(d_p1.shape) == tuple(self._p1.shape), "PlanePyramidTrainer.backward_from: d_p1 like the last forward's p1")
+        self._clear_grads()
+        torch.autograd.backward(self._p1, d_p1.contiguous())
+        return self._collect()
+
+    def losses(self, heads: "PlaneInstanceHeadsTrainer", feats: dict, memory: torch.Tensor, hs: torch.Tensor, targets: dict,
+               batch_stats: bool = True, num_masks: Optional[float] = None):
+        """Pyramid, then the instance heads, then their PlaneCriterion: -> (losses, indices) of heads.losses on this forward's p1 (under deep
+        supervision p1 feeds every supervised layer's masks).  hs [L, B, nq, 256]: constants, or PlaneDecoderTrainer.forward's output."""
+        self._heads = heads
+        return heads.losses(hs, self.forward(feats, memory, hs.shape[1], batch_stats), targets, num_masks)
+
+    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+        """The chain's backward: the instance heads' backward runs on through p1 into the pyramid.  -> the gradients of both trainers'
+        tensors by state-dict key (`.grads` holds the pyramid's)."""
+        _require(self._heads is not None, "PlanePyramidTrainer.backward: call losses() first (backward_from takes a gradient at p1)")
         self._clear_grads()
         head_grads = self._heads.backward(losses, loss_weights)
         return {**self._collect(), **head_grads}
