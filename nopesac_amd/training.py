@@ -1,7 +1,14 @@
-"""Training step of the camera head's refinement stage on MI355X (reference: `__forward_PlaneCamRefHead`,
-camera_net/camera_head.py:737-923; losses camera_modules.py:355-365; optimiser groups train_NopeSAC.py:88-169) - round 5.
+"""Training on MI355X, one trainer per module of the network (optimiser groups train_NopeSAC.py:88-169).  HeadTrainer is
+the base of all of them and nothing else: it owns the f32 leaf parameters under their state-dict keys, the gradients (`grads`,
+`input_grads` for the inputs a trainer watches), the sum-of-losses backward, the optimiser state and step (AdamW / SGD, global-norm
+clipping, the reference's norm / embedding / plain groups stated once in parameter_group) and write_back into the inference head; a
+subclass names its state-dict prefix (KEY_PREFIX) and its SOLVER.*_MULTIPLIER (LR_MULTIPLIER) and adds its forward.  ChainedTrainer adds
+the protocol of a trainer whose output feeds the instance heads: forward, then backward_from(gradient at the output), or
+losses(heads, ...) followed by backward.  The trainers: RefineTrainer (with CameraHeadTrainer on top of it), MatchingHeadTrainer,
+PlaneInstanceHeadsTrainer, and the chained PlaneDecoderTrainer and PlanePyramidTrainer.
 
-Forward = the kernels of the training-side twin (ops.geo_sequence, ops.ransac_score_maps, ops.ransac_soft_vote mode | 16,
+RefineTrainer is the camera head's refinement stage (reference: `__forward_PlaneCamRefHead`, camera_net/camera_head.py:737-923; losses
+camera_modules.py:355-365) - round 5.  Forward = the kernels of the training-side twin (ops.geo_sequence, ops.ransac_score_maps, ops.ransac_soft_vote mode | 16,
 ops.plane_cam_ref_losses) with the MLP stacks as one f32 GEMM launch per layer (every layer output is kept for the backward pass);
 backward = the hand-written vector-Jacobian kernels of csrc/refine_bwd.hip (losses, scoring + aggregation + pose heads, hypothesis x
 plane geometry) and, for every Linear layer, dgrad = dY W and wgrad = dY^T X on the library's f32 GEMM kernel + column sums for the
@@ -71,6 +78,9 @@ _BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked")
 MATCHER_PREFIX = "matching_head."
 GNN_LAYERS, GNN_HEADS, LN_EPS = 18, 8, 1e-5
 
+PLANE_PREFIX = "sem_seg_head."
+DECODER, TOP_DOWN = "context2plane_decoder", "top_down"              # the plane head's transformer decoder and top-down pyramid
+
 
 def is_norm_parameter(key: str) -> bool:
     """GroupNorm / BatchNorm affine tensors of the camera head (the modules the reference's build_optimizer gives WEIGHT_DECAY_NORM,
@@ -88,28 +98,46 @@ def is_norm_parameter(key: str) -> bool:
     return False
 
 
+def parameter_group(key: str) -> str:
+    """The optimiser group of a state-dict key, "norm", "embed" or "plain" (the reference's build_optimizer, train_NopeSAC.py:88-135:
+    norm module types take WEIGHT_DECAY_NORM, nn.Embedding WEIGHT_DECAY_EMBED).  Under sem_seg_head.: query_embed is the embedding, the
+    decoder's LayerNorms (norm, norm1-3) and the BatchNorm of every pyramid block (conv_bn_relu: Sequential(0 = conv, 1 = BatchNorm2d,
+    2 = ReLU)) are norms, the instance heads have neither; the camera head and the matcher: is_norm_parameter."""
+    if key.startswith(PLANE_PREFIX):
+        parts = key[len(PLANE_PREFIX):].split(".")
+        if parts[0] == "query_embed":
+            return "embed"
+        norm = (parts[0] == DECODER and parts[-2] in ("norm", "norm1", "norm2", "norm3")) or (parts[0] == TOP_DOWN and parts[-2] == "1")
+        return "norm" if norm else "plain"
+    return "norm" if is_norm_parameter(key) else "plain"
+
+
 MLPS = ("geo_encoder", "geo_proj_s1", "decoder_rot", "geo_proj_s2", "decoder_tran", "decoder_rot2", "decoder_tran2", "normal_score_proj",
         "param_score_proj")
 LINEARS = ("rots", "trans", "rot_score_reg", "trans_score_reg")
+_ACT_BACKWARD = {ops.ACT_NONE: None, ops.ACT_RELU: ops.relu_backward, ops.ACT_SIGMOID: ops.sigmoid_backward}      # of _Linear's epilogues
 
 
 class _Linear(torch.autograd.Function):
-    """y = act(x W^T + b) on the exact-f32 GEMM kernel; backward: dX = dY W, dW = dY^T X (the same kernel), db = column sums."""
+    """y = act(x W^T + b [+ residual]) on the exact-f32 GEMM kernel, act (ops.ACT_NONE / ACT_RELU / ACT_SIGMOID) and the residual in the
+    GEMM's epilogue as the inference heads launch them; backward: the activation's first (it reads y, which is saved only then), then
+    dX = dY W, dW = dY^T X (the same kernel), db = column sums of the gradient dY in front of the activation, which is the residual's."""
 
     @staticmethod
-    def forward(ctx, x, w, b, relu: bool):
+    def forward(ctx, x, w, b, act: int, residual):
+        _require(act in _ACT_BACKWARD, act)
         x = x.contiguous()
-        y = ops.linear(x, w, b, act=ops.ACT_RELU if relu else ops.ACT_NONE)
-        ctx.relu = relu
-        ctx.save_for_backward(x, w, y)
+        y = ops.linear(x, w, b, act=act, residual=None if residual is None else residual.contiguous())
+        ctx.act = act
+        ctx.save_for_backward(x, w, *(() if _ACT_BACKWARD[act] is None else (y,)))
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x, w, y = ctx.saved_tensors
+        x, w, *y = ctx.saved_tensors
         g = g.contiguous()
-        if ctx.relu:
-            g = ops.relu_backward(g, y)
+        if y:
+            g = _ACT_BACKWARD[ctx.act](g, y[0])
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = ops.linear(g, transpose(w))                      # [rows, N] x [N, K]
@@ -117,7 +145,20 @@ class _Linear(torch.autograd.Function):
             gw = ops.linear(transpose(g), transpose(x))           # [N, rows] x [rows, K]
         if ctx.needs_input_grad[2]:
             gb = col_sum(g)
-        return gx, gw, gb, None
+        return gx, gw, gb, None, (g if ctx.needs_input_grad[4] else None)
+
+
+def _linear(x, w, b=None, act: int = ops.ACT_NONE, residual=None):
+    return _Linear.apply(x, w, b, act, residual)
+
+
+def _mlp_stack(P: Dict[str, torch.Tensor], q: str, x, last_act: int = ops.ACT_NONE):
+    """The MLP under the key prefix q (`q.layers.i.{weight,bias}`): ReLU between the layers, last_act behind the last one."""
+    i = 0
+    while f"{q}.layers.{i + 1}.weight" in P:
+        x = _linear(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"], ops.ACT_RELU)
+        i += 1
+    return _linear(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"], last_act)
 
 
 class _ScoreMaps(torch.autograd.Function):
@@ -498,22 +539,188 @@ class _SinkhornEmbLoss(torch.autograd.Function):
         return d_dots, col_sum(d_bin.view(-1, 1)).view_as(bin_score), None, None, None, None, None, None, None, None, None
 
 
-class RefineTrainer:
-    """The refinement head's parameters as f32 leaf tensors + forward / backward / optimiser step.
+class HeadTrainer:
+    """What every trainer here is: a module's parameters as f32 leaf tensors under their state-dict keys (`params`), their gradients
+    after a backward (`grads`, and `input_grads` for the inputs the forward watched), the optimiser (`state`, `steps`) and write_back.
+    A subclass sets KEY_PREFIX (the state-dict prefix of its module, which the inference head's own keys lack), LR_MULTIPLIER (the name
+    of the SOLVER.*_MULTIPLIER its learning rate carries, train_NopeSAC.py:122-129, or None) and parameter_names, and adds its forward."""
+
+    KEY_PREFIX = ""
+    LR_MULTIPLIER: Optional[str] = None
+
+    def __init__(self, params: Dict[str, torch.Tensor]):
+        self.params = {k: v.detach().clone().float().contiguous().requires_grad_(True) for k, v in params.items()}
+        self.state: Dict[str, dict] = {}
+        self.steps = 0
+        self.grads: Dict[str, torch.Tensor] = {}
+        self.input_grads: Dict[str, torch.Tensor] = {}
+        self._inputs: Dict[str, torch.Tensor] = {}
+
+    @classmethod
+    def _read(cls, source, names, device=None) -> Dict[str, torch.Tensor]:
+        """{key: tensor} of the state-dict keys `names`, from an inference head (its raw tensors) or from a state dict (moved to device)."""
+        if hasattr(source, "raw"):
+            return {k: source.raw(k[len(cls.KEY_PREFIX):]) for k in names}
+        return {k: source[k].to(device) for k in names}
+
+    @classmethod
+    def _head_keys(cls, head) -> List[str]:
+        return [cls.KEY_PREFIX + k for k in head._spec_keys]
+
+    def write_back(self, head):
+        """Copy the trained parameters into the inference head (its packed / folded / bf16 copies are rebuilt on the next forward)."""
+        self._copy_into(head, self.params)
+
+    def _copy_into(self, head, tensors: Dict[str, torch.Tensor]):
+        with torch.no_grad():
+            for k, t in tensors.items():
+                head.raw(k[len(self.KEY_PREFIX):]).copy_(t)
+        head.invalidate()
+
+    # ---- backward
+    def _watch(self, inputs: Dict[str, torch.Tensor]):
+        """The inputs whose gradients `input_grads` reports after the backward.  A caller may chain its own graph in front: non-leaf
+        inputs keep their gradient only on request, and `input_grads` promises it."""
+        self._inputs = inputs
+        for t in inputs.values():
+            if t.requires_grad and not t.is_leaf:
+                t.retain_grad()
+
+    def _clear_grads(self):
+        for p in self.params.values():
+            p.grad = None
+        for t in self._inputs.values():
+            if t.requires_grad and t.is_leaf:
+                t.grad = None
+
+    def _collect(self) -> Dict[str, torch.Tensor]:
+        """-> `grads` = {state-dict key: gradient} (zeros where none arrived); `input_grads` = that of every watched input that requires
+        grad and has one."""
+        self.input_grads = {k: t.grad for k, t in self._inputs.items() if t.requires_grad and t.grad is not None}
+        self.grads = {k: (p.grad if p.grad is not None else torch.zeros_like(p)) for k, p in self.params.items()}
+        return self.grads
+
+    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+        """d (sum of the losses, optionally weighted) / d parameters -> {state-dict key: gradient}."""
+        self._clear_grads()
+        total = None
+        for k, v in losses.items():
+            term = v * float(loss_weights.get(k, 1.0)) if loss_weights else v
+            total = term if total is None else total + term
+        total.backward()
+        return self._collect()
+
+    # ---- optimiser (train_NopeSAC.py:88-169: AdamW / SGD over per-parameter groups)
+    def step(self, lr: float = 1e-4, optimizer: str = "ADAMW", weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8,
+             momentum: float = 0.9, weight_decay_norm: Optional[float] = None, weight_decay_embed: Optional[float] = None):
+        """`weight_decay_norm` / `weight_decay_embed` (if given): the decay of the tensors parameter_group calls "norm" / "embed" instead
+        of `weight_decay` - the reference's norm and embedding parameter groups."""
+        self.steps += 1
+        for k, p in self.params.items():
+            if p.grad is None:
+                continue
+            wd = self._weight_decay(k, weight_decay, weight_decay_norm, weight_decay_embed)
+            g = p.grad.contiguous()
+            st = self.state.setdefault(k, {})
+            with torch.no_grad():
+                if optimizer.upper() == "ADAMW":
+                    if not st:
+                        st["m1"], st["m2"] = torch.zeros_like(p), torch.zeros_like(p)
+                    ops.adamw_step(p, g, st["m1"], st["m2"], lr, betas[0], betas[1], eps, wd, self.steps)
+                elif optimizer.upper() == "SGD":
+                    first = "mom" not in st
+                    if first:
+                        st["mom"] = torch.zeros_like(p)
+                    ops.sgd_step(p, g, st["mom"], lr, momentum, wd, first)
+                else:
+                    raise NotImplementedError(f"no optimizer type {optimizer}")           # train_NopeSAC.py:158
+
+    @staticmethod
+    def _weight_decay(key: str, weight_decay: float, weight_decay_norm: Optional[float], weight_decay_embed: Optional[float] = None) -> float:
+        """The decay of one tensor's optimiser group."""
+        wd = {"plain": weight_decay, "norm": weight_decay_norm, "embed": weight_decay_embed}[parameter_group(key)]
+        return weight_decay if wd is None else wd
+
+    def clip_grad_norm(self, max_norm: float) -> torch.Tensor:
+        """torch.nn.utils.clip_grad_norm_ over ALL parameters of this trainer (the reference's FullModelGradientClippingOptimizer,
+        train_NopeSAC.py:139-148), on the device: returns the clip coefficient (f32[1]; 1 = not clipped) without a host sync."""
+        grads = [p.grad for p in self.params.values() if p.grad is not None]
+        acc = None
+        for g in grads:
+            acc = ops.sumsq_accumulate(g.contiguous(), acc)
+        coef = ops.clip_coefficient(acc, max_norm)
+        for p in self.params.values():
+            if p.grad is not None:
+                if not p.grad.is_contiguous():
+                    p.grad = p.grad.contiguous()
+                ops.scale_by(p.grad, coef)
+        return coef
+
+    def step_from_cfg(self, cfg):
+        """One optimiser step with the reference's solver settings (Trainer.build_optimizer, train_NopeSAC.py:88-169): SOLVER.OPTIMIZER
+        (ADAMW / SGD), BASE_LR, WEIGHT_DECAY, MOMENTUM, CLIP_GRADIENTS (CLIP_TYPE "full_model": global-norm clipping in front of the
+        step).  Norm tensors use WEIGHT_DECAY_NORM and embeddings WEIGHT_DECAY_EMBED (parameter_group), as the reference's module types
+        do; the learning rate carries `lr_multiplier(cfg)`."""
+        S = cfg.SOLVER
+        cg = S.CLIP_GRADIENTS
+        if cg.ENABLED and cg.CLIP_TYPE == "full_model" and cg.CLIP_VALUE > 0.0:
+            self.clip_grad_norm(float(cg.CLIP_VALUE))
+        elif cg.ENABLED:
+            raise NotImplementedError("SOLVER.CLIP_GRADIENTS.CLIP_TYPE %r (the reference's configs use full_model)" % (cg.CLIP_TYPE,))
+        self.step(lr=float(S.BASE_LR) * self.lr_multiplier(cfg), optimizer=str(S.OPTIMIZER), weight_decay=float(S.WEIGHT_DECAY),
+                  momentum=float(S.MOMENTUM), weight_decay_norm=float(S.WEIGHT_DECAY_NORM), weight_decay_embed=float(S.WEIGHT_DECAY_EMBED))
+
+    def lr_multiplier(self, cfg) -> float:
+        """The reference's per-module learning-rate multiplier of the module this trainer holds (train_NopeSAC.py:122-129): SOLVER's
+        LR_MULTIPLIER entry, or 1.  (BACKBONE_MULTIPLIER belongs to a module no trainer here holds; PLANE_MATCHER_HEAD_MULTIPLIER is keyed
+        on a module name the reference does not have, so it never fires there either.)"""
+        return 1.0 if self.LR_MULTIPLIER is None else float(getattr(cfg.SOLVER, self.LR_MULTIPLIER))
+
+
+class ChainedTrainer(HeadTrainer):
+    """A trainer whose output (OUTPUT: "hs" or "p1", kept by its forward in `_out`) is an input of PlaneInstanceHeadsTrainer: its backward
+    starts from the gradient the heads report there (backward_from) or, after losses(heads, ...) has put both on one graph, runs the
+    heads' backward on into this trainer (backward)."""
+
+    OUTPUT = ""
+
+    def __init__(self, params: Dict[str, torch.Tensor]):
+        super().__init__(params)
+        self._out = self._heads = None
+
+    def backward_from(self, d_out: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The gradient at the last forward's output (what PlaneInstanceHeadsTrainer.input_grads[OUTPUT] holds for it) -> {state-dict
+        key: gradient} of this trainer's tensors (also `.grads`); `.input_grads` = the gradients at the watched inputs."""
+        _require(self._out is not None and tuple(d_out.shape) == tuple(self._out.shape),
+                 "%s.backward_from: d_%s like the last forward's %s" % (type(self).__name__, self.OUTPUT, self.OUTPUT))
+        self._clear_grads()
+        torch.autograd.backward(self._out, d_out.contiguous())
+        return self._collect()
+
+    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+        """The chain's backward: the instance heads' backward runs on through OUTPUT into this trainer.  -> the gradients of both trainers'
+        tensors by state-dict key (the heads' own stay readable as their `.grads`; `.grads` here holds this trainer's)."""
+        _require(self._heads is not None, "%s.backward: call losses() first (backward_from takes a gradient at %s)" % (type(self).__name__, self.OUTPUT))
+        self._clear_grads()
+        head_grads = self._heads.backward(losses, loss_weights)
+        return {**self._collect(), **head_grads}
+
+
+class RefineTrainer(HeadTrainer):
+    """The camera head's refinement stage: forward / backward / optimiser step.
 
         tr = RefineTrainer.from_state_dict(sd, nq, device)             # or .from_head(model.camera_head_list[0])
         losses = tr.losses(A, planes1, planes2, n1, n2, init_trans, init_rot, init_trans_feat, init_rot_feat, gt_pose, suffix, weight)
         grads = tr.backward(losses)                                     # {state-dict key: gradient}; tr.input_grads for the feature inputs
         tr.step(lr=1e-4)                                                # AdamW (train_NopeSAC.py:150-153) on the device
         tr.write_back(head)                                             # into the inference model's packed weights
-    """
+    Optimiser groups: norm / embedding groups do not occur in this head."""
+
+    KEY_PREFIX = PREFIX
 
     def __init__(self, params: Dict[str, torch.Tensor], nq: int, warp_in_ref: bool = True):
+        super().__init__(params)
         self.nq, self.warp_in_ref = int(nq), bool(warp_in_ref)
-        self.params = {k: v.detach().clone().float().contiguous().requires_grad_(True) for k, v in params.items()}
-        self.state: Dict[str, dict] = {}
-        self.steps = 0
-        self.input_grads: Dict[str, torch.Tensor] = {}
 
     @staticmethod
     def parameter_names(sd_keys) -> List[str]:
@@ -528,23 +735,18 @@ class RefineTrainer:
 
     @classmethod
     def from_state_dict(cls, sd: dict, nq: int, device, warp_in_ref: bool = True) -> "RefineTrainer":
-        return cls({k: sd[k].to(device) for k in cls.parameter_names(sd.keys())}, nq, warp_in_ref)
+        return cls(cls._read(sd, cls.parameter_names(sd.keys()), device), nq, warp_in_ref)
 
     @classmethod
     def from_head(cls, head) -> "RefineTrainer":
-        names = cls.parameter_names(PREFIX + k for k in head._spec_keys)
-        return cls({k: head.raw(k[len(PREFIX):]) for k in names}, head.num_queries, head.warp_plane_in_cam_ref_on)
+        return cls(cls._read(head, cls.parameter_names(cls._head_keys(head))), head.num_queries, head.warp_plane_in_cam_ref_on)
 
     # ---- forward
     def _mlp(self, x, name: str, final_relu: bool = False):
-        i = 0
-        while f"{PREFIX}{name}.layers.{i + 1}.weight" in self.params:
-            x = _Linear.apply(x, self.params[f"{PREFIX}{name}.layers.{i}.weight"], self.params[f"{PREFIX}{name}.layers.{i}.bias"], True)
-            i += 1
-        return _Linear.apply(x, self.params[f"{PREFIX}{name}.layers.{i}.weight"], self.params[f"{PREFIX}{name}.layers.{i}.bias"], final_relu)
+        return _mlp_stack(self.params, PREFIX + name, x, ops.ACT_RELU if final_relu else ops.ACT_NONE)
 
-    def _lin(self, x, name: str):
-        return _Linear.apply(x, self.params[f"{PREFIX}{name}.weight"], self.params[f"{PREFIX}{name}.bias"], False)
+    def _lin(self, x, name: str, act: int = ops.ACT_NONE):
+        return _linear(x, self.params[f"{PREFIX}{name}.weight"], self.params[f"{PREFIX}{name}.bias"], act)
 
     def losses(self, A0, planes1, planes2, n1, n2, init_trans, init_rot, init_trans_feat, init_rot_feat, gt_pose, suffix: str = "",
                weight: float = 1.0) -> Dict[str, torch.Tensor]:
@@ -576,99 +778,9 @@ class RefineTrainer:
                                              fused_tran.view(B, nq, 256), w("rots"), bb("rots"), w("trans"), bb("trans"), rots_all, trans_all,
                                              dn_sum, dl2_sum, init_rot.detach(), init_trans.detach(), m)
         lv = _Losses.apply(pr, pt, ar, at, sr, st, l2, rots_all, trans_all, m, gt_pose, float(weight))
-        self._inputs = {"init_trans_feat": init_trans_feat, "init_rot_feat": init_rot_feat, "init_trans": init_trans, "init_rot": init_rot}
-        for t in self._inputs.values():                    # a caller may chain its own graph in front (CameraHeadTrainer does): non-leaf
-            if t.requires_grad and not t.is_leaf:          # inputs keep their gradient only on request, and `input_grads` promises it
-                t.retain_grad()
+        self._watch({"init_trans_feat": init_trans_feat, "init_rot_feat": init_rot_feat, "init_trans": init_trans, "init_rot": init_rot})
         self.last = {"pred_rot": pr, "pred_trans": pt, "avg_rot": ar, "avg_trans": at, "score_rot": sr, "score_trans": st, "m": m}
         return {"%s_%s" % (nm, suffix): lv[i] for i, nm in enumerate(ops.PLANE_CAM_REF_LOSS_NAMES)}
-
-    # ---- backward
-    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
-        """d (sum of the losses, optionally weighted) / d parameters -> {state-dict key: gradient}."""
-        for p in self.params.values():
-            p.grad = None
-        for t in self._inputs.values():
-            if t.requires_grad and t.is_leaf:
-                t.grad = None
-        total = None
-        for k, v in losses.items():
-            term = v * float(loss_weights.get(k, 1.0)) if loss_weights else v
-            total = term if total is None else total + term
-        total.backward()
-        self.input_grads = {k: t.grad for k, t in self._inputs.items() if t.requires_grad and t.grad is not None}
-        return {k: (p.grad if p.grad is not None else torch.zeros_like(p)) for k, p in self.params.items()}
-
-    # ---- optimiser (train_NopeSAC.py:88-169: AdamW / SGD over per-parameter groups; norm / embedding groups do not occur in this head)
-    def step(self, lr: float = 1e-4, optimizer: str = "ADAMW", weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8,
-             momentum: float = 0.9, weight_decay_norm: Optional[float] = None):
-        """`weight_decay_norm` (if given): the decay of the GroupNorm / BatchNorm affine tensors (is_norm_parameter) instead of
-        `weight_decay` - the reference's norm parameter groups."""
-        self.steps += 1
-        for k, p in self.params.items():
-            if p.grad is None:
-                continue
-            wd = self._weight_decay(k, weight_decay, weight_decay_norm)
-            g = p.grad.contiguous()
-            st = self.state.setdefault(k, {})
-            with torch.no_grad():
-                if optimizer.upper() == "ADAMW":
-                    if not st:
-                        st["m1"], st["m2"] = torch.zeros_like(p), torch.zeros_like(p)
-                    ops.adamw_step(p, g, st["m1"], st["m2"], lr, betas[0], betas[1], eps, wd, self.steps)
-                elif optimizer.upper() == "SGD":
-                    first = "mom" not in st
-                    if first:
-                        st["mom"] = torch.zeros_like(p)
-                    ops.sgd_step(p, g, st["mom"], lr, momentum, wd, first)
-                else:
-                    raise NotImplementedError(f"no optimizer type {optimizer}")           # train_NopeSAC.py:158
-
-    def _weight_decay(self, key: str, weight_decay: float, weight_decay_norm: Optional[float]) -> float:
-        """The decay of one tensor's optimiser group."""
-        return weight_decay if weight_decay_norm is None or not is_norm_parameter(key) else weight_decay_norm
-
-    def clip_grad_norm(self, max_norm: float) -> torch.Tensor:
-        """torch.nn.utils.clip_grad_norm_ over ALL parameters of this trainer (the reference's FullModelGradientClippingOptimizer,
-        train_NopeSAC.py:139-148), on the device: returns the clip coefficient (f32[1]; 1 = not clipped) without a host sync."""
-        grads = [p.grad for p in self.params.values() if p.grad is not None]
-        acc = None
-        for g in grads:
-            acc = ops.sumsq_accumulate(g.contiguous(), acc)
-        coef = ops.clip_coefficient(acc, max_norm)
-        for p in self.params.values():
-            if p.grad is not None:
-                if not p.grad.is_contiguous():
-                    p.grad = p.grad.contiguous()
-                ops.scale_by(p.grad, coef)
-        return coef
-
-    def step_from_cfg(self, cfg):
-        """One optimiser step with the reference's solver settings (Trainer.build_optimizer, train_NopeSAC.py:88-169): SOLVER.OPTIMIZER
-        (ADAMW / SGD), BASE_LR, WEIGHT_DECAY, MOMENTUM, CLIP_GRADIENTS (CLIP_TYPE "full_model": global-norm clipping in front of the
-        step).  GroupNorm / BatchNorm affine tensors (held with CameraHeadTrainer(conv_stacks=True)) use WEIGHT_DECAY_NORM, as the
-        reference's norm module types do; the learning rate carries `lr_multiplier(cfg)`, the per-module multiplier of the module a
-        trainer holds (SEM_SEG_HEAD for PlaneInstanceHeadsTrainer; BACKBONE / PLANE_MATCHER_HEAD and the embedding weight decay apply
-        to modules no trainer here holds)."""
-        S = cfg.SOLVER
-        cg = S.CLIP_GRADIENTS
-        if cg.ENABLED and cg.CLIP_TYPE == "full_model" and cg.CLIP_VALUE > 0.0:
-            self.clip_grad_norm(float(cg.CLIP_VALUE))
-        elif cg.ENABLED:
-            raise NotImplementedError("SOLVER.CLIP_GRADIENTS.CLIP_TYPE %r (the reference's configs use full_model)" % (cg.CLIP_TYPE,))
-        self.step(lr=float(S.BASE_LR) * self.lr_multiplier(cfg), optimizer=str(S.OPTIMIZER), weight_decay=float(S.WEIGHT_DECAY),
-                  momentum=float(S.MOMENTUM), weight_decay_norm=float(S.WEIGHT_DECAY_NORM))
-
-    def lr_multiplier(self, cfg) -> float:
-        """The reference's per-module learning-rate multiplier of the module this trainer holds (train_NopeSAC.py:122-129); 1 here."""
-        return 1.0
-
-    def write_back(self, head):
-        """Copy the trained parameters into the inference head (its packed / bf16 copies are rebuilt on the next forward)."""
-        with torch.no_grad():
-            for k, p in self.params.items():
-                head.raw(k[len(PREFIX):]).copy_(p)
-        head.invalidate()
 
 
 class CameraHeadTrainer(RefineTrainer):
@@ -718,16 +830,14 @@ class CameraHeadTrainer(RefineTrainer):
     @classmethod
     def from_state_dict(cls, sd: dict, nq: int, device, warp_in_ref: bool = True, conv_stacks: bool = False,
                         feature_grads: bool = False) -> "CameraHeadTrainer":
-        return cls({k: sd[k].to(device) for k in cls.parameter_names(sd.keys(), conv_stacks)}, nq, warp_in_ref,
-                   {k: sd[k].to(device) for k in cls.buffer_names(sd.keys())} if conv_stacks else None, conv_stacks, feature_grads)
+        return cls(cls._read(sd, cls.parameter_names(sd.keys(), conv_stacks), device), nq, warp_in_ref,
+                   cls._read(sd, cls.buffer_names(sd.keys()), device) if conv_stacks else None, conv_stacks, feature_grads)
 
     @classmethod
     def from_head(cls, head, conv_stacks: bool = False, feature_grads: bool = False) -> "CameraHeadTrainer":
-        keys = [PREFIX + k for k in head._spec_keys]
-        names = cls.parameter_names(keys, conv_stacks)
-        bufs = {k: head.raw(k[len(PREFIX):]) for k in cls.buffer_names(keys)} if conv_stacks else None
-        return cls({k: head.raw(k[len(PREFIX):]) for k in names}, head.num_queries, head.warp_plane_in_cam_ref_on, bufs, conv_stacks,
-                   feature_grads)
+        keys = cls._head_keys(head)
+        return cls(cls._read(head, cls.parameter_names(keys, conv_stacks)), head.num_queries, head.warp_plane_in_cam_ref_on,
+                   cls._read(head, cls.buffer_names(keys)) if conv_stacks else None, conv_stacks, feature_grads)
 
     # ---- the pixel pose net's conv stacks (conv_stacks=True), camera_head.py:642-667 / camera_modules.py:246-348
     def _cbl(self, x, name: str, stride: int = 1):
@@ -770,14 +880,11 @@ class CameraHeadTrainer(RefineTrainer):
 
     def pixel_pose(self, yt: torch.Tensor, yr: torch.Tensor):
         """The FC layers + regressors on the conv features yt / yr [B, 768] in the REFERENCE's flatten order (channel-major: c * 6 + hw)."""
-        trans_feat = self._lin_relu(yt, "fc_trans")
-        rots_feat = self._lin_relu(yr, "fc_rots")
+        trans_feat = self._lin(yt, "fc_trans", ops.ACT_RELU)
+        rots_feat = self._lin(yr, "fc_rots", ops.ACT_RELU)
         trans0 = self._lin(trans_feat, "trans")
         rot0 = _Normalize.apply(self._lin(rots_feat, "rots"), False)
         return trans0, rot0, trans_feat, rots_feat
-
-    def _lin_relu(self, x, name: str):
-        return _Linear.apply(x, self.params[f"{PREFIX}{name}.weight"], self.params[f"{PREFIX}{name}.bias"], True)
 
     def aim(self, trans_in: torch.Tensor, rot_in: torch.Tensor):
         """__forward_RotRecHead / __forward_TransRecHead (:685-735) on DETACHED inputs; returns (rec_trans, rec_rot, trans_feat, rot_feat,
@@ -833,11 +940,11 @@ class CameraHeadTrainer(RefineTrainer):
                 self.recorded["rot"] += [self.last["avg_rot"], self.last["pred_rot"]]
         if rand_rot is not None:
             rec(rand_trans, rand_rot, "_randCamRecLBS_N1")
-        self._inputs = inputs
+        self._watch(inputs)                                       # (the backbone maps, in place of what the last losses() call watched)
         return losses
 
 
-class MatchingHeadTrainer(RefineTrainer):
+class MatchingHeadTrainer(HeadTrainer):
     """The matching head in TRAINING mode (reference MatchingHead.forward + embedding_loss_forward, matching_net/matching_head.py:43-139;
     LoFTR-style GNN, transformer/gnn.py:73-134): every floating tensor under `matching_head.` is trainable - 185 tensors: 18 layers x
     (q_proj, k_proj, v_proj, merge, mlp.0, mlp.2, norm1 weight / bias, norm2 weight / bias), planeApp_proj and planeDesc_proj weight / bias
@@ -852,16 +959,18 @@ class MatchingHeadTrainer(RefineTrainer):
     attention (gnn.py masks) and -1e5 in the Sinkhorn, and its gt_corr entries are cleared by the logical_and of :69 - exactly what a row
     beyond the length is here - so the caller gathers the selected queries (and the matching rows / columns of gt_corr) to the front.
 
-    Optimiser groups (train_NopeSAC.py:88-135): the 72 LayerNorm tensors take WEIGHT_DECAY_NORM (is_norm_parameter), bin_score and every
+    Optimiser groups (train_NopeSAC.py:88-135): the 72 LayerNorm tensors take WEIGHT_DECAY_NORM (parameter_group), bin_score and every
     other tensor the plain WEIGHT_DECAY.  SOLVER.PLANE_MATCHER_HEAD_MULTIPLIER is NOT applied: the reference keys it on
     "plane_matcher_net" in module_name, the module is called `matching_head`, so it never fires there either."""
 
+    KEY_PREFIX = MATCHER_PREFIX
+
     def __init__(self, params: Dict[str, torch.Tensor], nq: int, offset_multiplier: float = 4.0, normal_multiplier: float = 8.0,
                  sinkhorn_iterations: int = 200):
-        super().__init__(params, nq)
+        super().__init__(params)
+        self.nq = int(nq)
         self.offset_multiplier, self.normal_multiplier = float(offset_multiplier), float(normal_multiplier)
         self.sinkhorn_iterations = int(sinkhorn_iterations)                       # matching_head.py:38
-        self._inputs: Dict[str, torch.Tensor] = {}
 
     @staticmethod
     def parameter_names(sd_keys) -> List[str]:
@@ -870,20 +979,12 @@ class MatchingHeadTrainer(RefineTrainer):
     @classmethod
     def from_state_dict(cls, sd: dict, nq: int, device, **kw) -> "MatchingHeadTrainer":
         names = [k for k in cls.parameter_names(sd.keys()) if torch.is_tensor(sd[k]) and sd[k].is_floating_point()]
-        return cls({k: sd[k].to(device) for k in names}, nq, **kw)
+        return cls(cls._read(sd, names, device), nq, **kw)
 
     @classmethod
     def from_head(cls, head) -> "MatchingHeadTrainer":
-        names = cls.parameter_names(MATCHER_PREFIX + k for k in head._spec_keys)
-        return cls({k: head.raw(k[len(MATCHER_PREFIX):]) for k in names}, head.num_queries, head.offset_multiplier, head.normal_multiplier,
+        return cls(cls._read(head, cls.parameter_names(cls._head_keys(head))), head.num_queries, head.offset_multiplier, head.normal_multiplier,
                    head.sinkhorn_iterations)
-
-    def write_back(self, head):
-        """Copy the trained parameters into the inference MatchingHead (its packed and fragment-major copies are rebuilt on the next forward)."""
-        with torch.no_grad():
-            for k, p in self.params.items():
-                head.raw(k[len(MATCHER_PREFIX):]).copy_(p)
-        head.invalidate()
 
     # ---- forward
     def _gnn_layer(self, i: int, x, src, nb: int, qlen, klen):
@@ -895,14 +996,14 @@ class MatchingHeadTrainer(RefineTrainer):
         w = lambda name: P[f"{p}.{name}.weight"]
         scale = 32 ** -0.5
         if x is src:
-            qkv = _Linear.apply(x, torch.cat([w("q_proj"), w("k_proj"), w("v_proj")], 0), None, False)
+            qkv = _linear(x, torch.cat([w("q_proj"), w("k_proj"), w("v_proj")], 0))
             msg = _AttentionFused.apply(None, qkv, nb, nq, nq, GNN_HEADS, scale, qlen, klen)
         else:
-            q = _Linear.apply(x, w("q_proj"), None, False)
-            kv = _Linear.apply(src, torch.cat([w("k_proj"), w("v_proj")], 0), None, False)
+            q = _linear(x, w("q_proj"))
+            kv = _linear(src, torch.cat([w("k_proj"), w("v_proj")], 0))
             msg = _AttentionFused.apply(q, kv, nb, nq, nq, GNN_HEADS, scale, qlen, klen)
-        msg = _LayerNorm.apply(_Linear.apply(msg, w("merge"), None, False), P[p + ".norm1.weight"], P[p + ".norm1.bias"], None)
-        out = _Linear.apply(_LinearSplit.apply(x, msg, w("mlp.0")), w("mlp.2"), None, False)
+        msg = _LayerNorm.apply(_linear(msg, w("merge")), P[p + ".norm1.weight"], P[p + ".norm1.bias"], None)
+        out = _linear(_LinearSplit.apply(x, msg, w("mlp.0")), w("mlp.2"))
         return _LayerNorm.apply(out, P[p + ".norm2.weight"], P[p + ".norm2.bias"], x)
 
     def matching_losses(self, app, n_all, cam7, planes1, planes2, gt_corr, suffix: str = "",
@@ -922,7 +1023,7 @@ class MatchingHeadTrainer(RefineTrainer):
         _require(app.shape == (2 * B, nq, 256) and gt.shape == (B, nq + 1, nq + 1) and n_all.dtype == torch.int32,
                  "matching_losses: app [2B,nq,256], gt_corr [B,nq+1,nq+1], n_all int32; got %s, %s, %s" % (tuple(app.shape), tuple(gt.shape), n_all.dtype))
         q = MATCHER_PREFIX
-        f = _Linear.apply(app.reshape(2 * rows, 256), P[q + "planeApp_proj.weight"].view(256, 256), P[q + "planeApp_proj.bias"], False)
+        f = _linear(app.reshape(2 * rows, 256), P[q + "planeApp_proj.weight"].view(256, 256), P[q + "planeApp_proj.bias"])
         for i in range(GNN_LAYERS):
             if i % 2 == 0:                       # 'self' (gnn.py:128-130): both sets in one call
                 f = self._gnn_layer(i, f, f, 2 * B, n_all, n_all)
@@ -930,13 +1031,11 @@ class MatchingHeadTrainer(RefineTrainer):
                 f0 = self._gnn_layer(i, f[:rows], f[rows:], B, n1, n2)
                 f1 = self._gnn_layer(i, f[rows:], f0, B, n2, n1)
                 f = torch.cat([f0, f1], 0)
-        d = _Linear.apply(f, P[q + "planeDesc_proj.weight"].view(256, 256), P[q + "planeDesc_proj.bias"], False)
+        d = _linear(f, P[q + "planeDesc_proj.weight"].view(256, 256), P[q + "planeDesc_proj.bias"])
         dots = _DescDot.apply(d[:rows].view(B, nq, 256), d[rows:].view(B, nq, 256), n1, n2)
         loss, log_scores = _SinkhornEmbLoss.apply(dots, P[q + "bin_score"].view(1), planes1.contiguous(), planes2.contiguous(), cam7.contiguous(),
                                                   n1, n2, gt, self.offset_multiplier, self.normal_multiplier, iters)
-        self._inputs = {"app": app}
-        if app.requires_grad and not app.is_leaf:
-            app.retain_grad()
+        self._watch({"app": app})
         self.last = {"log_scores_padded": log_scores, "desc_dot": dots.detach()}
         return {"losses_emb_%s" % suffix: loss}
 
@@ -1061,30 +1160,8 @@ class PlaneCriterion:
 
 
 # ---- the plane head's instance heads -----------------------------------------------------------------------------------------------------
-PLANE_PREFIX = "sem_seg_head."
 PLANE_INSTANCE_HEADS = ("plane_embedding", "pixel_embedding", "plane_prob", "plane_param", "plane_center", "pixel_plane_center")
 FOLD_WIDTH = 264                       # the folded mask operand's row: 256 mask weights | the mask bias | 7 zero columns (PlaneTRHead.pack)
-
-
-class _LinearSigmoid(torch.autograd.Function):
-    """y = sigmoid(x W^T + b), the sigmoid in the GEMM's epilogue as the inference head has it; backward: that of _Linear behind
-    ops.sigmoid_backward."""
-
-    @staticmethod
-    def forward(ctx, x, w, b):
-        x = x.contiguous()
-        y = ops.linear(x, w, b, act=ops.ACT_SIGMOID)
-        ctx.save_for_backward(x, w, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w, y = ctx.saved_tensors
-        g = ops.sigmoid_backward(g.contiguous(), y)
-        gx = ops.linear(g, transpose(w)) if ctx.needs_input_grad[0] else None
-        gw = ops.linear(transpose(g), transpose(x)) if ctx.needs_input_grad[1] else None
-        gb = col_sum(g) if ctx.needs_input_grad[2] else None
-        return gx, gw, gb
 
 
 class _MaskProduct(torch.autograd.Function):
@@ -1122,7 +1199,7 @@ class _MaskProduct(torch.autograd.Function):
         return g_fold, d_p1, d_wc.view_as(wc), d_bc, None, None, None
 
 
-class PlaneInstanceHeadsTrainer(RefineTrainer):
+class PlaneInstanceHeadsTrainer(HeadTrainer):
     """The plane head's instance heads in TRAINING mode (reference PlaneTRHead.forward, planeTR_head.py:146-192, under deep supervision):
     the 24 tensors of plane_embedding, pixel_embedding, plane_prob, plane_param, plane_center and pixel_plane_center, held under their
     state-dict keys (`sem_seg_head. ...`).  The head's trunk is frozen: its two outputs enter as inputs.
@@ -1137,15 +1214,18 @@ class PlaneInstanceHeadsTrainer(RefineTrainer):
     Linear as autograd views of the two pixel_embedding leaves, so their gradients come back as slices of one wgrad.  Every launch of
     the last layer is the launch PlaneTRHead.forward makes on its f32 route, so the same parameters give the same bits.
     Optimiser groups (train_NopeSAC.py:88-135): none of the 24 tensors is a norm or an embedding parameter; the learning rate carries
-    SOLVER.SEM_SEG_HEAD_MULTIPLIER."""
+    SOLVER.SEM_SEG_HEAD_MULTIPLIER (train_NopeSAC.py:126-127).  write_back drops the head's pe_fold, which is derived from pixel_embedding,
+    with its other packed copies."""
+
+    KEY_PREFIX, LR_MULTIPLIER = PLANE_PREFIX, "SEM_SEG_HEAD_MULTIPLIER"
 
     def __init__(self, params: Dict[str, torch.Tensor], nq: int, cfg=None):
-        super().__init__(params, nq)
+        super().__init__(params)
+        self.nq = int(nq)
         if cfg is None:
             from .config import get_cfg
             cfg = get_cfg()
         self.criterion = PlaneCriterion.from_cfg(cfg)
-        self._inputs: Dict[str, torch.Tensor] = {}
         _require(len(self.params) == 24, "PlaneInstanceHeadsTrainer: 24 tensors expected, got %d" % len(self.params))
 
     @staticmethod
@@ -1154,35 +1234,13 @@ class PlaneInstanceHeadsTrainer(RefineTrainer):
 
     @classmethod
     def from_state_dict(cls, sd: dict, nq: int, device, cfg=None) -> "PlaneInstanceHeadsTrainer":
-        return cls({k: sd[k].to(device) for k in cls.parameter_names(sd.keys())}, nq, cfg)
+        return cls(cls._read(sd, cls.parameter_names(sd.keys()), device), nq, cfg)
 
     @classmethod
     def from_head(cls, head, cfg=None) -> "PlaneInstanceHeadsTrainer":
-        names = cls.parameter_names(PLANE_PREFIX + k for k in head._spec_keys)
-        return cls({k: head.raw(k[len(PLANE_PREFIX):]) for k in names}, head.num_queries, cfg)
-
-    def lr_multiplier(self, cfg) -> float:
-        return float(cfg.SOLVER.SEM_SEG_HEAD_MULTIPLIER)                 # train_NopeSAC.py:126-127
-
-    def write_back(self, head):
-        """Copy the trained tensors into the inference PlaneTRHead and drop its packed copies (pe_fold, which is derived from
-        pixel_embedding, among them: they are rebuilt on the next forward)."""
-        with torch.no_grad():
-            for k, p in self.params.items():
-                head.raw(k[len(PLANE_PREFIX):]).copy_(p)
-        head.invalidate()
+        return cls(cls._read(head, cls.parameter_names(cls._head_keys(head))), head.num_queries, cfg)
 
     # ---- forward
-    def _stack(self, x, name: str, sigmoid: bool = False):
-        """MLP (planeTR_head.py:194-206): ReLU between the layers, optionally a sigmoid behind the last one."""
-        P, q, i = self.params, PLANE_PREFIX + name, 0
-        while f"{q}.layers.{i + 1}.weight" in P:
-            x = _Linear.apply(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"], True)
-            i += 1
-        if sigmoid:
-            return _LinearSigmoid.apply(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"])
-        return _Linear.apply(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"], False)
-
     def forward(self, hs: torch.Tensor, p1: torch.Tensor) -> dict:
         """hs [L, B, nq, 256] (hs[i] = the normed output of decoder layer 6 - L + i), p1 [B, h, w, 256] pixel-dense NHWC -> the reference's
         training dict: the last layer's pred_logits [B, nq, 2], pred_mask_logits [B, nq, h, w], pred_centers [B, nq, 2], pred_params
@@ -1196,13 +1254,13 @@ class PlaneInstanceHeadsTrainer(RefineTrainer):
                  "PlaneInstanceHeadsTrainer: p1 [%d, h, w, 256] f32 expected, got %s" % (B, tuple(p1.shape)))
         q = PLANE_PREFIX
         x = hs.reshape(L * B * nq, 256)
-        emb = self._stack(x, "plane_embedding")
+        emb = _mlp_stack(P, q + "plane_embedding", x)                                 # (MLP: planeTR_head.py:194-206)
         w_pe = P[q + "pixel_embedding.weight"].view(256, 256)
         w_fold = torch.cat([w_pe.t(), P[q + "pixel_embedding.bias"].view(1, 256), w_pe.new_zeros(FOLD_WIDTH - 257, 256)], 0)
-        fold = _Linear.apply(emb, w_fold, None, False)
-        logits = _Linear.apply(x, P[q + "plane_prob.weight"], P[q + "plane_prob.bias"], False).view(L, B, nq, -1)
-        params = self._stack(x, "plane_param").view(L, B, nq, 3)
-        centers = self._stack(x, "plane_center", sigmoid=True).view(L, B, nq, 2)
+        fold = _linear(emb, w_fold)
+        logits = _linear(x, P[q + "plane_prob.weight"], P[q + "plane_prob.bias"]).view(L, B, nq, -1)
+        params = _mlp_stack(P, q + "plane_param", x).view(L, B, nq, 3)
+        centers = _mlp_stack(P, q + "plane_center", x, ops.ACT_SIGMOID).view(L, B, nq, 2)
         masks, pixel_centers = _MaskProduct.apply(fold, p1, P[q + "pixel_plane_center.weight"], P[q + "pixel_plane_center.bias"], L, B, nq)
         layer = lambda l: {"pred_logits": logits[l], "pred_mask_logits": masks[l], "pred_centers": centers[l], "pred_params": params[l]}
         out = layer(L - 1)
@@ -1215,10 +1273,7 @@ class PlaneInstanceHeadsTrainer(RefineTrainer):
         """-> (losses, indices) of PlaneCriterion.from_cfg on forward(hs, p1), the autograd tape attached; hs / p1 may require grad (their
         gradients land in `input_grads` after backward())."""
         out = self.forward(hs, p1)
-        self._inputs = {"hs": hs, "p1": p1}
-        for t in self._inputs.values():
-            if t.requires_grad and not t.is_leaf:
-                t.retain_grad()
+        self._watch({"hs": hs, "p1": p1})
         self.last = out
         return self.criterion(out, targets, num_masks)
 
@@ -1227,27 +1282,6 @@ class PlaneInstanceHeadsTrainer(RefineTrainer):
         if loss_weights is None:
             return super().backward(self.criterion.weighted(losses))
         return super().backward(losses, loss_weights)
-
-
-class _LinearRes(torch.autograd.Function):
-    """y = x W^T + b + residual with the residual in the GEMM's epilogue, as the inference head launches it; backward: that of _Linear,
-    and the residual's gradient is the incoming one."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, residual):
-        x = x.contiguous()
-        y = ops.linear(x, w, b, residual=residual.contiguous())
-        ctx.save_for_backward(x, w)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        g = g.contiguous()
-        gx = ops.linear(g, transpose(w)) if ctx.needs_input_grad[0] else None
-        gw = ops.linear(transpose(g), transpose(x)) if ctx.needs_input_grad[1] else None
-        gb = col_sum(g) if ctx.needs_input_grad[2] else None
-        return gx, gw, gb, (g if ctx.needs_input_grad[3] else None)
 
 
 class _LayerNormPair(torch.autograd.Function):
@@ -1323,12 +1357,11 @@ class _Dropout(torch.autograd.Function):
         return gx, (g if ctx.needs_input_grad[1] else None), None, None, None
 
 
-DECODER = "context2plane_decoder"
 DECODER_LAYERS, DECODER_HEADS = 6, 8
 DROP_SELF_ATTN, DROP_1, DROP_CROSS_ATTN, DROP_2, DROP_FFN, DROP_3 = range(6)         # the dropout sites of a layer (ops.dropout_stream)
 
 
-class PlaneDecoderTrainer(RefineTrainer):
+class PlaneDecoderTrainer(ChainedTrainer):
     """The plane head's transformer decoder in TRAINING mode (reference: transformer/transformer.py:114-153, 293-322 as planeTR_head.py:88
     builds it - six pre-norm layers, dropout 0.1, return_intermediate): the 111 tensors of context2plane_decoder (per layer
     self_attn / multihead_attn in_proj + out_proj, linear1, linear2, norm1-3; the final norm) and query_embed.weight, held under their
@@ -1351,13 +1384,12 @@ class PlaneDecoderTrainer(RefineTrainer):
     norm2; its gradient is summed over the batch.  Optimiser groups (train_NopeSAC.py:88-135): the LayerNorm tensors take
     WEIGHT_DECAY_NORM, query_embed (an nn.Embedding) WEIGHT_DECAY_EMBED, and the learning rate carries SOLVER.SEM_SEG_HEAD_MULTIPLIER."""
 
+    KEY_PREFIX, LR_MULTIPLIER, OUTPUT = PLANE_PREFIX, "SEM_SEG_HEAD_MULTIPLIER", "hs"
+
     def __init__(self, params: Dict[str, torch.Tensor], nq: int, deep_supervision: bool = True):
-        super().__init__(params, nq)
+        super().__init__(params)
+        self.nq = int(nq)
         self.layers_out = 3 if deep_supervision else 1
-        self.weight_decay_embed: Optional[float] = None
-        self.grads: Dict[str, torch.Tensor] = {}
-        self._inputs: Dict[str, torch.Tensor] = {}
-        self._hs = self._heads = None
         _require(len(self.params) == 18 * DECODER_LAYERS + 3, "PlaneDecoderTrainer: 111 tensors expected, got %d" % len(self.params))
         _require(self.params[PLANE_PREFIX + "query_embed.weight"].shape == (self.nq, 256), "PlaneDecoderTrainer: query_embed.weight [nq, 256]")
 
@@ -1367,34 +1399,11 @@ class PlaneDecoderTrainer(RefineTrainer):
 
     @classmethod
     def from_state_dict(cls, sd: dict, nq: int, device, deep_supervision: bool = True) -> "PlaneDecoderTrainer":
-        return cls({k: sd[k].to(device) for k in cls.parameter_names(sd.keys())}, nq, deep_supervision)
+        return cls(cls._read(sd, cls.parameter_names(sd.keys()), device), nq, deep_supervision)
 
     @classmethod
     def from_head(cls, head) -> "PlaneDecoderTrainer":
-        names = cls.parameter_names(PLANE_PREFIX + k for k in head._spec_keys)
-        return cls({k: head.raw(k[len(PLANE_PREFIX):]) for k in names}, head.num_queries, head.deep_supervision)
-
-    def lr_multiplier(self, cfg) -> float:
-        return float(cfg.SOLVER.SEM_SEG_HEAD_MULTIPLIER)
-
-    def _weight_decay(self, key: str, weight_decay: float, weight_decay_norm: Optional[float]) -> float:
-        leaf = key.split(".")[-2]
-        if leaf == "query_embed":
-            return weight_decay if self.weight_decay_embed is None else self.weight_decay_embed
-        if leaf in ("norm", "norm1", "norm2", "norm3"):
-            return weight_decay if weight_decay_norm is None else weight_decay_norm
-        return weight_decay
-
-    def step_from_cfg(self, cfg):
-        self.weight_decay_embed = float(cfg.SOLVER.WEIGHT_DECAY_EMBED)
-        super().step_from_cfg(cfg)
-
-    def write_back(self, head):
-        """Copy the trained tensors into the inference PlaneTRHead and drop its packed copies (rebuilt on the next forward)."""
-        with torch.no_grad():
-            for k, p in self.params.items():
-                head.raw(k[len(PLANE_PREFIX):]).copy_(p)
-        head.invalidate()
+        return cls(cls._read(head, cls.parameter_names(cls._head_keys(head))), head.num_queries, head.deep_supervision)
 
     # ---- forward
     def forward(self, memory: torch.Tensor, pos: torch.Tensor, B: int, p: float = 0.0, seed: int = 0, step: int = 0) -> torch.Tensor:
@@ -1408,9 +1417,7 @@ class PlaneDecoderTrainer(RefineTrainer):
         Lm = memory.shape[0] // B
         _require(tuple(pos.shape) == (Lm, 256) and pos.dtype == torch.float32, "PlaneDecoderTrainer: pos [%d, 256] f32 expected, got %s" % (Lm, tuple(pos.shape)))
         mem = memory if memory.requires_grad else memory.detach().requires_grad_(True)
-        if not mem.is_leaf:
-            mem.retain_grad()
-        self._inputs = {"memory": mem}
+        self._watch({"memory": mem})                       # (its gradient: the value path and the key path, mem_k = memory + pos, summed)
         mem_k = _AddRows.apply(mem, pos.detach())
         scale = 32 ** -0.5
         qpos = P[PLANE_PREFIX + "query_embed.weight"]
@@ -1419,8 +1426,8 @@ class PlaneDecoderTrainer(RefineTrainer):
 
         def out_proj(o, w, b, tgt, i, s):              # tgt + dropout(o W^T + b)
             if p == 0.0:
-                return _LinearRes.apply(o, w, b, tgt)
-            return _Dropout.apply(_Linear.apply(o, w, b, False), tgt, p, int(seed), site(i, s))
+                return _linear(o, w, b, residual=tgt)
+            return _Dropout.apply(_linear(o, w, b), tgt, p, int(seed), site(i, s))
 
         tgt = torch.zeros(B * nq, 256, device=memory.device, dtype=torch.float32)
         norm = (P[f"{PLANE_PREFIX}{DECODER}.norm.weight"], P[f"{PLANE_PREFIX}{DECODER}.norm.bias"])
@@ -1429,48 +1436,26 @@ class PlaneDecoderTrainer(RefineTrainer):
             q = f"{PLANE_PREFIX}{DECODER}.layers.{i}."
             w, b = P[q + "self_attn.in_proj_weight"], P[q + "self_attn.in_proj_bias"]
             t2, q_in = _LayerNormPair.apply(tgt, P[q + "norm1.weight"], P[q + "norm1.bias"], qpos)
-            qk = _Linear.apply(q_in, w[:512], b[:512], False)
-            v = _Linear.apply(t2, w[512:], b[512:], False)
+            qk = _linear(q_in, w[:512], b[:512])
+            v = _linear(t2, w[512:], b[512:])
             o = att(qk[:, :256], qk[:, 256:], v, nq, i, DROP_SELF_ATTN)
             tgt = out_proj(o, P[q + "self_attn.out_proj.weight"], P[q + "self_attn.out_proj.bias"], tgt, i, DROP_1)
             w, b = P[q + "multihead_attn.in_proj_weight"], P[q + "multihead_attn.in_proj_bias"]
             t2, q_in = _LayerNormPair.apply(tgt, P[q + "norm2.weight"], P[q + "norm2.bias"], qpos)
-            qc = _Linear.apply(q_in, w[:256], b[:256], False)
-            kc = _Linear.apply(mem_k, w[256:512], b[256:512], False)
-            vc = _Linear.apply(mem, w[512:], b[512:], False)
+            qc = _linear(q_in, w[:256], b[:256])
+            kc = _linear(mem_k, w[256:512], b[256:512])
+            vc = _linear(mem, w[512:], b[512:])
             o = att(qc, kc, vc, Lm, i, DROP_CROSS_ATTN)
             tgt = out_proj(o, P[q + "multihead_attn.out_proj.weight"], P[q + "multihead_attn.out_proj.bias"], tgt, i, DROP_2)
             t2 = _LayerNorm.apply(tgt, P[q + "norm3.weight"], P[q + "norm3.bias"], None)
-            hdn = _Linear.apply(t2, P[q + "linear1.weight"], P[q + "linear1.bias"], True)
+            hdn = _linear(t2, P[q + "linear1.weight"], P[q + "linear1.bias"], ops.ACT_RELU)
             if p != 0.0:
                 hdn = _Dropout.apply(hdn, None, p, int(seed), site(i, DROP_FFN))
             tgt = out_proj(hdn, P[q + "linear2.weight"], P[q + "linear2.bias"], tgt, i, DROP_3)
             if i >= DECODER_LAYERS - self.layers_out:
                 inter.append(_LayerNorm.apply(tgt, norm[0], norm[1], None))
-        self._hs = torch.stack(inter).view(self.layers_out, B, nq, 256)
-        return self._hs
-
-    # ---- backward
-    def _clear_grads(self):
-        for t in self.params.values():
-            t.grad = None
-        for t in self._inputs.values():
-            if t.is_leaf:
-                t.grad = None
-
-    def _collect(self) -> Dict[str, torch.Tensor]:
-        self.input_grads = {k: t.grad for k, t in self._inputs.items() if t.grad is not None}
-        self.grads = {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in self.params.items()}
-        return self.grads
-
-    def backward_from(self, d_hs: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """The gradient at hs (what PlaneInstanceHeadsTrainer.input_grads["hs"] holds for the last forward's hs) -> {state-dict key:
-        gradient} of the 111 tensors (also `.grads`); `.input_grads["memory"]` = the gradient at the encoder memory, its value path and its
-        key path (mem_k = memory + pos, pos constant) summed."""
-        _require(self._hs is not None and tuple(d_hs.shape) == tuple(self._hs.shape), "PlaneDecoderTrainer.backward_from: d_hs like the last forward's hs")
-        self._clear_grads()
-        torch.autograd.backward(self._hs, d_hs.contiguous())
-        return self._collect()
+        self._out = torch.stack(inter).view(self.layers_out, B, nq, 256)
+        return self._out
 
     def losses(self, heads: "PlaneInstanceHeadsTrainer", memory: torch.Tensor, pos: torch.Tensor, p1: torch.Tensor, targets: dict, p: float = 0.0,
                seed: int = 0, step: int = 0, num_masks: Optional[float] = None):
@@ -1478,16 +1463,7 @@ class PlaneDecoderTrainer(RefineTrainer):
         self._heads = heads
         return heads.losses(self.forward(memory, pos, p1.shape[0], p, seed, step), p1, targets, num_masks)
 
-    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
-        """The chain's backward: the instance heads' backward runs on through hs into the decoder.  -> the gradients of both trainers'
-        tensors by state-dict key (the heads' own stay readable as their parameters' .grad; `.grads` holds the decoder's)."""
-        _require(self._heads is not None, "PlaneDecoderTrainer.backward: call losses() first (backward_from takes a gradient at hs)")
-        self._clear_grads()
-        head_grads = self._heads.backward(losses, loss_weights)
-        return {**self._collect(), **head_grads}
 
-
-TOP_DOWN = "top_down"
 PYRAMID_CONVS = ("up_conv3", "up_conv2", "up_conv1", "c4_conv", "c3_conv", "c2_conv", "c1_conv", "m_conv_dict.m4")
 PYRAMID_BN_EPS, PYRAMID_BN_MOMENTUM = 1e-5, 0.1                   # nn.BatchNorm2d's defaults (planeTR_head.py:212)
 
@@ -1502,52 +1478,33 @@ def _bn_statistics(src, up: bool, run_mean, run_var, batch_stats: bool):
 
 
 class _ConvBNTrain(torch.autograd.Function):
-    """A lateral of the top-down pyramid: relu(bn(conv1x1(x))) (+ addend) with a training-mode BatchNorm (batch statistics, the running
-    buffers updated in place) or, batch_stats=False, with the stored statistics as constants.  The raw conv output is saved."""
+    """A block of the top-down pyramid with a training-mode BatchNorm (batch statistics, the running buffers updated in place) or,
+    batch_stats=False, with the stored statistics as constants.  up=False, a lateral: relu(bn(conv1x1(x))) (+ addend).  up=True, an up
+    stage: relu(bn(conv1x1(up2(x)))) + addend, evaluated as relu(bn(up2(c))) + addend with c = conv1x1(x) at the LOW resolution (the 1x1
+    conv commutes with the bilinear interpolation, PlaneTRHead._pyramid); the batch statistics are those of up2(c), which the kernels
+    evaluate on the fly, and the backward gathers the bilinear adjoint inside the BatchNorm backward's launch.  The raw conv output is
+    saved; the conv's dgrad / wgrad run at its own (low) resolution."""
 
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, addend, run_mean, run_var, batch_stats: bool):
+    def forward(ctx, x, w, gamma, beta, addend, run_mean, run_var, batch_stats: bool, up: bool):
         x = x.contiguous()
         c = ops.conv2d(x, _ohwi(w, x.shape[3]))
-        mean, rstd = _bn_statistics(c, False, run_mean, run_var, batch_stats)
-        ctx.batch_stats = batch_stats
+        mean, rstd = _bn_statistics(c, up, run_mean, run_var, batch_stats)
+        ctx.conf = (batch_stats, up)
         ctx.save_for_backward(x, w, c, gamma, beta, mean, rstd)
-        return ops.bn_train_apply(c, gamma, beta, mean, rstd, ops.ACT_RELU, None if addend is None else addend.contiguous())
+        return ops.bn_train_apply(c, gamma, beta, mean, rstd, ops.ACT_RELU, None if addend is None else addend.contiguous(), up=up)
 
     @staticmethod
     def backward(ctx, g):
         x, w, c, gamma, beta, mean, rstd = ctx.saved_tensors
+        batch_stats, up = ctx.conf
         g = g.contiguous()
-        dc, dgamma, dbeta = ops.bn_train_backward(g, c, gamma, beta, mean, rstd, ops.ACT_RELU, batch_stats=ctx.batch_stats)
+        dc, dgamma, dbeta = ops.bn_train_backward(g, c, gamma, beta, mean, rstd, ops.ACT_RELU, up=up, batch_stats=batch_stats)
         dx, dw = _conv_input_grads(ctx, x, w, dc, 1, 0)
-        return dx, dw, dgamma, dbeta, (g if ctx.needs_input_grad[4] else None), None, None, None
+        return dx, dw, dgamma, dbeta, (g if ctx.needs_input_grad[4] else None), None, None, None, None
 
 
-class _UpStageTrain(torch.autograd.Function):
-    """An up stage of the top-down pyramid: relu(bn(conv1x1(up2(x)))) + lateral, evaluated as relu(bn(up2(t))) + lateral with
-    t = conv1x1(x) at the LOW resolution (the 1x1 conv commutes with the bilinear interpolation, PlaneTRHead._pyramid); the BatchNorm's
-    batch statistics are those of up2(t), which the kernels evaluate on the fly.  Backward: the BatchNorm backward and the bilinear adjoint
-    in one gather (ops.bn_train_backward with up=True), then the conv's dgrad / wgrad at the low resolution."""
-
-    @staticmethod
-    def forward(ctx, x, w, gamma, beta, lateral, run_mean, run_var, batch_stats: bool):
-        x = x.contiguous()
-        t = ops.conv2d(x, _ohwi(w, x.shape[3]))
-        mean, rstd = _bn_statistics(t, True, run_mean, run_var, batch_stats)
-        ctx.batch_stats = batch_stats
-        ctx.save_for_backward(x, w, t, gamma, beta, mean, rstd)
-        return ops.bn_train_apply(t, gamma, beta, mean, rstd, ops.ACT_RELU, lateral.contiguous(), up=True)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w, t, gamma, beta, mean, rstd = ctx.saved_tensors
-        g = g.contiguous()
-        dt, dgamma, dbeta = ops.bn_train_backward(g, t, gamma, beta, mean, rstd, ops.ACT_RELU, up=True, batch_stats=ctx.batch_stats)
-        dx, dw = _conv_input_grads(ctx, x, w, dt, 1, 0)
-        return dx, dw, dgamma, dbeta, (g if ctx.needs_input_grad[4] else None), None, None, None
-
-
-class PlanePyramidTrainer(RefineTrainer):
+class PlanePyramidTrainer(ChainedTrainer):
     """The plane head's top-down pyramid in TRAINING mode (reference top_down, planeTR_head.py:209-252, unfrozen: cfg.MODEL.FREEZE = []):
     eight 1x1 convs without bias, each followed by an nn.BatchNorm2d on BATCH statistics and a ReLU - 24 parameters (conv weight, BN
     weight, BN bias) under their state-dict keys, plus the 16 running-statistics buffers and the eight num_batches_tracked counters
@@ -1567,14 +1524,13 @@ class PlanePyramidTrainer(RefineTrainer):
     head's algebra (the conv at the low resolution).  Optimiser groups (train_NopeSAC.py:88-135): the 16 BatchNorm affine tensors take
     WEIGHT_DECAY_NORM; the learning rate carries SOLVER.SEM_SEG_HEAD_MULTIPLIER."""
 
+    KEY_PREFIX, LR_MULTIPLIER, OUTPUT = PLANE_PREFIX, "SEM_SEG_HEAD_MULTIPLIER", "p1"
+
     def __init__(self, params: Dict[str, torch.Tensor], buffers: Dict[str, torch.Tensor], feature_grads: bool = False):
-        super().__init__(params, 0)
+        super().__init__(params)
         self.feature_grads = bool(feature_grads)
         self.buffers = {k: (v.detach().clone().to(torch.int64) if k.endswith("num_batches_tracked") else v.detach().clone().float().contiguous())
                         for k, v in buffers.items()}
-        self.grads: Dict[str, torch.Tensor] = {}
-        self._inputs: Dict[str, torch.Tensor] = {}
-        self._p1 = self._heads = None
         _require(len(self.params) == 24 and len(self.buffers) == 24,
                  "PlanePyramidTrainer: 24 parameters and 24 buffers expected, got %d and %d" % (len(self.params), len(self.buffers)))
 
@@ -1594,28 +1550,17 @@ class PlanePyramidTrainer(RefineTrainer):
     @classmethod
     def from_state_dict(cls, sd: dict, device, feature_grads: bool = False) -> "PlanePyramidTrainer":
         keys = list(sd.keys())
-        return cls({k: sd[k].to(device) for k in cls.parameter_names(keys)}, {k: sd[k].to(device) for k in cls.buffer_names(keys)}, feature_grads)
+        return cls(cls._read(sd, cls.parameter_names(keys), device), cls._read(sd, cls.buffer_names(keys), device), feature_grads)
 
     @classmethod
     def from_head(cls, head, feature_grads: bool = False) -> "PlanePyramidTrainer":
-        keys = [PLANE_PREFIX + k for k in head._spec_keys]
-        raw = lambda k: head.raw(k[len(PLANE_PREFIX):])
-        return cls({k: raw(k) for k in cls.parameter_names(keys)}, {k: raw(k) for k in cls.buffer_names(keys)}, feature_grads)
-
-    def lr_multiplier(self, cfg) -> float:
-        return float(cfg.SOLVER.SEM_SEG_HEAD_MULTIPLIER)
-
-    def _weight_decay(self, key: str, weight_decay: float, weight_decay_norm: Optional[float]) -> float:
-        norm = key.split(".")[-2] == "1"                                           # conv_bn_relu: Sequential(0 = conv, 1 = BatchNorm2d, 2 = ReLU)
-        return weight_decay if weight_decay_norm is None or not norm else weight_decay_norm
+        keys = cls._head_keys(head)
+        return cls(cls._read(head, cls.parameter_names(keys)), cls._read(head, cls.buffer_names(keys)), feature_grads)
 
     def write_back(self, head):
         """Copy the trained tensors AND the running statistics / counters into the inference PlaneTRHead and drop its packed copies (the
         BatchNorm folds among them: rebuilt on the next forward)."""
-        with torch.no_grad():
-            for k, t in list(self.params.items()) + list(self.buffers.items()):
-                head.raw(k[len(PLANE_PREFIX):]).copy_(t)
-        head.invalidate()
+        self._copy_into(head, {**self.params, **self.buffers})
 
     # ---- forward
     def forward(self, feats: dict, memory: torch.Tensor, B: int, batch_stats: bool = True) -> torch.Tensor:
@@ -1633,45 +1578,21 @@ class PlanePyramidTrainer(RefineTrainer):
         _require(tuple(memory.shape) == (B * hc * wc, 256) and memory.dtype == torch.float32,
                  "PlanePyramidTrainer: memory [%d, 256] f32 expected, got %s" % (B * hc * wc, tuple(memory.shape)))
         mem = memory if memory.requires_grad else memory.detach().requires_grad_(True)
-        self._inputs = dict({"memory": mem}, **{k: t for k, t in c.items() if t.requires_grad})
-        for t in self._inputs.values():
-            if not t.is_leaf:
-                t.retain_grad()
+        self._watch(dict({"memory": mem}, **{k: t for k, t in c.items() if t.requires_grad}))       # (memory: through m_conv_dict.m4)
         bs = bool(batch_stats)
 
-        def stage(fn, x, nm, other):
+        def stage(up, x, nm, other):
             q = f"{PLANE_PREFIX}{TOP_DOWN}.{nm}"
-            y = fn.apply(x, P[q + ".0.weight"], P[q + ".1.weight"], P[q + ".1.bias"], other, Bf[q + ".1.running_mean"], Bf[q + ".1.running_var"], bs)
+            y = _ConvBNTrain.apply(x, P[q + ".0.weight"], P[q + ".1.weight"], P[q + ".1.bias"], other, Bf[q + ".1.running_mean"],
+                                   Bf[q + ".1.running_var"], bs, up)
             if bs:
                 Bf[q + ".1.num_batches_tracked"] += 1
             return y
-        p4 = stage(_ConvBNTrain, mem.view(B, hc, wc, 256), "m_conv_dict.m4", stage(_ConvBNTrain, c["res5"], "c4_conv", None))
-        p3 = stage(_UpStageTrain, p4, "up_conv3", stage(_ConvBNTrain, c["res4"], "c3_conv", None))
-        p2 = stage(_UpStageTrain, p3, "up_conv2", stage(_ConvBNTrain, c["res3"], "c2_conv", None))
-        self._p1 = stage(_UpStageTrain, p2, "up_conv1", stage(_ConvBNTrain, c["res2"], "c1_conv", None))
-        return self._p1
-
-    # ---- backward
-    def _clear_grads(self):
-        for t in self.params.values():
-            t.grad = None
-        for t in self._inputs.values():
-            if t.is_leaf:
-                t.grad = None
-
-    def _collect(self) -> Dict[str, torch.Tensor]:
-        self.input_grads = {k: t.grad for k, t in self._inputs.items() if t.grad is not None}
-        self.grads = {k: (t.grad if t.grad is not None else torch.zeros_like(t)) for k, t in self.params.items()}
-        return self.grads
-
-    def backward_from(self, d_p1: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """The gradient at p1 (what PlaneInstanceHeadsTrainer.input_grads["p1"] holds for the last forward's p1) -> {state-dict key:
-        gradient} of the 24 parameters (also `.grads`); `.input_grads["memory"]` = the gradient at the encoder memory through m_conv_dict.m4
-        and, with feature_grads, `.input_grads["res2" .. "res5"]` = the gradients at the backbone maps."""
-        _require(self._p1 is not None and tuple(d_p1.shape) == tuple(self._p1.shape), "PlanePyramidTrainer.backward_from: d_p1 like the last forward's p1")
-        self._clear_grads()
-        torch.autograd.backward(self._p1, d_p1.contiguous())
-        return self._collect()
+        p4 = stage(False, mem.view(B, hc, wc, 256), "m_conv_dict.m4", stage(False, c["res5"], "c4_conv", None))
+        p3 = stage(True, p4, "up_conv3", stage(False, c["res4"], "c3_conv", None))
+        p2 = stage(True, p3, "up_conv2", stage(False, c["res3"], "c2_conv", None))
+        self._out = stage(True, p2, "up_conv1", stage(False, c["res2"], "c1_conv", None))
+        return self._out
 
     def losses(self, heads: "PlaneInstanceHeadsTrainer", feats: dict, memory: torch.Tensor, hs: torch.Tensor, targets: dict,
                batch_stats: bool = True, num_masks: Optional[float] = None):
@@ -1679,14 +1600,6 @@ class PlanePyramidTrainer(RefineTrainer):
         supervision p1 feeds every supervised layer's masks).  hs [L, B, nq, 256]: constants, or PlaneDecoderTrainer.forward's output."""
         self._heads = heads
         return heads.losses(hs, self.forward(feats, memory, hs.shape[1], batch_stats), targets, num_masks)
-
-    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
-        """The chain's backward: the instance heads' backward runs on through p1 into the pyramid.  -> the gradients of both trainers'
-        tensors by state-dict key (`.grads` holds the pyramid's)."""
-        _require(self._heads is not None, "PlanePyramidTrainer.backward: call losses() first (backward_from takes a gradient at p1)")
-        self._clear_grads()
-        head_grads = self._heads.backward(losses, loss_weights)
-        return {**self._collect(), **head_grads}
 
 
 def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torch.Tensor, nq: int) -> torch.Tensor:

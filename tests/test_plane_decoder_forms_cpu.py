@@ -131,8 +131,8 @@ def test_the_trainer_holds_the_111_tensors_in_the_references_optimiser_groups():
     norm = [k for k in tr.params if k.split(".")[-2].startswith("norm")]
     assert len(norm) == 6 * 6 + 2 and all(decay[k] == 0.25 for k in norm)
     assert all(v == 0.5 for k, v in decay.items() if k not in norm)
-    tr.weight_decay_embed = 0.125
-    assert tr._weight_decay(D.PREFIX + "query_embed.weight", 0.5, 0.25) == 0.125 and tr._weight_decay(norm[0], 0.5, None) == 0.5
+    assert tr._weight_decay(D.PREFIX + "query_embed.weight", 0.5, 0.25, 0.125) == 0.125 and tr._weight_decay(norm[0], 0.5, None) == 0.5
+    assert not hasattr(tr, "weight_decay_embed")                                     # an argument of the step, not state carried across calls
     cfg = get_cfg()
     assert tr.lr_multiplier(cfg) == float(cfg.SOLVER.SEM_SEG_HEAD_MULTIPLIER)
     with pytest.raises(Exception):
