@@ -1244,6 +1244,26 @@ nps_status nopesac_bn_train_backward_f32(const float* dy, const float* src, int 
                                          float* dsrc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
 nps_status nopesac_upsample2x_bilinear_backward_f32(const float* du, float* dx, int B, int H, int W, int C, void* stream);
 
+/* ---- backward of a Linear with its operands read in place (csrc/linear_bwd.hip; training._LinearInPlace, PlaneEncoderTrainer) ---------
+ * For y = act(x W^T + b) with x [M][K] (row stride x_stride), W [N][K] dense, and g [M][N] (row stride g_stride) the gradient at the
+ * layer's output:  dx [M][K] (row stride dx_stride) = g' W,  dw [N][K] dense = g'^T x,  db [N] = column sums of g'.  g' is g behind two
+ * optional gates, applied as the tiles are loaded (no launch writes a gated or transposed copy of x, g or y):
+ *   y != null:  g'[m][n] = y[m][n] > 0 ? g[m][n] : 0        (the ReLU of the saved output, row stride y_stride);
+ *   p > 0:      g'[m][n] = keep(m N + n) ? g'[m][n] / (1 - p) : 0, keep = csrc/dropout.h's decision under (seed, stream_id) at the
+ *               row-major index in [M][N] - a dropout that sits directly behind the Linear (behind its ReLU, if both).
+ * Each of dx, dw, db may be null (not computed); w is needed for dx, x for dw.  Exact-f32 MFMA on 128 x 128 tiles
+ * (NPS_LINEAR_BWD_TILE); dw and db are split over `splits` (1 .. 1024) ranges of rows of M, rounded up to NPS_LINEAR_BWD_STAGE rows (a
+ * range past M contributes zeros), written as partials into ws and summed in a fixed order: no atomics, the same inputs give the same
+ * bits.  ws: at least NPS_LINEAR_BWD_WORKSPACE_FLOATS(N, K, splits) floats when dw or db is asked for (else it may be null).
+ * NPS_E_ARG: K, N or a stride not a multiple of 4, a stride narrower than its row, a pointer not 16-byte aligned, M outside
+ * 1 .. 2^31 - 1 (dx: at most 65535 row tiles), p outside [0, 1), a short workspace. */
+#define NPS_LINEAR_BWD_TILE 128
+#define NPS_LINEAR_BWD_STAGE 16
+#define NPS_LINEAR_BWD_WORKSPACE_FLOATS(N, K, splits) ((int64_t)(splits) * ((int64_t)(N) * (K) + (N)))
+nps_status nopesac_linear_backward_f32(const float* x, int64_t x_stride, const float* w, const float* g, int64_t g_stride, const float* y,
+                                       int64_t y_stride, double p, int64_t seed, int64_t stream_id, float* dx, int64_t dx_stride, float* dw,
+                                       float* db, float* ws, int64_t ws_floats, int64_t M, int K, int N, int splits, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

@@ -6,8 +6,9 @@
 //   key  = mix64(stream + mix64(seed))                 one word per (seed, site): dropout_key, wave-uniform, hoisted out of every loop
 //   keep = (mix64(index + key) >> 32) >= threshold     threshold = floor(p 2^32) (host, double arithmetic): P(keep) = 1 - threshold / 2^32
 //
-// `stream` names the dropout site (the decoder trainer uses step * 64 + layer * 8 + site), `index` is the row-major index of the element in
-// the logical tensor.  All arithmetic is modulo 2^64.  threshold == 0 (p == 0) keeps everything; callers test it first and skip the hash.
+// `stream` names the dropout site (the decoder trainer uses step * 64 + layer * 8 + site >= 0, the encoder trainer
+// -(step * 32 + layer * 4 + site) - 1 < 0: disjoint under one seed, and dropout_key works modulo 2^64), `index` is the row-major index of
+// the element in the logical tensor.  All arithmetic is modulo 2^64.  threshold == 0 (p == 0) keeps everything; callers test it first and skip the hash.
 #pragma once
 #include <stdint.h>
 

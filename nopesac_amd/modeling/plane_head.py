@@ -487,6 +487,15 @@ class PlaneTRHead(ParamModule):
             memory, _ = self._encoder_f32(src, self._pos(hc, wc, c4.device), B, hc * wc, self.nheads, 32 ** -0.5, f32)
             return memory, feats
 
+    def encoder_training_inputs(self, features: dict):
+        """The tensors where the FROZEN part ends when the whole head trains (training.PlaneEncoderTrainer in front of the decoder, the
+        pyramid and the instance heads): (feats: the four backbone maps res2 .. res5 as f32 NHWC, as pyramid_training_inputs returns
+        them; pos [Lm, 256]: the sine position embedding of res5's grid, a constant).  Without autograd."""
+        with torch.no_grad():
+            feats = {k: features[k].float().contiguous() for k in ("res2", "res3", "res4", "res5")}
+            c4 = feats["res5"]
+            return feats, self._pos(c4.shape[1], c4.shape[2], c4.device)
+
     def _heads(self, features, hs, memory, B, hc, wc, nq, want_logits, mark):
         P, gd = self.packed, self.gemm_dtype
         c1, c2, c3, c4 = features["res2"], features["res3"], features["res4"], features["res5"]

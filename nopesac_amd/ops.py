@@ -2357,3 +2357,72 @@ def attention_train_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
                                         float(p), int(seed), int(stream), _p(dq), so[0], _p(dk), so[1], _p(dv), so[2], _p(ws), ws.numel(),
                                         _stream())
     return dq, dk, dv
+
+
+# ---------------------------------------------------------------- Linear backward with the operands read in place (csrc/linear_bwd.hip)
+LINEAR_BWD_TILE, LINEAR_BWD_STAGE = _H.NPS_LINEAR_BWD_TILE, _H.NPS_LINEAR_BWD_STAGE       # output tile edge / rows of M per LDS stage
+
+
+def encoder_dropout_stream(step: int, layer: int, site: int) -> int:
+    """The counter stream of one dropout site of the plane head's encoder: -(step * 32 + layer * 4 + site) - 1, site 0 .. 3 = attention
+    probabilities, dropout1, FFN inner, dropout2.  Negative, so disjoint from every decoder stream (dropout_stream >= 0) under one seed."""
+    _require(0 <= site < 4 and 0 <= layer < 8 and step >= 0, "encoder_dropout_stream: step >= 0, layer 0..7, site 0..3")
+    return -(int(step) * 32 + int(layer) * 4 + int(site)) - 1
+
+
+def linear_backward_splits(M: int, K: int, N: int) -> int:
+    """Row-range count of linear_backward's dW / db launch: about 512 workgroups over the 128 x 128 tiles of dW, at least 256 rows each."""
+    tiles = -(-N // LINEAR_BWD_TILE) * -(-K // LINEAR_BWD_TILE)
+    return max(1, min(256, -(-512 // tiles), M // 256))
+
+
+def linear_backward_workspace_floats(K: int, N: int, splits: int) -> int:
+    """The header's NPS_LINEAR_BWD_WORKSPACE_FLOATS: per row range one partial of dW and one of db."""
+    return int(splits) * (int(N) * int(K) + int(N))
+
+
+def linear_backward(x: Optional[torch.Tensor], w: torch.Tensor, g: torch.Tensor, *, y: Optional[torch.Tensor] = None, p: float = 0.0,
+                    seed: int = 0, stream: int = 0, want=(True, True, True), dx: Optional[torch.Tensor] = None,
+                    splits: Optional[int] = None, ws: Optional[torch.Tensor] = None):
+    """Backward of y = act(x W^T + b): x [M, K], w [N, K] dense, g [M, N] the gradient at the output -> (dx [M, K], dw [N, K], db [N]),
+    None where `want` = (dx, dw, db) says no.  The gradient is gated as it is loaded: y (the saved output) = the ReLU's y > 0; p > 0 = the
+    counter-based dropout behind the Linear at the row-major index in [M, N] under (seed, stream), times 1 / (1 - p).  x, g, y and the
+    optional output `dx` may be column slices of wider row-major buffers; nothing is copied or transposed.  Deterministic.  `splits` /
+    `ws`: the row-range count of the dW / db launch and its workspace (default: linear_backward_splits, the cached per-stream buffer)."""
+    _require(g.dim() == 2 and w.dim() == 2, "linear_backward: g [M, N], w [N, K]")
+    M, N = g.shape
+    K = w.shape[1]
+    _require(w.shape[0] == N, "linear_backward: w [%d, K] expected, got %s" % (N, tuple(w.shape)))
+    _chk(w, torch.float32)
+    gs = _rows(g, M, N, "linear_backward: g")
+    want_dx, want_dw, want_db = (bool(t) for t in want)
+    xs = ys = ds = 0
+    if want_dw:
+        _require(x is not None and x.dim() == 2 and x.shape[1] == K, "linear_backward: x [M, %d] expected" % K)
+        xs = _rows(x, M, K, "linear_backward: x")
+    if y is not None:
+        _require(y.dim() == 2 and y.shape[1] == N, "linear_backward: y [M, %d] expected" % N)
+        ys = _rows(y, M, N, "linear_backward: y")
+    f32 = dict(device=g.device, dtype=torch.float32)
+    if want_dx:
+        if dx is None:
+            dx = torch.empty(M, K, **f32)
+        _require(dx.dim() == 2 and dx.shape[1] == K, "linear_backward: dx [M, %d] expected" % K)
+        ds = _rows(dx, M, K, "linear_backward: dx")
+    else:
+        dx = None
+    dw = torch.empty(N, K, **f32) if want_dw else None
+    db = torch.empty(N, **f32) if want_db else None
+    S = int(splits or linear_backward_splits(M, K, N))
+    n_ws = 0
+    if want_dw or want_db:
+        n_ws = linear_backward_workspace_floats(K, N, S)
+        if ws is None:
+            ws = wgrad_workspace(g.device, 4 * n_ws)
+        _chk(ws, torch.float32)
+        n_ws = ws.numel()
+    else:
+        ws = None
+    _C.nopesac_linear_backward_f32(_p(x) if want_dw else None, xs, _p(w), _p(g), gs, _p(y), ys, float(p), int(seed), int(stream), _p(dx), ds, _p(dw),
+                                   _p(db), _p(ws), n_ws, M, K, N, S, _stream())
+    return dx, dw, db

@@ -5,7 +5,7 @@ clipping, the reference's norm / embedding / plain groups stated once in paramet
 subclass names its state-dict prefix (KEY_PREFIX) and its SOLVER.*_MULTIPLIER (LR_MULTIPLIER) and adds its forward.  ChainedTrainer adds
 the protocol of a trainer whose output feeds the instance heads: forward, then backward_from(gradient at the output), or
 losses(heads, ...) followed by backward.  The trainers: RefineTrainer (with CameraHeadTrainer on top of it), MatchingHeadTrainer,
-PlaneInstanceHeadsTrainer, and the chained PlaneDecoderTrainer and PlanePyramidTrainer.
+PlaneInstanceHeadsTrainer, and the chained PlaneDecoderTrainer, PlanePyramidTrainer and PlaneEncoderTrainer.
 
 RefineTrainer is the camera head's refinement stage (reference: `__forward_PlaneCamRefHead`, camera_net/camera_head.py:737-923; losses
 camera_modules.py:355-365) - round 5.  Forward = the kernels of the training-side twin (ops.geo_sequence, ops.ransac_score_maps, ops.ransac_soft_vote mode | 16,
@@ -53,12 +53,20 @@ training-mode BatchNorm whose input is a matrix or the on-the-fly upsampling of 
 resolution, as in the inference head), with the bilinear adjoint gathered inside the backward's second launch.  The encoder memory is a
 shared input of this trainer and the decoder's: given the same leaf, autograd sums both paths.
 
-What this is NOT: a trainer for the whole network.  The backbone and the plane head's encoder have no backward kernels here - the
-gradients stop at the encoder memory and the backbone maps (`input_grads`, ready for an encoder / backbone backward to chain onto); the
+The plane head's transformer encoder (planeTR_head.py:77-82, 125-132, transformer/transformer.py:183-199: input_proj, six post-norm
+layers with dropout 0.1, the final norm - 76 tensors) is trained by PlaneEncoderTrainer, which takes the sum of the decoder's and the
+pyramid's gradients at the memory (backward_from) or chains all four plane-head trainers through one graph (losses / backward: the 235
+tensors of sem_seg_head).  Its Linears run on B x 300 rows, so their backward is _LinearInPlace: one call of ops.linear_backward
+(csrc/linear_bwd.hip) that reads x, the gradient and the saved output where they lie - the ReLU and the counter-based dropout behind
+the Linear are gates applied as the gradient's tiles are loaded - instead of _Linear's ReLU pass, three transposes, two GEMMs and a
+column sum.  _Linear and the trainers that use it are unchanged.
+
+What this is NOT: a trainer for the whole network.  The backbone has no backward kernels here - the gradients stop at the backbone
+maps (`input_grads`, ready for a backbone backward to chain onto); the
 backbone maps, the plane sets and their appearance features are inputs of the other stages, as they are of the reference functions, and
 receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
 against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py)
-and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py, tests/test_plane_pyramid_training_gpu.py)."""
+and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py, tests/test_plane_pyramid_training_gpu.py, tests/test_plane_encoder_training_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -80,6 +88,7 @@ GNN_LAYERS, GNN_HEADS, LN_EPS = 18, 8, 1e-5
 
 PLANE_PREFIX = "sem_seg_head."
 DECODER, TOP_DOWN = "context2plane_decoder", "top_down"              # the plane head's transformer decoder and top-down pyramid
+ENCODER, INPUT_PROJ = "context_SA", "input_proj"                     # its transformer encoder and the 1x1 conv on res5 in front of it
 
 
 def is_norm_parameter(key: str) -> bool:
@@ -101,13 +110,14 @@ def is_norm_parameter(key: str) -> bool:
 def parameter_group(key: str) -> str:
     """The optimiser group of a state-dict key, "norm", "embed" or "plain" (the reference's build_optimizer, train_NopeSAC.py:88-135:
     norm module types take WEIGHT_DECAY_NORM, nn.Embedding WEIGHT_DECAY_EMBED).  Under sem_seg_head.: query_embed is the embedding, the
-    decoder's LayerNorms (norm, norm1-3) and the BatchNorm of every pyramid block (conv_bn_relu: Sequential(0 = conv, 1 = BatchNorm2d,
+    decoder's and the encoder's LayerNorms (norm, norm1-3 / context_SA's norm, norm1-2) and the BatchNorm of every pyramid block (conv_bn_relu: Sequential(0 = conv, 1 = BatchNorm2d,
     2 = ReLU)) are norms, the instance heads have neither; the camera head and the matcher: is_norm_parameter."""
     if key.startswith(PLANE_PREFIX):
         parts = key[len(PLANE_PREFIX):].split(".")
         if parts[0] == "query_embed":
             return "embed"
-        norm = (parts[0] == DECODER and parts[-2] in ("norm", "norm1", "norm2", "norm3")) or (parts[0] == TOP_DOWN and parts[-2] == "1")
+        norm = ((parts[0] == DECODER and parts[-2] in ("norm", "norm1", "norm2", "norm3")) or (parts[0] == TOP_DOWN and parts[-2] == "1")
+                or (parts[0] == ENCODER and parts[-2] in ("norm", "norm1", "norm2")))
         return "norm" if norm else "plain"
     return "norm" if is_norm_parameter(key) else "plain"
 
@@ -150,6 +160,50 @@ class _Linear(torch.autograd.Function):
 
 def _linear(x, w, b=None, act: int = ops.ACT_NONE, residual=None):
     return _Linear.apply(x, w, b, act, residual)
+
+
+def _in_place_operand(t: torch.Tensor) -> torch.Tensor:
+    """t as ops.linear_backward reads it in place: rows of unit column stride, 16-byte aligned, a row stride that is a multiple of 4
+    (a column slice of a wider buffer qualifies); anything else is made dense."""
+    ok = t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+class _LinearInPlace(torch.autograd.Function):
+    """_Linear with the backward as ONE call of ops.linear_backward (csrc/linear_bwd.hip): no ReLU pass, no transposes, no column-sum
+    launch - x, the gradient and the saved output are read where they lie and the gates are applied as the tiles are loaded.  The
+    forward is _Linear's ops.linear launch (act: ops.ACT_NONE or ACT_RELU; a residual goes into the GEMM's epilogue), so the forward
+    bits are _Linear's.  p > 0: the dropout that sits directly behind the Linear is part of the Function -
+    out = ops.dropout(act(x W^T + b), p, seed, stream) + residual - and its mask is the backward call's second gate, recomputed from
+    the counter.  The residual's gradient is the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act: int, residual, p: float, seed: int, stream: int):
+        _require(act in (ops.ACT_NONE, ops.ACT_RELU), act)
+        _require(residual is None or act == ops.ACT_NONE, "_LinearInPlace: a residual goes with ACT_NONE")
+        x = x.contiguous()
+        res = None if residual is None else residual.contiguous()
+        if p == 0.0:
+            h = out = ops.linear(x, w, b, act=act, residual=res)
+        else:
+            h = ops.linear(x, w, b, act=act)
+            out = ops.dropout(h, p, seed, stream, residual=res)
+        ctx.conf = (float(p), int(seed), int(stream))
+        ctx.save_for_backward(x, w, *((h,) if act == ops.ACT_RELU else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, *y = ctx.saved_tensors
+        p, seed, stream = ctx.conf
+        g = _in_place_operand(g)
+        want = tuple(ctx.needs_input_grad[:3])
+        gx = gw = gb = None
+        if any(want):
+            gx, gw, gb = ops.linear_backward(x.view(-1, x.shape[-1]), w, g.view(-1, g.shape[-1]) if g.dim() != 2 else g,
+                                             y=y[0].view(-1, y[0].shape[-1]) if y else None, p=p, seed=seed, stream=stream, want=want)
+            gx = None if gx is None else gx.view(x.shape)
+        return gx, gw, gb, None, (g if ctx.needs_input_grad[4] else None), None, None, None
 
 
 def _mlp_stack(P: Dict[str, torch.Tensor], q: str, x, last_act: int = ops.ACT_NONE):
@@ -678,7 +732,8 @@ class HeadTrainer:
 
 
 class ChainedTrainer(HeadTrainer):
-    """A trainer whose output (OUTPUT: "hs" or "p1", kept by its forward in `_out`) is an input of PlaneInstanceHeadsTrainer: its backward
+    """A trainer whose output (OUTPUT: "hs", "p1" or - one trainer further up - "memory", kept by its forward in `_out`) feeds
+    PlaneInstanceHeadsTrainer: its backward
     starts from the gradient the heads report there (backward_from) or, after losses(heads, ...) has put both on one graph, runs the
     heads' backward on into this trainer (backward)."""
 
@@ -1600,6 +1655,192 @@ class PlanePyramidTrainer(ChainedTrainer):
         supervision p1 feeds every supervised layer's masks).  hs [L, B, nq, 256]: constants, or PlaneDecoderTrainer.forward's output."""
         self._heads = heads
         return heads.losses(hs, self.forward(feats, memory, hs.shape[1], batch_stats), targets, num_masks)
+
+
+class _ConvBiasInPlace(torch.autograd.Function):
+    """_ConvBias for a 1x1 conv (input_proj): the same forward launch; backward: one ops.linear_backward call on the pixels as rows."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x = x.contiguous()
+        ctx.save_for_backward(x, w)
+        return ops.conv2d(x, _ohwi(w, x.shape[3]), bias=b.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        Cout, Cin = w.shape[:2]
+        dx, dw, db = ops.linear_backward(x.view(-1, Cin), w.view(Cout, Cin), g.contiguous().view(-1, Cout), want=tuple(ctx.needs_input_grad))
+        return (None if dx is None else dx.view(x.shape)), (None if dw is None else dw.view(w.shape)), db
+
+
+class _EncoderAttention(torch.autograd.Function):
+    """Self attention of an encoder layer on qk = q | k [rows, 512] (one N = 512 Linear on src + pos) and v [rows, 256].  Forward at
+    p = 0: ops.attention, the inference head's launch; at p > 0: ops.attention_train.  Backward: ops.attention_train_backward, which
+    writes dq and dk straight into the two halves of one [rows, 512] gradient."""
+
+    @staticmethod
+    def forward(ctx, qk, v, B: int, L: int, heads: int, scale: float, p: float, seed: int, stream: int):
+        W = heads * 32
+        qk, v = qk.contiguous(), v.contiguous()
+        if p == 0.0:
+            o = ops.attention(qk[:, :W], qk[:, W:], v, B, L, L, heads, scale)
+        else:
+            o = ops.attention_train(qk[:, :W], qk[:, W:], v, B, L, L, heads, scale, p=p, seed=seed, stream=stream)
+        ctx.conf = (B, L, heads, float(scale), float(p), int(seed), int(stream))
+        ctx.save_for_backward(qk, v)
+        return o
+
+    @staticmethod
+    def backward(ctx, g):
+        qk, v = ctx.saved_tensors
+        B, L, heads, scale, p, seed, stream = ctx.conf
+        W = heads * 32
+        dqk, dv = torch.empty_like(qk), torch.empty_like(v)
+        ops.attention_train_backward(qk[:, :W], qk[:, W:], v, g.contiguous(), B, L, L, heads, scale, p=p, seed=seed, stream=stream,
+                                     out=(dqk[:, :W], dqk[:, W:], dv))
+        return dqk, dv, None, None, None, None, None, None, None
+
+
+ENCODER_LAYERS, ENCODER_HEADS = 6, 8
+ENC_DROP_ATTN, ENC_DROP_1, ENC_DROP_FFN, ENC_DROP_2 = range(4)                       # the dropout sites of a layer (ops.encoder_dropout_stream)
+
+
+class PlaneEncoderTrainer(ChainedTrainer):
+    """The plane head's transformer encoder in TRAINING mode (reference: planeTR_head.py:77-82, 125-132 and transformer/transformer.py:
+    183-199 with normalize_before=False, dropout 0.1): input_proj (the 1x1 conv 2048 -> 256 on res5), the six post-norm layers of
+    context_SA (self_attn in_proj + out_proj, linear1, linear2, norm1, norm2) and the final norm - 76 tensors under their state-dict
+    keys.  With it all 235 tensors of sem_seg_head train through one graph; only the backbone stays behind.
+
+        feats, pos = model.sem_seg_head.encoder_training_inputs(features)          # {res2 .. res5: f32 NHWC}, [Lm, 256] (no autograd)
+        enc = PlaneEncoderTrainer.from_head(model.sem_seg_head)                    # or .from_state_dict(sd, device)
+        memory = enc.forward(feats["res5"], B, p=0.1, seed=seed, step=it)          # [B*Lm, 256], autograd tape attached
+        enc.backward_from(d_memory)                                                # d_memory: the decoder's + the pyramid's input_grads["memory"]
+      or the whole head on one graph:
+        losses, indices = enc.losses(heads, decoder, pyramid, feats, targets, p=0.1, seed=seed, step=it)
+        grads = enc.backward(losses)                                               # all 235 tensors by key; each trainer's .grads is filled
+
+    At p = 0 every launch of the forward is the launch PlaneTRHead._encoder_f32 makes on its f32 route (input_proj included), so the same
+    parameters give decoder_training_inputs' memory bit for bit.  At p > 0 the four dropout sites of every layer are active: the
+    attention probabilities inside ops.attention_train, the two residual branches as ops.dropout(branch, residual=src) behind a plain
+    Linear, the FFN's hidden layer through ops.dropout behind its ReLU; the masks are functions of
+    (seed, ops.encoder_dropout_stream(step, layer, site), element index), recomputed in the backward, never stored.  in_proj_weight /
+    bias are one leaf each: the q | k rows and the v rows enter the Linears as autograd views.  Every Linear goes through LINEAR:
+    _LinearInPlace, whose backward is one ops.linear_backward call with the ReLU and dropout gates applied as the gradient is loaded
+    (set LINEAR = _Linear for the composition of the other trainers: the same forward bits).  Optimiser groups (train_NopeSAC.py:88-135):
+    the 26 LayerNorm tensors take WEIGHT_DECAY_NORM; the learning rate carries SOLVER.SEM_SEG_HEAD_MULTIPLIER."""
+
+    KEY_PREFIX, LR_MULTIPLIER, OUTPUT = PLANE_PREFIX, "SEM_SEG_HEAD_MULTIPLIER", "memory"
+    LINEAR = _LinearInPlace
+
+    def __init__(self, params: Dict[str, torch.Tensor], feature_grads: bool = False, pos=None):
+        super().__init__(params)
+        self.feature_grads = bool(feature_grads)
+        self._pos_of = pos                              # (h, w, device) -> the sine embedding [h w, 256]; default: the head's own function
+        self._pos_cache: Dict[tuple, torch.Tensor] = {}
+        self._chain = None
+        _require(len(self.params) == 12 * ENCODER_LAYERS + 4, "PlaneEncoderTrainer: 76 tensors expected, got %d" % len(self.params))
+        _require(self.LINEAR in (_LinearInPlace, _Linear), "PlaneEncoderTrainer.LINEAR: _LinearInPlace or _Linear (forward and _linear_site know these two)")
+
+    @staticmethod
+    def parameter_names(sd_keys) -> List[str]:
+        return sorted(k for k in sd_keys if k.startswith(PLANE_PREFIX + ENCODER + ".") or k.startswith(PLANE_PREFIX + INPUT_PROJ + "."))
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device, feature_grads: bool = False) -> "PlaneEncoderTrainer":
+        return cls(cls._read(sd, cls.parameter_names(sd.keys()), device), feature_grads)
+
+    @classmethod
+    def from_head(cls, head, feature_grads: bool = False) -> "PlaneEncoderTrainer":
+        return cls(cls._read(head, cls.parameter_names(cls._head_keys(head))), feature_grads, head._pos)
+
+    def pos(self, h: int, w: int, device) -> torch.Tensor:
+        """The head's sine position embedding of an h x w map, [h w, 256] f32 on `device`: a constant."""
+        if self._pos_of is not None:
+            return self._pos_of(h, w, device)
+        key = (h, w, str(device))
+        if key not in self._pos_cache:
+            from .modeling.plane_head import sine_position_embedding
+            self._pos_cache[key] = sine_position_embedding(h, w).to(device)
+        return self._pos_cache[key]
+
+    # ---- forward
+    def _linear_site(self, x, w, b, act: int = ops.ACT_NONE, residual=None, p: float = 0.0, seed: int = 0, stream: int = 0):
+        """act(x W^T + b), then (p > 0) the dropout that sits behind it, then + residual."""
+        if self.LINEAR is _LinearInPlace:
+            return _LinearInPlace.apply(x, w, b, act, residual, p, seed, stream)
+        if p == 0.0:
+            return self.LINEAR.apply(x, w, b, act, residual)
+        return _Dropout.apply(self.LINEAR.apply(x, w, b, act, None), residual, p, seed, stream)
+
+    def forward(self, res5: torch.Tensor, B: int, p: float = 0.0, seed: int = 0, step: int = 0, pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """res5 [B, h, w, 2048] f32 NHWC (pyramid_training_inputs' / encoder_training_inputs' feats["res5"]) -> memory [B*h*w, 256], the
+        encoder's output with rows in (b, token) order, autograd tape attached.  p: the dropout rate (0 = the inference head's launches),
+        seed / step: the counter's seed and the training step the masks are drawn for; pos [h w, 256]: the position embedding, if not the
+        head's."""
+        P, nh = self.params, ENCODER_HEADS
+        p, seed = float(p), int(seed)
+        _require(res5.dim() == 4 and res5.shape[0] == B and res5.shape[3] == 2048 and res5.dtype == torch.float32,
+                 "PlaneEncoderTrainer: res5 [%d, h, w, 2048] f32 expected, got %s" % (B, tuple(res5.shape)))
+        h, w = res5.shape[1:3]
+        L = h * w
+        pos = (self.pos(h, w, res5.device) if pos is None else pos).detach()
+        _require(tuple(pos.shape) == (L, 256) and pos.dtype == torch.float32, "PlaneEncoderTrainer: pos [%d, 256] f32 expected, got %s" % (L, tuple(pos.shape)))
+        c4 = res5.detach().requires_grad_(True) if self.feature_grads and not res5.requires_grad else res5
+        self._watch({"res5": c4} if c4.requires_grad else {})
+        q = PLANE_PREFIX + INPUT_PROJ
+        if self.LINEAR is _LinearInPlace:
+            src = _ConvBiasInPlace.apply(c4, P[q + ".weight"], P[q + ".bias"]).view(B * L, 256)
+        else:
+            src = _ConvBias.apply(c4, P[q + ".weight"], P[q + ".bias"], 0).view(B * L, 256)
+        q_in = _AddRows.apply(src, pos)
+        scale = 32 ** -0.5
+        site = lambda i, s: ops.encoder_dropout_stream(step, i, s)
+        for i in range(ENCODER_LAYERS):
+            q = f"{PLANE_PREFIX}{ENCODER}.layers.{i}."
+            wi, bi = P[q + "self_attn.in_proj_weight"], P[q + "self_attn.in_proj_bias"]
+            qk = self._linear_site(q_in, wi[:512], bi[:512])
+            v = self._linear_site(src, wi[512:], bi[512:])
+            o = _EncoderAttention.apply(qk, v, B, L, nh, scale, p, seed, site(i, ENC_DROP_ATTN))
+            s = self._linear_site(o, P[q + "self_attn.out_proj.weight"], P[q + "self_attn.out_proj.bias"], residual=src, p=p, seed=seed,
+                          stream=site(i, ENC_DROP_1))
+            src = _LayerNorm.apply(s, P[q + "norm1.weight"], P[q + "norm1.bias"], None)
+            hdn = self._linear_site(src, P[q + "linear1.weight"], P[q + "linear1.bias"], ops.ACT_RELU, p=p, seed=seed, stream=site(i, ENC_DROP_FFN))
+            s = self._linear_site(hdn, P[q + "linear2.weight"], P[q + "linear2.bias"], residual=src, p=p, seed=seed, stream=site(i, ENC_DROP_2))
+            src, q_in = _LayerNormPair.apply(s, P[q + "norm2.weight"], P[q + "norm2.bias"], pos)
+        q = f"{PLANE_PREFIX}{ENCODER}.norm."
+        self._out, _ = _LayerNormPair.apply(src, P[q + "weight"], P[q + "bias"], pos)
+        return self._out
+
+    # ---- the whole head on one graph
+    def losses(self, heads: "PlaneInstanceHeadsTrainer", decoder: "PlaneDecoderTrainer", pyramid: "PlanePyramidTrainer", feats: dict,
+               targets: dict, p: float = 0.0, seed: int = 0, step: int = 0, batch_stats: bool = True, num_masks: Optional[float] = None):
+        """Encoder, then the decoder and the pyramid on this forward's memory, then the instance heads and their PlaneCriterion:
+        -> (losses, indices) of heads.losses.  feats: res2 .. res5 f32 NHWC.  The decoder and the pyramid each take their own view of
+        the one non-leaf memory, so each reports its own path in input_grads["memory"] and the encoder receives their two-term sum."""
+        res5 = feats["res5"]
+        B, h, w = res5.shape[:3]
+        memory = self.forward(res5, B, p, seed, step)
+        if "res5" in self._inputs:                                  # the leaf the encoder watches is the pyramid's too: both paths sum
+            feats = dict(feats, res5=self._inputs["res5"])
+        hs = decoder.forward(memory.view_as(memory), self.pos(h, w, res5.device), B, p, seed, step)
+        p1 = pyramid.forward(feats, memory.view_as(memory), B, batch_stats)
+        self._heads, self._chain = heads, (decoder, pyramid)
+        return heads.losses(hs, p1, targets, num_masks)
+
+    def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+        """The chain's backward: the instance heads' backward runs on through the decoder and the pyramid into the encoder.  -> the
+        gradients of all 235 tensors of sem_seg_head by state-dict key; every trainer's `.grads` / `.input_grads` is filled."""
+        _require(self._heads is not None and self._chain is not None, "PlaneEncoderTrainer.backward: call losses() first (backward_from takes a gradient at memory)")
+        chain = (self,) + tuple(self._chain)
+        for t in chain:
+            t._clear_grads()
+        head_grads = self._heads.backward(losses, loss_weights)
+        out: Dict[str, torch.Tensor] = {}
+        for t in chain:
+            out.update(t._collect())
+        out.update(head_grads)
+        return out
 
 
 def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torch.Tensor, nq: int) -> torch.Tensor:
