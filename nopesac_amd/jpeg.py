@@ -3,10 +3,16 @@ libjpeg-turbo decode, NopeSAC_Net/data/planercnn_transforms.py:210-227 and :306-
 
 Host side (this file): marker walk, restart-interval split, removal of the byte stuffing, Huffman lookup tables - a few numpy calls
 per file, no entropy decoding.  Device side (csrc/jpeg.hip, include/nopesac_hip.h `nopesac_jpeg_*`): Huffman decode (restart-free
-files: self-synchronising, one lane per 2048-bit subsequence; files with restart markers and streams the lanes do not settle on: one
-wave per restart interval on the scalar unit), dequantisation + libjpeg's 13-bit "islow" inverse DCT,
+files: self-synchronising, one lane per 2048-bit subsequence; files with restart markers and streams the lanes do not settle on within
+NOPESAC_JPEG_SYNC_PASSES passes: one wave per restart interval on the scalar unit), dequantisation + libjpeg's 13-bit "islow" inverse DCT,
 "fancy" (triangle) chroma upsampling and the 16-bit fixed-point YCbCr -> RGB conversion, bit for bit what libjpeg-turbo produces with
-its default decompression parameters (tests/test_jpeg_gpu.py against Pillow-decoded fixtures and oracle/jpeg_oracle.py).
+its default decompression parameters (tests/test_jpeg_gpu.py against Pillow-decoded fixtures and oracle/jpeg_oracle.py;
+tests/test_jpeg_streams_gpu.py on written streams no encoder produces, against the writer's coefficients and the oracle's pixels).
+
+One documented deviation, outside what a conforming encoder writes: where the inverse DCT's value before the range limit leaves
+[-512, 511] (dense coefficients of +-32 at q = 8 get there), the kernel follows jidctint.c's range-limit table, which WRAPS modulo
+1024 - libjpeg-turbo's SIMD inverse DCT, which Pillow runs, SATURATES, and the two differ by up to 255 there (pinned by
+tests/test_jpeg_streams_cpu.py on the `idct_wrap` stream).
 
 Supported: SOF0 / SOF1 (baseline / extended sequential Huffman), 8-bit, ONE scan with all components, gray or YCbCr with luma sampling
 1x1 / 2x1 / 2x2 and 1x1 chroma.  Everything else (progressive, arithmetic, CMYK, multi-scan) raises JpegUnsupported: the caller
@@ -156,7 +162,8 @@ def parse_markers(data: bytes, fast: bool = True) -> JpegInfo:
                 ecs = data[p:end.start()]
                 cuts = [m_.start() for m_ in _RST.finditer(ecs)] if info.dri else []
             # (after stuffing, FF D0..D7 inside the scan can only be a restart marker)
-            parts = [ecs[a:b] for a, b in zip([0] + [c + 2 for c in cuts], cuts + [len(ecs)])]
+            # (a part that ends on FFs ends on fill bytes in front of the marker, T.81 B.1.1.2: a data FF is followed by its stuffed zero)
+            parts = [ecs[a:b].rstrip(b"\xff") for a, b in zip([0] + [c + 2 for c in cuts], cuts + [len(ecs)])]
             info.intervals = [q.replace(b"\xff\x00", b"\xff") for q in parts]
             break
         p += L
@@ -418,7 +425,9 @@ def decode_batch(files: Sequence[bytes], device, bgr: bool = False, infos: Seque
     current stream.  Raises JpegUnsupported if any file is outside the supported subset (nothing is decoded then).
     parallel: restart-free streams go through the self-synchronising decoder (nopesac_jpeg_huffman_parallel; images it does not
     settle fall through to the one-wave-per-interval kernel on the device, no host involvement).  stats: receives the device tensors
-    "par_done" (int32 per image) and "changed" (lanes that moved per pass and image) for diagnostics.  host: the batch's HostBatch when
+    "par_done" (int32 per image) and "changed" (lanes that moved per pass and image) for diagnostics when the batch has lanes, and always
+    "coef" (the batch's quantised coefficients, int16, per component [block rows][blocks per row][64] in zigzag order with the DC
+    prediction resolved) with "coef_off" (host int64 [n][3]: the element offset of every component in it).  host: the batch's HostBatch when
     the caller prepared it already (prepare_batch, e.g. on a reader thread)."""
     if host is None:
         infos = list(infos) if infos is not None else [parse(f) for f in files]
@@ -436,6 +445,8 @@ def decode_batch(files: Sequence[bytes], device, bgr: bool = False, infos: Seque
     t_words = up(host.words)
     img64 = host.img64
     coef = torch.zeros(host.coef_off, device=dev, dtype=torch.int16)
+    if stats is not None:                                 # the entropy stage's output as the IDCT reads it, and where each component starts
+        stats["coef"], stats["coef_off"] = coef, img64[:, 0:3]
     planes = torch.empty(host.plane_off, device=dev, dtype=torch.uint8)
     out = torch.empty(host.out_off, device=dev, dtype=torch.uint8)
     st = _stream()

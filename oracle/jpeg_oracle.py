@@ -95,29 +95,23 @@ def parse(data: bytes) -> dict:
             if (seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns]) != (0, 63, 0):
                 raise Unsupported("spectral selection / successive approximation")
             p += L
-            e = p
-            while True:                                   # end of the entropy-coded segment: FF followed by neither 00 nor RSTn
-                e = data.find(b"\xff", e)
+            intervals, s, e = [], p, p
+            while True:                                   # an interval ends at an FF that is not stuffing: a marker, or fill bytes (any
+                e = data.find(b"\xff", e)                  # number of FFs, T.81 B.1.1.2) in front of one - RSTn goes on, anything else ends
                 if e < 0 or e + 1 >= n:
                     raise Unsupported("no EOI")
-                if data[e + 1] == 0 or 0xD0 <= data[e + 1] <= 0xD7:
+                if data[e + 1] == 0:
                     e += 2
                     continue
-                break
-            ecs = data[p:e]
-            intervals, s = [], 0
-            while True:                                   # split at RSTn (after stuffing, FF Dn can only be a marker)
-                k = s
-                while True:
-                    k = ecs.find(b"\xff", k)
-                    if k < 0 or (k + 1 < len(ecs) and 0xD0 <= ecs[k + 1] <= 0xD7):
-                        break
-                    k += 2
-                part = ecs[s:k if k >= 0 else len(ecs)]
-                intervals.append(part.replace(b"\xff\x00", b"\xff"))
-                if k < 0:
+                f = e
+                while f + 1 < n and data[f + 1] == 0xFF:
+                    f += 1
+                if f + 1 >= n:
+                    raise Unsupported("no EOI")
+                intervals.append(data[s:e].replace(b"\xff\x00", b"\xff"))
+                if not 0xD0 <= data[f + 1] <= 0xD7:
                     break
-                s = k + 2
+                s = e = f + 2
             break
         p += L
     else:

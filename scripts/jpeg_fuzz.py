@@ -59,6 +59,6 @@ for s in range(0, n_cases, 32):
         g = o.cpu().numpy()
         if g.shape != refs[s + i].shape or not np.array_equal(g, refs[s + i]) or not torch.equal(o, o2):
             bad += 1
-            print("MISMATCH", desc[s + i], "bytes", len(files[s + i]), "settled", int(st["par_done"][i]) if st else None, flush=True)
+            print("MISMATCH", desc[s + i], "bytes", len(files[s + i]), "settled", int(st["par_done"][i]) if "par_done" in st else None, flush=True)
 print("%d cases, %d mismatching, %.1f s; file sizes %d .. %d bytes" % (n_cases, bad, time.time() - t0, min(map(len, files)), max(map(len, files))))
 sys.exit(1 if bad else 0)

@@ -183,8 +183,9 @@ def test_same_size_batch_is_resized_in_one_launch_and_stays_in_hbm(device, tmp_p
 
 
 def test_self_synchronising_decoder_settles_and_matches_the_serial_kernel(device):
-    """restart-free files of >= 4 KB go through nopesac_jpeg_huffman_parallel: every image must settle (par_done) and give the bytes the
-    one-wave-per-interval kernel gives (parallel=False)"""
+    """restart-free files whose scan has at least jpeg.PARALLEL_MIN_BYTES bytes (four lanes of NOPESAC_JPEG_SUB_WORDS words) go through
+    nopesac_jpeg_huffman_parallel: every image must settle (par_done) within NOPESAC_JPEG_SYNC_PASSES passes and give the bytes the
+    one-wave-per-interval kernel gives (parallel=False).  (The file-size filter below only selects fixtures well above that.)"""
     from nopesac_amd import jpeg
     big = [p for p in FILES if os.path.getsize(p) >= 8192 and "rst" not in p]
     assert len(big) >= 2
