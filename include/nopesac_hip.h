@@ -139,7 +139,9 @@ nps_status nopesac_conv2d_nhwc_p8n(const void* x, const void* w, const float* sc
  * layer itself is the pixel decoder's `layer_3` output conv, camera_modules.py:271-321).  A unit = (tile, slice of the 64-channel groups);
  * partial tiles leave as f32 into workspace[splits][M][Cout] (M = B * OH * OW; >= splits * M * Cout * 4 bytes, 16-byte aligned, < 2 GB) and a
  * second launch on the same stream sums the slices in fixed order (deterministic) and applies the epilogue.  variant must carry + 32
- * (channel-major K order); 2 <= splits <= min(Cin / 64, 16).  Everything else as nopesac_conv2d_nhwc_p8n. */
+ * (channel-major K order); 2 <= splits <= min(Cin / 64, 16).  Everything else as nopesac_conv2d_nhwc_p8n.
+ * nopesac_conv2d_p8n_splitk_workspace_bytes: splits * M * Cout * 4, the size the launcher checks (a value; 0 for an argument <= 0). */
+int64_t nopesac_conv2d_p8n_splitk_workspace_bytes(int splits, int64_t M, int Cout);
 nps_status nopesac_conv2d_nhwc_p8n_splitk(const void* x, const void* w, const float* scale, const float* bias, void* y, int B, int H, int W,
                                           int Cin, int Cout, int KH, int KW, int stride, int pad, int64_t x_cstride, int64_t y_cstride, int act,
                                           int variant, int splits, void* workspace, int64_t workspace_bytes, void* stream);
@@ -319,7 +321,9 @@ nps_status nopesac_upsample2x_nearest_add_nhwc(const void* x, const void* latera
                                                int C, int dt, void* stream);
 
 /* GroupNorm(G groups, eps) [+ReLU] on NHWC, per image; camera_modules.py:271-303 (d2 get_norm "GN").
- * workspace: f32[B*16*G*2] scratch for the split statistics (NULL selects the slower single-kernel path). */
+ * workspace: nopesac_groupnorm_workspace_floats(B, G) = B * 16 * G * 2 floats of scratch for the split statistics (NULL selects the
+ * slower single-kernel path).  The size is a value (0 for an argument <= 0). */
+int64_t nopesac_groupnorm_workspace_floats(int B, int G);
 nps_status nopesac_groupnorm_nhwc(const void* x, const float* gamma, const float* beta, void* y,
                                   int B, int HW, int C, int G, float eps, int act, int dt, float* workspace, void* stream);
 
@@ -965,8 +969,12 @@ nps_status nopesac_col_sum_f32(const float* x, int rows, int cols, int64_t x_ld,
 nps_status nopesac_relu_backward_f32(const float* g, const float* y, int64_t n, float* out, void* stream);
 nps_status nopesac_normalize_rows_backward(const float* x, const float* g, int rows, int D, int canonical_sign, float* out, void* stream);
 /* full-model gradient clipping (train_NopeSAC.py:139-148 -> torch.nn.utils.clip_grad_norm_): out[0] += sum x^2 (one launch per tensor on the
- * same accumulator, fixed order); coef[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)); x *= coef[0]. */
-nps_status nopesac_sumsq_accumulate_f32(const float* x, int64_t n, float* out, void* stream);
+ * same accumulator, fixed order); coef[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)); x *= coef[0].
+ * sumsq: n <= 16384 is one workgroup and ws may be null; above, slices of chunk = ((n + 255) / 256 + 4095) / 4096 * 4096 elements (at
+ * most 256) leave one partial each in ws, summed in slice order by a second launch.  nopesac_sumsq_workspace_floats(n) = that slice
+ * count (a value; 0 for n <= 16384); a null or shorter ws is NPS_E_ARG - the algorithm, and so the sum's bits, depend on n alone. */
+int64_t nopesac_sumsq_workspace_floats(int64_t n);
+nps_status nopesac_sumsq_accumulate_f32(const float* x, int64_t n, float* out, float* ws, int64_t ws_floats, void* stream);
 nps_status nopesac_clip_coefficient(const float* sumsq, float max_norm, float* coef, void* stream);
 nps_status nopesac_scale_by_f32(float* x, int64_t n, const float* coef, void* stream);
 nps_status nopesac_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
@@ -975,8 +983,10 @@ nps_status nopesac_sgd_step(float* param, const float* grad, float* momentum_buf
                             int first_step, void* stream);
 
 /* ---- backward of the pixel pose net's conv stacks (csrc/conv_bwd.hip; training.CameraHeadTrainer(conv_stacks=True)) ------------------
- * f32, NHWC activations, f32 accumulation; every buffer (workspaces included) is the caller's; no atomics: cross-workgroup sums are
- * reduced in a fixed order, so two runs give bit-identical results.
+ * f32, NHWC activations, f32 accumulation; every buffer (workspaces included) is the caller's - this holds for the whole library: no
+ * entry point allocates or frees device memory (no hipMalloc* under csrc/), and every split reduction has a *_workspace_floats / _bytes
+ * entry that returns the size its launcher checks; no atomics: cross-workgroup sums are reduced in a fixed order, so two runs give
+ * bit-identical results.
  *  conv2d_dgrad:  dY [B,OH,OW,Cout] (channel stride dy_cstride), w [Cout][Cin][KH][KW] (state-dict layout) -> dX [B,H,W,Cin] (channel
  *                 stride dx_cstride).  k 1 or 3, stride 1 or 2, pad < k.  Stride 1 (same-size conv): w is rotated / transposed into w_ws
  *                 ([Cin][KH][KW][Cout], Cin * Cout * KH * KW floats) and dX is the f32 MFMA implicit-GEMM conv of dY with it; stride 2: a
@@ -988,13 +998,13 @@ nps_status nopesac_sgd_step(float* param, const float* grad, float* momentum_buf
  *                 c [rows][C]: y = act(c s + beta - mean s), s = gamma / sqrt(var + eps); backward from the saved c: dc, dgamma, dbeta
  *                 (ws: nopesac_bn_act_backward_workspace_floats).
  *  groupnorm_backward: x (the GroupNorm input) [B][HW][C], dY -> dX, dgamma, dbeta (optional ReLU after the affine; C / groups divides
- *                 256; ws: B * 2 * C floats).
+ *                 256; ws: nopesac_groupnorm_backward_workspace_floats(B, C) = B * 2 * C floats).
  *  maxpool2x2_backward: 2x2 / stride 2 pool of x [B,H,W,C]: dY goes to the window's first maximum in row-major order (torch's choice).
  *  upsample2x_nearest_add_backward: y = lateral + nearest-2x(coarse [B,H,W,C]): dcoarse = 2x2 block sums of dY (dlateral = dY).
  *  corr_softmax_backward: rows of a softmax A over C channels (row stride a_ld; padding beyond C ignored), dA -> dS = A (dA - sum dA A)
  *                 as ds [B*P][C] and transposed per batch entry as ds_t [B][C][P].
  *  transpose_batched: x [B][rows][cols] -> y [B][cols][rows].
- * The two *_workspace_* entries return a size (a value, never negative). */
+ * The three *_workspace_* entries return a size (a value, never negative). */
 nps_status nopesac_conv2d_dgrad_f32(const float* dy, const float* w, float* dx, float* w_ws, int64_t w_ws_bytes, int B, int H, int W, int Cin,
                                     int Cout, int KH, int KW, int stride, int pad, int64_t dy_cstride, int64_t dx_cstride, void* stream);
 int64_t nopesac_conv2d_wgrad_workspace_bytes(int Cout, int Cin, int KH, int KW, int splits);
@@ -1006,6 +1016,7 @@ int64_t nopesac_bn_act_backward_workspace_floats(int rows, int C);
 nps_status nopesac_bn_act_backward_f32(const float* dy, const float* c, const float* gamma, const float* beta, const float* mean, const float* var,
                                        float eps, int act, int rows, int C, float* dc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats,
                                        void* stream);
+int64_t nopesac_groupnorm_backward_workspace_floats(int B, int C);
 nps_status nopesac_groupnorm_backward_f32(const float* x, const float* dy, const float* gamma, const float* beta, int B, int HW, int C, int groups,
                                           float eps, int relu, float* dx, float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
 nps_status nopesac_maxpool2x2_backward_f32(const float* x, const float* dy, float* dx, int B, int H, int W, int C, void* stream);
@@ -1167,9 +1178,11 @@ nps_status nopesac_plane_corr_matrix(const int32_t* gt_corrs, int K, const int32
  *            NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS(L, B, nq, center_rows = 0 or 2, splits) floats: per range, image and row 256
  *            partial sums and the row's own sum - and are summed in split order, the shared rows over the images in order.
  * mask_product_dgrad: d_p1[b][p][k] = sum_{l,q} dM F + sum_c dZ wc, written once (M = h w, N = 256, K = L nq + 2 per image).
- * sigmoid_backward: out = g y (1 - y) for the output y of a sigmoid, n elements. */
+ * sigmoid_backward: out = g y (1 - y) for the output y of a sigmoid, n elements.
+ * nopesac_mask_product_wgrad_workspace_floats: the macro's value for callers that cannot read it (0 for an argument < 0). */
 #define NPS_MASK_PRODUCT_WS_ROW_FLOATS 257
 #define NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS(L, B, nq, center_rows, splits) ((int64_t)(splits) * (B) * ((int64_t)(L) * (nq) + (center_rows)) * NPS_MASK_PRODUCT_WS_ROW_FLOATS)
+int64_t nopesac_mask_product_wgrad_workspace_floats(int L, int B, int nq, int center_rows, int splits);
 nps_status nopesac_mask_product_wgrad_f32(const float* d_logits, const float* d_center, const float* p1, float* d_fold, int64_t d_fold_ld,
                                           float* d_beta, int64_t d_beta_stride, float* d_wc, float* d_bc, float* ws, int64_t ws_floats, int L,
                                           int B, int nq, int h, int w, int C, int64_t p1_pstride, int64_t p1_bstride, int splits, void* stream);
@@ -1195,11 +1208,13 @@ nps_status nopesac_sigmoid_backward_f32(const float* g, const float* y, int64_t 
  *   rows >= qlen[b], zero dk / dv on keys >= klen[b], every row written, heads * 32 values each).  Nothing of a forward launch is read:
  *   a statistics kernel recomputes row max, 1 / row sum and D_i = sum_j P_ij dP_ij into ws (at least
  *   NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS(B, heads, Lq) floats), a dq kernel (one workgroup per query
- *   tile) and a dk / dv kernel (one per key tile) recompute P from them; the mask is regenerated from the counter. */
+ *   tile) and a dk / dv kernel (one per key tile) recompute P from them; the mask is regenerated from the counter.
+ * nopesac_attention_train_backward_workspace_floats: the macro's value for callers that cannot read it (0 for an argument < 0). */
 #define NPS_ATT_TRAIN_TQ 64
 #define NPS_ATT_TRAIN_TK 64
 #define NPS_ATT_TRAIN_WS_ROW_FLOATS 3
 #define NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS(B, heads, Lq) ((int64_t)(B) * (heads) * (Lq) * NPS_ATT_TRAIN_WS_ROW_FLOATS)
+int64_t nopesac_attention_train_backward_workspace_floats(int B, int heads, int Lq);
 nps_status nopesac_dropout_keep_mask(uint8_t* out, int64_t n, double p, int64_t seed, int64_t stream_id, void* stream);
 nps_status nopesac_dropout_f32(const float* x, const float* residual, float* y, int64_t n, double p, int64_t seed, int64_t stream_id,
                                void* stream);
@@ -1230,9 +1245,11 @@ nps_status nopesac_attention_train_backward(const float* q, int64_t q_stride, co
  *                     up2^T(dv) [B][H][W][C] dense, dv evaluated inside the gather and never written.  batch_stats = 0: mean and rstd
  *                     are stored statistics, constants of the backward: dv = gamma rstd dz (dgamma, dbeta as above).
  *  upsample2x_bilinear_backward: du [B][2H][2W][C] -> dx [B][H][W][C] = up2^T(du), a gather over the at most 4 x 4 outputs an input
- *                     feeds (per axis 0.25, 0.75, 0.75, 0.25; the clamped border taps folded back in). */
+ *                     feeds (per axis 0.25, 0.75, 0.75, 0.25; the clamped border taps folded back in).
+ * nopesac_bn_train_workspace_floats: the macro's value for callers that cannot read it (0 for an argument < 0). */
 #define NPS_BN_TRAIN_RPS 256
 #define NPS_BN_TRAIN_WORKSPACE_FLOATS(n, C) ((((int64_t)(n) + NPS_BN_TRAIN_RPS - 1) / NPS_BN_TRAIN_RPS) * 2 * (C))
+int64_t nopesac_bn_train_workspace_floats(int64_t n, int C);
 nps_status nopesac_bn_train_stats_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, float eps, float momentum,
                                       float* mean, float* var, float* rstd, float* running_mean, float* running_var, float* ws,
                                       int64_t ws_floats, void* stream);
@@ -1256,10 +1273,12 @@ nps_status nopesac_upsample2x_bilinear_backward_f32(const float* du, float* dx, 
  * range past M contributes zeros), written as partials into ws and summed in a fixed order: no atomics, the same inputs give the same
  * bits.  ws: at least NPS_LINEAR_BWD_WORKSPACE_FLOATS(N, K, splits) floats when dw or db is asked for (else it may be null).
  * NPS_E_ARG: K, N or a stride not a multiple of 4, a stride narrower than its row, a pointer not 16-byte aligned, M outside
- * 1 .. 2^31 - 1 (dx: at most 65535 row tiles), p outside [0, 1), a short workspace. */
+ * 1 .. 2^31 - 1 (dx: at most 65535 row tiles), p outside [0, 1), a short workspace.
+ * nopesac_linear_backward_workspace_floats: the macro's value for callers that cannot read it (0 for an argument < 0). */
 #define NPS_LINEAR_BWD_TILE 128
 #define NPS_LINEAR_BWD_STAGE 16
 #define NPS_LINEAR_BWD_WORKSPACE_FLOATS(N, K, splits) ((int64_t)(splits) * ((int64_t)(N) * (K) + (N)))
+int64_t nopesac_linear_backward_workspace_floats(int N, int K, int splits);
 nps_status nopesac_linear_backward_f32(const float* x, int64_t x_stride, const float* w, const float* g, int64_t g_stride, const float* y,
                                        int64_t y_stride, double p, int64_t seed, int64_t stream_id, float* dx, int64_t dx_stride, float* dw,
                                        float* db, float* ws, int64_t ws_floats, int64_t M, int K, int N, int splits, void* stream);

@@ -456,6 +456,8 @@ extern "C" int nopesac_bn_act_backward_f32(const float* dy, const float* c, cons
     NPS_LAUNCH_RET();
 }
 
+extern "C" int64_t nopesac_groupnorm_backward_workspace_floats(int B, int C) { return B > 0 && C > 0 ? (int64_t)B * 2 * C : 0; }
+
 extern "C" int nopesac_groupnorm_backward_f32(const float* x, const float* dy, const float* gamma, const float* beta, int B, int HW, int C,
                                               int groups, float eps, int relu, float* dx, float* dgamma, float* dbeta, float* ws,
                                               int64_t ws_floats, void* stream) {
@@ -463,7 +465,7 @@ extern "C" int nopesac_groupnorm_backward_f32(const float* x, const float* dy, c
     NPS_CHECK_ARG(x && dy && gamma && beta && dx && dgamma && dbeta && ws, "groupnorm_backward: null pointer");
     NPS_CHECK_ARG(B > 0 && HW > 0 && C > 0 && groups > 0 && eps > 0.f, "groupnorm_backward: bad dims B=%d HW=%d C=%d groups=%d", B, HW, C, groups);
     NPS_CHECK_ARG(C % groups == 0 && 256 % (C / groups) == 0, "groupnorm_backward: channels per group must divide 256");
-    NPS_CHECK_ARG(ws_floats >= (int64_t)B * 2 * C, "groupnorm_backward: workspace too small");
+    NPS_CHECK_ARG(ws_floats >= nopesac_groupnorm_backward_workspace_floats(B, C), "groupnorm_backward: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     gn_bwd_kernel<<<B * groups, 256, 0, st>>>(x, dy, gamma, beta, HW, C, groups, eps, relu ? 1 : 0, dx, ws);
     sum_partials_kernel<<<(2 * C + 255) / 256, 256, 0, st>>>(ws, B, C, dgamma, dbeta);

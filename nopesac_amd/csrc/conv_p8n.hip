@@ -439,6 +439,10 @@ __global__ __launch_bounds__(256) void p8n_split_reduce_kernel(const float* __re
 
 extern int nps_p8_num_cus();
 
+extern "C" int64_t nopesac_conv2d_p8n_splitk_workspace_bytes(int splits, int64_t M, int Cout) {
+    return splits > 0 && M > 0 && Cout > 0 ? (int64_t)splits * M * Cout * 4 : 0;
+}
+
 // x [B,H,W,Cin] bf16 (pixel stride x_cstride), w [Cout][KH][KW][Cin] bf16 (plain K-contiguous rows), Cin % 64 == 0, Cout % 128 == 0;
 // y bf16 = act(conv * scale + bias), act in {none, ReLU, LeakyReLU}; variant: 0, + 32 = channel-major K order, + (n << 8) = at most n
 // persistent workgroups (tuning aid).
@@ -468,7 +472,7 @@ static int p8n_launch(const void* x, const void* w, const float* scale, const fl
     p.tiles_n = p.N / N8_BN;
     const hipStream_t st = (hipStream_t)stream;
     if (splits > 1) {
-        const long long need = (long long)splits * p.M * p.N * 4;
+        const long long need = nopesac_conv2d_p8n_splitk_workspace_bytes(splits, p.M, p.N);
         NPS_CHECK_ARG(kmajor, "conv2d_p8n_splitk: variant must carry + 32 (channel-major K order)");
         NPS_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= need,
                       "conv2d_p8n_splitk: workspace of splits * M * N * 4 bytes, 16-byte aligned");

@@ -406,6 +406,10 @@ extern "C" int nopesac_attention_train_forward(const float* q, int64_t q_stride,
     NPS_LAUNCH_RET();
 }
 
+extern "C" int64_t nopesac_attention_train_backward_workspace_floats(int B, int heads, int Lq) {
+    return B >= 0 && heads >= 0 && Lq >= 0 ? NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS(B, heads, Lq) : 0;
+}
+
 extern "C" int nopesac_attention_train_backward(const float* q, int64_t q_stride, const float* k, int64_t k_stride, const float* v,
                                                 int64_t v_stride, const float* d_out, int64_t do_stride, int B, int Lq, int Lk, int heads,
                                                 float scale, const int32_t* qlen, const int32_t* klen, double p, int64_t seed,
@@ -418,7 +422,7 @@ extern "C" int nopesac_attention_train_backward(const float* q, int64_t q_stride
     const int64_t ms = std::min(std::min(std::min(q_stride, k_stride), std::min(v_stride, do_stride)),
                                 std::min(dq_stride, std::min(dk_stride, dv_stride)));
     if (int rc = attention_train_check("attention_train_backward", B, Lq, Lk, heads, ms)) return rc;
-    NPS_CHECK_ARG(ws_floats >= NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS(B, heads, Lq), "attention_train_backward: workspace too small");
+    NPS_CHECK_ARG(ws_floats >= nopesac_attention_train_backward_workspace_floats(B, heads, Lq), "attention_train_backward: workspace too small");
     const dim3 qgrid((Lq + DT_TQ - 1) / DT_TQ, heads, B), kgrid((Lk + DT_TK - 1) / DT_TK, heads, B);
     hipLaunchKernelGGL(attention_train_rows_kernel<true>, qgrid, dim3(256), 0, (hipStream_t)stream, q, (long long)q_stride, k, (long long)k_stride,
                        v, (long long)v_stride, d_out, (long long)do_stride, (float*)nullptr, 0ll, ws, Lq, Lk, heads, scale, qlen, klen, site);

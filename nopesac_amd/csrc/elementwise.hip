@@ -511,6 +511,8 @@ extern "C" int nopesac_upsample2x_nearest_add_nhwc(const void* x, const void* la
     NPS_LAUNCH_RET();
 }
 
+extern "C" int64_t nopesac_groupnorm_workspace_floats(int B, int G) { return B > 0 && G > 0 ? (int64_t)B * GN_SPLITS * G * 2 : 0; }
+
 extern "C" int nopesac_groupnorm_nhwc(const void* x, const float* gamma, const float* beta, void* y, int B, int HW,
                                       int C, int G, float eps, int act, int dt, float* workspace, void* stream) {
     NPS_CHECK_ARG(x && gamma && beta && y && B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, "groupnorm: bad args");

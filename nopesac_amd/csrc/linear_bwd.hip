@@ -245,6 +245,10 @@ __global__ __launch_bounds__(256) void linear_bwd_reduce_kernel(const float* __r
 
 }  // namespace nps
 
+extern "C" int64_t nopesac_linear_backward_workspace_floats(int N, int K, int splits) {
+    return N >= 0 && K >= 0 && splits >= 0 ? NPS_LINEAR_BWD_WORKSPACE_FLOATS(N, K, splits) : 0;
+}
+
 extern "C" int nopesac_linear_backward_f32(const float* x, int64_t x_stride, const float* w, const float* g, int64_t g_stride, const float* y,
                                            int64_t y_stride, double p, int64_t seed, int64_t stream_id, float* dx, int64_t dx_stride,
                                            float* dw, float* db, float* ws, int64_t ws_floats, int64_t M, int K, int N, int splits,
@@ -270,8 +274,8 @@ extern "C" int nopesac_linear_backward_f32(const float* x, int64_t x_stride, con
     hipStream_t st = (hipStream_t)stream;
     const unsigned mt = (unsigned)((M + LB_BM - 1) / LB_BM), kt = (unsigned)((K + LB_BN - 1) / LB_BN), nt = (unsigned)((N + LB_BM - 1) / LB_BM);
     if (dw || db) {
-        NPS_CHECK_ARG(ws && ws_floats >= NPS_LINEAR_BWD_WORKSPACE_FLOATS(N, K, splits), "linear_backward: workspace too small (%lld floats, %lld needed)",
-                      (long long)ws_floats, (long long)NPS_LINEAR_BWD_WORKSPACE_FLOATS(N, K, splits));
+        NPS_CHECK_ARG(ws && ws_floats >= nopesac_linear_backward_workspace_floats(N, K, splits), "linear_backward: workspace too small (%lld floats, %lld needed)",
+                      (long long)ws_floats, (long long)nopesac_linear_backward_workspace_floats(N, K, splits));
     }
     if (dx) {
         NPS_CHECK_ARG(mt <= 65535u, "linear_backward: M = %lld needs more than 65535 row tiles", (long long)M);

@@ -261,6 +261,10 @@ static bool mp_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 static_assert(NPS_MASK_PRODUCT_WS_ROW_FLOATS == nps::MP_BN + 1, "workspace row: 256 partial sums + the row sum");
 
+extern "C" int64_t nopesac_mask_product_wgrad_workspace_floats(int L, int B, int nq, int center_rows, int splits) {
+    return L >= 0 && B >= 0 && nq >= 0 && center_rows >= 0 && splits >= 0 ? NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS(L, B, nq, center_rows, splits) : 0;
+}
+
 extern "C" int nopesac_mask_product_wgrad_f32(const float* d_logits, const float* d_center, const float* p1, float* d_fold, int64_t d_fold_ld,
                                               float* d_beta, int64_t d_beta_stride, float* d_wc, float* d_bc, float* ws, int64_t ws_floats,
                                               int L, int B, int nq, int h, int w, int C, int64_t p1_pstride, int64_t p1_bstride, int splits,
@@ -276,7 +280,7 @@ extern "C" int nopesac_mask_product_wgrad_f32(const float* d_logits, const float
     NPS_CHECK_ARG(d_fold_ld >= C && d_beta_stride >= 1, "mask_product_wgrad: d_fold_ld %lld / d_beta_stride %lld", (long long)d_fold_ld,
                   (long long)d_beta_stride);
     NPS_CHECK_ARG(splits >= 1 && splits <= 1024, "mask_product_wgrad: splits %d not in [1, 1024]", splits);
-    NPS_CHECK_ARG(ws_floats >= NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS(L, B, nq, R - LQ, splits), "mask_product_wgrad: workspace too small");
+    NPS_CHECK_ARG(ws_floats >= nopesac_mask_product_wgrad_workspace_floats(L, B, nq, R - LQ, splits), "mask_product_wgrad: workspace too small");
     int chunk = (HW + splits - 1) / splits;
     chunk = (chunk + MP_WK - 1) / MP_WK * MP_WK;                // split boundaries on LDS-stage boundaries
     float* wsF = ws;

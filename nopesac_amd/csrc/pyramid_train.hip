@@ -408,7 +408,7 @@ static long long bn_train_rows(const char* who, const void* src, int up, int B, 
     return n;
 }
 
-static inline int64_t bn_train_workspace_floats(long long n, int C) { return NPS_BN_TRAIN_WORKSPACE_FLOATS(n, C); }
+extern "C" int64_t nopesac_bn_train_workspace_floats(int64_t n, int C) { return n > 0 && C > 0 ? NPS_BN_TRAIN_WORKSPACE_FLOATS(n, C) : 0; }
 
 extern "C" int nopesac_bn_train_stats_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, float eps, float momentum,
                                           float* mean, float* var, float* rstd, float* running_mean, float* running_var, float* ws,
@@ -420,7 +420,7 @@ extern "C" int nopesac_bn_train_stats_f32(const float* src, int up, int B, int H
     NPS_CHECK_ARG(n >= 2, "bn_train_stats: batch statistics need more than one value per channel (n = %lld)", n);
     NPS_CHECK_ARG(eps > 0.f && momentum >= 0.f && momentum <= 1.f, "bn_train_stats: eps / momentum out of range");
     NPS_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "bn_train_stats: running_mean and running_var come together");
-    NPS_CHECK_ARG(ws_floats >= bn_train_workspace_floats(n, C), "bn_train_stats: workspace too small");
+    NPS_CHECK_ARG(ws_floats >= nopesac_bn_train_workspace_floats(n, C), "bn_train_stats: workspace too small");
     const int S = (int)((n + BT_RPS - 1) / BT_RPS);
     hipStream_t st = (hipStream_t)stream;
     const Src s{src, up, H, W, (long long)src_cstride};
@@ -451,7 +451,7 @@ extern "C" int nopesac_bn_train_backward_f32(const float* dy, const float* src, 
     NPS_CHECK_ARG(dy && gamma && beta && mean && rstd && dsrc && dgamma && dbeta && ws, "bn_train_backward: null pointer");
     NPS_CHECK_ARG(quad_aligned({dy, src, gamma, beta, mean, rstd, dsrc, dgamma, dbeta, ws}), "bn_train_backward: every pointer must be 16-byte aligned");
     NPS_CHECK_ARG(act == NPS_ACT_NONE || act == NPS_ACT_RELU, "bn_train_backward: bad act %d", act);
-    NPS_CHECK_ARG(ws_floats >= bn_train_workspace_floats(n, C), "bn_train_backward: workspace too small");
+    NPS_CHECK_ARG(ws_floats >= nopesac_bn_train_workspace_floats(n, C), "bn_train_backward: workspace too small");
     const int S = (int)((n + BT_RPS - 1) / BT_RPS), relu = act == NPS_ACT_RELU;
     const float inv_n = batch_stats ? 1.f / (float)n : 0.f;      // stored statistics: mean and rstd are constants, dv = gamma rstd dz
     hipStream_t st = (hipStream_t)stream;

@@ -612,24 +612,26 @@ extern "C" int nopesac_normalize_rows_backward(const float* x, const float* g, i
     NPS_LAUNCH_RET();
 }
 
-extern "C" int nopesac_sumsq_accumulate_f32(const float* x, int64_t n, float* out, void* stream) {
+// slices of a multiple of 4096 elements, at most 256 of them (n > 16384)
+static inline long long sumsq_chunk(long long n) { return ((n + 255) / 256 + 4095) / 4096 * 4096; }
+
+extern "C" int64_t nopesac_sumsq_workspace_floats(int64_t n) {
+    if (n <= 16384) return 0;
+    const long long chunk = sumsq_chunk(n);
+    return (n + chunk - 1) / chunk;
+}
+
+extern "C" int nopesac_sumsq_accumulate_f32(const float* x, int64_t n, float* out, float* ws, int64_t ws_floats, void* stream) {
     using namespace nps;
+    const int nb = (int)nopesac_sumsq_workspace_floats(n);          // one partial sum per slice, in the caller's ws; 0: one workgroup
+    NPS_CHECK_ARG(nb == 0 || (ws && ws_floats >= nb), "sumsq_accumulate_f32: workspace too small (%lld floats, %d needed)",
+                  (long long)(ws ? ws_floats : 0), nb);
     NPS_CHECK_ARG(x && out && n > 0, "sumsq_accumulate_f32: bad arguments");
-    if (n <= 16384) {
+    if (nb == 0) {
         hipLaunchKernelGGL(sumsq_accum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, (long long)n, out);
     } else {
-        // slices of a multiple of 4096 elements, at most 256 of them; the partial sums live in stream-ordered scratch
-        long long chunk = ((n + 255) / 256 + 4095) / 4096 * 4096;
-        const int nb = (int)((n + chunk - 1) / chunk);
-        float* partials = nullptr;
-        if (hipMallocAsync((void**)&partials, 256 * sizeof(float), (hipStream_t)stream) != hipSuccess || !partials) {
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(sumsq_accum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, (long long)n, out);   // (same value class, one CU)
-        } else {
-            hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)n, chunk, partials);
-            hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nb, out);
-            (void)hipFreeAsync(partials, (hipStream_t)stream);
-        }
+        hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, (long long)n, sumsq_chunk(n), ws);
+        hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, nb, out);
     }
     NPS_LAUNCH_RET();
 }

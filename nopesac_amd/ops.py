@@ -196,20 +196,44 @@ CONV_CFG_KERNEL = {1: "conv_igemm_kernel<128x128>", 2: "conv_igemm_kernel<64x64>
                    13: "conv_igemm_p8n_kernel", 14: "conv_igemm_p8n_kernel<tap-major>", 15: "conv_igemm_p8n_kernel<split-K>"}
 P8N_TUNABLE = [os.environ.get("NOPESAC_P8N", "1") != "0"]           # NOPESAC_P8N=0: the tuner never offers the 256x128-tile kernel (A/B runs)
 P8_SK_TUNABLE = [os.environ.get("NOPESAC_P8_SK", "0") == "1"]      # NOPESAC_P8_SK=1: the tuner may pick the stream-K form (wins isolated launches, loses 1.2 % in the four-in-flight loop: profiles/r5_b_*)
+_SCRATCH = {}                          # (device index, stream handle) -> the stream's scratch arena, f32 (grown on demand, never shrunk)
 _P8_SK_WS = {}                         # (device index, stream handle) -> workspace tensor of the stream-K conv
 
 
+def _stream_key(device) -> tuple:
+    return (device.index if device.index is not None else torch.cuda.current_device(), _stream())
+
+
+def scratch(device, nbytes: int) -> torch.Tensor:
+    """The one place a kernel workspace comes from: f32, at least `nbytes` long (rounded up to whole floats), 16-byte aligned, content
+    undefined.  For partials that one wrapper's launches write and then read, nothing else: no result and no state lives here.
+    Not capturing: the ONE buffer of (device, current stream), whole - launches of one stream are ordered, so every op on it shares
+    the buffer; it grows to the largest request and is kept.  A wrapper that needs two regions alive at once asks once and slices.
+    Capturing: a fresh torch.empty from the capture's private pool, never cached, so that every captured graph owns its scratch - two
+    graphs replayed side by side must not share one, and a stream handle (which torch hands out round-robin from a small pool) does not
+    tell two captures apart."""
+    n = (int(nbytes) + 3) // 4
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(n, device=device, dtype=torch.float32)
+    key = _stream_key(device)
+    buf = _SCRATCH.get(key)
+    if buf is None or buf.numel() < n:
+        buf = _SCRATCH[key] = torch.empty(n, device=device, dtype=torch.float32)
+    return buf                          # (no view of n elements: the launchers take "at least", and a slice costs what a torch.empty did)
+
+
 def p8_sk_workspace(device) -> torch.Tensor:
-    """The stream-K conv's workspace for the CURRENT stream of `device` (arrival counters + partial-tile slabs, 128 MB): launches of one
-    stream are ordered, so they share one; every stream gets its own.  Zeroed once - the kernel leaves the counters zero.  Inside a
-    graph capture the allocation (and its zero fill, harmlessly replayed) belongs to the capture's private pool."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(), torch.cuda.is_current_stream_capturing())
-    ws = _P8_SK_WS.get(key)
+    """The stream-K conv's workspace for the CURRENT stream of `device` (arrival counters + partial-tile slabs, 128 MB).  Not scratch():
+    its first 16 KB are STATE - arrival counters that must be zero on entry and that the kernel leaves zero - and any other user of the
+    arena would scribble on them.  So it keeps a buffer of its own, zeroed once, under scratch()'s rule: one per (device, stream) outside
+    a capture; inside one a fresh buffer with a fresh zero fill (harmlessly replayed) from the capture's private pool, never cached."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    ws = None if capturing else _P8_SK_WS.get(_stream_key(device))
     if ws is None:
-        n = int(_C.nopesac_conv2d_p8_sk_workspace_bytes())
-        ws = torch.empty(n, device=device, dtype=torch.uint8)
+        ws = torch.empty(int(_C.nopesac_conv2d_p8_sk_workspace_bytes()), device=device, dtype=torch.uint8)
         ws[:16384].zero_()
-        _P8_SK_WS[key] = ws
+        if not capturing:
+            _P8_SK_WS[_stream_key(device)] = ws
     return ws
 
 
@@ -301,7 +325,7 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, scale=None, bias=None, residual=Non
 
     def launch(cfg):
         if cfg == CFG_P8N_SPLIT:
-            ws = torch.empty(p8n_splits * B * OH * OW * Cout, device=x.device, dtype=torch.float32)    # (caching allocator: capture-safe)
+            ws = scratch(x.device, int(_C.nopesac_conv2d_p8n_splitk_workspace_bytes(p8n_splits, B * OH * OW, Cout)))
             _C.nopesac_conv2d_nhwc_p8n_splitk(_p(x), _p(w), _p(scale), _p(bias), _p(out), B, H, W, Cin, Cout, KH, KW, stride, pad, x_cs,
                                               y_cs, act, 32, p8n_splits, _p(ws), ws.numel() * 4, _stream())
             return
@@ -638,7 +662,7 @@ def groupnorm(x: torch.Tensor, gamma, beta, groups: int, eps: float, act=ACT_NON
     _chk(x)
     B, H, W, C = x.shape
     y = torch.empty_like(x)
-    ws = torch.empty(B * 16 * groups * 2, device=x.device, dtype=torch.float32)
+    ws = scratch(x.device, 4 * int(_C.nopesac_groupnorm_workspace_floats(B, groups)))
     _C.nopesac_groupnorm_nhwc(_p(x), _p(_chk(gamma, torch.float32)), _p(_chk(beta, torch.float32)), _p(y), B, H * W, C,
                               groups, eps, act, _DT[x.dtype], _p(ws), _stream())
     return y
@@ -1573,20 +1597,6 @@ def conv3x3_c64(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, bias: tor
 
 
 # ---------------------------------------------------------------- backward of the pixel pose net's conv stacks (csrc/conv_bwd.hip)
-_WGRAD_WS = {}                         # (device index, stream handle, capturing) -> split-K workspace of conv2d_wgrad (grown on demand)
-
-
-def wgrad_workspace(device, nbytes: int) -> torch.Tensor:
-    """conv2d_wgrad's partial-tile workspace for the CURRENT stream of `device`, at least `nbytes` (launches of one stream are ordered,
-    so they share one; it only grows)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream(), torch.cuda.is_current_stream_capturing())
-    ws = _WGRAD_WS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
-        _WGRAD_WS[key] = ws
-    return ws
-
-
 def wgrad_splits(pixels: int, Cout: int, N: int) -> int:
     """Split-K factor of conv2d_wgrad: about 1024 workgroups over the 128 x 128 output tiles, at least 256 pixels per split."""
     tiles = ((Cout + 127) // 128) * ((N + 127) // 128)
@@ -1615,8 +1625,8 @@ def conv2d_dgrad(dy: torch.Tensor, w: torch.Tensor, in_hw, *, stride: int = 1, p
     if out is None:
         out = torch.empty((B, H, W, Cin), device=dy.device, dtype=torch.float32)
     _require(out.shape == (B, H, W, Cin) and out.dtype == torch.float32, "out must be [B, H, W, Cin] f32")
-    wws = torch.empty(w.numel() if stride == 1 else 0, device=dy.device, dtype=torch.float32)
-    _C.nopesac_conv2d_dgrad_f32(_p(dy), _p(w), _p(out), _p(wws) if wws.numel() else None, wws.numel() * 4, B, H, W, Cin, Cout, KH, KW,
+    wws = scratch(dy.device, 4 * w.numel()) if stride == 1 else None        # the rotated weights: the call's only workspace
+    _C.nopesac_conv2d_dgrad_f32(_p(dy), _p(w), _p(out), _p(wws), wws.numel() * 4 if stride == 1 else 0, B, H, W, Cin, Cout, KH, KW,
                                 stride, pad, _nhwc_cs(dy), _nhwc_cs(out), _stream())
     return out
 
@@ -1625,7 +1635,7 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, kernel_size: int, *, stride:
                  splits: Optional[int] = None) -> torch.Tensor:
     """Gradient of conv2d with respect to its weights.  x [B,H,W,Cx] f32 NHWC (the first `cin` channels are the conv's input; the
     rest - zero padding - get no gradient), dy [B,OH,OW,Cout] -> dw [Cout,cin,k,k] (state-dict layout).  Split-K over pixel ranges into
-    the cached workspace, reduced in a fixed order."""
+    scratch(), reduced in a fixed order."""
     _chk(x, torch.float32, contiguous=False); _chk(dy, torch.float32, contiguous=False)
     B, H, W, Cx = x.shape
     Cin = int(cin or Cx)
@@ -1634,8 +1644,7 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, kernel_size: int, *, stride:
     Bd, OH, OW, Cout = dy.shape
     _require(Bd == B and (H + 2 * pad - KH) // stride + 1 == OH and (W + 2 * pad - KW) // stride + 1 == OW, "dy does not match x")
     S = int(splits or wgrad_splits(B * OH * OW, Cout, KH * KW * Cin))
-    nbytes = int(_C.nopesac_conv2d_wgrad_workspace_bytes(Cout, Cin, KH, KW, S))
-    ws = wgrad_workspace(x.device, nbytes)
+    ws = scratch(x.device, int(_C.nopesac_conv2d_wgrad_workspace_bytes(Cout, Cin, KH, KW, S)))
     dw = torch.empty((Cout, Cin, KH, KW), device=x.device, dtype=torch.float32)
     _C.nopesac_conv2d_wgrad_f32(_p(x), _p(dy), _p(dw), _p(ws), ws.numel() * 4, B, H, W, Cin, Cout, KH, KW, stride, pad, _nhwc_cs(x),
                                 _nhwc_cs(dy), S, _stream())
@@ -1668,7 +1677,7 @@ def bn_act_backward(dy: torch.Tensor, c: torch.Tensor, gamma, beta, mean, var, e
     dc = torch.empty_like(c)
     dg = torch.empty(C, device=c.device, dtype=torch.float32)
     db = torch.empty(C, device=c.device, dtype=torch.float32)
-    ws = torch.empty(int(_C.nopesac_bn_act_backward_workspace_floats(rows, C)), device=c.device, dtype=torch.float32)
+    ws = scratch(c.device, 4 * int(_C.nopesac_bn_act_backward_workspace_floats(rows, C)))
     _C.nopesac_bn_act_backward_f32(_p(dy), _p(c), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), int(act), rows, C, _p(dc), _p(dg),
                                    _p(db), _p(ws), ws.numel(), _stream())
     return dc, dg, db
@@ -1684,7 +1693,7 @@ def groupnorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma, beta, groups: i
     dx = torch.empty_like(x)
     dg = torch.empty(C, device=x.device, dtype=torch.float32)
     db = torch.empty(C, device=x.device, dtype=torch.float32)
-    ws = torch.empty(B * 2 * C, device=x.device, dtype=torch.float32)
+    ws = scratch(x.device, 4 * int(_C.nopesac_groupnorm_backward_workspace_floats(B, C)))
     _C.nopesac_groupnorm_backward_f32(_p(x), _p(dy), _p(gamma), _p(beta), B, H * W, C, groups, float(eps), int(act == ACT_RELU), _p(dx),
                                       _p(dg), _p(db), _p(ws), ws.numel(), _stream())
     return dx, dg, db
@@ -1726,8 +1735,8 @@ def _bn_train_src(src: torch.Tensor, up: bool):
 
 
 def bn_train_workspace_floats(n: int, C: int) -> int:
-    """The header's NPS_BN_TRAIN_WORKSPACE_FLOATS: per block of NPS_BN_TRAIN_RPS rows two partials per channel."""
-    return -(-int(n) // _H.NPS_BN_TRAIN_RPS) * 2 * int(C)
+    """The library's nopesac_bn_train_workspace_floats, what both training-BatchNorm launchers check against."""
+    return int(_C.nopesac_bn_train_workspace_floats(n, C))
 
 
 def bn_train_stats(src: torch.Tensor, *, up: bool = False, eps: float = 1e-5, momentum: float = 0.1, running_mean=None, running_var=None):
@@ -1740,7 +1749,7 @@ def bn_train_stats(src: torch.Tensor, *, up: bool = False, eps: float = 1e-5, mo
     if running_mean is not None:
         _bn_vecs(C, running_mean, running_var)
     mean, var, rstd = (torch.empty(C, device=src.device, dtype=torch.float32) for _ in range(3))
-    ws = torch.empty(bn_train_workspace_floats(n, C), device=src.device, dtype=torch.float32)
+    ws = scratch(src.device, 4 * bn_train_workspace_floats(n, C))
     _C.nopesac_bn_train_stats_f32(_p(src), int(up), B, H, W, C, cs, float(eps), float(momentum), _p(mean), _p(var), _p(rstd), _p(running_mean),
                                   _p(running_var), _p(ws), ws.numel(), _stream())
     return mean, var, rstd
@@ -1772,7 +1781,7 @@ def bn_train_backward(dy: torch.Tensor, src: torch.Tensor, gamma, beta, mean, rs
     dsrc = torch.empty(tuple(src.shape) if up else shape, device=src.device, dtype=torch.float32)
     dg = torch.empty(C, device=src.device, dtype=torch.float32)
     db = torch.empty(C, device=src.device, dtype=torch.float32)
-    ws = torch.empty(bn_train_workspace_floats(n, C), device=src.device, dtype=torch.float32)
+    ws = scratch(src.device, 4 * bn_train_workspace_floats(n, C))
     _C.nopesac_bn_train_backward_f32(_p(dy), _p(src), int(up), B, H, W, C, cs, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), int(bool(batch_stats)), _p(dsrc), _p(dg),
                                      _p(db), _p(ws), ws.numel(), _stream())
     return dsrc, dg, db
@@ -1983,7 +1992,7 @@ def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, e
     _sized(gamma, torch.float32, D, "layernorm_backward: gamma")
     _sized(dy, torch.float32, rows * D, "layernorm_backward: dy")
     dx, dgamma, dbeta = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
-    ws = torch.empty(int(_C.nopesac_layernorm_backward_workspace_floats(rows)), device=x.device, dtype=torch.float32)
+    ws = scratch(x.device, 4 * int(_C.nopesac_layernorm_backward_workspace_floats(rows)))
     _C.nopesac_layernorm_backward(_p(x), _p(gamma), _p(dy), rows, D, float(eps), _p(dx), _p(dgamma), _p(dbeta), _p(ws), ws.numel(), _stream())
     return dx, dgamma, dbeta
 
@@ -2083,7 +2092,8 @@ def sumsq_accumulate(x: torch.Tensor, acc: Optional[torch.Tensor] = None) -> tor
     if acc is None:
         acc = torch.zeros(1, device=x.device, dtype=torch.float32)
     _sized(acc, torch.float32, 1, "sumsq_accumulate: acc")
-    _C.nopesac_sumsq_accumulate_f32(_p(x), x.numel(), _p(acc), _stream())
+    n_ws = int(_C.nopesac_sumsq_workspace_floats(x.numel()))                             # 0: the one-workgroup form, no workspace
+    _C.nopesac_sumsq_accumulate_f32(_p(x), x.numel(), _p(acc), _p(scratch(x.device, 4 * n_ws)) if n_ws else None, n_ws, _stream())
     return acc
 
 
@@ -2233,8 +2243,8 @@ def mask_product_splits(L: int, B: int, nq: int, hw: int, center_rows: int = 0) 
 
 
 def mask_product_workspace_floats(L: int, B: int, nq: int, center_rows: int, splits: int) -> int:
-    """The header's NPS_MASK_PRODUCT_WGRAD_WORKSPACE_FLOATS: the wgrad launch's partial tiles."""
-    return splits * B * (L * nq + center_rows) * _H.NPS_MASK_PRODUCT_WS_ROW_FLOATS
+    """The library's nopesac_mask_product_wgrad_workspace_floats, what the wgrad launcher checks against."""
+    return int(_C.nopesac_mask_product_wgrad_workspace_floats(L, B, nq, center_rows, splits))
 
 
 def mask_product_backward(d_logits: torch.Tensor, fold: torch.Tensor, p1: torch.Tensor, d_center: Optional[torch.Tensor] = None,
@@ -2247,7 +2257,7 @@ def mask_product_backward(d_logits: torch.Tensor, fold: torch.Tensor, p1: torch.
     front of the centre map's sigmoid with w_center [2, 256], or both None
     -> (d_fold [L, B, nq, 256], d_beta [L, B, nq], d_p1 [B, h, w, 256]) and, with the centre rows, (+ d_w_center [2, 256], d_b_center [2]).
     d_fold / d_beta: optional outputs (column slices of one wider gradient matrix).  which = "wgrad" / "dgrad": only that launch (the
-    other outputs are None).  Two launches + the fixed-order reduction; the partial tiles live in the cached per-device workspace."""
+    other outputs are None).  Two launches + the fixed-order reduction; the partial tiles live in scratch()."""
     _chk(d_logits, torch.float32)
     _chk(p1, torch.float32, contiguous=False)
     _require(d_logits.dim() == 5 and p1.dim() == 4, "mask_product_backward: d_logits [L,B,nq,h,w], p1 [B,h,w,256]")
@@ -2281,8 +2291,7 @@ def mask_product_backward(d_logits: torch.Tensor, fold: torch.Tensor, p1: torch.
         if extra:
             d_wc, d_bc = torch.empty(2, C, **f32), torch.empty(2, **f32)
         S = int(splits or mask_product_splits(L, B, nq, h * w, extra))
-        n_ws = mask_product_workspace_floats(L, B, nq, extra, S)
-        ws = wgrad_workspace(dev, 4 * max(n_ws, 1))
+        ws = scratch(dev, 4 * mask_product_workspace_floats(L, B, nq, extra, S))
         _C.nopesac_mask_product_wgrad_f32(_p(d_logits), _p(d_center), _p(p1), _p(of2), of_ld, _p(ob), ob.stride(0), _p(d_wc), _p(d_bc), _p(ws),
                                           ws.numel(), L, B, nq, h, w, C, p1.stride(2), p1.stride(0), S, _stream())
     if which != "wgrad":
@@ -2352,7 +2361,7 @@ def attention_train_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
         out = tuple(torch.empty(rows, W, device=q.device, dtype=torch.float32) for rows in (B * Lq, B * Lk, B * Lk))
     dq, dk, dv = out
     so = [_rows(t, rows, W, "attention_train_backward: out") for t, rows in ((dq, B * Lq), (dk, B * Lk), (dv, B * Lk))]
-    ws = torch.empty(B * heads * Lq * _H.NPS_ATT_TRAIN_WS_ROW_FLOATS, device=q.device, dtype=torch.float32)     # the header's NPS_ATT_TRAIN_BACKWARD_WORKSPACE_FLOATS
+    ws = scratch(q.device, 4 * int(_C.nopesac_attention_train_backward_workspace_floats(B, heads, Lq)))
     _C.nopesac_attention_train_backward(_p(q), sq, _p(k), sk, _p(v), sv, _p(d_out), sg, B, Lq, Lk, heads, float(scale), _p(qlen), _p(klen),
                                         float(p), int(seed), int(stream), _p(dq), so[0], _p(dk), so[1], _p(dv), so[2], _p(ws), ws.numel(),
                                         _stream())
@@ -2376,11 +2385,6 @@ def linear_backward_splits(M: int, K: int, N: int) -> int:
     return max(1, min(256, -(-512 // tiles), M // 256))
 
 
-def linear_backward_workspace_floats(K: int, N: int, splits: int) -> int:
-    """The header's NPS_LINEAR_BWD_WORKSPACE_FLOATS: per row range one partial of dW and one of db."""
-    return int(splits) * (int(N) * int(K) + int(N))
-
-
 def linear_backward(x: Optional[torch.Tensor], w: torch.Tensor, g: torch.Tensor, *, y: Optional[torch.Tensor] = None, p: float = 0.0,
                     seed: int = 0, stream: int = 0, want=(True, True, True), dx: Optional[torch.Tensor] = None,
                     splits: Optional[int] = None, ws: Optional[torch.Tensor] = None):
@@ -2388,7 +2392,7 @@ def linear_backward(x: Optional[torch.Tensor], w: torch.Tensor, g: torch.Tensor,
     None where `want` = (dx, dw, db) says no.  The gradient is gated as it is loaded: y (the saved output) = the ReLU's y > 0; p > 0 = the
     counter-based dropout behind the Linear at the row-major index in [M, N] under (seed, stream), times 1 / (1 - p).  x, g, y and the
     optional output `dx` may be column slices of wider row-major buffers; nothing is copied or transposed.  Deterministic.  `splits` /
-    `ws`: the row-range count of the dW / db launch and its workspace (default: linear_backward_splits, the cached per-stream buffer)."""
+    `ws`: the row-range count of the dW / db launch and its workspace (default: linear_backward_splits, scratch())."""
     _require(g.dim() == 2 and w.dim() == 2, "linear_backward: g [M, N], w [N, K]")
     M, N = g.shape
     K = w.shape[1]
@@ -2416,9 +2420,8 @@ def linear_backward(x: Optional[torch.Tensor], w: torch.Tensor, g: torch.Tensor,
     S = int(splits or linear_backward_splits(M, K, N))
     n_ws = 0
     if want_dw or want_db:
-        n_ws = linear_backward_workspace_floats(K, N, S)
         if ws is None:
-            ws = wgrad_workspace(g.device, 4 * n_ws)
+            ws = scratch(g.device, 4 * int(_C.nopesac_linear_backward_workspace_floats(N, K, S)))
         _chk(ws, torch.float32)
         n_ws = ws.numel()
     else:

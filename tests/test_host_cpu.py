@@ -154,6 +154,9 @@ def test_header_states_which_results_are_statuses():
         "nopesac_jpeg_batch_scan_host", "nopesac_jpeg_batch_fill_host", "nopesac_jpeg_batch_free_host", "nopesac_rle_compress_host",
         "nopesac_rle_compress_batch_host", "nopesac_conv2d_wgrad_workspace_bytes", "nopesac_bn_act_backward_workspace_floats",
         "nopesac_layernorm_backward_workspace_floats", "nopesac_plane_criterion_workspace_floats", "nopesac_png_info_host",
+        "nopesac_bn_train_workspace_floats", "nopesac_linear_backward_workspace_floats", "nopesac_mask_product_wgrad_workspace_floats",
+        "nopesac_attention_train_backward_workspace_floats", "nopesac_groupnorm_workspace_floats",
+        "nopesac_groupnorm_backward_workspace_floats", "nopesac_conv2d_p8n_splitk_workspace_bytes", "nopesac_sumsq_workspace_floats",
         "nopesac_png_decode_host", "nopesac_png_decode_files_host", "nopesac_inflate_zlib_host"}
     text = open(_lib.HEADER_PATH).read()
     assert _lib.read_header(text).status == _lib.STATUS

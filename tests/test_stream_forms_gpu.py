@@ -335,9 +335,10 @@ def test_clip_grad_norm_against_f64(n, device):
     bound = S.FLOOR_FACTOR * S.floor_sumsq()
     gd = g.to(device)
     accs = []
+    ws = torch.empty(256, device=device)
     for _ in range(2):
         acc = torch.zeros(1, device=device)
-        ops._C.nopesac_sumsq_accumulate_f32(gd.data_ptr(), n, acc.data_ptr(), ops._stream())
+        ops._C.nopesac_sumsq_accumulate_f32(gd.data_ptr(), n, acc.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
         accs.append(acc.cpu())
     assert _same_bits(accs[0], accs[1]), "sum of squares differs run to run"
     ss, norm, _, _ = S.clip_ref(g, 1.0)

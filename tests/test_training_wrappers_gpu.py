@@ -342,9 +342,9 @@ def case_clip(dev, n):
         return acc, coef, y
 
     def raw(x):
-        acc, coef, y = torch.zeros(1, device=dev), _f32(dev, 1), x.clone()
-        _raw("nopesac_sumsq_accumulate_f32", x, n, acc)
-        _raw("nopesac_sumsq_accumulate_f32", x, n // 2 + 1, acc)
+        acc, coef, y, ws = torch.zeros(1, device=dev), _f32(dev, 1), x.clone(), _f32(dev, 256)
+        _raw("nopesac_sumsq_accumulate_f32", x, n, acc, ws, 256)
+        _raw("nopesac_sumsq_accumulate_f32", x, n // 2 + 1, acc, ws, 256)
         _raw("nopesac_clip_coefficient", acc, 1.0, coef)
         _raw("nopesac_scale_by_f32", y, n, coef)
         return acc, coef, y
