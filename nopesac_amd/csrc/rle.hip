@@ -14,6 +14,10 @@
 // 300 KB map (L2 resident) 16 bytes per lane and compacts the positions where "pixel belongs to plane p" flips.
 // String side: nopesac_rle_compress_device (a workgroup per mask, two passes: sizes + boxes, then the characters) turns the flip
 // positions into the COCO strings + boxes on the device; nopesac_rle_compress_host is the plain-C single-mask form.
+//
+// Tests: tests/rle_forms.py (cases, numpy references, emulations of the partitions below), tests/test_rle_forms_cpu.py (host forms,
+// planted errors) and tests/test_rle_forms_gpu.py (every kernel here on every seam: lane, step, wave range, chunk); the end-to-end
+// strings of random maps are in tests/test_kernels_gpu.py.
 #include "common.h"
 
 namespace nps {
@@ -26,7 +30,7 @@ __global__ __launch_bounds__(256) void rle_labels_kernel(const uint8_t* __restri
     const int v = blockIdx.z, tx = threadIdx.x, ty = threadIdx.y, tid = ty * 32 + tx;
     if (tid < 128) lut[tid] = 0xFF;
     __syncthreads();
-    const int n = n_kept[v];
+    const int n = min(n_kept[v], nq);               // as decode_masks_kernel: never past the view's own row of kept_idx
     if (tid < n) {
         const int q = kept_idx[(long long)v * nq + tid];
         if (q >= 0 && q < 128) lut[q] = (uint8_t)tid;
