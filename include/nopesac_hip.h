@@ -1283,6 +1283,34 @@ nps_status nopesac_linear_backward_f32(const float* x, int64_t x_stride, const f
                                        int64_t y_stride, double p, int64_t seed, int64_t stream_id, float* dx, int64_t dx_stride, float* dw,
                                        float* db, float* ws, int64_t ws_floats, int64_t M, int K, int N, int splits, void* stream);
 
+/* ---- backward of the ResNet-50 backbone (csrc/backbone_bwd.hip; nopesac_amd/training.py::BackboneTrainer) --------------------------------
+ * f32, NHWC, deterministic (no atomics), caller-owned buffers, argument errors -> NPS_E_ARG + nopesac_last_error.
+ * nopesac_conv2d_dgrad_s2_f32: input gradient of a stride-2 conv with k 1 or 3 and pad (k - 1) / 2, any H, W >= 1:
+ *   dY [B,OH,OW,Cout] (channel stride dy_cstride), w [Cout][Cin][KH][KW] (state-dict layout) -> dX [B,H,W,Cin] (channel stride dx_cstride).
+ *   Implicit GEMM on the exact-f32 MFMA, decomposed by the parity of the input pixel: each of the four classes (row parity, column
+ *   parity) is a GEMM with M = the class's pixels, N = Cin, K = its taps x Cout (k = 3: 1 / 2 / 2 / 4 taps; k = 1: one tap for
+ *   even / even, and the other three classes are written as exact zeros), so the multiply count is the forward's.  w is repacked into
+ *   w_ws as [KH][KW][Cout][Cin] (NPS_DGRAD_S2_WORKSPACE_BYTES: the weights' own size).  A workgroup computes NPS_DGRAD_S2_PIXELS pixels of one class x
+ *   NPS_DGRAD_S2_CHANNELS input channels, NPS_DGRAD_S2_STAGE values of K per LDS stage.  Every element of dX is written once; with a channel
+ *   stride above Cin the rest of a pixel is left as it was.  NPS_E_ARG: Cin, Cout or dy_cstride not a multiple of 4, dy or w_ws not
+ *   16-byte aligned, a stride narrower than its channels, a short workspace.
+ * nopesac_maxpool3x3s2_backward_f32: 3x3 / stride 2 / pad 1 max-pool of x [B,H,W,C], dY [B,OH,OW,C], OH = (H - 1) / 2 + 1 -> dX: every
+ *   input element sums, in row-major window order, the dY of those of its up-to-four windows whose first maximum in row-major order
+ *   over the in-bounds taps (torch.max_pool2d: strict >, padding never wins) is the element itself.
+ * nopesac_frozen_bn_act_backward_f32: backward of y = act(c scale + shift [+ residual]) from the saved post-activation y, for g [rows][C]
+ *   (row stride g_stride) and y (row stride y_stride): dz = act == RELU ? (y > 0 ? g : 0) : g (both zeros are "not > 0"),
+ *   dc [rows][C] dense = dz * scale[c]; dz [rows][C] dense is written when the pointer is not null (the residual's gradient).  act: NONE
+ *   or RELU.  No affine gradients: a FrozenBN has none. */
+#define NPS_DGRAD_S2_PIXELS 128
+#define NPS_DGRAD_S2_CHANNELS 128
+#define NPS_DGRAD_S2_STAGE 16
+#define NPS_DGRAD_S2_WORKSPACE_BYTES(Cin, Cout, KH, KW) ((int64_t)(Cin) * (Cout) * (KH) * (KW) * 4)
+nps_status nopesac_conv2d_dgrad_s2_f32(const float* dy, const float* w, float* dx, float* w_ws, int64_t w_ws_bytes, int B, int H, int W, int Cin,
+                                       int Cout, int KH, int KW, int pad, int64_t dy_cstride, int64_t dx_cstride, void* stream);
+nps_status nopesac_maxpool3x3s2_backward_f32(const float* x, const float* dy, float* dx, int B, int H, int W, int C, void* stream);
+nps_status nopesac_frozen_bn_act_backward_f32(const float* g, const float* y, const float* scale, int act, int64_t rows, int C, int64_t g_stride,
+                                              int64_t y_stride, float* dc, float* dz, void* stream);
+
 /* ---- host-side PNG decode for the data mapper (csrc/png_host.hip; no kernel) ---------------------------------------------------------
  * The mp3d split stores 480 x 640 PNG frames (reference: data/planercnn_transforms.py:210-227 -> detectron2 utils.read_image -> PIL).
  * PIL decodes PNGs with the interpreter lock held; these entry points are called through ctypes with the lock released, so the reader

@@ -1651,6 +1651,64 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, kernel_size: int, *, stride:
     return dw
 
 
+def conv2d_dgrad_strided(dy: torch.Tensor, w: torch.Tensor, in_hw, *, stride: int = 2, pad: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of a stride-2 conv2d with respect to its input, on the f32 MFMA (csrc/backbone_bwd.hip: one GEMM per parity class of the
+    input pixels, no multiply meets an inserted zero).  dy [B,OH,OW,Cout] f32 NHWC, w [Cout,Cin,k,k] (state-dict layout), k 1 or 3,
+    pad = (k - 1) / 2, in_hw = (H, W), any H, W >= 1 -> dx [B,H,W,Cin] (or into `out`); dy and out may be channel slices of wider
+    buffers.  Every element of dx is written (k = 1: odd rows / columns as exact zeros).  Cin, Cout and dy's channel stride % 4 == 0."""
+    _chk(dy, torch.float32, contiguous=False); _chk(w, torch.float32)
+    _require(w.dim() == 4 and dy.dim() == 4, "dy must be [B, OH, OW, Cout] and w [Cout, Cin, KH, KW]")
+    _require(stride == 2, "conv2d_dgrad_strided: stride 2 (conv2d_dgrad takes stride 1)")
+    Cout, Cin, KH, KW = w.shape
+    B, OH, OW, C = dy.shape
+    _require(C == Cout, (C, Cout))
+    H, W = int(in_hw[0]), int(in_hw[1])
+    _require(H >= 1 and W >= 1 and (H + 2 * pad - KH) // 2 + 1 == OH and (W + 2 * pad - KW) // 2 + 1 == OW, "dy does not match the input size")
+    if out is None:
+        out = torch.empty((B, H, W, Cin), device=dy.device, dtype=torch.float32)
+    _chk(out, torch.float32, contiguous=False)
+    _require(out.shape == (B, H, W, Cin), "out must be [B, H, W, Cin] f32")
+    wws = scratch(dy.device, 4 * w.numel())                               # the repacked weights (NPS_DGRAD_S2_WORKSPACE_BYTES): the call's only workspace
+    _C.nopesac_conv2d_dgrad_s2_f32(_p(dy), _p(w), _p(out), _p(wws), wws.numel() * 4, B, H, W, Cin, Cout, KH, KW, int(pad), _nhwc_cs(dy),
+                                   _nhwc_cs(out), _stream())
+    return out
+
+
+def maxpool3x3s2_backward(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
+    """Backward of the 3x3 / stride-2 / pad-1 max-pool of x [B,H,W,C] f32 (ops.maxpool(x, 3, 2, 1)): each window's dY goes to its first
+    maximum in row-major order over the in-bounds taps, as torch.max_pool2d; overlapping windows add in row-major window order."""
+    _chk(x, torch.float32); _chk(dy, torch.float32)
+    _require(x.dim() == 4, x.shape)
+    B, H, W, C = x.shape
+    _require(dy.shape == (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), (dy.shape, x.shape))
+    dx = torch.empty_like(x)
+    _C.nopesac_maxpool3x3s2_backward_f32(_p(x), _p(dy), _p(dx), B, H, W, C, _stream())
+    return dx
+
+
+def frozen_bn_act_backward(g: torch.Tensor, y: torch.Tensor, scale: torch.Tensor, act: int = ACT_RELU, want_dz: bool = False):
+    """Backward of y = act(conv * scale + shift [+ residual]) (FrozenBN folded, act NONE or RELU) from the saved post-activation output:
+    dz = y > 0 ? g : 0 (RELU) or g, dc = dz * scale.  g, y: [..., C] f32 with unit channel stride, rows dense or [rows, C] with a row
+    stride -> dc (dense, g's shape), or (dc, dz) when want_dz (the residual's gradient).  No affine gradients."""
+    _chk(g, torch.float32, contiguous=False); _chk(y, torch.float32, contiguous=False); _chk(scale, torch.float32)
+    _require(g.shape == y.shape and g.dim() >= 2, (g.shape, y.shape))
+    _require(act in (ACT_NONE, ACT_RELU), act)
+    C = g.shape[-1]
+    _require(scale.numel() == C, (scale.numel(), C))
+    rows = g.numel() // C
+
+    def row_stride(t):
+        if t.is_contiguous():
+            return C
+        return _rows(t, rows, C, "frozen_bn_act_backward")
+
+    g_ld, y_ld = row_stride(g), row_stride(y)
+    dc = torch.empty(g.shape, device=g.device, dtype=torch.float32)
+    dz = torch.empty_like(dc) if want_dz else None
+    _C.nopesac_frozen_bn_act_backward_f32(_p(g), _p(y), _p(scale), int(act), rows, C, g_ld, y_ld, _p(dc), _p(dz), _stream())
+    return (dc, dz) if want_dz else dc
+
+
 def _bn_vecs(C, *vs):
     for v in vs:
         _chk(v, torch.float32)

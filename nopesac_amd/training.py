@@ -5,7 +5,7 @@ clipping, the reference's norm / embedding / plain groups stated once in paramet
 subclass names its state-dict prefix (KEY_PREFIX) and its SOLVER.*_MULTIPLIER (LR_MULTIPLIER) and adds its forward.  ChainedTrainer adds
 the protocol of a trainer whose output feeds the instance heads: forward, then backward_from(gradient at the output), or
 losses(heads, ...) followed by backward.  The trainers: RefineTrainer (with CameraHeadTrainer on top of it), MatchingHeadTrainer,
-PlaneInstanceHeadsTrainer, and the chained PlaneDecoderTrainer, PlanePyramidTrainer and PlaneEncoderTrainer.
+PlaneInstanceHeadsTrainer, the chained PlaneDecoderTrainer, PlanePyramidTrainer and PlaneEncoderTrainer, and BackboneTrainer.
 
 RefineTrainer is the camera head's refinement stage (reference: `__forward_PlaneCamRefHead`, camera_net/camera_head.py:737-923; losses
 camera_modules.py:355-365) - round 5.  Forward = the kernels of the training-side twin (ops.geo_sequence, ops.ransac_score_maps, ops.ransac_soft_vote mode | 16,
@@ -61,12 +61,19 @@ tensors of sem_seg_head).  Its Linears run on B x 300 rows, so their backward is
 the Linear are gates applied as the gradient's tiles are loaded - instead of _Linear's ReLU pass, three transposes, two GEMMs and a
 column sum.  _Linear and the trainers that use it are unchanged.
 
-What this is NOT: a trainer for the whole network.  The backbone has no backward kernels here - the gradients stop at the backbone
-maps (`input_grads`, ready for a backbone backward to chain onto); the
-backbone maps, the plane sets and their appearance features are inputs of the other stages, as they are of the reference functions, and
+The ResNet-50 backbone (configs/Base.yaml: FREEZE_AT 0, FrozenBN, SOLVER.BACKBONE_MULTIPLIER 0.1 - the 53 conv weights) is trained by
+BackboneTrainer: its forward is the inference backbone's f32 launches (conv + FrozenBN + residual + ReLU in one epilogue), of which only
+the post-activation outputs are kept; the backward is csrc/backbone_bwd.hip - the FrozenBN / ReLU gate from the saved output, the
+input gradient of the six stride-2 convs as four parity-class GEMMs on the f32 MFMA, the stem's overlapping max-pool - plus the
+stride-1 dgrad and the wgrad of csrc/conv_bwd.hip.  It takes the gradients the other trainers report at the backbone maps
+(`input_grads`, through backward_from) or continues their graph (joined_backward), so one optimiser step can move every trainable
+tensor of the model.
+
+What this is NOT: one forward of the meta-architecture in training mode that drives all trainers - each trainer is called by its user.
+The image, the plane sets and their appearance features are inputs of the stages, as they are of the reference functions, and
 receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
 against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py)
-and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py, tests/test_plane_pyramid_training_gpu.py, tests/test_plane_encoder_training_gpu.py)."""
+and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py, tests/test_plane_pyramid_training_gpu.py, tests/test_plane_encoder_training_gpu.py, tests/test_backbone_training_gpu.py)."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -726,8 +733,8 @@ class HeadTrainer:
 
     def lr_multiplier(self, cfg) -> float:
         """The reference's per-module learning-rate multiplier of the module this trainer holds (train_NopeSAC.py:122-129): SOLVER's
-        LR_MULTIPLIER entry, or 1.  (BACKBONE_MULTIPLIER belongs to a module no trainer here holds; PLANE_MATCHER_HEAD_MULTIPLIER is keyed
-        on a module name the reference does not have, so it never fires there either.)"""
+        LR_MULTIPLIER entry, or 1.  (BACKBONE_MULTIPLIER is BackboneTrainer's; PLANE_MATCHER_HEAD_MULTIPLIER is keyed on a module name
+        the reference does not have, so it never fires there either.)"""
         return 1.0 if self.LR_MULTIPLIER is None else float(getattr(cfg.SOLVER, self.LR_MULTIPLIER))
 
 
@@ -1841,6 +1848,170 @@ class PlaneEncoderTrainer(ChainedTrainer):
             out.update(t._collect())
         out.update(head_grads)
         return out
+
+
+BACKBONE_PREFIX, FROZEN_BN_EPS = "backbone.", 1e-5
+BACKBONE_MAPS = ("res2", "res3", "res4", "res5")
+
+
+class _ConvFrozenBN(torch.autograd.Function):
+    """conv (no bias) + FrozenBN (scale / shift constants) [+ residual] + act, as ONE ops.conv2d launch - the launch HipResNet50.forward
+    makes on its f32 route.  Only x, w and the post-activation output are kept: the backward takes the ReLU gate from y > 0
+    (ops.frozen_bn_act_backward), then dgrad (stride 1: ops.conv2d_dgrad, stride 2: ops.conv2d_dgrad_strided) and wgrad; the residual
+    receives dz.  x may carry zero padding channels beyond w's Cin (the stem's fourth): their weight gradient is dropped."""
+
+    @staticmethod
+    def forward(ctx, x, w, scale, shift, residual, stride: int, pad: int, act: int):
+        x = x.contiguous()
+        y = ops.conv2d(x, _ohwi(w, x.shape[3]), scale, shift, residual, stride=stride, pad=pad, act=act)
+        ctx.conf = (stride, pad, act)
+        ctx.save_for_backward(x, w, y, scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, y, scale = ctx.saved_tensors
+        stride, pad, act = ctx.conf
+        want_dz = bool(ctx.needs_input_grad[4])
+        r = ops.frozen_bn_act_backward(g.contiguous(), y, scale, act, want_dz)
+        dc, dz = r if want_dz else (r, None)
+        dx = dw = None
+        B, H, W, Cx = x.shape
+        Cin, k = w.shape[1], w.shape[2]
+        if ctx.needs_input_grad[0]:
+            _require(Cx == Cin, "_ConvFrozenBN: an input with padding channels takes no gradient")
+            dx = torch.empty_like(x)
+            if stride == 1:
+                ops.conv2d_dgrad(dc, w, (H, W), stride=1, pad=pad, out=dx)
+            else:
+                ops.conv2d_dgrad_strided(dc, w, (H, W), stride=stride, pad=pad, out=dx)
+        if ctx.needs_input_grad[1]:
+            # (the wgrad kernel needs Cin % 4 == 0: the stem runs on all four channels of its padded input and drops the fourth)
+            dw = ops.conv2d_wgrad(x, dc, k, stride=stride, pad=pad, cin=None)[:, :Cin] if Cx > Cin else \
+                ops.conv2d_wgrad(x, dc, k, stride=stride, pad=pad, cin=Cin)
+        return dx, dw, None, None, dz, None, None, None
+
+
+class _MaxPool3(torch.autograd.Function):
+    """The stem's 3x3 / stride-2 / pad-1 max-pool."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return ops.maxpool(x, 3, 2, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool3x3s2_backward(x, g.contiguous())
+
+
+class BackboneTrainer(HeadTrainer):
+    """The ResNet-50 backbone in TRAINING mode as the reference trains it (configs/Base.yaml: FREEZE_AT 0, NORM FrozenBN,
+    SOLVER.BACKBONE_MULTIPLIER 0.1): the trainable set is the 53 conv weights - the stem, 16 x 3 bottleneck convs, 4 projection
+    shortcuts - under their state-dict keys; the FrozenBN scale / shift vectors (eps 1e-5) are constants folded once (`norms`).
+
+        bb = BackboneTrainer.from_backbone(model.backbone)                         # or .from_state_dict(sd, device)
+        feats = bb.forward(x)                                                      # x [N, H, W, 4] f32 normalised NHWC -> {res2 .. res5}
+        bb.backward_from({"res5": d_res5, ...})                                    # any subset of the maps -> .grads (53 tensors)
+      or with another trainer's graph behind the maps (they take tensors that require grad as they are):
+        losses, _ = enc.losses(heads, decoder, pyramid, feats, targets)
+        grads = bb.joined_backward(enc, losses)                                    # the 53 + the other trainer's, by state-dict key
+        bb.step_from_cfg(cfg); bb.write_back(model.backbone)
+
+    Every launch of the forward is the one HipResNet50.forward makes on its f32 route (one ops.conv2d per conv with scale, shift, residual
+    and ReLU in the epilogue, ops.maxpool), so the same parameters give the inference backbone's f32 maps bit for bit.  Each returned map
+    is a view of the activation the next stage consumes: its gradient is what the consumers behind the backbone send, not the
+    backbone's own paths, so a consumer's `input_grads` is exactly what backward_from takes.  The backward is csrc/backbone_bwd.hip (the
+    ReLU gate from the saved output, the stride-2 dgrad on the MFMA, the overlapping max-pool) plus conv2d_dgrad / conv2d_wgrad of
+    csrc/conv_bwd.hip.  The image takes no gradient (the stem has no dgrad).  Optimiser group: all 53 are "plain"."""
+
+    KEY_PREFIX, LR_MULTIPLIER = BACKBONE_PREFIX, "BACKBONE_MULTIPLIER"
+    BLOCKS = {"res2": 3, "res3": 4, "res4": 6, "res5": 3}               # bottlenecks per stage (synth.RES_STAGES)
+
+    def __init__(self, params: Dict[str, torch.Tensor], norms: Dict[str, tuple]):
+        super().__init__(params)
+        self.norms = {k: (s.detach().float().contiguous(), b.detach().float().contiguous()) for k, (s, b) in norms.items()}
+        self._out: Dict[str, torch.Tensor] = {}
+        _require(len(self.params) == 53 and set(self.norms) == {k[:-len(".weight")] for k in self.params},
+                 "BackboneTrainer: 53 conv weights, each with its FrozenBN, expected, got %d and %d" % (len(self.params), len(self.norms)))
+
+    @staticmethod
+    def parameter_names(sd_keys) -> List[str]:
+        return sorted(k for k in sd_keys if k.startswith(BACKBONE_PREFIX) and k.endswith(".weight") and ".norm." not in k)
+
+    @classmethod
+    def _build(cls, source, keys, device=None) -> "BackboneTrainer":
+        names = cls.parameter_names(keys)
+        norms = {}
+        for k in names:
+            q = k[:-len(".weight")]
+            n = cls._read(source, [q + ".norm." + leaf for leaf in ("weight", "bias", "running_mean", "running_var")], device)
+            w, b, mean, var = (t.float() for t in n.values())
+            scale = w * torch.rsqrt(var + FROZEN_BN_EPS)                  # (modeling.params.fold_bn's expression: the same bits)
+            norms[q] = (scale, b - mean * scale)
+        return cls(cls._read(source, names, device), norms)
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device) -> "BackboneTrainer":
+        return cls._build(sd, list(sd.keys()), device)
+
+    @classmethod
+    def from_backbone(cls, backbone) -> "BackboneTrainer":
+        return cls._build(backbone, cls._head_keys(backbone))
+
+    # ---- forward
+    def _conv(self, x, name: str, stride: int = 1, pad: int = 0, act: int = ops.ACT_RELU, residual=None):
+        scale, shift = self.norms[BACKBONE_PREFIX + name]
+        return _ConvFrozenBN.apply(x, self.params[BACKBONE_PREFIX + name + ".weight"], scale, shift, residual, stride, pad, act)
+
+    def forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """x [N, H, W, 4] f32 NHWC, normalised, the fourth channel zero (ops.preprocess) -> {res2 .. res5} f32 NHWC, autograd tape attached."""
+        x = self.stem(x)
+        out = {}
+        for name in BACKBONE_MAPS:
+            x = self.stage(x, name)
+            out[name] = x.view_as(x)
+        self._out = out
+        return out
+
+    def stem(self, x: torch.Tensor) -> torch.Tensor:
+        """The 7x7 / stride-2 conv on the 4-channel padded image and the 3x3 / stride-2 max-pool -> [N, H / 4, W / 4, 64]."""
+        _require(x.dim() == 4 and x.shape[3] == 4 and x.dtype == torch.float32, "BackboneTrainer: x [N, H, W, 4] f32 expected, got %s" % (tuple(x.shape),))
+        return _MaxPool3.apply(self._conv(x.detach(), "stem.conv1", 2, 3))
+
+    def stage(self, x: torch.Tensor, name: str) -> torch.Tensor:
+        """One of res2 .. res5 on the previous stage's output: its bottlenecks, the first with a projection shortcut (stride 2 in its
+        3x3 conv and its shortcut, except res2)."""
+        for i in range(self.BLOCKS[name]):
+            p = f"{name}.{i}"
+            stride = 2 if (i == 0 and name != "res2") else 1
+            y = self._conv(x, p + ".conv1")
+            y = self._conv(y, p + ".conv2", stride, 1)
+            sc = self._conv(x, p + ".shortcut", stride, 0, ops.ACT_NONE) if i == 0 else x
+            x = self._conv(y, p + ".conv3", residual=sc)
+        return x
+
+    # ---- backward
+    def backward_from(self, d_feats: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Gradients at any subset of the last forward's maps ({"res2" .. "res5": like the map}) -> {state-dict key: gradient} of the 53
+        weights (also `.grads`)."""
+        _require(self._out and d_feats and all(k in self._out and tuple(g.shape) == tuple(self._out[k].shape) for k, g in d_feats.items()),
+                 "BackboneTrainer.backward_from: {res2 .. res5: gradient like the last forward's map}")
+        keys = [k for k in BACKBONE_MAPS if k in d_feats]
+        self._clear_grads()
+        torch.autograd.backward([self._out[k] for k in keys], [d_feats[k].contiguous() for k in keys])
+        return self._collect()
+
+    def joined_backward(self, trainer: HeadTrainer, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+        """The backward of a graph that runs on from this forward's maps into another trainer (its losses / forward were given the maps
+        themselves): `trainer.backward(losses, loss_weights)` continues into the backbone.  -> both trainers' gradients by state-dict
+        key; `.grads` here holds the backbone's 53."""
+        _require(bool(self._out), "BackboneTrainer.joined_backward: call forward() first")
+        self._clear_grads()
+        other = trainer.backward(losses, loss_weights)
+        return {**self._collect(), **other}
 
 
 def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torch.Tensor, nq: int) -> torch.Tensor:

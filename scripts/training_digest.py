@@ -215,8 +215,22 @@ def shared_memory(dev, d):
     rounds(d, {"decoder": dec, "pyramid": pyr, "heads": hd}, one)
 
 
+def backbone(dev, d):
+    """BackboneTrainer at N = 2, 64 x 96 (tests/backbone_forms.py): forward, backward_from unit-normal cotangents at the four maps."""
+    from tests import backbone_forms as BF
+    x, cots = BF.net_inputs(BF.NET_CASES[0])
+    tr = T.BackboneTrainer.from_state_dict(BF.backbone_state_dict(), dev)
+    x, cots = x.to(dev), {k: v.to(dev) for k, v in cots.items()}
+
+    def one(i):
+        feats = tr.forward(x)
+        return {k: v.detach() for k, v in feats.items()}, tr.backward_from(cots), tr.input_grads
+    rounds(d, {"backbone": tr}, one)
+
+
 CONFIGS = (("refine", refine), ("camera", camera(False)), ("camera_conv_stacks", camera(True)), ("matcher", matcher), ("heads", heads),
-           ("decoder_p0", decoder(0.0)), ("decoder_p0.1", decoder(0.1)), ("pyramid", pyramid), ("decoder_pyramid_shared_memory", shared_memory))
+           ("decoder_p0", decoder(0.0)), ("decoder_p0.1", decoder(0.1)), ("pyramid", pyramid), ("decoder_pyramid_shared_memory", shared_memory),
+           ("backbone", backbone))
 
 
 def run_length(names):
