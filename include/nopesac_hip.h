@@ -982,6 +982,67 @@ nps_status nopesac_adamw_step(float* param, const float* grad, float* exp_avg, f
 nps_status nopesac_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float weight_decay,
                             int first_step, void* stream);
 
+/* ---- model-wide optimiser step (csrc/optimizer.hip; nopesac_amd/optim.py::ModelOptimizer) ----------------------------------------------
+ * One gather launch and one step launch for ANY number of tensors.  State lives in three flat f32 arenas of the caller (arena_floats
+ * each): G = the gathered gradients, M1 / M2 = AdamW's moments (SGD: M1 = the momentum buffer, M2 unused and may be null).  Every
+ * tensor (SEGMENT) owns the slice [offset, offset + n) of each arena; offset is a multiple of NPS_OPT_ALIGN floats, segments do not
+ * overlap, and the padding between them is zero and stays zero (the gather writes zeros there, the step never touches it), so a sum
+ * of squares over the whole of G is the gradient norm.  Work is cut into UNITS of NPS_OPT_CHUNK elements, one 256-thread workgroup
+ * each (four float4 per thread); a unit never crosses a segment end, and the static map `units` tells workgroup u its (segment, chunk
+ * index) in one load - chunk c covers the elements [c NPS_OPT_CHUNK, min(n, (c + 1) NPS_OPT_CHUNK)) of its segment.
+ *   segments  device, static: nopesac_opt_segment[n_segments]
+ *   sources   device, written per step: nopesac_opt_source[n_segments] = where this step's gradient of the segment lies (contiguous f32,
+ *             any 4-byte alignment) and flags: NPS_OPT_PRESENT, NPS_OPT_FIRST (SGD: the segment's first momentum step, buffer = gradient)
+ *   units     device, static: nopesac_opt_unit[n_units]
+ * nopesac_opt_gather: G[offset + i] = src[i] of every present segment, 0 of every absent one.
+ * nopesac_opt_step: per element of every PRESENT segment g = G[i] * coef[0] (coef null: 1), then the update of nopesac_adamw_step /
+ * nopesac_sgd_step in the same operation order with the segment's group {lr, weight_decay} - the bits of nopesac_scale_by_f32 followed
+ * by the per-tensor entry.  AdamW's bias corrections are 1 - powf(beta, (float)step), formed on the host as nopesac_adamw_step forms
+ * them.  Absent segments are skipped whole: parameter and moments untouched.  float4 accesses where the pointer on the caller's side
+ * (src / param) is 16-byte aligned, scalar ones otherwise; the arenas must be 16-byte aligned.  A unit whose segment index, chunk or
+ * arena range lies outside the tables' own bounds is skipped by the kernel (the tables are the caller's: a wrong one must not fault). */
+#define NPS_OPT_CHUNK 4096
+#define NPS_OPT_ALIGN 64
+#define NPS_OPT_MAX_GROUPS 16
+#define NPS_OPT_MAX_SEGMENTS 65536
+#define NPS_OPT_PRESENT 1
+#define NPS_OPT_FIRST 2
+#define NPS_OPT_ADAMW 0
+#define NPS_OPT_SGD 1
+typedef struct nopesac_opt_segment {
+    float* param;
+    int64_t offset;
+    int64_t n;
+    int group, reserved;
+} nopesac_opt_segment;
+typedef struct nopesac_opt_source {
+    const float* src;
+    int flags, reserved;
+} nopesac_opt_source;
+typedef struct nopesac_opt_unit {
+    int segment, chunk;
+} nopesac_opt_unit;
+typedef struct nopesac_opt_group {
+    float lr, weight_decay;
+} nopesac_opt_group;
+typedef struct nopesac_opt_step_args {
+    const nopesac_opt_segment* segments;
+    const nopesac_opt_source* sources;
+    const nopesac_opt_unit* units;
+    int64_t n_units;
+    int64_t arena_floats;
+    float* G;
+    float* M1;
+    float* M2;
+    const float* coef;
+    int n_segments, mode, n_groups, step;
+    float beta1, beta2, eps, momentum;
+    nopesac_opt_group groups[NPS_OPT_MAX_GROUPS];
+} nopesac_opt_step_args;
+nps_status nopesac_opt_gather(const nopesac_opt_segment* segments, const nopesac_opt_source* sources, const nopesac_opt_unit* units,
+                              int n_segments, int64_t n_units, float* G, int64_t arena_floats, void* stream);
+nps_status nopesac_opt_step(const nopesac_opt_step_args* a, void* stream);
+
 /* ---- backward of the pixel pose net's conv stacks (csrc/conv_bwd.hip; training.CameraHeadTrainer(conv_stacks=True)) ------------------
  * f32, NHWC activations, f32 accumulation; every buffer (workspaces included) is the caller's - this holds for the whole library: no
  * entry point allocates or frees device memory (no hipMalloc* under csrc/), and every split reduction has a *_workspace_floats / _bytes

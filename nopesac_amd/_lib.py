@@ -137,6 +137,8 @@ STATUS = _HEADER.status                                         # the entry poin
 H = SimpleNamespace(**_HEADER.constants)                        # H.NPS_ACT_RELU, H.NOPESAC_JPEG_IMG_I32, ...
 MlpLayer, MlpChain = _HEADER.structs["nopesac_mlp_layer"], _HEADER.structs["nopesac_mlp_chain"]
 PlaneCriterionArgs = _HEADER.structs["nopesac_plane_criterion"]
+OptSegment, OptSource, OptUnit = (_HEADER.structs["nopesac_opt_" + n] for n in ("segment", "source", "unit"))
+OptStepArgs = _HEADER.structs["nopesac_opt_step_args"]
 MLP_MAX_IN, MLP_MAX_WIDTH, MLP_MAX_LAYERS = H.NOPESAC_MLP_MAX_IN, H.NOPESAC_MLP_MAX_WIDTH, H.NOPESAC_MLP_MAX_LAYERS
 
 _lib = None

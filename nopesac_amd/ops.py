@@ -2171,6 +2171,143 @@ def scale_by(x: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
     return x
 
 
+# ---- model-wide optimiser step (csrc/optimizer.hip; nopesac_amd/optim.py) -----------------------------------------------------------------
+OPT_CHUNK, OPT_ALIGN, OPT_MAX_GROUPS, OPT_MAX_SEGMENTS = _H.NPS_OPT_CHUNK, _H.NPS_OPT_ALIGN, _H.NPS_OPT_MAX_GROUPS, _H.NPS_OPT_MAX_SEGMENTS
+OPT_PRESENT, OPT_FIRST = _H.NPS_OPT_PRESENT, _H.NPS_OPT_FIRST
+OPT_MODES = {"ADAMW": _H.NPS_OPT_ADAMW, "SGD": _H.NPS_OPT_SGD}
+
+
+def opt_unit_map(sizes):
+    """The ONE place the layout of the optimiser arenas and the work split of the two kernels are derived: segment sizes (elements, each
+    >= 1) -> (offsets int64 [S], units int32 [U, 2] = (segment, chunk index) per workgroup, arena_floats).  Every segment starts at a
+    multiple of OPT_ALIGN floats, right behind its predecessor's padded end; it is cut into ceil(n / OPT_CHUNK) units, none of which
+    crosses its end.  Host arithmetic only (numpy): what tests/test_model_optimizer_cpu.py proves before a table reaches a GPU."""
+    import numpy as np
+    sizes = np.asarray(list(sizes), dtype=np.int64).reshape(-1)
+    if sizes.size == 0 or sizes.size > OPT_MAX_SEGMENTS or int(sizes.min()) < 1:
+        raise OpsArgumentError("opt_unit_map: 1..%d segments of at least one element each, got %d (smallest %s)"
+                               % (OPT_MAX_SEGMENTS, sizes.size, sizes.min() if sizes.size else None))
+    padded = (sizes + OPT_ALIGN - 1) // OPT_ALIGN * OPT_ALIGN
+    offsets = np.concatenate([np.zeros(1, np.int64), np.cumsum(padded)[:-1]])
+    chunks = (sizes + OPT_CHUNK - 1) // OPT_CHUNK
+    if int(chunks.sum()) >= 2 ** 31:
+        raise OpsArgumentError("opt_unit_map: %d units (a grid holds at most 2^31 - 1)" % int(chunks.sum()))
+    segment = np.repeat(np.arange(sizes.size, dtype=np.int64), chunks)
+    first = np.repeat(np.cumsum(chunks) - chunks, chunks)
+    units = np.stack([segment, np.arange(segment.size, dtype=np.int64) - first], axis=1).astype(np.int32)
+    return offsets, units, int(padded.sum())
+
+
+class OptLayout:
+    """The static tables of one set of parameters for opt_gather / opt_step, built from LIVE tensors only (data_ptr(), numel()) and kept
+    with them: params are f32, contiguous, on one device (any 4-byte alignment: a misaligned one takes the kernels' scalar path) and
+    must not be re-seated while the layout lives; `groups[i]` in 0..OPT_MAX_GROUPS-1 is the hyper-parameter group of params[i].
+    sources() writes the per-step table into one of two pinned staging buffers, alternated behind an event each, so that an upload
+    still in flight is never overwritten, and enqueues its copy on the current stream."""
+
+    def __init__(self, params, groups):
+        import numpy as np
+        params, groups = list(params), [int(g) for g in groups]
+        _require(len(params) == len(groups) and len(params) >= 1, "OptLayout: one group index per parameter, at least one parameter")
+        dev = params[0].device
+        for i, p in enumerate(params):
+            _chk(p, torch.float32)
+            _require(p.device == dev and p.numel() >= 1, "OptLayout: parameter %d: empty or on %s, not %s" % (i, p.device, dev))
+            _require(0 <= groups[i] < OPT_MAX_GROUPS, "OptLayout: group %d outside 0..%d" % (groups[i], OPT_MAX_GROUPS - 1))
+        spans = sorted((p.data_ptr(), p.data_ptr() + 4 * p.numel()) for p in params)
+        _require(all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), "OptLayout: two parameters share memory")
+        self.params, self.device, self.n_groups = params, dev, max(groups) + 1
+        self.sizes = np.array([p.numel() for p in params], dtype=np.int64)
+        self.offsets, self.units, self.arena_floats = opt_unit_map(self.sizes)
+        self.n_segments, self.n_units = len(params), int(self.units.shape[0])
+        seg = np.zeros((self.n_segments, 4), dtype=np.int64)                    # nopesac_opt_segment: param, offset, n, (group, reserved)
+        seg[:, 0], seg[:, 1], seg[:, 2], seg[:, 3] = [p.data_ptr() for p in params], self.offsets, self.sizes, groups
+        _require(seg.strides == (ctypes.sizeof(_lib.OptSegment), 8) and self.units.strides == (ctypes.sizeof(_lib.OptUnit), 4)
+                 and ctypes.sizeof(_lib.OptSource) == 16, "OptLayout: the header's table rows are not the rows written here")
+        self.segments_dev = torch.from_numpy(seg).to(dev)
+        self.units_dev = torch.from_numpy(np.ascontiguousarray(self.units)).to(dev)
+        self.sources_dev = torch.zeros(self.n_segments, 2, dtype=torch.int64, device=dev)     # nopesac_opt_source: src, (flags, reserved)
+        self._staging = [torch.zeros(self.n_segments, 2, dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._events = [None, None]
+        self._slot = 0
+
+    def arena(self) -> torch.Tensor:
+        """A zeroed f32 arena of this layout (G, M1 or M2): torch allocates it, the library allocates nothing."""
+        return torch.zeros(self.arena_floats, device=self.device, dtype=torch.float32)
+
+    def view(self, arena: torch.Tensor, i: int) -> torch.Tensor:
+        """Segment i of an arena, in the shape of its parameter."""
+        o = int(self.offsets[i])
+        return arena[o:o + int(self.sizes[i])].view(self.params[i].shape)
+
+    def sources(self, grads, first=None, absent_as_zeros: bool = False) -> torch.Tensor:
+        """This step's source table on the device: grads[i] is the gradient of params[i] (f32, contiguous, same element count; kept
+        alive by the caller until the gather is enqueued) or None = absent; first[i] marks a segment's first SGD momentum step.
+        absent_as_zeros: an absent segment is PRESENT with a null source - the gather fills zeros and the step runs over it."""
+        _require(len(grads) == self.n_segments and (first is None or len(first) == self.n_segments), "OptLayout.sources: one entry per parameter")
+        self._slot ^= 1
+        if self._events[self._slot] is not None:
+            self._events[self._slot].synchronize()                              # the upload of two steps ago: long done, never a wait in practice
+        host = self._staging[self._slot]
+        rows = host.numpy()
+        for i, g in enumerate(grads):
+            flags = OPT_FIRST if (first is not None and first[i]) else 0
+            if g is None:
+                rows[i, 0], rows[i, 1] = 0, (flags | OPT_PRESENT) if absent_as_zeros else 0
+                continue
+            _chk(g, torch.float32)
+            if g.numel() != self.sizes[i] or g.device != self.device:
+                raise OpsArgumentError("OptLayout.sources: gradient %d: shape %s on %s for a parameter of %d elements on %s"
+                                       % (i, tuple(g.shape), g.device, self.sizes[i], self.device))
+            rows[i, 0], rows[i, 1] = g.data_ptr(), flags | OPT_PRESENT
+        self.sources_dev.copy_(host, non_blocking=True)
+        ev = self._events[self._slot] = self._events[self._slot] or torch.cuda.Event()
+        ev.record()
+        return self.sources_dev
+
+    def _arena(self, t: Optional[torch.Tensor], what: str):
+        _require(t is not None, what + ": missing")
+        _sized(t, torch.float32, self.arena_floats, what)
+        _require(t.device == self.device and t.data_ptr() % 16 == 0, "%s: on %s and 16-byte aligned" % (what, self.device))
+        return _p(t)
+
+
+def opt_gather(layout: OptLayout, sources: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """One launch: G[offset_i + j] = grads_i[j] for every present segment, zeros for every absent one (and in the padding)."""
+    _sized(sources, torch.int64, 2 * layout.n_segments, "opt_gather: sources")
+    _C.nopesac_opt_gather(_p(layout.segments_dev), _p(sources), _p(layout.units_dev), layout.n_segments, layout.n_units,
+                          layout._arena(G, "opt_gather: G"), layout.arena_floats, _stream())
+    return G
+
+
+def opt_step(layout: OptLayout, sources: torch.Tensor, G: torch.Tensor, M1: Optional[torch.Tensor], M2: Optional[torch.Tensor],
+             coef: Optional[torch.Tensor], optimizer: str, groups, step: int, betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.0):
+    """One launch: every present segment's parameter and moments take one AdamW / SGD step from G * coef[0] (coef None: 1) with the
+    {lr, weight_decay} of its group - the bits of scale_by followed by adamw_step / sgd_step per tensor.  groups: [(lr, weight_decay)],
+    at most OPT_MAX_GROUPS; step counts from 1 (AdamW's bias correction); M1 = exp_avg or the momentum buffer (None for SGD without
+    momentum), M2 = exp_avg_sq (None for SGD)."""
+    name = str(optimizer).upper()
+    if name not in OPT_MODES:
+        raise NotImplementedError(f"no optimizer type {optimizer}")           # train_NopeSAC.py:158
+    groups = [(float(lr), float(wd)) for lr, wd in groups]
+    _require(layout.n_groups <= len(groups) <= OPT_MAX_GROUPS, "opt_step: %d..%d groups, got %d" % (layout.n_groups, OPT_MAX_GROUPS, len(groups)))
+    _sized(sources, torch.int64, 2 * layout.n_segments, "opt_step: sources")
+    sgd = name == "SGD"
+    a = _lib.OptStepArgs()
+    a.segments, a.sources, a.units = _p(layout.segments_dev), _p(sources), _p(layout.units_dev)
+    a.n_units, a.arena_floats, a.n_segments = layout.n_units, layout.arena_floats, layout.n_segments
+    a.G = layout._arena(G, "opt_step: G")
+    a.M1 = None if (sgd and float(momentum) == 0.0) else layout._arena(M1, "opt_step: M1")
+    a.M2 = None if sgd else layout._arena(M2, "opt_step: M2")
+    a.coef = None if coef is None else _p(_sized(coef, torch.float32, 1, "opt_step: coef"))
+    _require(coef is None or coef.device == layout.device, "opt_step: coef on another device")
+    a.mode, a.n_groups, a.step = OPT_MODES[name], len(groups), int(step)
+    a.beta1, a.beta2, a.eps, a.momentum = float(betas[0]), float(betas[1]), float(eps), float(momentum)
+    for k, (lr, wd) in enumerate(groups):
+        a.groups[k].lr, a.groups[k].weight_decay = lr, wd
+    _C.nopesac_opt_step(ctypes.byref(a), _stream())
+
+
 # ---- set criterion of the plane head (csrc/plane_criterion.hip) --------------------------------------------------------------------------
 PLANE_MAX_QUERIES, PLANE_MAX_TARGETS, PLANE_MAX_LAYERS = _lib.H.NPS_PLANE_MAX_QUERIES, _lib.H.NPS_PLANE_MAX_TARGETS, _lib.H.NPS_PLANE_MAX_LAYERS
 PLANE_COST_NAMES = ("cost_class", "cost_mask", "cost_dice", "cost_center", "cost_param", "cost_offset", "cost_angle")

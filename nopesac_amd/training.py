@@ -69,6 +69,11 @@ stride-1 dgrad and the wgrad of csrc/conv_bwd.hip.  It takes the gradients the o
 (`input_grads`, through backward_from) or continues their graph (joined_backward), so one optimiser step can move every trainable
 tensor of the model.
 
+One optimiser step over SEVERAL trainers belongs to nopesac_amd/optim.py: ModelOptimizer clips the gradient norm over all of their
+parameters (the reference's full-model clip - HeadTrainer.clip_grad_norm sees one trainer's), keeps one step counter, follows the
+WarmupMultiStepLR schedule, averages gradients across ranks and saves / resumes its state, in a fixed number of launches.
+HeadTrainer.step_from_cfg remains the single-trainer form, and the yardstick that ModelOptimizer is held to bit for bit.
+
 What this is NOT: one forward of the meta-architecture in training mode that drives all trainers - each trainer is called by its user.
 The image, the plane sets and their appearance features are inputs of the stages, as they are of the reference functions, and
 receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
