@@ -701,6 +701,42 @@ nps_status nopesac_resize_bilinear_u8(const uint8_t* src, int H, int W, int C, u
 nps_status nopesac_resize_bilinear_u8_batch(const uint8_t* src, int n, int64_t src_stride, int H, int W, int C, uint8_t* dst, int OH, int OW, int chw,
                                             void* stream);
 
+/* Training-time image augmentation (csrc/augment.hip): the reference mapper's ColorJitter / RandomGrayscale / GaussianBlur chain
+ * (data/planercnn_transforms.py:183-191, data/augmentation.py:22) on n uint8 HWC images of one size, src_stride bytes apart, with
+ * Pillow's 8-bit arithmetic per pixel.  One nopesac_aug_row per image: flags (NPS_AUG_JITTER | NPS_AUG_GREY | NPS_AUG_BLUR), the
+ * order the four jitter operations run in (a permutation of NPS_AUG_BRIGHTNESS .. NPS_AUG_HUE), their factors indexed by operation,
+ * and the blur's sigma.  A row without flags copies its image.  Channels are taken in MEMORY order (channel 0 is Pillow's red). */
+#define NPS_AUG_OPS 4
+#define NPS_AUG_BRIGHTNESS 0
+#define NPS_AUG_CONTRAST 1
+#define NPS_AUG_SATURATION 2
+#define NPS_AUG_HUE 3
+#define NPS_AUG_JITTER 1
+#define NPS_AUG_GREY 2
+#define NPS_AUG_BLUR 4
+#define NPS_AUG_MAX_SIGMA 2 /* the reference draws sigma from [0.1, 2.0]: box radius 0 or 1, six passes reach NPS_AUG_APRON pixels */
+#define NPS_AUG_APRON 6
+#define NPS_AUG_TILE 32     /* the fused pass works on NPS_AUG_TILE x NPS_AUG_TILE output pixels per workgroup */
+#define NPS_AUG_PARTIALS 64 /* luma partial sums per image of the contrast pre-pass */
+typedef struct nopesac_aug_row {
+    int flags;
+    int order[NPS_AUG_OPS];
+    float factor[NPS_AUG_OPS];
+    float sigma;
+} nopesac_aug_row;
+/* nopesac_augment_workspace_bytes: bytes[0] = n * NPS_AUG_PARTIALS * 4, the uint32 luma partials of the contrast pre-pass (0 for an
+ * argument <= 0; H and W do not enter it).  bytes is a HOST pointer; a status, not a value: null bytes is NPS_E_ARG. */
+nps_status nopesac_augment_workspace_bytes(int n, int H, int W, int64_t* bytes);
+/* rows_host: the table in HOST memory, checked here before any launch; rows_dev: the same table in device memory, read by the kernels.
+ * Outputs (each nullable, at least one): chw_out uint8 [n][3][H][W]; nhwc_out f32 [n][H][W][4] = (v - mean[c]) / std[c] with a zero pad
+ * channel (what nopesac_preprocess_nchw_to_nhwc writes from the float image; mean, std: f32[3] on the device).
+ * NPS_E_ARG before any launch: C != 3, H * W * 255 >= 2^32, a workspace shorter than nopesac_augment_workspace_bytes states, unknown flags, an
+ * order that is no permutation of 0-3, a hue factor outside [-0.5, 0.5], sigma <= 0 or > NPS_AUG_MAX_SIGMA.  Two launches (contrast
+ * luma partials in fixed order, then the fused pass); deterministic. */
+nps_status nopesac_augment_u8(const uint8_t* src, int n, int64_t src_stride, int H, int W, int C, const nopesac_aug_row* rows_host,
+                              const nopesac_aug_row* rows_dev, uint8_t* chw_out, float* nhwc_out, const float* mean, const float* std,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Pre-norm counterpart for the decoder layers (transformer/transformer.py:293-322, after the cross-attention), same kernel:
  *   s = tgt + attn . wo^T + bo;  u = s + relu(LN3(s) . w1^T + b1) . w2^T + b2;  n = LN_next(u)
  * y = u (f32 residual stream), y_bf16 = bf16(n), ypos_bf16 = bf16(n + pos[row % pos_rows]), yn = n in f32 (each nullable);

@@ -127,13 +127,17 @@ class PairMapper:
     """dataset dict -> model input dict (the `image` tensors stay on the host unless `device` is given, exactly like the
     reference mapper's output; ScanNet images pass through the GPU resize kernel)."""
 
-    def __init__(self, cfg, dataset_name: str = "", device=None, uint8: bool = False, gpu_jpeg: bool = None):
-        """uint8: keep the decoded 8-bit samples (uint8 CHW tensors; the model widens them on the device - bit-identical results,
+    def __init__(self, cfg, dataset_name: str = "", device=None, uint8: bool = False, gpu_jpeg: bool = None, train: bool = False, seed: int = 0):
+        """train, seed: with train = True and cfg.DATALOADER.AUGMENTATION set, map_batch(..., step=k) applies the reference's training-time
+        augmentation (nopesac_amd/augment.py) on the device, its rows drawn from (seed, k, position); otherwise nothing changes.
+        uint8: keep the decoded 8-bit samples (uint8 CHW tensors; the model widens them on the device - bit-identical results,
         a quarter of the host-to-device bytes) instead of the reference mapper's float32 tensors.
         gpu_jpeg: decode baseline JPEG files on the GPU (default: whenever a GPU is present); files the decoder does not support go
         through PIL like every file does in the reference (counted in `self.host_decoded`)."""
         self.uint8 = uint8
         self.gpu_jpeg = gpu_jpeg
+        self.augmentation = bool(train) and bool(getattr(cfg.DATALOADER, "AUGMENTATION", False))
+        self.seed = int(seed)
         self.host_decoded = 0
         self.img_format = cfg.INPUT.FORMAT
         self.root_dir = cfg.DATASETS.ROOT_DIR
@@ -273,12 +277,99 @@ class PairMapper:
         return [n[0] for n in names] + [n[1] for n in names]
 
     def map_batch(self, entries: List[dict], blobs: List[bytes] = None, infos: list = None, sync: bool = True, keep_device: bool = False,
-                  host=None) -> List[dict]:
+                  host=None, step: int = None, first: int = 0, total: int = None) -> List[dict]:
         """The mapped dicts of a batch of pairs with all 2 * len(entries) images decoded together (decode_files; blobs / infos in
-        batch_paths order)."""
+        batch_paths order).
+        step: the training step; a training mapper with cfg.DATALOADER.AUGMENTATION (see __init__) then augments the 2B images on the
+        device in one launch chain (augment_files), after the ScanNet resize and in place of the CHW transpose.  Row p of
+        augment.sample_params(2 * total, seed, step) belongs to the image at position p of the STEP's batch in batch_paths order; a
+        caller that maps the step's `total` pairs in several pieces (or on several ranks) says where its piece begins (`first`), and
+        every image gets the transform it would get in one piece.  Defaults: this call is the whole batch."""
         B = len(entries)
-        imgs = self.decode_files(self.batch_paths(entries), blobs, infos, sync=sync, keep_device=keep_device, host=host)
+        paths = self.batch_paths(entries)
+        if self.augmentation and step is not None:
+            imgs = self.augment_files(paths, int(step), int(first), B if total is None else int(total), blobs, infos, sync=sync,
+                                      keep_device=keep_device, host=host)
+        else:
+            imgs = self.decode_files(paths, blobs, infos, sync=sync, keep_device=keep_device, host=host)
         return [self(e, images=[imgs[i], imgs[B + i]]) for i, e in enumerate(entries)]
+
+    def decode_files_hwc(self, paths: List[str], blobs: List[bytes] = None, infos: list = None, host=None) -> List[torch.Tensor]:
+        """The images of `paths` as uint8 [H,W,3] DEVICE tensors in cfg.INPUT.FORMAT order, resized for ScanNet: what the augmentation
+        kernels read.  JPEG files the GPU decoder takes are decoded there in one chain (views of its one buffer, or of the batched
+        resize's); every other file is decoded on the host, as in decode_files, and uploaded."""
+        from . import jpeg, ops
+        dev = self._resize_device
+        if dev is None:
+            raise RuntimeError("the training-time augmentation runs on the GPU (nopesac_amd has no CPU path)")
+        n = len(paths)
+        blobs = list(blobs) if blobs is not None else [None] * n
+        infos = list(infos) if infos is not None else [None] * n
+        out = [None] * n
+        with torch.cuda.device(dev):
+            if host is not None and host.n == n and self._use_gpu_jpeg():
+                gpu_idx, dec = list(range(n)), jpeg.decode_batch(None, dev, bgr=(self.img_format == "BGR"), host=host)
+            else:
+                gpu_idx = []
+                for i, p in enumerate(paths):
+                    if not (self._use_gpu_jpeg() and is_jpeg_path(p)):
+                        continue
+                    if blobs[i] is None:
+                        with open(p, "rb") as f:
+                            blobs[i] = f.read()
+                    if infos[i] is None:
+                        try:
+                            infos[i] = jpeg.parse(blobs[i])
+                        except jpeg.JpegUnsupported:
+                            infos[i] = False
+                    if infos[i]:
+                        gpu_idx.append(i)
+                dec = jpeg.decode_batch([blobs[i] for i in gpu_idx], dev, bgr=(self.img_format == "BGR"),
+                                        infos=[infos[i] for i in gpu_idx]) if gpu_idx else []
+            if dec and self.scannet and len({tuple(t.shape) for t in dec}) == 1 and tuple(dec[0].shape[:2]) != (480, 640):
+                batch = ops.resize_bilinear_u8_batch(dec, 480, 640, chw=False) if len(dec) > 1 else None
+                if batch is not None:
+                    dec = [batch[k] for k in range(len(dec))]
+            for i, t in zip(gpu_idx, dec):
+                out[i] = t
+            for i, p in enumerate(paths):
+                if out[i] is None:
+                    if is_jpeg_path(p) and self._use_gpu_jpeg():
+                        self.host_decoded += 1
+                    out[i] = torch.from_numpy(read_image(p, self.img_format).copy()).to(dev)
+                if self.scannet and tuple(out[i].shape[:2]) != (480, 640):
+                    out[i] = ops.resize_bilinear_u8(out[i].contiguous(), 480, 640)
+        return out
+
+    def augment_files(self, paths: List[str], step: int, first: int = 0, total: int = None, blobs: List[bytes] = None, infos: list = None,
+                      sync: bool = True, keep_device: bool = False, host=None) -> List[torch.Tensor]:
+        """decode_files with the training-time augmentation: `paths` are the 2B files of B pairs in batch_paths order, pairs
+        first .. first + B of a step's `total`; image (view v, pair j) takes row v * total + first + j of the step's table."""
+        from . import augment
+        dev = self._resize_device
+        n, B = len(paths), len(paths) // 2
+        total = B if total is None else total
+        if n != 2 * B or first < 0 or first + B > total:
+            raise ValueError("augment_files: 2 B files of pairs %d .. %d of %d expected, got %d files" % (first, first + B, total, n))
+        imgs = self.decode_files_hwc(paths, blobs, infos, host)
+        rows = np.concatenate([augment.sample_params(B, self.seed, step, first=v * total + first).rows for v in (0, 1)])
+        params = augment.AugmentParams(rows).to(dev)
+        with torch.cuda.device(dev):
+            if len({tuple(t.shape) for t in imgs}) == 1:
+                a = imgs[0]
+                stride = (imgs[1].data_ptr() - a.data_ptr()) if n > 1 else a.numel()
+                in_place = stride >= a.numel() and all(t.is_contiguous() and t.data_ptr() == a.data_ptr() + k * stride and
+                                                       t.untyped_storage().data_ptr() == a.untyped_storage().data_ptr() for k, t in enumerate(imgs))
+                batches = [augment.augment(imgs if in_place else torch.stack(imgs), params)]       # the decoder's buffer is read in place
+            else:                                   # images of several sizes (mp3d files that disagree): one launch chain per image
+                batches = [augment.augment(t.contiguous()[None], params[k]) for k, t in enumerate(imgs)]
+            if not self.uint8:
+                batches = [b.float() for b in batches]
+            if self.device is None and not keep_device:
+                batches = [b.cpu() for b in batches]
+            elif sync:
+                torch.cuda.current_stream(dev).synchronize()
+        return [b[k] for b in batches for k in range(b.shape[0])]
 
 
 class LazyPairs:

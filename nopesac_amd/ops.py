@@ -1441,6 +1441,52 @@ def resize_bilinear_u8_batch(imgs, out_h: int, out_w: int, chw: bool = True) -> 
     return out
 
 
+def augment_workspace_bytes(n: int, H: int, W: int) -> int:
+    """Bytes of scratch augment_images needs for n images of H x W (the contrast pre-pass's luma partials)."""
+    out = ctypes.c_int64()
+    _C.nopesac_augment_workspace_bytes(int(n), int(H), int(W), ctypes.byref(out))
+    return out.value
+
+
+def augment_images(src, params, *, chw_out: Optional[torch.Tensor] = None, nhwc_out: Optional[torch.Tensor] = None,
+                   mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None) -> None:
+    """The training-time augmentation of csrc/augment.hip on n uint8 [H,W,3] device images of ONE size: `src` a contiguous [n,H,W,3]
+    tensor, or a list of views lying evenly spaced in one buffer (jpeg.decode_batch's output, read in place).  params: an
+    augment.AugmentParams with its device copy (.to(device)).  Outputs, at least one: chw_out uint8 [n,3,H,W]; nhwc_out f32 [n,H,W,4]
+    = (v - mean) / std with a zero pad channel (mean, std f32[3]), bit for bit what `preprocess` makes of the float image."""
+    if isinstance(src, torch.Tensor):
+        _chk(src, torch.uint8)
+        _require(src.dim() == 4, "augment_images: [n,H,W,3] expected")
+        n, H, W, C = src.shape
+        a, stride = src, H * W * C
+    else:
+        a = src[0]
+        _chk(a, torch.uint8)
+        _require(a.dim() == 3, "augment_images: [H,W,3] images expected")
+        H, W, C = a.shape
+        n = len(src)
+        stride = (src[1].data_ptr() - a.data_ptr()) if n > 1 else H * W * C
+        st = a.untyped_storage().data_ptr()
+        _require(stride >= H * W * C and all(im.shape == a.shape and im.is_contiguous() and im.data_ptr() == a.data_ptr() + k * stride
+                                             and im.untyped_storage().data_ptr() == st for k, im in enumerate(src)),
+                 "augment_images: the images must have one size and lie evenly spaced in one buffer")
+    rows, dev_rows = params.rows, params.device_rows
+    _require(len(rows) == n and rows.flags["C_CONTIGUOUS"] and rows.itemsize == 40, "augment_images: one 40-byte parameter row per image")
+    _require(dev_rows is not None and dev_rows.device == a.device, "augment_images: params.to(device) first")
+    _sized(dev_rows, torch.int32, 10 * n, "augment_images: device rows")
+    _require(chw_out is not None or nhwc_out is not None, "augment_images: no output asked for")
+    if chw_out is not None:
+        _sized(chw_out, torch.uint8, n * 3 * H * W, "augment_images: chw_out")
+    if nhwc_out is not None:
+        _sized(nhwc_out, torch.float32, n * H * W * 4, "augment_images: nhwc_out")
+        _sized(mean, torch.float32, 3, "augment_images: mean")
+        _sized(std, torch.float32, 3, "augment_images: std")
+    nbytes = augment_workspace_bytes(n, H, W)
+    ws = scratch(a.device, nbytes)
+    _C.nopesac_augment_u8(_p(a), n, stride, H, W, C, rows.ctypes.data, _p(dev_rows), _p(chw_out), _p(nhwc_out),
+                          _p(mean) if nhwc_out is not None else None, _p(std) if nhwc_out is not None else None, _p(ws), ws.numel() * 4, _stream())
+
+
 def mask_head(c1: torch.Tensor, t1: torch.Tensor, w_lat_frag: torch.Tensor, scale, bias, mask_w: torch.Tensor, mask_b: torch.Tensor,
               sigmoid: bool = True, want_p1: bool = False, planar: bool = False, fold: Optional[torch.Tensor] = None, taps1: bool = False,
               pipe: bool = False):
