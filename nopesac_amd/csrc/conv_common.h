@@ -51,6 +51,17 @@ template <> struct VecT<float, 1> { typedef float type; };
         asm volatile("" ::: "memory");                         \
     } while (0)
 
+// Phase barrier of the staggered schedules (conv_p8.hip, conv_p8n.hip): a bare s_barrier that neither the compiler's scheduler nor its
+// memory model moves anything across, and that waits for no counter (the phases place their own counted vmcnt).
+#define NPS_PHASE_BAR()                            \
+    do {                                           \
+        __builtin_amdgcn_sched_barrier(0);         \
+        asm volatile("" ::: "memory");             \
+        __builtin_amdgcn_s_barrier();              \
+        asm volatile("" ::: "memory");             \
+        __builtin_amdgcn_sched_barrier(0);         \
+    } while (0)
+
 template <int BM, int BN, int TM, int TN, int WAVES_M = 2, int WAVES_N = 2>
 __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[TM][TN], float* epi, int lds_bytes, const ConvParams& p, int m0, int n0,
                                               int bz, int wm, int wn, int lane, int tid) {
@@ -144,5 +155,46 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[TM][TN], float* epi,
 }
 
 typedef __attribute__((address_space(3))) void* lptr_t;
+
+}  // namespace nps
+
+// ---- host only: what the launchers of conv_igemm.hip, conv_p8.hip and conv_p8n.hip share
+int nps_p8_num_cus();              // compute units of the current device (conv_p8.hip)
+
+namespace nps {
+
+// The fields every conv launcher fills the same way (everything else zero): the call's pointers and dimensions, the output size and
+// the GEMM view M = B * OH * OW, N = Cout, K = KH * KW * Cin.  `act` without its flag bits.
+inline void conv_params_fill(ConvParams& p, const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y,
+                             int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int64_t x_cstride,
+                             int64_t y_cstride, int64_t r_cstride, int act, int res_after, int out_dt) {
+    memset(&p, 0, sizeof(p));
+    p.x = x; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
+    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
+    p.OH = (H + 2 * pad - KH) / stride + 1;
+    p.OW = (W + 2 * pad - KW) / stride + 1;
+    p.x_cs = x_cstride; p.y_cs = y_cstride; p.r_cs = r_cstride;
+    p.rows_per_b = p.OH * p.OW;
+    p.M = B * p.rows_per_b; p.N = Cout; p.K = KH * KW * Cin;
+    p.act = act; p.out_dt = out_dt; p.res_after = res_after;
+}
+
+// conv_epilogue's vectorised path needs 8-channel runs that are 16-byte aligned in every buffer it touches
+inline int conv_epi_vec(int out_dt, const void* y, int64_t y_cstride, const void* residual, int64_t r_cstride, const float* scale,
+                        const float* bias) {
+    const int al = out_dt == NPS_DT_F32 ? 4 : 8;     // elements per 16 bytes
+    bool ok = (y_cstride % al == 0) && ((uintptr_t)y % 16 == 0);
+    if (residual) ok = ok && (r_cstride % al == 0) && ((uintptr_t)residual % 16 == 0);
+    if (scale) ok = ok && ((uintptr_t)scale % 16 == 0);
+    if (bias) ok = ok && ((uintptr_t)bias % 16 == 0);
+    return ok ? 1 : 0;
+}
+
+// Workgroups of a persistent launch: one per compute unit, at most `grid_cap` (> 0: tuning aid) and at most one per work unit
+inline int conv_persistent_grid(int grid_cap, long long units) {
+    int nwg = nps_p8_num_cus();
+    if (grid_cap > 0 && grid_cap < nwg) nwg = grid_cap;
+    return units < nwg ? (int)units : nwg;
+}
 
 }  // namespace nps

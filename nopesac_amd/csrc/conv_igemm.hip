@@ -827,18 +827,12 @@ extern "C" int nopesac_conv2d_nhwc_ex(const void* x, const void* w, const float*
     act &= 0xff;
     NPS_CHECK_ARG(act >= 0 && act <= 3, "conv2d: bad act %d", act);
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-    p.OH = (H + 2 * pad - KH) / stride + 1;
-    p.OW = (W + 2 * pad - KW) / stride + 1;
+    conv_params_fill(p, x, w, scale, bias, residual, y, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, r_cstride, act, res_after, out_dt);
     NPS_CHECK_ARG(p.OH > 0 && p.OW > 0, "conv2d: empty output");
-    p.x_cs = x_cstride; p.y_cs = y_cstride; p.r_cs = r_cstride; p.w_bs = w_bstride;
-    p.rows_per_b = p.OH * p.OW;
+    p.w_bs = w_bstride;
     p.batched = w_bstride != 0;
-    p.M = p.batched ? p.rows_per_b : B * p.rows_per_b;
-    p.N = Cout; p.K = KH * KW * Cin;
-    p.act = act; p.out_dt = out_dt; p.res_after = res_after; p.bias_bs = bias_batched ? Cout : 0;
+    if (p.batched) p.M = p.rows_per_b;           // grid.y = batch index
+    p.bias_bs = bias_batched ? Cout : 0;
     p.dense1x1 = (KH == 1 && KW == 1 && stride == 1 && pad == 0) ? 1 : 0;
     {
         // kernel_cfg (per call, e.g. from the load-time autotuner) or NOPESAC_CONV_FORCE (tuning aid):
@@ -858,17 +852,8 @@ extern "C" int nopesac_conv2d_nhwc_ex(const void* x, const void* w, const float*
             else if (!strcmp(e, "glds32")) { p.force = 4; }
         }
     }
-    {   // vectorised epilogue needs 8-channel runs that are 16-byte aligned in every buffer it touches
-        const size_t osz = out_dt == NPS_DT_F32 ? 4 : 2;
-        const int al = out_dt == NPS_DT_F32 ? 4 : 8;     // elements per 16 bytes
-        bool ok = (y_cstride % al == 0) && ((uintptr_t)y % 16 == 0);
-        if (residual) ok = ok && (r_cstride % al == 0) && ((uintptr_t)residual % 16 == 0);
-        if (scale) ok = ok && ((uintptr_t)scale % 16 == 0);
-        if (bias) ok = ok && ((uintptr_t)bias % 16 == 0) && (!bias_batched || Cout % 4 == 0);
-        (void)osz;
-        p.epi_vec = ok ? 1 : 0;
-        NPS_CHECK_ARG(out_dt != NPS_DT_FP8 || (ok && Cout % 8 == 0), "conv2d: fp8 output needs Cout %% 8 == 0 and 8-channel-aligned y / scale / bias");
-    }
+    p.epi_vec = conv_epi_vec(out_dt, y, y_cstride, residual, r_cstride, scale, bias) && (!bias_batched || Cout % 4 == 0);
+    NPS_CHECK_ARG(out_dt != NPS_DT_FP8 || (p.epi_vec && Cout % 8 == 0), "conv2d: fp8 output needs Cout %% 8 == 0 and 8-channel-aligned y / scale / bias");
     if (in_dt == NPS_DT_BF16) launch_dtype<bf16_t, bf16_t>(p, (hipStream_t)stream);
     else if (in_dt == NPS_DT_F32_BF16W) launch_dtype<float, bf16_t>(p, (hipStream_t)stream);
     else launch_dtype<float, float>(p, (hipStream_t)stream);
@@ -893,24 +878,9 @@ static int bfrag_launch(bool fp8, const void* x, const void* w_frag, const float
     const int res_after = (act & NPS_ACT_RES_AFTER) ? 1 : 0;
     act &= 0xff;
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w_frag; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-    p.OH = (H + 2 * pad - KH) / stride + 1;
-    p.OW = (W + 2 * pad - KW) / stride + 1;
-    p.x_cs = x_cstride; p.y_cs = y_cstride; p.r_cs = r_cstride; p.w_bs = 0;
-    p.rows_per_b = p.OH * p.OW;
-    p.batched = 0;
-    p.M = B * p.rows_per_b; p.N = Cout; p.K = KH * KW * Cin;
-    p.act = act; p.out_dt = out_dt; p.res_after = res_after; p.force = kmajor;
-    {
-        const int al = out_dt == NPS_DT_F32 ? 4 : 8;
-        bool ok = (y_cstride % al == 0) && ((uintptr_t)y % 16 == 0);
-        if (residual) ok = ok && (r_cstride % al == 0) && ((uintptr_t)residual % 16 == 0);
-        if (scale) ok = ok && ((uintptr_t)scale % 16 == 0);
-        if (bias) ok = ok && ((uintptr_t)bias % 16 == 0);
-        p.epi_vec = ok ? 1 : 0;
-    }
+    conv_params_fill(p, x, w_frag, scale, bias, residual, y, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, r_cstride, act, res_after, out_dt);
+    p.force = kmajor;
+    p.epi_vec = conv_epi_vec(out_dt, y, y_cstride, residual, r_cstride, scale, bias);
     p.tiles_m = (p.M + 127) / 128;
     p.tiles_n = p.N / 128;
     const dim3 grid(p.tiles_m * p.tiles_n);

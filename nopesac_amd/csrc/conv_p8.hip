@@ -1,48 +1,24 @@
-// 256x256-tile implicit-GEMM NHWC convolution for the MFMA-bound bf16 layers (Cin % 64 == 0, Cout % 256 == 0): PERSISTENT
-// 8-wave workgroups (one per CU), both operands through LDS-DMA, phase-interleaved schedule with counted vmcnt, the epilogue of
-// one tile overlapped with the first DMAs of the next.
-//
-// Why another kernel: conv_igemm_bfrag_kernel / conv_igemm_glds_kernel own 128x128 tiles - every K = 64 step moves 32 KB from
-// L2 for 2.1 MFLOP (64 FLOP/B; the 3x3 256->256 layer at 60x80 pulls 5.7 GB = 14.5 TB/s through L2 at 928 TFLOP/s) and the
-// waves of a 4-wave workgroup read fragments and issue MFMAs in lockstep, so the matrix pipe idles during every LDS-read /
-// barrier interval (PMC: MFMA-busy 44 %, waves parked 45 % of their cycles).  Here:
-//   * tile 256 pixels x 256 channels x K 64: 64 KB per K-tile for 8.4 MFLOP (128 FLOP/B, half the L2 traffic per FLOP);
-//     wave grid 2 (pixels) x 4 (channels), wave tile 128 x 64 = 4 x 2 accumulators of v_mfma_f32_32x32x16_bf16;
-//   * the two waves that share a SIMD (wave w and w + 4 = the two pixel halves) run STAGGERED by one barrier interval:
-//     while one issues its LDS fragment reads and its share of the next tiles' DMAs, the other issues 8 MFMAs (256 cycles of
-//     the SIMD's matrix pipe) - the pipe is fed from one wave or the other all the time (MI355X_MICROARCH.md "Two waves per
-//     SIMD"); the younger half gets one static s_setprio 1.  Measured with in-kernel cycle stamps: 282 cycles per interval
-//     (256 = the 8 MFMAs);
-//   * a K-tile is 4 phases (pixel half mi x K half kh: 2x2 accumulators x 2 k-steps = 8 MFMAs each, 4 independent
-//     accumulator chains); fragment reads per phase 8 / 8 / 4 / 4 ds_read_b128 (the channel fragments of both K halves stay in
-//     registers for the second pixel half);
-//   * LDS = 2 K-tile buffers x 64 KB; each buffer is staged as FOUR 16 KB pieces (pixel-half A0 / A1, channel halves BL / BH),
-//     one piece per phase, into whichever piece is already dead: A0, BL, BH are last read in phase 2, A1 in phase 4, so
-//     while tile t computes, phases 1-3 stage BL, BH, A1 of tile t+1 (other buffer) and phase 4 stages A0 of tile t+2 (this
-//     buffer).  DMA completion is a counted s_waitcnt vmcnt: "A1(t) landed" before phase 3 (6 newer DMAs may stay in flight),
-//     "A0, BL, BH of tile t+1 landed" before the next tile (4 newer ones in flight) - never vmcnt(0) in the steady state;
-//     every piece has >= 2 phases (~1000 cycles) between issue and wait;
-//   * im2col addressing as in conv_igemm_glds_kernel: loop-invariant per-lane voffset, tap-validity bit mask, wave-uniform
-//     SGPR tap offset, out-of-image taps / rows >= M read zeros through the buffer bounds check; bank-conflict XOR swizzle on
-//     the source chunk and on the ds_read_b128;
-//   * PERSISTENT: the grid is one workgroup per CU; a workgroup walks its XCD's contiguous run of tiles with stride 32.  With
-//     one workgroup per CU nothing else can hide a tile's prologue (index math + the first DMA round trip: 12 k cycles) and
-//     epilogue (13-50 k cycles; all CUs reach it together) - together they were as long as the 82 k-cycle K loop.  So, after
-//     the K loop of tile i: compute tile i+1's addresses, issue the four pieces of ITS K-tile 0 into buffer 0, and only then
-//     run tile i's epilogue (f32 staging in the LDS above buffer 0: four passes of 64 pixel rows; thread t owns the 8-channel
-//     chunk t % 32, scale / bias loaded once, every wave-uniform decision taken once per pass, each wave store instruction
-//     writes two whole 512-byte pixel rows; LDS-only barriers so that stores are never waited for).  The stores drain under
-//     the next tile's K loop.
-// Hazards (the rules of cdna_hip_programming.md "8-phase template"): a piece is re-staged >= 2 phases after its last
-// ds_read (the lagging wave group reads one interval later and its reads retire after the following barrier); a staged piece
-// is read >= 1 phase after the wait that retires it (both groups have then passed their own vmcnt and a common barrier).
-#include "conv_common.h"
+// 256x256-tile implicit-GEMM NHWC convolution for the MFMA-bound bf16 layers (Cin % 64 == 0, Cout % 256 == 0): PERSISTENT 8-wave
+// workgroups (one per CU), both operands through LDS-DMA, phase-interleaved schedule with counted vmcnt, the epilogue of one tile
+// overlapped with the first DMAs of the next.  Tile walk, row table, K cursor and pixel DMA are conv_p8_tile.h's, shared with
+// conv_p8n.hip; the reasoning and the measurements behind the design are in docs/kernels.md, "The two 256-row conv kernels".  In short:
+//   * tile 256 pixels x 256 channels x K 64; wave grid 2 (pixels) x 4 (channels), wave tile 128 x 64 = 4 x 2 accumulators of
+//     v_mfma_f32_32x32x16_bf16; the two waves that share a SIMD (wave w and w + 4 = the two pixel halves) run STAGGERED by one barrier
+//     interval: while one reads fragments and issues DMAs, the other issues 8 MFMAs; the younger half gets one static s_setprio 1;
+//   * a K-tile is 4 phases (pixel half mi x K half kh); LDS = 2 K-tile buffers x 64 KB, each staged as FOUR 16 KB pieces (pixel-half
+//     A0 / A1, channel halves BL / BH), one piece per phase, into whichever piece is already dead: while tile t computes, phases 1-3
+//     stage BL, BH, A1 of tile t+1 (other buffer) and phase 4 stages A0 of tile t+2 (this buffer).  DMA completion is a counted
+//     s_waitcnt vmcnt: "A1(t) landed" before phase 3 (6 newer DMAs may stay in flight), "A0, BL, BH of tile t+1 landed" before the
+//     next tile (4 newer ones in flight) - never vmcnt(0) in the steady state;
+//   * after the K loop of tile i: compute tile i+1's addresses, issue the four pieces of ITS K-tile 0 into buffer 0, and only then run
+//     tile i's epilogue (staging in the LDS above buffer 0).  The stores drain under the next tile's K loop.
+// Hazards (the rules of cdna_hip_programming.md "8-phase template"): a piece is re-staged >= 2 phases after its last ds_read (the
+// lagging wave group reads one interval later and its reads retire after the following barrier); a staged piece is read >= 1 phase
+// after the wait that retires it (both groups have then passed their own vmcnt and a common barrier).
 #include "conv_forms.h"
+#include "conv_p8_tile.h"
 
 namespace nps {
-
-template <int K>
-struct IC { static constexpr int value = K; };
 
 constexpr int P8_BM = 256, P8_BN = 256, P8_BK = 64, P8_ROWB = 128;
 constexpr int P8_A_BYTES = P8_BM * P8_ROWB, P8_B_BYTES = P8_BN * P8_ROWB, P8_STAGE = P8_A_BYTES + P8_B_BYTES;   // 32 + 32 KB
@@ -58,15 +34,6 @@ constexpr int P8_LDS = P8_FLAG_OFF + 16;                           // 131 KB (ON
 constexpr int P8_SK_HDR = P8_SK_MAX_TILES * 4;
 constexpr int P8_SK_SLAB = P8_BM * P8_BN * 4;                      // 256 KB
 
-// LDS-only workgroup barrier: orders this wave's LDS accesses (lgkmcnt) and synchronises, WITHOUT the vmcnt(0) that
-// __syncthreads() carries - the epilogue's global stores must not be waited for.
-#define P8_LDS_SYNC()                                          \
-    do {                                                       \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     \
-        __builtin_amdgcn_s_barrier();                          \
-        asm volatile("" ::: "memory");                         \
-    } while (0)
-
 // Epilogue of one 256x256 tile: four passes, pass q = accumulator row tile q of BOTH pixel halves (64 pixel rows x 256
 // channels f32 in LDS, rows padded by 16 bytes: conflict-free ds_write_b128).  Arithmetic order is conv_epilogue's
 // (v * scale + bias, residual before or after the activation): results are identical to the other conv kernels'.
@@ -76,7 +43,6 @@ constexpr int P8_SK_SLAB = P8_BM * P8_BN * 4;                      // 256 KB
 // owns, for its pixel row, the 32 channels wc*64 + j*32 + 8q + 4*(lane >> 5) + e: their scale / bias values sit in 64 registers
 // (loaded once per tile, before the next tile's DMAs), the staged tile is bf16 (half the LDS bytes of the f32 staging) and the
 // second stage is a pure 16-byte LDS -> global copy.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct P8EpiRegs16 {
     float sc[2][4][4], bs[2][4][4];
@@ -129,7 +95,7 @@ __device__ __forceinline__ void p8_epilogue16(f32x16 (&acc)[4][2], unsigned char
             // descriptor's bounds check) - a counted wait, the stores are never waited for (round 4; was vmcnt(0))
             if (drain_dma) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         }
-        P8_LDS_SYNC();
+        NPS_LDS_SYNC();
         u32x4 o[4];
 #pragma unroll
         for (int it = 0; it < 4; ++it) o[it] = *(const u32x4*)(epi + (it * 16 + rg) * P8_ELD16 + c8 * 8);
@@ -139,7 +105,7 @@ __device__ __forceinline__ void p8_epilogue16(f32x16 (&acc)[4][2], unsigned char
             const unsigned m = (unsigned)(m0 + (rs >> 5) * 128 + pass * 32 + (rs & 31));
             __builtin_amdgcn_raw_buffer_store_b128(o[it], ry, (int)((m * (unsigned)p.y_cs + (unsigned)(n0 + c8 * 8)) * 2u), 0, 0);
         }
-        P8_LDS_SYNC();
+        NPS_LDS_SYNC();
     };
     do_pass(IC<0>{});
     do_pass(IC<1>{});
@@ -222,7 +188,7 @@ __device__ __forceinline__ void p8_epilogue(f32x16 (&acc)[4][2], unsigned char* 
                 *(f32x4*)(epi + rs * P8_ELD + c) = v;
             }
         if constexpr (STAMP && pass == 0) est[7] = __builtin_readcyclecounter();
-        P8_LDS_SYNC();
+        NPS_LDS_SYNC();
         if constexpr (STAMP && pass == 0) est[8] = __builtin_readcyclecounter();
         // all 4 items of the thread at once: straight-line code, every wave-uniform decision (residual kind, activation, output
         // type) taken ONCE per pass around fully unrolled item loops (a per-element activation switch compiled to 20 k lines of
@@ -307,7 +273,7 @@ __device__ __forceinline__ void p8_epilogue(f32x16 (&acc)[4][2], unsigned char* 
                 }
         }
         if constexpr (STAMP) est[pass] = __builtin_readcyclecounter();
-        P8_LDS_SYNC();                                          // staging rows free for the next pass / for the DMAs of buffer 1
+        NPS_LDS_SYNC();                                          // staging rows free for the next pass / for the DMAs of buffer 1
     };
     do_pass(IC<0>{});
     do_pass(IC<1>{});
@@ -373,7 +339,7 @@ __device__ __forceinline__ void p8_epilogue4(f32x16 (&acc)[4][2], unsigned char*
                 const f32x4 v = {a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
                 *(f32x4*)(epi + rs * P8_ELD + c) = v;
             }
-        P8_LDS_SYNC();
+        NPS_LDS_SYNC();
         float v[4][8];
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
@@ -414,7 +380,7 @@ __device__ __forceinline__ void p8_epilogue4(f32x16 (&acc)[4][2], unsigned char*
 #pragma unroll
             for (int it = 0; it < 4; ++it) rc[it] = rn[it];
         }
-        P8_LDS_SYNC();                                          // staging rows free for the next pass / for the DMAs of buffer 1
+        NPS_LDS_SYNC();                                          // staging rows free for the next pass / for the DMAs of buffer 1
     };
     do_pass(IC<0>{});
     do_pass(IC<1>{});
@@ -441,153 +407,50 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
     unsigned long long ts[4] = {0, 0, 0, 0}, est[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if constexpr (STAMP) ts[0] = __builtin_readcyclecounter();
 
-    // ---- this workgroup's tiles: XCD x (= blockIdx % 8: private L2) owns a contiguous run of tiles, its workgroups walk the run
-    //      with stride = workgroups on that XCD, so the 32 CUs of an XCD always work on 32 neighbouring tiles (shared halo rows)
-    const int ntiles = p.tiles_m * p.tiles_n;
-    const int nx = (int)gridDim.x < 8 ? (int)gridDim.x : 8;     // XCDs that host workgroups of this grid
-    const int xcd = blockIdx.x % 8, slot = blockIdx.x / 8;
-    const int tq = ntiles / nx, tr = ntiles % nx;
-    const int run_begin = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-    const int run_end = run_begin + tq + (xcd < tr ? 1 : 0);
-    const int stride = ((int)gridDim.x - xcd + 7) / 8;
+    const P8TileWalk walk(p.tiles_m * p.tiles_n);
     const int nk = p.K / P8_BK;
-    // SK: this workgroup's units [ub, ue) of the XCD's line of (run_end - run_begin) * nk K-tile units; `cur` = next unit
-    const int sk_units = SK ? (run_end - run_begin) * nk : 0;
-    auto sk_begin = [&](int s_) { return (int)(((long long)sk_units * s_) / stride); };
-    const int ue = SK ? sk_begin(slot + 1) : 0;
-    int cur = SK ? sk_begin(slot) : 0;
-    int tile = SK ? run_begin + cur / nk : run_begin + slot;
-    if (SK ? cur >= ue : tile >= run_end) return;
+    // SK: this workgroup's units [ub, ue) of the XCD's line of (walk.run_end - walk.run_begin) * nk K-tile units; `cur` = next unit
+    const int sk_units = SK ? (walk.run_end - walk.run_begin) * nk : 0;
+    auto sk_begin = [&](int s_) { return (int)(((long long)sk_units * s_) / walk.stride); };
+    const int ue = SK ? sk_begin(walk.slot + 1) : 0;
+    int cur = SK ? sk_begin(walk.slot) : 0;
+    int tile = SK ? walk.run_begin + cur / nk : walk.run_begin + walk.slot;
+    if (SK ? cur >= ue : tile >= walk.run_end) return;
 
-    // ---- DMA sources.  One 1-KB DMA = 8 tile rows x 128 B, lane -> row (lane >> 3), physical 16-byte slot (lane & 7).
-    //   A piece h (pixel half mi = h of BOTH wave rows): DMA j of wave w fills rows j*128 + h*64 + w*8 .. +7
-    //   B piece h (channels h*128 .. +127):              DMA j of wave w fills rows h*128 + (2w + j)*8 .. +7
-    constexpr unsigned OOB = 0xFFFFFF00u;
-    const int slot8 = lane & 7, rsub = lane >> 3;
-    const long long padb = ((long long)p.pad * p.W + p.pad) * p.x_cs * 2;
-    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)p.x - padb), 0, (int)(((long long)p.B * p.H * p.W * p.x_cs) * 2 + padb), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)((long long)p.N * p.K * 2), 0x00020000);
-    // EPI 1-4: output (EPI 4: and residual) through descriptors that end with row M - 1 (rows >= M of the last tile: zeros in, dropped out)
-    const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.res, 0, EPI == 4 ? (int)((((long long)p.M - 1) * p.r_cs + p.N) * 2) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        p.y, 0, EPI >= 1 ? (int)((((long long)p.M - 1) * p.y_cs + p.N) * 2) : 0, 0x00020000);
+    // ---- DMA sources: the pixel halves are P8Rows'; B piece h (channels h*128 .. +127): DMA j of wave w fills rows h*128 + (2w + j)*8 .. +7
+    // EPI 1-4: output (EPI 4: and residual) through descriptors that end with row M - 1
+    const __amdgpu_buffer_rsrc_t xsrc = p8_x_rsrc(p), wsrc = p8_w_rsrc(p);
+    const __amdgpu_buffer_rsrc_t rres = p8_rows_rsrc(p.res, p, p.r_cs, EPI == 4), ry = p8_rows_rsrc(p.y, p, p.y_cs, EPI >= 1);
     const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(p.sk_ws, 0, SK ? p.sk_ws_bytes : 0, 0x00020000);
-    unsigned a_voff[2][2], a_mask[2][2], b_voff[2][2];
-    int m0 = 0, n0 = 0;
-    // wave-uniform K-tile cursor of the NEXT tile to stage (tiles are staged strictly in order)
-    int cur_tap = 0, cur_kw = 0, cur_c0 = 0;
-    unsigned cur_tapoff = 0u, cur_k0b = 0u;
-    const int ntaps = p.KH * p.KW;
-    // Index math of a tile.  Every tile row is addressed by 8 lanes (its eight 16-byte chunks) of 4 different DMAs, so the
-    // row -> (image, oh, ow) -> byte offset + tap-validity mask computation is done ONCE per row by threads 0..255 into a 2 KB LDS
-    // table, and every lane then picks up its four rows (first version: each lane did it 4 times - ~900 instructions per wave with
-    // 32-bit integer divisions, 64-bit products and a 9-tap loop: 5-6 k cycles per tile):
-    //   * row -> (image, oh, ow) by float reciprocal + one-step fix-up (exact for M < 2^23)
-    //   * every product is a 24-bit multiply (v_mul_u32_u24): pixel indices, channel strides and K are < 2^24 and every byte offset
-    //     < 2^31 (checked by the launcher)
-    //   * tap mask = row-validity bits x column-validity bits
-    const float rcp_rpb = 1.0f / (float)p.rows_per_b, rcp_ow = 1.0f / (float)p.OW;
-    auto divmod = [](int a, int d, float rcp, int& q, int& r) {
-        q = (int)((float)a * rcp);
-        r = a - __mul24(q, d);
-        if (r < 0) { --q; r += d; }
-        if (r >= d) { ++q; r -= d; }
-    };
-    const unsigned xcs = (unsigned)p.x_cs;
-    uint2* rowtab = reinterpret_cast<uint2*>(lds + P8_TAB_OFF);        // [256] {byte offset of the row's pixel, tap mask}
-    unsigned a_coff[2][2], b_base[2][2];                               // per-lane constants: swizzled chunk offsets / weight-row offsets
+    P8Rows<P8_BM, P8_ROWB, P8_TAB_OFF> rows;
+    P8KCursor<P8_BK> kc(p);
+    rows.init(p, wave, lane);
+    unsigned b_voff[2][2], b_base[2][2];                               // per lane: weight-row offsets of the tile / of channel tile 0
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int pr = j * 128 + h * 64 + wave * 8 + rsub;
-            a_coff[h][j] = (unsigned)(slot8 ^ ((pr >> 1) & 7)) * 16u;
-            const int br = h * 128 + (wave * 2 + j) * 8 + rsub;
-            b_base[h][j] = (__umul24((unsigned)br, (unsigned)p.K) + (unsigned)(slot8 ^ ((br >> 1) & 7)) * 8u) * 2u;
+            const int br = h * 128 + (wave * 2 + j) * 8 + (lane >> 3);
+            b_base[h][j] = (__umul24((unsigned)br, (unsigned)p.K) + (unsigned)((lane & 7) ^ ((br >> 1) & 7)) * 8u) * 2u;
         }
+    int m0 = 0, n0 = 0;
     auto set_tile = [&](int t) {                                       // workgroup-collective (contains a barrier)
         m0 = (t / p.tiles_n) * P8_BM;
         n0 = (t % p.tiles_n) * P8_BN;
-        if (tid < P8_BM) {
-            const int m = m0 + tid;
-            uint2 e = make_uint2(0u, 0u);
-            if (m < p.M) {
-                int b, rem, oh, ow;
-                divmod(m, p.rows_per_b, rcp_rpb, b, rem);
-                divmod(rem, p.OW, rcp_ow, oh, ow);
-                const int ih0 = __mul24(oh, p.stride) - p.pad, iw0 = __mul24(ow, p.stride) - p.pad;
-                const unsigned pix = __umul24(__umul24((unsigned)b, (unsigned)p.H) + (unsigned)(ih0 + p.pad), (unsigned)p.W) + (unsigned)(iw0 + p.pad);
-                unsigned colbits = 0u;
-                for (int kw = 0; kw < p.KW; ++kw) colbits |= ((unsigned)(iw0 + kw) < (unsigned)p.W ? 1u : 0u) << kw;
-                unsigned mk = 0u;
-                for (int kh = 0; kh < p.KH; ++kh)
-                    if ((unsigned)(ih0 + kh) < (unsigned)p.H) mk |= colbits << __mul24(kh, p.KW);
-                e = make_uint2(__umul24(pix, xcs) * 2u, mk);
-            }
-            rowtab[tid] = e;
-        }
-        P8_LDS_SYNC();
+        rows.set_tile(lds, p, m0, tid, wave, lane);
         const unsigned nb = __umul24((unsigned)n0, (unsigned)p.K) * 2u;
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const uint2 e = rowtab[j * 128 + h * 64 + wave * 8 + rsub];
-                a_voff[h][j] = e.x + a_coff[h][j];                  // rows >= M have mask 0: every tap reads out of bounds
-                a_mask[h][j] = e.y;
-                b_voff[h][j] = b_base[h][j] + nb;                    // Cout % 256 == 0: every weight row of the tile exists
-            }
-        cur_tap = 0; cur_kw = 0; cur_c0 = 0; cur_tapoff = 0u; cur_k0b = 0u;
+            for (int j = 0; j < 2; ++j) b_voff[h][j] = b_base[h][j] + nb;       // Cout % 256 == 0: every weight row of the tile exists
+        kc.reset(0);
     };
-    // K order: p.force == 0: tap-major (all channels of tap 0, then tap 1 ...: the natural order of the weight rows);
-    //          p.force == 1: CHANNEL-major (the KH*KW taps of channels 0-63, then of channels 64-127 ...): the pixels a workgroup
-    //          re-reads for the nine taps of one 64-channel slice are ONE 128-byte line each, so the slice stays in the XCD's L2
-    //          between the taps (tap-major streams all Cin channels of the tile's pixels nine times: L2 hit rate 76 %).
-    auto advance = [&]() {
-        if (p.force == 0) {
-            cur_k0b += P8_BK * 2;
-            cur_c0 += P8_BK;
-            if (cur_c0 >= p.Cin) {
-                cur_c0 = 0; ++cur_tap; ++cur_kw;
-                cur_tapoff += (unsigned)p.x_cs * 2u;
-                if (cur_kw == p.KW) { cur_kw = 0; cur_tapoff += (unsigned)(p.W - p.KW) * (unsigned)p.x_cs * 2u; }
-            }
-        } else {
-            ++cur_tap; ++cur_kw;
-            cur_k0b += (unsigned)p.Cin * 2u;
-            cur_tapoff += (unsigned)p.x_cs * 2u;
-            if (cur_kw == p.KW) { cur_kw = 0; cur_tapoff += (unsigned)(p.W - p.KW) * (unsigned)p.x_cs * 2u; }
-            if (cur_tap == ntaps) {
-                cur_tap = 0; cur_kw = 0; cur_tapoff = 0u;
-                cur_c0 += P8_BK;
-                cur_k0b = (unsigned)cur_c0 * 2u;
-            }
-        }
-    };
-    auto set_cursor = [&](int kt) {                          // SK: cursor -> K-tile kt of the current tile (wave-uniform integer math)
-        int tap, c0;
-        if (p.force == 0) { const int per = p.Cin / P8_BK; tap = kt / per; c0 = (kt - tap * per) * P8_BK; }
-        else { const int cs = kt / ntaps; tap = kt - cs * ntaps; c0 = cs * P8_BK; }
-        const int kh = tap / p.KW, kw = tap - kh * p.KW;
-        cur_tap = tap; cur_kw = kw; cur_c0 = c0;
-        cur_tapoff = (unsigned)(kh * p.W + kw) * (unsigned)p.x_cs * 2u;
-        cur_k0b = (unsigned)(tap * p.Cin + c0) * 2u;
-    };
-    auto stage_a = [&](unsigned char* buf, int h) {          // pixel-half piece h at the cursor's K-tile
-        const unsigned soff = cur_tapoff + (unsigned)cur_c0 * 2u;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const unsigned vo = ((a_mask[h][j] >> cur_tap) & 1u) ? a_voff[h][j] : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrc, (lptr_t)(buf + (j * 128 + h * 64 + wave * 8) * P8_ROWB), 16, vo, soff, 0, 0);
-        }
-    };
+    auto stage_a = [&](unsigned char* buf, int h) { rows.stage_a(xsrc, buf, h, wave, kc); };
     auto stage_b = [&](unsigned char* buf, int h) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrc, (lptr_t)(buf + P8_A_BYTES + (h * 128 + (wave * 2 + j) * 8) * P8_ROWB), 16,
-                                                     b_voff[h][j], cur_k0b, 0, 0);
+                                                     b_voff[h][j], kc.k0b, 0, 0);
     };
     auto stage_first = [&]() {                               // the four pieces of K-tile 0 -> buffer 0 (cursor at K-tile 0)
         stage_a(lds, 0);
@@ -602,20 +465,11 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
     const int so0 = ((0 + (lane >> 5)) ^ sw) * 16, so1 = ((2 + (lane >> 5)) ^ sw) * 16, so2 = ((4 + (lane >> 5)) ^ sw) * 16,
               so3 = ((6 + (lane >> 5)) ^ sw) * 16;
 
-#define P8_BAR()                                   \
-    do {                                           \
-        __builtin_amdgcn_sched_barrier(0);         \
-        asm volatile("" ::: "memory");             \
-        __builtin_amdgcn_s_barrier();              \
-        asm volatile("" ::: "memory");             \
-        __builtin_amdgcn_sched_barrier(0);         \
-    } while (0)
-
     set_tile(tile);
     int kb = 0;                                              // SK: first K-tile of the current piece (only a range's first piece starts inside a tile)
     if constexpr (SK) {
-        kb = cur - (tile - run_begin) * nk;
-        if (kb) set_cursor(kb);
+        kb = cur - (tile - walk.run_begin) * nk;
+        if (kb) kc.set_cursor(p, kb);
     }
     stage_first();
     bool first = true;
@@ -634,7 +488,7 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
         bf16x8 af[2][2], bfr[2][4];
-        advance();                                               // cursor -> K-tile 1
+        kc.advance(p);                                               // cursor -> K-tile 1
         if (nkl > 1) stage_a(lds + P8_STAGE, 0);                 // A0(1)
         if (first) {                                             // A0(0), BL(0), BH(0) must have landed; A1(0) [, A0(1)] may fly
             if (nkl > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -683,10 +537,10 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
             }
             load_a(0, so0, so1);
             if (has1) stage_b(nb, 0);
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[1] = __builtin_readcyclecounter(); }
             mfma_phase(IC<0>{}, IC<0>{});
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[2] = __builtin_readcyclecounter(); }
             // ---- phase 2: pixel half 0, K half 1.  reads A0 + B(kh1); stages BH(t+1); A1(t) must have landed before phase 3
 #pragma unroll
@@ -701,33 +555,33 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[3] = __builtin_readcyclecounter(); }
             mfma_phase(IC<0>{}, IC<1>{});
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[4] = __builtin_readcyclecounter(); }
             // ---- phase 3: pixel half 1, K half 0.  reads A1; stages A1(t+1)
             load_a(1, so0, so1);
             if (has1) stage_a(nb, 1);
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[5] = __builtin_readcyclecounter(); }
             mfma_phase(IC<1>{}, IC<0>{});
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[6] = __builtin_readcyclecounter(); }
             // ---- phase 4: pixel half 1, K half 1.  reads A1; stages A0(t+2) into THIS buffer (A0 of tile t is dead since phase 2);
             //      A0 / BL / BH of tile t+1 must have landed before the next tile's phase 1
             load_a(1, so2, so3);
-            if (has1) advance();                                  // cursor -> tile t+2
+            if (has1) kc.advance(p);                                  // cursor -> tile t+2
             if (has2) {
                 stage_a(sb, 0);
                 asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // newer than BH(t+1): A1(t+1), A0(t+2)
             } else if (has1) {
                 asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // newer than BH(t+1): A1(t+1)
             }
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[7] = __builtin_readcyclecounter(); }
             mfma_phase(IC<1>{}, IC<1>{});
-            P8_BAR();
+            NPS_PHASE_BAR();
             if constexpr (STAMP) { if (pst) est[8] = __builtin_readcyclecounter(); }
         };
         {
@@ -740,40 +594,40 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
         }
         if (wr == 0) __builtin_amdgcn_s_barrier();               // pairs with the lagging group's last barrier
         else __builtin_amdgcn_s_setprio(0);
-        P8_LDS_SYNC();                                           // every fragment read of the tile is done: both buffers are free
+        NPS_LDS_SYNC();                                           // every fragment read of the tile is done: both buffers are free
         if constexpr (STAMP) {
             if (stamp_now) ts[2] = __builtin_readcyclecounter();
         }
         // ---- next tile's addresses and the DMAs of its K-tile 0 (buffer 0) BEFORE this tile's epilogue (staging above buffer 0)
         const int cur_m0 = m0, cur_n0 = n0;
         if constexpr (SK) cur += nkl;
-        const int next = SK ? tile + 1 : tile + stride;
-        const bool more = SK ? cur < ue : next < run_end;
+        const int next = SK ? tile + 1 : tile + walk.stride;
+        const bool more = SK ? cur < ue : next < walk.run_end;
         if constexpr (SK) {
             if (nkl < nk) {
                 // ---- a PARTIAL piece of tile `tile`: arrive.  Contributors = the XCD's workgroup slots whose ranges meet the tile's units
                 //      [a, b): s_lo = the first slot with end > a, s_hi = the last slot with begin < b (ranges: [floor(U s / S), floor(U (s + 1) / S)))
-                const long long ua = (long long)(tile - run_begin) * nk, ub_ = ua + nk;
-                const int s_lo = (int)(((ua + 1) * stride + sk_units - 1) / sk_units) - 1;
-                const int s_hi = (int)((ub_ * stride + sk_units - 1) / sk_units) - 1;
+                const long long ua = (long long)(tile - walk.run_begin) * nk, ub_ = ua + nk;
+                const int s_lo = (int)(((ua + 1) * walk.stride + sk_units - 1) / sk_units) - 1;
+                const int s_hi = (int)((ub_ * walk.stride + sk_units - 1) / sk_units) - 1;
                 const int ncon = s_hi - s_lo + 1;
                 volatile int* flag = reinterpret_cast<volatile int*>(lds + P8_FLAG_OFF);
                 int* cnt = reinterpret_cast<int*>(p.sk_ws) + tile;
                 auto slab_of = [&](int s_) {                     // byte offset of slot s_'s slab for THIS tile: slab 0 = its range's first piece
-                    const int first_tile = run_begin + sk_begin(s_) / nk;
-                    return (unsigned)P8_SK_HDR + (unsigned)(((s_ * 8 + xcd) * 2 + (first_tile == tile ? 0 : 1))) * (unsigned)P8_SK_SLAB;
+                    const int first_tile = walk.run_begin + sk_begin(s_) / nk;
+                    return (unsigned)P8_SK_HDR + (unsigned)(((s_ * 8 + walk.xcd) * 2 + (first_tile == tile ? 0 : 1))) * (unsigned)P8_SK_SLAB;
                 };
                 bool last = false;
                 if (kb == 0) {
                     // the head piece is the LAST piece of this workgroup's range: the others (tail / middle pieces, done first in their
                     // ranges) have normally arrived long ago - look before writing 256 KB nobody would read
                     if (tid == 0) flag[0] = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    P8_LDS_SYNC();
+                    NPS_LDS_SYNC();
                     last = __builtin_amdgcn_readfirstlane(flag[0]) == ncon - 1;     // (uniform by construction - say so, or every loop bound downstream becomes a VGPR)
-                    P8_LDS_SYNC();
+                    NPS_LDS_SYNC();
                 }
                 if (!last) {
-                    const unsigned so = slab_of(slot);
+                    const unsigned so = slab_of(walk.slot);
 #pragma unroll
                     for (int b = 0; b < 8; ++b)
 #pragma unroll
@@ -783,11 +637,11 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rws, tid * 16, (int)(so + (unsigned)(b * 4 + q) * 8192u), 16);
                         }
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every slab store of this wave is written through
-                    P8_LDS_SYNC();                                           // ... of every wave
+                    NPS_LDS_SYNC();                                           // ... of every wave
                     if (tid == 0) flag[0] = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    P8_LDS_SYNC();
+                    NPS_LDS_SYNC();
                     last = __builtin_amdgcn_readfirstlane(flag[0]) == ncon - 1;     // (uniform by construction - say so, or every loop bound downstream becomes a VGPR)
-                    P8_LDS_SYNC();
+                    NPS_LDS_SYNC();
                 }
                 if (!last) {
                     // somebody else finishes this tile.  Next piece (if any): its first DMAs, waited for at the loop top like a first tile's
@@ -801,7 +655,7 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
                 // ---- reduce: acc = sum over the contributors in K (= slot) order.  With this piece at position 0 or 1 of that order the
                 //      running sum can live in acc itself ((me + c1) + c2 ... and (c0 + me) + c2 ... are the canonical (c0 + c1) + c2 ...
                 //      with the first pair commuted); from position 2 on the pieces before it are summed separately first.
-                const int me = slot - s_lo;
+                const int me = walk.slot - s_lo;
                 auto add_slab = [&](int s_, auto COPYC) {
                     constexpr bool COPY = decltype(COPYC)::value != 0;
                     const unsigned so = slab_of(s_);
@@ -852,8 +706,8 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) { a_mask[h][j] = 0u; b_voff[h][j] = OOB; }
-                cur_tap = 0; cur_kw = 0; cur_c0 = 0; cur_tapoff = 0u; cur_k0b = 0u;
+                    for (int j = 0; j < 2; ++j) { rows.mask[h][j] = 0u; b_voff[h][j] = P8_OOB; }
+                kc.reset(0);
             }
             stage_first();
         } else if (more) {
@@ -906,7 +760,6 @@ __global__ __launch_bounds__(512) void conv_igemm_p8_kernel(const ConvParams p) 
             if (tile_no == p.dbg_tile) ts[0] = __builtin_readcyclecounter();     // "prologue" of a later tile = from here to its first barrier
         }
     }
-#undef P8_BAR
 #endif
 }
 
@@ -918,7 +771,7 @@ static int g_p8_dbg_tile = 0;
 extern "C" void nps_p8_debug_buffer(void* buf) { g_p8_dbg = (unsigned long long*)buf; }
 extern "C" void nps_p8_debug_tile(int tile_no) { g_p8_dbg_tile = tile_no; }     // which tile of every workgroup gets stamped
 
-static int p8_num_cus() {
+int nps_p8_num_cus() {                                   // (declared in conv_common.h)
     static int cus[64] = {0};
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -929,8 +782,6 @@ static int p8_num_cus() {
     }
     return cus[dev];
 }
-
-int nps_p8_num_cus() { return p8_num_cus(); }             // (conv_p8n.hip)
 
 // x [B,H,W,Cin] bf16 (pixel stride x_cstride), w [Cout][KH][KW][Cin] bf16 (plain K-contiguous rows - NOT fragment-major),
 // Cin % 64 == 0, Cout % 256 == 0; epilogue = nopesac_conv2d_nhwc's (scale / bias / residual / activation / output dtype).
@@ -953,25 +804,18 @@ static int p8_launch(const void* x, const void* w, const float* scale, const flo
     const int res_after = (act & NPS_ACT_RES_AFTER) ? 1 : 0;
     act &= 0xff;
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-    p.OH = (H + 2 * pad - KH) / stride + 1;
-    p.OW = (W + 2 * pad - KW) / stride + 1;
-    p.x_cs = x_cstride; p.y_cs = y_cstride; p.r_cs = r_cstride; p.w_bs = 0;
-    p.rows_per_b = p.OH * p.OW;
-    p.M = B * p.rows_per_b; p.N = Cout; p.K = KH * KW * Cin;
-    p.act = act; p.out_dt = out_dt; p.res_after = res_after; p.force = kmajor;
-    p.epi_vec = 1;                                 // (conv_p8_refusal: every buffer and stride 16-byte aligned)
+    conv_params_fill(p, x, w, scale, bias, residual, y, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, r_cstride, act, res_after, out_dt);
+    p.force = kmajor;
+    p.epi_vec = 1;                                // (conv_p8_refusal: every buffer and stride 16-byte aligned)
     p.tiles_m = (p.M + P8_BM - 1) / P8_BM;
     p.tiles_n = p.N / P8_BN;
-    const int ntiles = p.tiles_m * p.tiles_n;
-    int nwg = p8_num_cus();                        // persistent: one workgroup per CU (129 KB of LDS each)
-    if (grid_cap > 0 && grid_cap < nwg) nwg = grid_cap;
+    const int ntiles = p.tiles_m * p.tiles_n, nkt = p.K / P8_BK;
+    // persistent: one workgroup per CU (129 KB of LDS each); work units = tiles, stream-K: K-tiles (no workgroup count that passes the
+    // loop below exceeds ntiles * nkt, so this bound changes nothing there)
+    int nwg = conv_persistent_grid(grid_cap, sk ? (long long)ntiles * nkt : ntiles);
     if (sk) {
         // stream-K: every XCD's run of tiles must hold at least one K-tile unit per workgroup of that XCD (smallest run x K-tiles >= the
         // largest per-XCD workgroup count), else fewer workgroups
-        const int nkt = p.K / P8_BK;
         NPS_CHECK_ARG((uintptr_t)ws % 16 == 0, "conv2d_p8_sk: workspace alignment");
         while (nwg > 1) {
             const int nx = nwg < 8 ? nwg : 8;
@@ -982,7 +826,7 @@ static int p8_launch(const void* x, const void* w, const float* scale, const flo
         NPS_CHECK_ARG(ws_bytes >= need && need < (1ll << 31), "conv2d_p8_sk: workspace of %lld bytes, %lld needed", (long long)ws_bytes, need);
         p.sk_ws = ws;
         p.sk_ws_bytes = (int)need;
-    } else if (ntiles < nwg) nwg = ntiles;
+    }
     const dim3 grid(nwg);
     // epilogue specialisation (code size, see p8_epilogue): the common no-residual / bf16-output forms get their own build
     int epi = 0;
@@ -1021,7 +865,7 @@ extern "C" int nopesac_conv2d_nhwc_p8(const void* x, const void* w, const float*
 // 16 KB (the arrival counters) are ZERO on entry; they are zero again when the launch has completed, so one workspace serves every launch
 // of a stream (launches on different streams need different workspaces).
 extern "C" int64_t nopesac_conv2d_p8_sk_workspace_bytes(void) {
-    return (int64_t)nps::P8_SK_HDR + (int64_t)p8_num_cus() * 2 * nps::P8_SK_SLAB;
+    return (int64_t)nps::P8_SK_HDR + (int64_t)nps_p8_num_cus() * 2 * nps::P8_SK_SLAB;
 }
 
 extern "C" int nopesac_conv2d_nhwc_p8_sk(const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y,

@@ -1,39 +1,19 @@
 // 256x128-tile implicit-GEMM NHWC convolution for the MFMA-bound bf16 layers with Cout % 128 == 0 that conv_igemm_p8_kernel cannot take
-// (Cout % 256 != 0: the 3x3 128 -> 128 convs of res3 and of the top-down / pose-net stacks - 0.25-0.27 of the MFMA peak on
-// conv_igemm_bfrag_kernel<4, 32> in round 4): the SAME machinery as conv_p8.hip - persistent 8-wave workgroups (one per CU) walking
-// their XCD's run of tiles, both operands through LDS-DMA with counted vmcnt, the two waves of a SIMD staggered by one barrier interval
-// (one issues 8 MFMAs = 256 cycles of the matrix pipe while the other reads fragments and issues DMAs) - on a tile that is half as wide.
-//
-// What changes with 128 output channels per tile (wave grid 2 pixel halves x 4 channel quarters, wave tile 128 x 32 = 4 x 1 accumulators):
-//   * a K-tile (64 channels of one tap) is 16 MFMAs per wave = TWO phases of 8 (pixel half mi x all four k-steps; p8: four phases over
-//     pixel half x K half).  The channel fragments of all four k-steps are read in phase 1 and stay in registers for phase 2
-//     (12 + 8 ds_read_b128 per K-tile = 1.25 per MFMA; p8: 0.75 - LDS read time 640 of 1024 MFMA cycles per K-tile and CU);
-//   * a K-tile is 48 KB in LDS (pixels 32 KB + weights 16 KB), staged as THREE groups of DMAs: G = {pixel half 0, weights} (4 per wave)
-//     in phase 1 and H = {pixel half 1} (2 per wave) in phase 2 - 6 DMAs per 4.2 MFLOP (p8: 8 per 8.4);
-//   * the ring is THREE K-tiles deep (144 KB): with two phases per K-tile a two-deep ring would leave one phase (~300 cycles) between a
-//     DMA's issue and its wait; here tile t + 2 is staged while tile t computes, into the slot tile t - 1 left: G(t + 2) in phase 1 (its
-//     pieces were last read in phase 1 of t - 1), H(t + 2) in phase 2 (last read in phase 2 of t - 1) - the rule of conv_p8.hip (a piece
-//     is re-staged >= 2 phases after its last ds_read, read >= 1 phase after the wait that retires it) with four phases between issue and
-//     use.  Issue order G0 H0 G1 H1 G2 ...: "H(t) landed" before phase 2 of t leaves G(t+1), H(t+1), G(t+2) in flight (vmcnt 10),
-//     "G(t+1) landed" before the next tile leaves H(t+1), G(t+2), H(t+2) (vmcnt 8);
-//   * tile boundary as in p8: after the K loop the NEXT tile's row table and its first TWO K-tiles (slots 0 and 1) are issued before the
-//     epilogue, which stages through slot 2 (bf16, arithmetic in the accumulator layout, 16-byte stores through a bounds-checked buffer
-//     descriptor, LDS-only barriers: stores are never waited for; the DMAs are the oldest operations in flight and are retired by one
-//     counted wait in the last pass).
-// SPLIT (round 6): split-K for the layers with FEW tiles and a LONG K loop (the pose net's first conv: 3x3, 2048 -> 128 at 15 x 20 x 64 images =
-// 75 tiles x 288 K-tiles - 75 busy CUs for 230 us, or 221 us on 300 workgroups of the round-1 LDS-DMA kernel at 0.16 of the MFMA peak).  A
-// work unit = (tile, slice s of the 64-channel groups): the K walk is channel-major, so a slice is a contiguous run of groups with all their
-// taps; the unit's accumulators leave as raw f32 into workspace[s][M][N] (16-byte stores straight from the accumulator layout: a row's 32
-// channels of one wave = one 128-byte line), and p8n_split_reduce_kernel sums the slices in fixed order and applies the epilogue.
-// Epilogue forms: no residual, bf16 output, ReLU / none / LeakyReLU (every Cout = 128 layer on the path is one of these); anything else is
-// rejected by the entry point and stays on the other conv kernels.
-#include "conv_common.h"
+// (Cout % 256 != 0: the 3x3 128 -> 128 convs of res3 and of the top-down / pose-net stacks).  Tile walk, row table, K cursor and pixel DMA
+// are conv_p8_tile.h's, shared with conv_p8.hip; this file owns what a tile half as wide changes (docs/kernels.md, "The two 256-row conv
+// kernels", has the reasoning): wave tile 128 x 32 = 4 x 1 accumulators, a K-tile = TWO phases of 8 MFMAs, staged as G = {pixel half 0,
+// weights} in phase 1 and H = {pixel half 1} in phase 2 into a ring THREE K-tiles deep (tile t + 2 is staged while tile t computes).
+// Issue order G0 H0 G1 H1 G2 ...: "H(t) landed" before phase 2 of t leaves G(t+1), H(t+1), G(t+2) in flight (vmcnt 10), "G(t+1) landed"
+// before the next tile leaves H(t+1), G(t+2), H(t+2) (vmcnt 8).  At a tile boundary the NEXT tile's row table and first TWO K-tiles
+// (slots 0, 1) are issued before the epilogue, which stages through slot 2.
+// SPLIT: split-K for the layers with FEW tiles and a LONG K loop.  A work unit = (tile, slice s of the 64-channel groups): the K walk is
+// channel-major, so a slice is a contiguous run of groups with all their taps; the unit's accumulators leave as raw f32 into
+// workspace[s][M][N], and p8n_split_reduce_kernel sums the slices in fixed order and applies the epilogue.
+// Epilogue forms: no residual, bf16 output, ReLU / none / LeakyReLU; anything else is rejected by the entry point.
 #include "conv_forms.h"
+#include "conv_p8_tile.h"
 
 namespace nps {
-
-template <int K>
-struct ICn { static constexpr int value = K; };
 
 constexpr int N8_BM = 256, N8_BN = 128, N8_BK = 64, N8_ROWB = 128;
 constexpr int N8_A_BYTES = N8_BM * N8_ROWB, N8_B_BYTES = N8_BN * N8_ROWB, N8_STAGE = N8_A_BYTES + N8_B_BYTES;   // 32 + 16 KB
@@ -42,24 +22,6 @@ constexpr int N8_ELD16 = N8_BN + 8;                                 // bf16 elem
 constexpr int N8_EPI_OFF = 2 * N8_STAGE;                            // the epilogue stages through ring slot 2 (slots 0 / 1: the next tile's first K-tiles)
 constexpr int N8_TAB_OFF = N8_NSTAGE * N8_STAGE;                    // row table above the ring
 constexpr int N8_LDS = N8_TAB_OFF + N8_BM * 8;                      // 146 KB
-
-typedef unsigned int n8_u32x4 __attribute__((ext_vector_type(4)));
-
-#define N8_LDS_SYNC()                                          \
-    do {                                                       \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     \
-        __builtin_amdgcn_s_barrier();                          \
-        asm volatile("" ::: "memory");                         \
-    } while (0)
-
-#define N8_BAR()                                   \
-    do {                                           \
-        __builtin_amdgcn_sched_barrier(0);         \
-        asm volatile("" ::: "memory");             \
-        __builtin_amdgcn_s_barrier();              \
-        asm volatile("" ::: "memory");             \
-        __builtin_amdgcn_sched_barrier(0);         \
-    } while (0)
 
 struct N8EpiRegs {
     float sc[4][4], bs[4][4];      // the lane's 16 channels: wc * 32 + 8 q + 4 (lane >> 5) + e
@@ -74,53 +36,22 @@ __global__ __launch_bounds__(512) void conv_igemm_p8n_kernel(const ConvParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;                 // pixel half / 32-channel quarter of the workgroup tile; stagger group = wr
 
-    // ---- tiles of this workgroup: XCD x (= blockIdx % 8) owns a contiguous run, its workgroups walk it with stride = workgroups on that XCD
-    const int ntiles = p.tiles_m * p.tiles_n * (SPLIT ? p.ksplit : 1);       // SPLIT: work units (tile, K slice), slice fastest
-    const int nx = (int)gridDim.x < 8 ? (int)gridDim.x : 8;
-    const int xcd = blockIdx.x % 8, slot = blockIdx.x / 8;
-    const int tq = ntiles / nx, tr = ntiles % nx;
-    const int run_begin = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-    const int run_end = run_begin + tq + (xcd < tr ? 1 : 0);
-    const int stride = ((int)gridDim.x - xcd + 7) / 8;
-    int tile = run_begin + slot;
-    if (tile >= run_end) return;
+    const P8TileWalk walk(p.tiles_m * p.tiles_n * (SPLIT ? p.ksplit : 1));      // SPLIT: work units (tile, K slice), slice fastest
+    int tile = walk.run_begin + walk.slot;
+    if (tile >= walk.run_end) return;
 
-    // ---- DMA sources (as conv_p8.hip): one 1-KB DMA = 8 tile rows x 128 B, lane -> row (lane >> 3), physical 16-byte slot (lane & 7)
-    //   A piece h (pixel half mi = h of BOTH wave rows): DMA j of wave w fills rows j*128 + h*64 + w*8 .. +7
-    //   B (the tile's 128 channels):                       DMA j of wave w fills rows (2w + j)*8 .. +7
-    constexpr unsigned OOB = 0xFFFFFF00u;
-    const int slot8 = lane & 7, rsub = lane >> 3;
-    const long long padb = ((long long)p.pad * p.W + p.pad) * p.x_cs * 2;
-    const __amdgpu_buffer_rsrc_t xsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)p.x - padb), 0, (int)(((long long)p.B * p.H * p.W * p.x_cs) * 2 + padb), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)((long long)p.N * p.K * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)((((long long)p.M - 1) * p.y_cs + p.N) * 2), 0x00020000);
-    unsigned a_voff[2][2], a_mask[2][2], b_voff[2];
-    int m0 = 0, n0 = 0;
-    int cur_tap = 0, cur_kw = 0, cur_c0 = 0;                 // wave-uniform K-tile cursor of the NEXT K-tile to stage
-    unsigned cur_tapoff = 0u, cur_k0b = 0u;
-    const float rcp_rpb = 1.0f / (float)p.rows_per_b, rcp_ow = 1.0f / (float)p.OW;
-    auto divmod = [](int a, int d, float rcp, int& q, int& r) {
-        q = (int)((float)a * rcp);
-        r = a - __mul24(q, d);
-        if (r < 0) { --q; r += d; }
-        if (r >= d) { ++q; r -= d; }
-    };
-    const unsigned xcs = (unsigned)p.x_cs;
-    uint2* rowtab = reinterpret_cast<uint2*>(lds + N8_TAB_OFF);         // [256] {byte offset of the row's pixel, tap mask}
-    unsigned a_coff[2][2], b_base[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int pr = j * 128 + h * 64 + wave * 8 + rsub;
-            a_coff[h][j] = (unsigned)(slot8 ^ ((pr >> 1) & 7)) * 16u;
-        }
+    // ---- DMA sources: the pixel halves are P8Rows'; B (the tile's 128 channels): DMA j of wave w fills rows (2w + j)*8 .. +7
+    const __amdgpu_buffer_rsrc_t xsrc = p8_x_rsrc(p), wsrc = p8_w_rsrc(p), ry = p8_rows_rsrc(p.y, p, p.y_cs);
+    P8Rows<N8_BM, N8_ROWB, N8_TAB_OFF> rows;
+    P8KCursor<N8_BK> kc(p);
+    rows.init(p, wave, lane);
+    unsigned b_voff[2], b_base[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int br = (wave * 2 + j) * 8 + rsub;
-        b_base[j] = (__umul24((unsigned)br, (unsigned)p.K) + (unsigned)(slot8 ^ ((br >> 1) & 7)) * 8u) * 2u;
+        const int br = (wave * 2 + j) * 8 + (lane >> 3);
+        b_base[j] = (__umul24((unsigned)br, (unsigned)p.K) + (unsigned)((lane & 7) ^ ((br >> 1) & 7)) * 8u) * 2u;
     }
+    int m0 = 0, n0 = 0;
     const int ntaps = p.KH * p.KW;
     int nk = p.K / N8_BK;                                     // K-tiles of the current work unit (SPLIT: of its slice)
     int ks = 0;                                               // SPLIT: the unit's slice
@@ -136,79 +67,24 @@ __global__ __launch_bounds__(512) void conv_igemm_p8n_kernel(const ConvParams p)
         }
         m0 = (t / p.tiles_n) * N8_BM;
         n0 = (t % p.tiles_n) * N8_BN;
-        if (tid < N8_BM) {
-            const int m = m0 + tid;
-            uint2 e = make_uint2(0u, 0u);
-            if (m < p.M) {
-                int b, rem, oh, ow;
-                divmod(m, p.rows_per_b, rcp_rpb, b, rem);
-                divmod(rem, p.OW, rcp_ow, oh, ow);
-                const int ih0 = __mul24(oh, p.stride) - p.pad, iw0 = __mul24(ow, p.stride) - p.pad;
-                const unsigned pix = __umul24(__umul24((unsigned)b, (unsigned)p.H) + (unsigned)(ih0 + p.pad), (unsigned)p.W) + (unsigned)(iw0 + p.pad);
-                unsigned colbits = 0u;
-                for (int kw = 0; kw < p.KW; ++kw) colbits |= ((unsigned)(iw0 + kw) < (unsigned)p.W ? 1u : 0u) << kw;
-                unsigned mk = 0u;
-                for (int kh = 0; kh < p.KH; ++kh)
-                    if ((unsigned)(ih0 + kh) < (unsigned)p.H) mk |= colbits << __mul24(kh, p.KW);
-                e = make_uint2(__umul24(pix, xcs) * 2u, mk);
-            }
-            rowtab[tid] = e;
-        }
-        N8_LDS_SYNC();
+        rows.set_tile(lds, p, m0, tid, wave, lane);
         const unsigned nb = __umul24((unsigned)n0, (unsigned)p.K) * 2u;
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const uint2 e = rowtab[j * 128 + h * 64 + wave * 8 + rsub];
-                a_voff[h][j] = e.x + a_coff[h][j];
-                a_mask[h][j] = e.y;
-            }
-#pragma unroll
         for (int j = 0; j < 2; ++j) b_voff[j] = b_base[j] + nb;          // Cout % 128 == 0: every weight row of the tile exists
-        cur_tap = 0; cur_kw = 0; cur_c0 = c_begin; cur_tapoff = 0u; cur_k0b = (unsigned)c_begin * 2u;
+        kc.reset(c_begin);
     };
-    // K order: p.force == 0 tap-major, 1 channel-major (the KH*KW taps of a 64-channel slice back to back: the slice stays in L2)
-    auto advance = [&]() {
-        if (p.force == 0) {
-            cur_k0b += N8_BK * 2;
-            cur_c0 += N8_BK;
-            if (cur_c0 >= p.Cin) {
-                cur_c0 = 0; ++cur_tap; ++cur_kw;
-                cur_tapoff += (unsigned)p.x_cs * 2u;
-                if (cur_kw == p.KW) { cur_kw = 0; cur_tapoff += (unsigned)(p.W - p.KW) * (unsigned)p.x_cs * 2u; }
-            }
-        } else {
-            ++cur_tap; ++cur_kw;
-            cur_k0b += (unsigned)p.Cin * 2u;
-            cur_tapoff += (unsigned)p.x_cs * 2u;
-            if (cur_kw == p.KW) { cur_kw = 0; cur_tapoff += (unsigned)(p.W - p.KW) * (unsigned)p.x_cs * 2u; }
-            if (cur_tap == ntaps) {
-                cur_tap = 0; cur_kw = 0; cur_tapoff = 0u;
-                cur_c0 += N8_BK;
-                cur_k0b = (unsigned)cur_c0 * 2u;
-            }
-        }
-    };
-    auto stage_a = [&](unsigned char* buf, int h) {          // pixel-half piece h at the cursor's K-tile
-        const unsigned soff = cur_tapoff + (unsigned)cur_c0 * 2u;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const unsigned vo = ((a_mask[h][j] >> cur_tap) & 1u) ? a_voff[h][j] : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xsrc, (lptr_t)(buf + (j * 128 + h * 64 + wave * 8) * N8_ROWB), 16, vo, soff, 0, 0);
-        }
-    };
+    auto stage_a = [&](unsigned char* buf, int h) { rows.stage_a(xsrc, buf, h, wave, kc); };
     auto stage_b = [&](unsigned char* buf) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrc, (lptr_t)(buf + N8_A_BYTES + ((wave * 2 + j) * 8) * N8_ROWB), 16, b_voff[j], cur_k0b, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wsrc, (lptr_t)(buf + N8_A_BYTES + ((wave * 2 + j) * 8) * N8_ROWB), 16, b_voff[j], kc.k0b, 0, 0);
     };
     auto stage_first = [&]() {                               // G0 H0 [G1 H1] -> slots 0 [, 1]; leaves the cursor at K-tile min(2, nk)
         stage_a(lds, 0); stage_b(lds); stage_a(lds, 1);
-        advance();
+        kc.advance(p);
         if (nk > 1) {
             stage_a(lds + N8_STAGE, 0); stage_b(lds + N8_STAGE); stage_a(lds + N8_STAGE, 1);
-            advance();
+            kc.advance(p);
         }
     };
 
@@ -273,44 +149,45 @@ __global__ __launch_bounds__(512) void conv_igemm_p8n_kernel(const ConvParams p)
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-            N8_BAR();
-            mfma_phase(ICn<0>{});
-            N8_BAR();
+            NPS_PHASE_BAR();
+            mfma_phase(IC<0>{});
+            NPS_PHASE_BAR();
             // ---- phase 2: pixel half 1.  reads A1; stages H(t+2); G(t+1) must have landed before the next tile
             load_a(1);
             if (has2) {
                 stage_a(fb, 1);
-                advance();                                            // cursor -> tile t+3
+                kc.advance(p);                                            // cursor -> tile t+3
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // newer than G(t+1): H(t+1), G(t+2), H(t+2)
             } else if (has1) {
                 asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // newer than G(t+1): H(t+1)
             }
-            N8_BAR();
-            mfma_phase(ICn<1>{});
-            N8_BAR();
+            NPS_PHASE_BAR();
+            mfma_phase(IC<1>{});
+            NPS_PHASE_BAR();
         };
         {
             int t = 0;
             for (; t + 2 < nk; t += 3) {
-                ktile(ICn<0>{}, t);
-                ktile(ICn<1>{}, t + 1);
-                ktile(ICn<2>{}, t + 2);
+                ktile(IC<0>{}, t);
+                ktile(IC<1>{}, t + 1);
+                ktile(IC<2>{}, t + 2);
             }
-            if (t < nk) ktile(ICn<0>{}, t);
-            if (t + 1 < nk) ktile(ICn<1>{}, t + 1);
+            if (t < nk) ktile(IC<0>{}, t);
+            if (t + 1 < nk) ktile(IC<1>{}, t + 1);
         }
         if (wr == 0) __builtin_amdgcn_s_barrier();               // pairs with the lagging group's last barrier
         else __builtin_amdgcn_s_setprio(0);
-        N8_LDS_SYNC();                                           // every fragment read of the tile is done: the ring is free
+        NPS_LDS_SYNC();                                           // every fragment read of the tile is done: the ring is free
 
         // ---- next tile's addresses and its first two K-tiles (slots 0, 1) BEFORE this tile's epilogue (staging in slot 2)
         const int cur_m0 = m0, cur_n0 = n0, cur_ks = ks;
-        const int next = tile + stride;
-        const bool more = next < run_end;
+        const int next = tile + walk.stride;
+        const bool more = next < walk.run_end;
         if constexpr (SPLIT) {
             // raw f32 partial tile -> workspace[slice][M][N]: lane (pixel l31, half) holds channels wc * 32 + 8 q + 4 half + e of its pixel -
             // 16 stores of 16 bytes per lane, unconditional (rows >= M go to an out-of-range offset the descriptor drops)
             if (more) { set_tile(next); stage_first(); }
+            __builtin_amdgcn_sched_barrier(0);                // every DMA of stage_first() is issued before the first store: vmcnt(16) below counts on it
             const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(p.sk_ws, 0, p.sk_ws_bytes, 0x00020000);
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
@@ -319,8 +196,8 @@ __global__ __launch_bounds__(512) void conv_igemm_p8n_kernel(const ConvParams p)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const f32x4 v = {acc[a][4 * q], acc[a][4 * q + 1], acc[a][4 * q + 2], acc[a][4 * q + 3]};
-                    const unsigned off = m < (unsigned)p.M ? (row + 8u * q) * 4u : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(n8_u32x4, v), rws, (int)off, 0, 0);
+                    const unsigned off = m < (unsigned)p.M ? (row + 8u * q) * 4u : P8_OOB;
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rws, (int)off, 0, 0);
                 }
             }
             if (more) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // the next unit's 12 DMAs are older than these 16 stores
@@ -374,21 +251,21 @@ __global__ __launch_bounds__(512) void conv_igemm_p8n_kernel(const ConvParams p)
                     // 6 stores of passes 0-2 (unconditional: rows >= M are dropped by the descriptor's bounds check)
                     if (more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
                 }
-                N8_LDS_SYNC();
-                n8_u32x4 o[2];
+                NPS_LDS_SYNC();
+                u32x4 o[2];
 #pragma unroll
-                for (int it = 0; it < 2; ++it) o[it] = *(const n8_u32x4*)(epi + (it * 32 + rg) * N8_ELD16 + c8 * 8);
+                for (int it = 0; it < 2; ++it) o[it] = *(const u32x4*)(epi + (it * 32 + rg) * N8_ELD16 + c8 * 8);
 #pragma unroll
                 for (int it = 0; it < 2; ++it) {
                     const unsigned m = (unsigned)(cur_m0 + it * 128 + pass * 32 + rg);
                     __builtin_amdgcn_raw_buffer_store_b128(o[it], ry, (int)((m * (unsigned)p.y_cs + (unsigned)(cur_n0 + c8 * 8)) * 2u), 0, 0);
                 }
-                N8_LDS_SYNC();
+                NPS_LDS_SYNC();
             };
-            do_pass(ICn<0>{});
-            do_pass(ICn<1>{});
-            do_pass(ICn<2>{});
-            do_pass(ICn<3>{});
+            do_pass(IC<0>{});
+            do_pass(IC<1>{});
+            do_pass(IC<2>{});
+            do_pass(IC<3>{});
         }
         if (!more) break;
         tile = next;
@@ -437,8 +314,6 @@ __global__ __launch_bounds__(256) void p8n_split_reduce_kernel(const float* __re
 
 }  // namespace nps
 
-extern int nps_p8_num_cus();
-
 extern "C" int64_t nopesac_conv2d_p8n_splitk_workspace_bytes(int splits, int64_t M, int Cout) {
     return splits > 0 && M > 0 && Cout > 0 ? (int64_t)splits * M * Cout * 4 : 0;
 }
@@ -459,15 +334,8 @@ static int p8n_launch(const void* x, const void* w, const float* scale, const fl
     const int grid_cap = variant >> 8;
     NPS_CHECK_ARG((variant & 0xdf) == 0, "conv2d_p8n: variant must be 0 (+ 32: channel-major K order, + (n << 8): grid cap)");
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.scale = scale; p.bias = bias; p.res = nullptr; p.y = y;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-    p.OH = (H + 2 * pad - KH) / stride + 1;
-    p.OW = (W + 2 * pad - KW) / stride + 1;
-    p.x_cs = x_cstride; p.y_cs = y_cstride;
-    p.rows_per_b = p.OH * p.OW;
-    p.M = B * p.rows_per_b; p.N = Cout; p.K = KH * KW * Cin;
-    p.act = act; p.out_dt = NPS_DT_BF16; p.force = kmajor;
+    conv_params_fill(p, x, w, scale, bias, nullptr, y, B, H, W, Cin, Cout, KH, KW, stride, pad, x_cstride, y_cstride, 0, act, 0, NPS_DT_BF16);
+    p.force = kmajor;
     p.tiles_m = (p.M + N8_BM - 1) / N8_BM;
     p.tiles_n = p.N / N8_BN;
     const hipStream_t st = (hipStream_t)stream;
@@ -477,21 +345,14 @@ static int p8n_launch(const void* x, const void* w, const float* scale, const fl
         NPS_CHECK_ARG(workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= need,
                       "conv2d_p8n_splitk: workspace of splits * M * N * 4 bytes, 16-byte aligned");
         p.ksplit = splits; p.sk_ws = workspace; p.sk_ws_bytes = (int)need;
-        const int units = p.tiles_m * p.tiles_n * splits;
-        int nwg = nps_p8_num_cus();
-        if (grid_cap > 0 && grid_cap < nwg) nwg = grid_cap;
-        if (units < nwg) nwg = units;
-        hipLaunchKernelGGL((conv_igemm_p8n_kernel<NPS_ACT_NONE, true>), dim3(nwg), dim3(512), 0, st, p);
+        const dim3 grid(conv_persistent_grid(grid_cap, p.tiles_m * p.tiles_n * splits));
+        hipLaunchKernelGGL((conv_igemm_p8n_kernel<NPS_ACT_NONE, true>), grid, dim3(512), 0, st, p);
         const long long items = (long long)p.M * (p.N / 8);
         hipLaunchKernelGGL(p8n_split_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, (const float*)workspace, splits, p.M, p.N,
                            scale, bias, (bf16_t*)y, (long long)y_cstride, act);
         NPS_LAUNCH_RET();
     }
-    const int ntiles = p.tiles_m * p.tiles_n;
-    int nwg = nps_p8_num_cus();
-    if (grid_cap > 0 && grid_cap < nwg) nwg = grid_cap;
-    if (ntiles < nwg) nwg = ntiles;
-    const dim3 grid(nwg);
+    const dim3 grid(conv_persistent_grid(grid_cap, p.tiles_m * p.tiles_n));
     if (act == NPS_ACT_RELU) hipLaunchKernelGGL((conv_igemm_p8n_kernel<NPS_ACT_RELU>), grid, dim3(512), 0, st, p);
     else if (act == NPS_ACT_LEAKY) hipLaunchKernelGGL((conv_igemm_p8n_kernel<NPS_ACT_LEAKY>), grid, dim3(512), 0, st, p);
     else hipLaunchKernelGGL((conv_igemm_p8n_kernel<NPS_ACT_NONE>), grid, dim3(512), 0, st, p);

@@ -1,5 +1,6 @@
 """Kernel configurations of ops.conv2d side by side on the backbone's 3x3 layers: time per launch, TFLOP/s, equality with the heuristic
-kernel's result.  usage: conv_variant_bench.py"""
+kernel's result.  usage: conv_variant_bench.py [--cfgs 11,13,14,15]   (--cfgs: these configurations on every layer, in place of the
+lists below; a layer a configuration cannot take prints "rejected")"""
 import os
 import sys
 
@@ -13,6 +14,7 @@ dev = torch.device("cuda:0")
 torch.manual_seed(0)
 NAMES = dict(ops.CONV_CFG_KERNEL)
 NAMES[0] = "heuristic"
+CFGS = tuple(int(c) for c in sys.argv[sys.argv.index("--cfgs") + 1].split(",")) if "--cfgs" in sys.argv else None
 
 
 def run(B, H, W, Cin, Cout, k, stride, cfgs, residual=False):
@@ -27,7 +29,7 @@ def run(B, H, W, Cin, Cout, k, stride, cfgs, residual=False):
     ops.TUNER.loaded = {"_": 0}
     ref = None
     print("x(%d,%d,%d,%d) w(%d,%dx%d) s%d%s" % (B, H, W, Cin, Cout, k, k, stride, " +res" if residual else ""))
-    for cfg in cfgs:
+    for cfg in ((0,) + CFGS if CFGS else cfgs):
         ops.TUNER.choose = lambda key, launch, extra=(), c=cfg: c
         try:
             y = ops.conv2d(x, w, sc, bs, res, stride=stride, pad=pad, act=ops.ACT_RELU)
