@@ -737,6 +737,40 @@ nps_status nopesac_augment_u8(const uint8_t* src, int n, int64_t src_stride, int
                               const nopesac_aug_row* rows_dev, uint8_t* chw_out, float* nhwc_out, const float* mean, const float* std,
                               void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Ground truth for training (csrc/train_targets.hip; nopesac_amd/targets.py): a dataset's per-view record -> the targets of
+ * nopesac_plane_criterion (prepare_targets, siamese_planeTR.py:475-532; get_coordinate_map, :815-839).  Deterministic: integer sums, and
+ * tables whose CONTENT does not depend on the order of their atomics.  Argument errors -> NPS_E_ARG before any launch.
+ * nopesac_label_ids: labels int32 [B][H][W] (any int32 value) -> per image the distinct values in ascending SIGNED order, the first
+ *   dropped when it is 0 (torch.unique, then `if plane_ids[0] == 0`: with a negative label present 0 stays a plane): ids int32
+ *   [B][NPS_LABEL_MAX_IDS] (0 from n_all[b] on), n_all[b] = their number, n[b] = min(n_all[b], nmax_limit), bad[b] = 1 when the image holds
+ *   more than NPS_LABEL_MAX_IDS distinct values (0 included) - then n_all[b] = n[b] = 0 and the row of ids is 0.  One workgroup per image:
+ *   an open-addressed table of NPS_LABEL_TABLE_SLOTS slots in LDS (slot = value mod slots, linear probing), then a rank sort.
+ * nopesac_label_targets: labels, ids (row stride NPS_LABEL_MAX_IDS, ascending), n int32 [B] (clamped to [0, nmax]) -> masks uint8
+ *   [B][nmax][H][W] = (ids[b][j] == label), rows j >= n[b] zero; plane_centers f32 [B][nmax][2] = (float)(sum x / W / count), (float)(sum y / H
+ *   / count) in f64 from exact integer sums (what nopesac_plane_targets computes from the masks, bit for bit), rows j >= n[b] zero;
+ *   pixel_centers f32 [B][2][H][W] = the centre of the pixel's plane, 0 where no plane lies.  1 <= nmax <= NPS_PLANE_MAX_TARGETS, H W <= 2^30.
+ *   Three launches: integer partial sums per NPS_LABEL_CHUNK pixels into the workspace (nopesac_label_targets_workspace_bytes writes
+ *   its size to the HOST pointer `bytes`, 0 for an argument <= 0; a status: null bytes is NPS_E_ARG), the centres, then the mask pass (the label map is read once per pixel, every plane row written from registers,
+ *   16 bytes per lane where H W % 16 == 0 and the buffers are 16-byte aligned).
+ * nopesac_bits_to_masks: bits int32 [n_rows][ceil(H W / 32)] in the layout of nopesac_rle_runs_to_bits (bit p & 31 of word p >> 5 is pixel
+ *   p = x H + y), offsets int64 [B + 1] on the device (view b owns rows offsets[b] .. offsets[b + 1]) -> masks uint8 [B][nmax][H][W]
+ *   row-major; a view with more than nmax rows keeps its first nmax, the rows it lacks are zero.
+ * nopesac_depth_u16_to_f32: out[i] = (float)src[i] / scale, an IEEE division (the reference's astype(float32) / 1000.), scale > 0.
+ * nopesac_coordinate_map: kinv f32 [B][9] row-major (the host inverts K in f64 and rounds once) -> out f32 [B][3][H][W],
+ *   out[c] = fma(kinv[3c + 1], y, kinv[3c] * x) + kinv[3c + 2] with x = (float)col / W * 640, y = (float)row / H * 480 in f32. */
+#define NPS_LABEL_MAX_IDS 1024
+#define NPS_LABEL_TABLE_SLOTS 2048
+#define NPS_LABEL_CHUNK 4096
+nps_status nopesac_label_ids(const int32_t* labels, int B, int H, int W, int nmax_limit, int32_t* ids, int32_t* n_all, int32_t* n,
+                             int32_t* bad, void* stream);
+nps_status nopesac_label_targets_workspace_bytes(int B, int nmax, int H, int W, int64_t* bytes);
+nps_status nopesac_label_targets(const int32_t* labels, const int32_t* ids, const int32_t* n, int B, int nmax, int H, int W, uint8_t* masks,
+                                 float* plane_centers, float* pixel_centers, void* workspace, int64_t workspace_bytes, void* stream);
+nps_status nopesac_bits_to_masks(const int32_t* bits, int64_t n_rows, const int64_t* offsets, int B, int nmax, int H, int W, uint8_t* masks,
+                                 void* stream);
+nps_status nopesac_depth_u16_to_f32(const uint16_t* src, int64_t n, float scale, float* out, void* stream);
+nps_status nopesac_coordinate_map(const float* kinv, int B, int H, int W, float* out, void* stream);
+
 /* Pre-norm counterpart for the decoder layers (transformer/transformer.py:293-322, after the cross-attention), same kernel:
  *   s = tgt + attn . wo^T + bo;  u = s + relu(LN3(s) . w1^T + b1) . w2^T + b2;  n = LN_next(u)
  * y = u (f32 residual stream), y_bf16 = bf16(n), ypos_bf16 = bf16(n + pos[row % pos_rows]), yn = n in f32 (each nullable);

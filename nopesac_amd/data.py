@@ -8,7 +8,8 @@
 Decoding: baseline JPEG files (the ScanNet colour frames) are decoded ON THE GPU when one is present (nopesac_amd/jpeg.py,
 csrc/jpeg.hip - bit-exact with the PIL / libjpeg-turbo decode detectron2's `utils.read_image` performs); PNG files (Matterport3D) and
 JPEG variants outside the decoder's subset (progressive, CMYK, ...) are decoded by PIL on the host, as the reference decodes every
-file.  Ground-truth masks / depth / k-means pose classes are not read: nothing on the inference path consumes them.
+file.  Ground-truth masks / depth are not read here: nothing on the inference path consumes them (training reads them through nopesac_amd/targets.py;
+the k-means pose classes are read nowhere).
 """
 from __future__ import annotations
 

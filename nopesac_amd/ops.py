@@ -1487,6 +1487,104 @@ def augment_images(src, params, *, chw_out: Optional[torch.Tensor] = None, nhwc_
                           _p(mean) if nhwc_out is not None else None, _p(std) if nhwc_out is not None else None, _p(ws), ws.numel() * 4, _stream())
 
 
+# ---- ground truth for training (csrc/train_targets.hip; nopesac_amd/targets.py) ---------------------------------------------------------
+LABEL_MAX_IDS, LABEL_TABLE_SLOTS = _lib.H.NPS_LABEL_MAX_IDS, _lib.H.NPS_LABEL_TABLE_SLOTS
+
+
+def _out(out: Optional[torch.Tensor], shape, dtype, device, what: str) -> torch.Tensor:
+    """The caller's output buffer (any shape of the right size: contiguous, `dtype`, on `device`) viewed as `shape`, or a fresh one."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    if out is None:
+        return torch.empty(tuple(shape), device=device, dtype=dtype)
+    _require(out.device == device, what + ": output on another device")
+    return _sized(out, dtype, n, what).view(tuple(shape))
+
+
+def label_ids(labels: torch.Tensor, nmax_limit: int = _lib.H.NPS_PLANE_MAX_TARGETS, out=None):
+    """labels int32 [B, H, W] -> (ids int32 [B, LABEL_MAX_IDS], n_all int32 [B], n int32 [B], bad int32 [B]) on the device: per image the
+    distinct labels ascending, a leading 0 dropped (torch.unique + `if plane_ids[0] == 0`, siamese_planeTR.py:488-495), their number,
+    n = min(n_all, nmax_limit), and bad = 1 for an image with more than LABEL_MAX_IDS distinct labels (n_all = n = 0 there).  No host
+    sync.  out: optionally the four buffers."""
+    _chk(labels, torch.int32)
+    _require(labels.dim() == 3, "label_ids: labels [B, H, W] expected")
+    B, H, W = labels.shape
+    dev, o = labels.device, (out or (None,) * 4)
+    _require(len(o) == 4, "label_ids: out = (ids, n_all, n, bad)")
+    ids = _out(o[0], (B, LABEL_MAX_IDS), torch.int32, dev, "label_ids: ids")
+    n_all, n, bad = (_out(t, (B,), torch.int32, dev, "label_ids: " + k) for t, k in zip(o[1:], ("n_all", "n", "bad")))
+    _C.nopesac_label_ids(_p(labels), B, H, W, int(nmax_limit), _p(ids), _p(n_all), _p(n), _p(bad), _stream())
+    return ids, n_all, n, bad
+
+
+def label_targets_workspace_bytes(B: int, nmax: int, H: int, W: int) -> int:
+    """Bytes of scratch label_targets needs (the integer partial sums of every NPS_LABEL_CHUNK pixels)."""
+    out = ctypes.c_int64()
+    _C.nopesac_label_targets_workspace_bytes(int(B), int(nmax), int(H), int(W), ctypes.byref(out))
+    return out.value
+
+
+def label_targets(labels: torch.Tensor, ids: torch.Tensor, n: torch.Tensor, nmax: int, out=None):
+    """labels int32 [B, H, W], ids int32 [B, LABEL_MAX_IDS] (label_ids), n int32 [B] on the device -> (masks uint8 [B, nmax, H, W],
+    plane_centers f32 [B, nmax, 2], pixel_centers f32 [B, 2, H, W]): masks[b, j] = ids[b, j] == labels[b], rows j >= n[b] zero; the
+    centres are bit for bit those of plane_targets on these masks.  The label map is read once per pass, not once per plane."""
+    _chk(labels, torch.int32)
+    _require(labels.dim() == 3, "label_targets: labels [B, H, W] expected")
+    B, H, W = labels.shape
+    nmax, dev = int(nmax), labels.device
+    _sized(ids, torch.int32, B * LABEL_MAX_IDS, "label_targets: ids")
+    _sized(n, torch.int32, B, "label_targets: n")
+    _require(ids.device == dev and n.device == dev, "label_targets: ids / n on another device")
+    _require(1 <= nmax <= PLANE_MAX_TARGETS, "label_targets: nmax=%d outside 1..%d" % (nmax, PLANE_MAX_TARGETS))
+    o = out or (None,) * 3
+    _require(len(o) == 3, "label_targets: out = (masks, plane_centers, pixel_centers)")
+    masks = _out(o[0], (B, nmax, H, W), torch.uint8, dev, "label_targets: masks")
+    centers = _out(o[1], (B, nmax, 2), torch.float32, dev, "label_targets: plane_centers")
+    pixel = _out(o[2], (B, 2, H, W), torch.float32, dev, "label_targets: pixel_centers")
+    ws = scratch(dev, label_targets_workspace_bytes(B, nmax, H, W))
+    _C.nopesac_label_targets(_p(labels), _p(ids), _p(n), B, nmax, H, W, _p(masks), _p(centers), _p(pixel), _p(ws), ws.numel() * 4, _stream())
+    return masks, centers, pixel
+
+
+def bits_to_masks(bits: torch.Tensor, offsets: torch.Tensor, nmax: int, H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The bit-packed masks of rle.segmentation_bits (int32 [N, ceil(H W / 32)], bit p = x H + y) and the views' exclusive offsets (int64
+    [B + 1] on the device) -> masks uint8 [B, nmax, H, W] row-major: view b gets its first nmax rows, the rows it lacks are zero."""
+    _chk(bits, torch.int32); _chk(offsets, torch.int64)
+    H, W, nmax = int(H), int(W), int(nmax)
+    _require(H >= 1 and W >= 1, "bits_to_masks: H, W >= 1")
+    words = (H * W + 31) // 32
+    _require(bits.dim() == 2 and (bits.shape[0] == 0 or bits.shape[1] == words), "bits_to_masks: bits [N, %d] expected, got %s" % (words, tuple(bits.shape)))
+    _require(offsets.dim() == 1 and offsets.numel() >= 2 and offsets.device == bits.device, "bits_to_masks: offsets int64 [B + 1] on the bits' device")
+    _require(1 <= nmax <= PLANE_MAX_TARGETS, "bits_to_masks: nmax=%d outside 1..%d" % (nmax, PLANE_MAX_TARGETS))
+    B, N = offsets.numel() - 1, int(bits.shape[0])
+    masks = _out(out, (B, nmax, H, W), torch.uint8, bits.device, "bits_to_masks: masks")
+    _C.nopesac_bits_to_masks(_p(bits) if N else None, N, _p(offsets), B, nmax, H, W, _p(masks), _stream())
+    return masks
+
+
+def depth_from_u16(src: torch.Tensor, scale: float = 1000.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint16 depth (the 16-bit PNG's millimetres; torch.uint16, or int16 holding the same bits) -> f32 of the same shape,
+    (float)v / scale with an IEEE division: numpy's astype(float32) / 1000."""
+    _require(src.dtype in (torch.uint16, torch.int16), "depth_from_u16: uint16 (or int16 bits) expected, got %s" % src.dtype)
+    _chk(src)
+    _require(src.numel() >= 1 and float(scale) > 0.0, "depth_from_u16: an empty image, or scale <= 0")
+    res = _out(out, tuple(src.shape), torch.float32, src.device, "depth_from_u16: out")
+    _C.nopesac_depth_u16_to_f32(_p(src), src.numel(), float(scale), _p(res), _stream())
+    return res
+
+
+def coordinate_map(kinv: torch.Tensor, H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """kinv f32 [B, 3, 3] or [B, 9] (K^-1, inverted on the host in float64 and rounded once) -> k_inv_dot_xy1 f32 [B, 3, H, W] of
+    get_coordinate_map (siamese_planeTR.py:815-839): K^-1 . (x, y, 1) with x = col / W * 640, y = row / H * 480 in f32."""
+    _chk(kinv, torch.float32)
+    _require(kinv.dim() in (2, 3) and kinv.numel() == 9 * kinv.shape[0], "coordinate_map: kinv [B, 3, 3] expected")
+    B, H, W = kinv.shape[0], int(H), int(W)
+    res = _out(out, (B, 3, H, W), torch.float32, kinv.device, "coordinate_map: out")
+    _C.nopesac_coordinate_map(_p(kinv), B, H, W, _p(res), _stream())
+    return res
+
+
 def mask_head(c1: torch.Tensor, t1: torch.Tensor, w_lat_frag: torch.Tensor, scale, bias, mask_w: torch.Tensor, mask_b: torch.Tensor,
               sigmoid: bool = True, want_p1: bool = False, planar: bool = False, fold: Optional[torch.Tensor] = None, taps1: bool = False,
               pipe: bool = False):
