@@ -1392,6 +1392,39 @@ nps_status nopesac_bn_train_backward_f32(const float* dy, const float* src, int 
                                          float* dsrc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
 nps_status nopesac_upsample2x_bilinear_backward_f32(const float* du, float* dx, int B, int H, int W, int C, void* stream);
 
+/* ---- training-mode BatchNorm of the camera head's conv stacks on GROUPED batch statistics (csrc/camera_bn_train.hip;
+ * training.CameraHeadTrainer(batch_stats=True); reference Conv2d + nn.BatchNorm2d(eps 0.001, momentum 0.01) + LeakyReLU, camera_modules.py:36-48) --
+ * c [G n][C] f32, dense; group g is the rows [g n, (g + 1) n): every group has its own statistics (the siamese tower runs once per view,
+ * camera_head.py:646-647: G = 2 over the 2B-image batch, view 1 first; G = 1 elsewhere).  One call covers all groups.  Deterministic (no
+ * atomics: per-block partials of NPS_BN_GROUPED_RPS rows of a group in ws, finished in NPS_BN_GROUPED_SEGMENTS runs in a fixed order); with
+ * G > 1 every per-group result has the bits of a G = 1 call on that group's rows.  A thread works on four channels: C % 4 == 0 and every
+ * pointer 16-byte aligned, 1 <= G <= NPS_BN_GROUPED_MAX_GROUPS (else NPS_E_ARG, before any launch).  mean, var, rstd: [G][C].
+ * ws: at least NPS_BN_GROUPED_WORKSPACE_FLOATS(G, n, C) floats (both launchers).
+ *  bn_train_grouped_stats:    per group and channel mean, biased variance, rstd = 1 / sqrt(var + eps) (per-block mean and centred sum of
+ *                             squares merged by Chan's formula: never E[x^2] - E[x]^2).  running_mean / running_var [C] (both or neither)
+ *                             are updated in place in the same launch, r <- (1 - momentum) r + momentum stat_g for g = 0, 1, .. in that
+ *                             order, the variance unbiased (n / (n - 1)): what G module calls in a row leave.  n < 2: NPS_E_ARG.
+ *  bn_train_grouped_apply:    y = act(gamma (c - mean_g) rstd_g + beta); act NPS_ACT_NONE, NPS_ACT_RELU or NPS_ACT_LEAKY (slope 0.01).
+ *  bn_train_grouped_backward: dz = dy act'(z), z recomputed with apply's own expression (the side of the kink is the forward's, bit for
+ *                             bit); per group S1_g = sum dz, S2_g = sum dz xhat; dc = gamma rstd_g (dz - S1_g / n - xhat S2_g / n);
+ *                             dbeta = sum_g S1_g, dgamma = sum_g S2_g, added in group order.  batch_stats = 0: mean and rstd are
+ *                             constants of the backward, dc = gamma rstd_g dz (dgamma, dbeta as above).
+ *  bn_train_grouped_workspace_floats: the macro's value into *floats for callers that cannot read it (a status entry: NPS_E_ARG and 0 for
+ *                             arguments the launchers refuse). */
+#define NPS_BN_GROUPED_RPS 256
+#define NPS_BN_GROUPED_SEGMENTS 16
+#define NPS_BN_GROUPED_MAX_GROUPS 64
+#define NPS_BN_GROUPED_WORKSPACE_FLOATS(G, n, C) ((int64_t)(G) * ((((int64_t)(n) + NPS_BN_GROUPED_RPS - 1) / NPS_BN_GROUPED_RPS) + 1) * 2 * (C))
+nps_status nopesac_bn_train_grouped_workspace_floats(int G, int64_t n, int C, int64_t* floats);
+nps_status nopesac_bn_train_grouped_stats_f32(const float* c, int G, int64_t n, int C, float eps, float momentum, float* mean, float* var,
+                                              float* rstd, float* running_mean, float* running_var, float* ws, int64_t ws_floats,
+                                              void* stream);
+nps_status nopesac_bn_train_grouped_apply_f32(const float* c, int G, int64_t n, int C, const float* gamma, const float* beta,
+                                              const float* mean, const float* rstd, int act, float* y, void* stream);
+nps_status nopesac_bn_train_grouped_backward_f32(const float* dy, const float* c, int G, int64_t n, int C, const float* gamma,
+                                                 const float* beta, const float* mean, const float* rstd, int act, int batch_stats,
+                                                 float* dc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
+
 /* ---- backward of a Linear with its operands read in place (csrc/linear_bwd.hip; training._LinearInPlace, PlaneEncoderTrainer) ---------
  * For y = act(x W^T + b) with x [M][K] (row stride x_stride), W [N][K] dense, and g [M][N] (row stride g_stride) the gradient at the
  * layer's output:  dx [M][K] (row stride dx_stride) = g' W,  dw [N][K] dense = g'^T x,  db [N] = column sums of g'.  g' is g behind two

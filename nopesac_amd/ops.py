@@ -1989,6 +1989,75 @@ def bn_train_backward(dy: torch.Tensor, src: torch.Tensor, gamma, beta, mean, rs
     return dsrc, dg, db
 
 
+def _bn_grouped_src(c: torch.Tensor, groups: int):
+    """The input of a grouped training-mode BatchNorm kernel, contiguous f32 [..., C] cut into `groups` runs of consecutive rows
+    -> (G, rows per group, C)."""
+    _chk(c, torch.float32)
+    _require(isinstance(groups, int) and not isinstance(groups, bool) and 1 <= groups <= _H.NPS_BN_GROUPED_MAX_GROUPS,
+             "bn_train_grouped: 1 <= groups <= %d expected, got %r" % (_H.NPS_BN_GROUPED_MAX_GROUPS, groups))
+    _require(c.dim() >= 2 and c.numel() > 0, "bn_train_grouped: [..., C] with at least one row expected, got %s" % (tuple(c.shape),))
+    C = c.shape[-1]
+    _require(C % 4 == 0, "bn_train_grouped: a multiple of 4 channels expected, got %d" % C)
+    rows = c.numel() // C
+    _require(rows % groups == 0, "bn_train_grouped: %d rows do not divide into %d groups" % (rows, groups))
+    return groups, rows // groups, C
+
+
+def bn_train_grouped_workspace_floats(groups: int, n: int, C: int) -> int:
+    """The library's nopesac_bn_train_grouped_workspace_floats, what both grouped training-BatchNorm launchers check against."""
+    out = ctypes.c_int64(0)
+    _C.nopesac_bn_train_grouped_workspace_floats(int(groups), int(n), int(C), ctypes.addressof(out))
+    return int(out.value)
+
+
+def bn_train_grouped_stats(c: torch.Tensor, groups: int, *, eps: float, momentum: float, running_mean=None, running_var=None):
+    """Batch statistics of a training-mode BatchNorm per group of rows of c [..., C] (group g: rows [g n, (g + 1) n) of the rows x C
+    matrix) -> (mean, biased var, rstd = 1 / sqrt(var + eps)), [groups, C] each.  running_mean / running_var [C] (both or neither) take
+    the groups' statistics one after the other, in place on the device, as `groups` calls of torch.nn.BatchNorm2d in a row do
+    (momentum, unbiased variance); no host sync.  One value per channel and group is refused."""
+    G, n, C = _bn_grouped_src(c, groups)
+    _require(n >= 2, "bn_train_grouped_stats: more than one value per channel and group expected")
+    _require((running_mean is None) == (running_var is None), "running_mean and running_var come together")
+    if running_mean is not None:
+        _bn_vecs(C, running_mean, running_var)
+    mean, var, rstd = (torch.empty((G, C), device=c.device, dtype=torch.float32) for _ in range(3))
+    ws = scratch(c.device, 4 * bn_train_grouped_workspace_floats(G, n, C))
+    _C.nopesac_bn_train_grouped_stats_f32(_p(c), G, n, C, float(eps), float(momentum), _p(mean), _p(var), _p(rstd), _p(running_mean),
+                                          _p(running_var), _p(ws), ws.numel(), _stream())
+    return mean, var, rstd
+
+
+def bn_train_grouped_apply(c: torch.Tensor, gamma, beta, mean, rstd, act=ACT_LEAKY, groups: int = 1) -> torch.Tensor:
+    """act(gamma (c - mean_g) rstd_g + beta) with mean, rstd [groups, C]; act: NONE, RELU or LEAKY (slope 0.01)."""
+    G, n, C = _bn_grouped_src(c, groups)
+    _require(act in (ACT_NONE, ACT_RELU, ACT_LEAKY), act)
+    _bn_vecs(C, gamma, beta)
+    _bn_vecs(G * C, mean, rstd)
+    y = torch.empty_like(c)
+    _C.nopesac_bn_train_grouped_apply_f32(_p(c), G, n, C, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), _p(y), _stream())
+    return y
+
+
+def bn_train_grouped_backward(dy: torch.Tensor, c: torch.Tensor, gamma, beta, mean, rstd, act=ACT_LEAKY, groups: int = 1, *,
+                              batch_stats: bool = True):
+    """Backward of bn_train_grouped_apply through every group's batch statistics, from the saved input c (z is recomputed with the
+    forward's expression) -> (dc, dgamma, dbeta); dgamma / dbeta sum the groups in group order.  batch_stats=False: mean / rstd are
+    constants of the backward (dc = gamma rstd dz)."""
+    G, n, C = _bn_grouped_src(c, groups)
+    _require(act in (ACT_NONE, ACT_RELU, ACT_LEAKY), act)
+    _chk(dy, torch.float32)
+    _require(dy.shape == c.shape, (tuple(dy.shape), tuple(c.shape)))
+    _bn_vecs(C, gamma, beta)
+    _bn_vecs(G * C, mean, rstd)
+    dc = torch.empty_like(c)
+    dg = torch.empty(C, device=c.device, dtype=torch.float32)
+    db = torch.empty(C, device=c.device, dtype=torch.float32)
+    ws = scratch(c.device, 4 * bn_train_grouped_workspace_floats(G, n, C))
+    _C.nopesac_bn_train_grouped_backward_f32(_p(dy), _p(c), G, n, C, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), int(bool(batch_stats)),
+                                             _p(dc), _p(dg), _p(db), _p(ws), ws.numel(), _stream())
+    return dc, dg, db
+
+
 def upsample2x_bilinear_backward(du: torch.Tensor) -> torch.Tensor:
     """The adjoint of upsample2x_bilinear: du [B, 2H, 2W, C] f32 -> dx [B, H, W, C]."""
     _chk(du, torch.float32)

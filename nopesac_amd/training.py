@@ -18,8 +18,10 @@ broadcast of the initial-pose features are torch views / a [B, nq, 256] sum.  Ev
 The pixel pose net's conv stacks (pixel decoder, convs_backbone, the two strided branches, the correlation softmax between them) are
 trainable on request: CameraHeadTrainer(conv_stacks=True) runs them from the trainer's own f32 parameters through the autograd Functions
 below, whose backward passes are the kernels of csrc/conv_bwd.hip (conv dgrad / wgrad, BatchNorm + LeakyReLU, GroupNorm, max-pool,
-upsample-add, correlation softmax).  BatchNorm runs with its stored statistics and a trainable affine (detectron2's FrozenBatchNorm2d
-regime, as forward_train); batch statistics and running-stat updates are not implemented.
+upsample-add, correlation softmax).  By default BatchNorm runs with its stored statistics and a trainable affine (detectron2's
+FrozenBatchNorm2d regime, as forward_train).  batch_stats=True trains the 18 conv + nn.BatchNorm2d + LeakyReLU blocks as the reference
+does (camera_modules.py:36-48, never frozen): on BATCH statistics - per view in the siamese tower, which the reference calls once per
+view - with the backward through them and the running buffers and counters updated on the device (csrc/camera_bn_train.hip).
 
 The matching head (matching_net/matching_head.py:43-139: planeApp_proj, the 18 GNN layers, planeDesc_proj, the Sinkhorn with its
 bin_score and the embedding loss) is trained by MatchingHeadTrainer: the forward is the unfused f32 route of modeling/matching_head.py
@@ -92,6 +94,7 @@ PREFIX = "camera_head_list.0."
 CONV_STACKS = ("pixel_decoder", "convs_backbone", "convs_trans", "convs_rots")       # the pixel pose net's conv stacks (conv_stacks=True)
 BACKBONE_CONVS = (0, 1, 3, 4, 6, 7)
 BN_EPS, GN_EPS, GN_GROUPS = 1e-3, 1e-5, 32
+BN_MOMENTUM = 0.01                     # nn.BatchNorm2d(eps=0.001, momentum=0.01) of the pixel pose net's conv blocks (camera_modules.py:45)
 _BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked")
 
 
@@ -370,6 +373,29 @@ class _ConvBNAct(torch.autograd.Function):
         return dx, dw, dgamma, dbeta, None, None, None, None, None
 
 
+class _ConvBNActBatch(torch.autograd.Function):
+    """conv (no bias) + training-mode BatchNorm on GROUPED batch statistics + LeakyReLU: the batch's rows are cut into `groups` runs of
+    consecutive images, each normalised by its own mean and variance (the siamese tower: one run per view), and the running buffers
+    take the runs' statistics in that order, in place (ops.bn_train_grouped_*).  The raw conv output is saved."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, run_mean, run_var, stride: int, pad: int, groups: int):
+        x = x.contiguous()
+        c = ops.conv2d(x, _ohwi(w, x.shape[3]), stride=stride, pad=pad)
+        mean, _var, rstd = ops.bn_train_grouped_stats(c, groups, eps=BN_EPS, momentum=BN_MOMENTUM, running_mean=run_mean, running_var=run_var)
+        ctx.conf = (stride, pad, groups)
+        ctx.save_for_backward(x, w, c, gamma, beta, mean, rstd)
+        return ops.bn_train_grouped_apply(c, gamma, beta, mean, rstd, ops.ACT_LEAKY, groups)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, c, gamma, beta, mean, rstd = ctx.saved_tensors
+        stride, pad, groups = ctx.conf
+        dc, dgamma, dbeta = ops.bn_train_grouped_backward(g.contiguous(), c, gamma, beta, mean, rstd, ops.ACT_LEAKY, groups)
+        dx, dw = _conv_input_grads(ctx, x, w, dc, stride, pad)
+        return dx, dw, dgamma, dbeta, None, None, None, None, None
+
+
 class _ConvGN(torch.autograd.Function):
     """d2 Conv2d (no bias) + GroupNorm(32) [+ ReLU] of the pixel decoder (camera_modules.py:271-303)."""
 
@@ -634,8 +660,13 @@ class HeadTrainer:
         return [cls.KEY_PREFIX + k for k in head._spec_keys]
 
     def write_back(self, head):
-        """Copy the trained parameters into the inference head (its packed / folded / bf16 copies are rebuilt on the next forward)."""
-        self._copy_into(head, self.params)
+        """Copy the trained parameters (and what else `_written_back` names) into the inference head (its packed / folded / bf16 copies
+        are rebuilt on the next forward)."""
+        self._copy_into(head, self._written_back())
+
+    def _written_back(self) -> Dict[str, torch.Tensor]:
+        """The tensors write_back copies: the parameters; a trainer that updates buffers adds them."""
+        return self.params
 
     def _copy_into(self, head, tensors: Dict[str, torch.Tensor]):
         with torch.no_grad():
@@ -858,9 +889,19 @@ class CameraHeadTrainer(RefineTrainer):
 
     conv_stacks=True trains them too (179 tensors: + 24 conv weights, mask_features.bias, 10 GroupNorm and 36 BatchNorm affine tensors,
     the reference's step-2 / step-3 recipe): the pixel pose net runs in f32 from this trainer's parameters on the 2B images (view 1
-    first, siamese weights shared) and its backward is csrc/conv_bwd.hip.  BatchNorm uses the stored running statistics (buffers, never
-    updated) with a trainable affine - batch-statistics BatchNorm is not implemented.  feature_grads=True also returns the gradients of
-    the backbone maps in `input_grads["res3" / "res4" / "res5"]` (NHWC, [2B, h, w, C]).
+    first, siamese weights shared) and its backward is csrc/conv_bwd.hip.  By default BatchNorm uses the stored running statistics
+    (buffers, never updated) with a trainable affine.  feature_grads=True also returns the gradients of the backbone maps in
+    `input_grads["res3" / "res4" / "res5"]` (NHWC, [2B, h, w, C]).
+
+    batch_stats=True (needs conv_stacks=True) trains the 18 conv + BatchNorm + LeakyReLU blocks as the reference does, which never freezes
+    them (MODEL.FREEZE = []): every BatchNorm normalises by the batch's own mean and variance and is differentiated through them
+    (csrc/camera_bn_train.hip).  The siamese tower convs_backbone runs once per view in the reference (camera_head.py:646-647): its
+    statistics are taken over view 1's B images and over view 2's B images separately (groups = 2 over the 2B-image batch), its running
+    buffers are updated twice per iteration in that order and its counters advance by 2; the two branches see the B pairs once
+    (groups = 1, counters + 1).  `buffers` then holds clones of the 36 running statistics (f32, updated in place on the device; momentum
+    0.01, unbiased variance) and the 18 num_batches_tracked counters (int64); one camera_head_losses call is one training iteration, and
+    write_back copies the buffers into the inference head too.  `tr.batch_stats = False` between steps runs the stored-statistics path
+    on the trainer's current buffers (validation) and leaves them untouched.
     Detach points as in the reference: the AIM re-embeds a detached copy of the pixel pose (:694, :723); the geometry sequences are built
     from detached initial poses (:354-365)."""
 
@@ -868,11 +909,17 @@ class CameraHeadTrainer(RefineTrainer):
     EXTRA_LINEARS = ("fc_trans", "fc_rots")
 
     def __init__(self, params: Dict[str, torch.Tensor], nq: int, warp_in_ref: bool = True, buffers: Optional[Dict[str, torch.Tensor]] = None,
-                 conv_stacks: bool = False, feature_grads: bool = False):
+                 conv_stacks: bool = False, feature_grads: bool = False, batch_stats: bool = False):
         super().__init__(params, nq, warp_in_ref)
-        self.conv_stacks, self.feature_grads = bool(conv_stacks), bool(feature_grads)
+        self.conv_stacks, self.feature_grads, self.batch_stats = bool(conv_stacks), bool(feature_grads), bool(batch_stats)
         _require(not self.feature_grads or self.conv_stacks, "feature_grads needs conv_stacks=True")
-        self.buffers = {k: v.detach().float().contiguous() for k, v in (buffers or {}).items()}
+        _require(not self.batch_stats or self.conv_stacks, "batch_stats needs conv_stacks=True")
+        if self.batch_stats:                                      # the trainer's own copies: a forward updates them in place
+            self.buffers = {k: (v.detach().clone().to(torch.int64) if k.endswith("num_batches_tracked") else v.detach().clone().float().contiguous())
+                            for k, v in (buffers or {}).items()}
+            _require(len(self.buffers) == 54, "batch_stats=True: 36 running statistics and 18 counters expected, got %d buffers" % len(self.buffers))
+        else:
+            self.buffers = {k: v.detach().float().contiguous() for k, v in (buffers or {}).items()}
         if self.conv_stacks:
             missing = [k for k in self.parameter_names(list(self.params) + list(self.buffers), True) if k not in self.params]
             _require(not missing, "conv_stacks=True: missing parameters %s" % (missing,))
@@ -889,28 +936,45 @@ class CameraHeadTrainer(RefineTrainer):
         return sorted(out)
 
     @staticmethod
-    def buffer_names(sd_keys) -> List[str]:
-        """The BatchNorm running statistics of the conv stacks (fixed inputs of the conv_stacks=True forward)."""
+    def buffer_names(sd_keys, counters: bool = False) -> List[str]:
+        """The BatchNorm running statistics of the conv stacks (fixed inputs of the stored-statistics forward; updated by a
+        batch-statistics one), with `counters` also their num_batches_tracked."""
+        leaves = _BUFFER_LEAVES if counters else ("running_mean", "running_var")
         return sorted(k for k in sd_keys if k.startswith(PREFIX) and k[len(PREFIX):].split(".")[0] in CONV_STACKS
-                      and k.split(".")[-1] in ("running_mean", "running_var"))
+                      and k.split(".")[-1] in leaves)
 
     @classmethod
     def from_state_dict(cls, sd: dict, nq: int, device, warp_in_ref: bool = True, conv_stacks: bool = False,
-                        feature_grads: bool = False) -> "CameraHeadTrainer":
+                        feature_grads: bool = False, batch_stats: bool = False) -> "CameraHeadTrainer":
         return cls(cls._read(sd, cls.parameter_names(sd.keys(), conv_stacks), device), nq, warp_in_ref,
-                   cls._read(sd, cls.buffer_names(sd.keys()), device) if conv_stacks else None, conv_stacks, feature_grads)
+                   cls._read(sd, cls.buffer_names(sd.keys(), batch_stats), device) if conv_stacks else None, conv_stacks, feature_grads,
+                   batch_stats)
 
     @classmethod
-    def from_head(cls, head, conv_stacks: bool = False, feature_grads: bool = False) -> "CameraHeadTrainer":
+    def from_head(cls, head, conv_stacks: bool = False, feature_grads: bool = False, batch_stats: bool = False) -> "CameraHeadTrainer":
         keys = cls._head_keys(head)
         return cls(cls._read(head, cls.parameter_names(keys, conv_stacks)), head.num_queries, head.warp_plane_in_cam_ref_on,
-                   cls._read(head, cls.buffer_names(keys)) if conv_stacks else None, conv_stacks, feature_grads)
+                   cls._read(head, cls.buffer_names(keys, batch_stats)) if conv_stacks else None, conv_stacks, feature_grads, batch_stats)
+
+    def _written_back(self) -> Dict[str, torch.Tensor]:
+        """write_back copies the trained parameters; a trainer built with batch_stats=True also its running statistics and counters (the
+        head's BatchNorm folds are dropped with its other packed copies and rebuilt on the next forward)."""
+        counted = any(k.endswith("num_batches_tracked") for k in self.buffers)
+        return {**self.params, **self.buffers} if counted else self.params
 
     # ---- the pixel pose net's conv stacks (conv_stacks=True), camera_head.py:642-667 / camera_modules.py:246-348
     def _cbl(self, x, name: str, stride: int = 1):
-        """conv3x3 (no bias) + BatchNorm2d(eps 1e-3, stored statistics) + LeakyReLU(0.01) (camera_modules.py:36-48)."""
+        """conv3x3 (no bias) + BatchNorm2d(eps 1e-3, momentum 0.01) + LeakyReLU(0.01) (camera_modules.py:36-48): on the stored statistics,
+        or with batch_stats on the batch's (per view in the siamese tower), the running buffers and the counter updated in place."""
         P, Bf = self.params, self.buffers
         q = PREFIX + name
+        if self.batch_stats:
+            groups = 2 if name.startswith("convs_backbone.") else 1
+            _require(q + ".1.num_batches_tracked" in Bf, "batch_stats: this trainer was built without the BatchNorm counters (batch_stats=True)")
+            y = _ConvBNActBatch.apply(x, P[q + ".0.weight"], P[q + ".1.weight"], P[q + ".1.bias"], Bf[q + ".1.running_mean"],
+                                      Bf[q + ".1.running_var"], stride, 1, groups)
+            Bf[q + ".1.num_batches_tracked"] += groups
+            return y
         return _ConvBNAct.apply(x, P[q + ".0.weight"], P[q + ".1.weight"], P[q + ".1.bias"], Bf[q + ".1.running_mean"],
                                 Bf[q + ".1.running_var"], stride, 1, ops.ACT_LEAKY)
 

@@ -100,11 +100,11 @@ def refine(dev, d):
     rounds(d, {"refine": tr}, one)
 
 
-def camera(conv_stacks):
+def camera(conv_stacks, **kw):
     def run(dev, d):
         from tests.test_pose_net_training_gpu import _losses, _setup
         nq, c, sd, model, head, feats = _setup(dev)
-        tr = T.CameraHeadTrainer.from_head(head, conv_stacks=conv_stacks, feature_grads=conv_stacks)
+        tr = T.CameraHeadTrainer.from_head(head, conv_stacks=conv_stacks, feature_grads=conv_stacks, **kw)
 
         def one(i):
             losses = _losses(tr, head, feats, c, dev)
@@ -230,7 +230,7 @@ def backbone(dev, d):
 
 CONFIGS = (("refine", refine), ("camera", camera(False)), ("camera_conv_stacks", camera(True)), ("matcher", matcher), ("heads", heads),
            ("decoder_p0", decoder(0.0)), ("decoder_p0.1", decoder(0.1)), ("pyramid", pyramid), ("decoder_pyramid_shared_memory", shared_memory),
-           ("backbone", backbone))
+           ("backbone", backbone), ("camera_conv_stacks_batch_stats", camera(True, batch_stats=True)))
 
 
 def run_length(names):
