@@ -1001,9 +1001,11 @@ nps_status nopesac_posenet_branch_tail_bf16(const void* x_trans, const void* x_r
  *                       [B,nq,256] x 2 and, per pair, of rots / trans weights + biases and of the two score regressors.
  *  score_maps_backward: gradients of normal_score / param_score / l2_dist [B,nq+1,nq] -> rot_raw [B,nq,4] (through its normalisation),
  *                       trans_raw [B,nq,3], init_rot [B,4], init_trans [B,3].
- * m int32[B]: losses_backward and vote_backward REQUIRE m >= 1 for every pair, as their forwards do (the parameter loss and the average
- * pose divide by m: a pair with m = 0 is 0 / 0 by the reference's own definition and what is written for THAT pair is unspecified; the
- * other pairs of the launch are not affected by it).  score_maps_backward is defined at m = 0: both scores are masked out there, so
+ * m int32[B]: the parameter loss and the average pose divide by m, so a pair with m = 0 is 0 / 0 by the reference's own definition.
+ * nopesac_plane_cam_ref_losses leaves such a pair out of its sums (it adds nothing; the mean still divides by B - the convention of the
+ * embedding loss for a batch that selects nothing) and losses_backward writes exact zeros for it; the vote kernel's average pose of
+ * that pair stays 0 / 0 and vote_backward is specified for it only under those zero cotangents (it then writes zeros).  The other pairs
+ * of the launch are not affected by it.  score_maps_backward is defined at m = 0: both scores are masked out there, so
  * only g_l2_dist (which is never masked) reaches the gradients, for every hypothesis and every plane of the pair.
  * Every element of every output is written by each call (exact zeros: g_score_* off the picked hypothesis, g_l2_dist off the
  * diagonal [b, 1 + j, j], g_sf_* rows h > m, g_fused_* rows k >= m).  Held per element to float64 VJPs by tests/test_refine_bwd_forms_gpu.py. */
@@ -1291,6 +1293,40 @@ nps_status nopesac_plane_losses_backward(const nopesac_plane_criterion* a, void*
  * of the two views -> out uint8 [B, nq+1, nq+1] with the dustbin row and column, the form nopesac_matcher_sinkhorn_train takes */
 nps_status nopesac_plane_corr_matrix(const int32_t* gt_corrs, int K, const int32_t* match1, const int32_t* match2, int B, int nq, int nmax,
                                      uint8_t* out, void* stream);
+
+/* ---- where the plane head's outputs meet the two-view heads in training (csrc/two_view_train.hip; siamese_planeTR.py:237-299) ------------
+ * refine_score_maps_backward_geo: the cotangent of nopesac_ransac_score_maps that nopesac_refine_score_maps_backward leaves out - the
+ *   gradients of normal_score / param_score / l2_dist [B,nq+1,nq] -> g_geo_local f32 [B,nq,6] (first plane, second plane).  One thread
+ *   per (pair, matched plane) walks the nq + 1 hypotheses in order: the transpose of the other kernel's walk, the same masks and guards
+ *   (dn > 0, dl2 > 0, |w_r| >= 1e-12) and the same quaternion normalisation.  Rows j >= m are exact zeros (geo_sequence pads them with zero
+ *   planes, whose distances have no gradient).
+ * geo_sequence_backward: backward of nopesac_geo_sequence with respect to the planes (init_trans / init_rot are detached in the reference,
+ *   camera_head.py:353-368; sig is piecewise constant): g_geo_local [B,nq,6] and g_geo_enc [B,nq,8] at the sequence positions ->
+ *   g_planes1 / g_planes2 f32 [B,nq,3].  One workgroup per pair recomputes the row-major positions as the forward does, the cut at nq
+ *   pairs included; a plane that occurs in several pairs (a row or a column of the assignment with several ones) receives their sum in
+ *   sequence order; unmatched planes and planes at or beyond n1 / n2 get exact zeros.
+ * match_compact: x f32 [N,nq,256], params f32 [N,nq,3], match_q int32 [N,nmax], n int32 [N] -> the n[i] queries match_q[i, 0..n[i]-1] of image
+ *   i at rows 0 .. n[i]-1 of x_c / params_c in ASCENDING query index (the reference's sorted indices[bi][0], matching_head.py:51-69), zero
+ *   rows behind; order int32 [N,nq] = the query at row r or -1, rank int32 [N,nq] = the row of query q or -1.  An image whose input breaks
+ *   the contract (an index outside [0,nq), a query named twice, n[i] outside [0, min(nq,nmax)]) is treated as n[i] = 0 and bad[i] = 1
+ *   (int32 [N], else 0); nothing is read or written out of bounds.  1 <= nmax <= NPS_PLANE_MAX_QUERIES.
+ * match_compact_backward: g_x_c [N,nq,256], rank -> g_x [N,nq,256], the scatter back: an exact copy, zero rows for unmatched queries
+ *   (params_c carries no gradient: the matcher detaches its geometry, matching_head.py:98-99).
+ * corr_compact: gt_corr uint8 [B,nq+1,nq+1] (nopesac_plane_corr_matrix) gathered through both views' order with the dustbin index nq
+ *   mapped to itself: out[r,c] = gt_corr[order1[r], order2[c]] for r < n1 (or r = nq) and c < n2 (or c = nq), 0 elsewhere.
+ * All f32 / integer, nq <= NPS_PLANE_MAX_QUERIES, no float atomics, two runs give the same bits; every element of every output is written.
+ * Held to float64 VJPs per element and to a numpy restatement by tests/test_two_view_forms_gpu.py. */
+nps_status nopesac_refine_score_maps_backward_geo(const float* geo_local, const float* rot_raw, const float* trans_raw, const float* init_rot,
+                                                  const float* init_trans, const int32_t* m, int B, int nq, const float* g_normal_score,
+                                                  const float* g_param_score, const float* g_l2_dist, float* g_geo_local, void* stream);
+nps_status nopesac_geo_sequence_backward(const float* assignment, const float* planes1, const float* planes2, const int32_t* n1,
+                                         const int32_t* n2, const float* init_trans, const float* init_rot, int B, int nq, int warp_in_ref,
+                                         const float* g_geo_local, const float* g_geo_enc, float* g_planes1, float* g_planes2, void* stream);
+nps_status nopesac_match_compact(const float* x, const float* params, const int32_t* match_q, const int32_t* n, int N, int nq, int nmax,
+                                 float* x_c, float* params_c, int32_t* order, int32_t* rank, int32_t* bad, void* stream);
+nps_status nopesac_match_compact_backward(const float* g_x_c, const int32_t* rank, int N, int nq, float* g_x, void* stream);
+nps_status nopesac_corr_compact(const uint8_t* gt_corr, const int32_t* order1, const int32_t* order2, const int32_t* n1, const int32_t* n2,
+                                int B, int nq, uint8_t* out, void* stream);
 
 /* ---- backward of the plane head's instance heads (csrc/plane_head_bwd.hip; nopesac_amd/training.py::PlaneInstanceHeadsTrainer) ----------
  * The folded mask logits M[l,b,q,p] = sum_k F[l,b,q,k] p1[b,p,k] + beta[l,b,q] of L <= 3 supervised decoder layers (F = E W_pe,

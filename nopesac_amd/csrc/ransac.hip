@@ -314,6 +314,7 @@ __global__ __launch_bounds__(64) void plane_cam_ref_losses_kernel(
     float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int b = threadIdx.x; b < B; b += 64) {
         const int m = min(max(mp[b], 0), nq);
+        if (m == 0) continue;   // an empty sequence is 0 / 0 in the reference: such a pair adds nothing (the convention of the embedding loss)
         const float* gt = gt_pose + 7 * b;
         acc[0] += vec3_dist(gt, avg_trans + 3 * b);
         acc[1] += quat_dist_normalised(gt + 3, avg_rot + 4 * b);

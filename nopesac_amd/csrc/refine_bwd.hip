@@ -54,6 +54,13 @@ __global__ __launch_bounds__(64) void refine_losses_bwd_kernel(
     if (b >= B) return;
     const int NH = nq + 1;
     const int m = min(max(mp[b], 0), nq);
+    if (m == 0) {                                              // the forward skips an empty pair: every gradient of it is zero
+        for (int d = 0; d < 4; ++d) { g_avg_rot[4 * b + d] = 0.f; g_pred_rot[4 * b + d] = 0.f; }
+        for (int d = 0; d < 3; ++d) { g_avg_trans[3 * b + d] = 0.f; g_pred_trans[3 * b + d] = 0.f; }
+        for (int h = 0; h < NH; ++h) { g_score_rot[(long long)b * NH + h] = 0.f; g_score_trans[(long long)b * NH + h] = 0.f; }
+        for (int e = 0; e < NH * nq; ++e) g_l2_dist[(long long)b * NH * nq + e] = 0.f;
+        return;
+    }
     const float* gt = gt_pose + 7 * b;
     const float invB = 1.f / (float)B;
     // translation terms: d |gt - t| / dt = (t - gt) / |gt - t|

@@ -44,6 +44,7 @@ class PlaneCameraHead(ParamModule):
         self.initial_cam_weight = float(getattr(C, "INITIAL_CAM_WEIGHT", 1.0))
         self.plane_cam_weight = float(getattr(C, "PLANE_CAM_WEIGHT", 1.0))
         self.plane_cam_weight_predplane = float(getattr(C, "PLANE_CAM_WEIGHT_PREDPLANE", 0.1))
+        self.rand_cam_on = bool(getattr(C, "RAND_ON", False))           # the AIM's random-pose losses (camera_head.py:40, :172); training only
         assert C.REFINE_ON and C.CAM_REC_ON and not C.INFERENCE_SP_TOPCAM_ON and cfg.MODEL.EMBEDDING_ON and cfg.MODEL.MASK_ON, \
             "implemented: the shipped inference configuration (REFINE_ON, CAM_REC_ON, plane matcher on; inference_mp3d.yaml:17-23)"
         assert not cfg.TEST.POSE_REFINEMENT_WITH_GT_MATCHERS, "GT matchers are an evaluation-only mode"

@@ -2633,6 +2633,105 @@ def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torc
     return out
 
 
+# ---------------------------------------------------------------- the plane head's outputs in front of the two-view heads (csrc/two_view_train.hip)
+def ransac_score_maps_backward_geo(geo_local, rot_raw, trans_raw, init_rot, init_trans, m, g_normal_score, g_param_score, g_l2_dist):
+    """The cotangent of ransac_score_maps that ransac_score_maps_backward leaves out: the gradients of normal_score / param_score / l2_dist
+    [B,nq+1,nq] -> g_geo_local [B,nq,6] (exact zeros in rows j >= m)."""
+    _chk(geo_local, torch.float32)
+    _require(geo_local.dim() == 3 and geo_local.shape[2] == 6, "ransac_score_maps_backward_geo: geo_local [B,nq,6]")
+    B, nq, _ = geo_local.shape
+    _sized(rot_raw, torch.float32, B * nq * 4, "ransac_score_maps_backward_geo: rot_raw")
+    _sized(trans_raw, torch.float32, B * nq * 3, "ransac_score_maps_backward_geo: trans_raw")
+    _sized(init_rot, torch.float32, B * 4, "ransac_score_maps_backward_geo: init_rot")
+    _sized(init_trans, torch.float32, B * 3, "ransac_score_maps_backward_geo: init_trans")
+    _sized(m, torch.int32, B, "ransac_score_maps_backward_geo: m")
+    for t in (g_normal_score, g_param_score, g_l2_dist):
+        _sized(t, torch.float32, B * (nq + 1) * nq, "ransac_score_maps_backward_geo: score gradient [B,nq+1,nq]")
+    out = torch.empty(B, nq, 6, device=geo_local.device, dtype=torch.float32)
+    _C.nopesac_refine_score_maps_backward_geo(_p(geo_local), _p(rot_raw), _p(trans_raw), _p(init_rot), _p(init_trans), _p(m), B, nq,
+                                              _p(g_normal_score), _p(g_param_score), _p(g_l2_dist), _p(out), _stream())
+    return out
+
+
+def geo_sequence_backward(assignment, planes1, planes2, n1, n2, init_trans, init_rot, g_geo_local, g_geo_enc, warp_in_ref=True):
+    """Backward of geo_sequence with respect to the planes: g_geo_local [B,nq,6], g_geo_enc [B,nq,8] -> (g_planes1, g_planes2) [B,nq,3]
+    (exact zeros for unmatched planes and planes at or beyond n1 / n2; the pose is a constant)."""
+    _chk(assignment, torch.float32)
+    _require(assignment.dim() == 3 and assignment.shape[1] == assignment.shape[2], "geo_sequence_backward: assignment [B,nq,nq]")
+    B, nq, _ = assignment.shape
+    _sized(planes1, torch.float32, B * nq * 3, "geo_sequence_backward: planes1")
+    _sized(planes2, torch.float32, B * nq * 3, "geo_sequence_backward: planes2")
+    _sized(n1, torch.int32, B, "geo_sequence_backward: n1")
+    _sized(n2, torch.int32, B, "geo_sequence_backward: n2")
+    _sized(init_trans, torch.float32, B * 3, "geo_sequence_backward: init_trans")
+    _sized(init_rot, torch.float32, B * 4, "geo_sequence_backward: init_rot")
+    _sized(g_geo_local, torch.float32, B * nq * 6, "geo_sequence_backward: g_geo_local")
+    _sized(g_geo_enc, torch.float32, B * nq * 8, "geo_sequence_backward: g_geo_enc")
+    f32 = dict(device=assignment.device, dtype=torch.float32)
+    out = (torch.empty(B, nq, 3, **f32), torch.empty(B, nq, 3, **f32))
+    _C.nopesac_geo_sequence_backward(_p(assignment), _p(planes1), _p(planes2), _p(n1), _p(n2), _p(init_trans), _p(init_rot), B, nq,
+                                     int(bool(warp_in_ref)), _p(g_geo_local), _p(g_geo_enc), _p(out[0]), _p(out[1]), _stream())
+    return out
+
+
+def match_compact(x, params, match_q, n, check: bool = False):
+    """The matched queries of every image to the front, in ascending query index: x [N,nq,256], params [N,nq,3], match_q int32 [N,nmax],
+    n int32 [N] -> (x_c, params_c, order int32 [N,nq], rank int32 [N,nq], bad int32 [N]); rows behind n[i] are zeros, order / rank are -1
+    where nothing lies.  An image whose input breaks the contract (an index outside [0,nq), a query named twice, n[i] outside
+    [0, min(nq,nmax)]) is compacted as n[i] = 0 and flagged in `bad`: read it at a sync the caller already pays (match_compact_check), or
+    pass check=True to raise ValueError here (one host sync)."""
+    _chk(x, torch.float32)
+    _require(x.dim() == 3 and x.shape[2] == 256, "match_compact: x [N,nq,256]")
+    N, nq, _ = x.shape
+    _sized(params, torch.float32, N * nq * 3, "match_compact: params [N,nq,3]")
+    _chk(match_q, torch.int32)
+    _require(match_q.dim() == 2 and match_q.shape[0] == N, "match_compact: match_q [N,nmax]")
+    _sized(n, torch.int32, N, "match_compact: n")
+    dev = x.device
+    x_c, params_c = torch.empty(N, nq, 256, device=dev, dtype=torch.float32), torch.empty(N, nq, 3, device=dev, dtype=torch.float32)
+    order, rank = torch.empty(N, nq, device=dev, dtype=torch.int32), torch.empty(N, nq, device=dev, dtype=torch.int32)
+    bad = torch.empty(N, device=dev, dtype=torch.int32)
+    _C.nopesac_match_compact(_p(x), _p(params), _p(match_q), _p(n), N, nq, match_q.shape[1], _p(x_c), _p(params_c), _p(order), _p(rank),
+                             _p(bad), _stream())
+    if check:
+        match_compact_check(bad)
+    return x_c, params_c, order, rank, bad
+
+
+def match_compact_check(bad: torch.Tensor):
+    """ValueError if match_compact flagged an image (reads `bad` on the host)."""
+    flagged = torch.nonzero(bad).flatten().tolist()
+    if flagged:
+        raise ValueError("match_compact: match_q / n of image(s) %s break the contract (index outside [0,nq), a query named twice, or n "
+                         "outside [0, min(nq,nmax)])" % flagged)
+
+
+def match_compact_backward(g_x_c, rank):
+    """The scatter back of match_compact: g_x_c [N,nq,256], rank int32 [N,nq] -> g_x [N,nq,256] (zero rows for unmatched queries)."""
+    _chk(g_x_c, torch.float32)
+    _require(g_x_c.dim() == 3 and g_x_c.shape[2] == 256, "match_compact_backward: g_x_c [N,nq,256]")
+    N, nq, _ = g_x_c.shape
+    _sized(rank, torch.int32, N * nq, "match_compact_backward: rank [N,nq]")
+    out = torch.empty_like(g_x_c)
+    _C.nopesac_match_compact_backward(_p(g_x_c), _p(rank), N, nq, _p(out), _stream())
+    return out
+
+
+def corr_compact(gt_corr, order1, order2, n1, n2):
+    """gt_corr uint8 [B,nq+1,nq+1] (plane_corr_matrix) gathered through both views' `order` of match_compact, the dustbin index mapped to
+    itself; entries outside the live block [n1, n2] (plus dustbins) are zero."""
+    _chk(gt_corr, torch.uint8)
+    _require(gt_corr.dim() == 3 and gt_corr.shape[1] == gt_corr.shape[2] and gt_corr.shape[1] >= 2, "corr_compact: gt_corr [B,nq+1,nq+1]")
+    B, nq = gt_corr.shape[0], gt_corr.shape[1] - 1
+    _sized(order1, torch.int32, B * nq, "corr_compact: order1 [B,nq]")
+    _sized(order2, torch.int32, B * nq, "corr_compact: order2 [B,nq]")
+    _sized(n1, torch.int32, B, "corr_compact: n1")
+    _sized(n2, torch.int32, B, "corr_compact: n2")
+    out = torch.empty_like(gt_corr)
+    _C.nopesac_corr_compact(_p(gt_corr), _p(order1), _p(order2), _p(n1), _p(n2), B, nq, _p(out), _stream())
+    return out
+
+
 # ---------------------------------------------------------------- backward of the plane head's instance heads (csrc/plane_head_bwd.hip)
 def sigmoid_backward(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """g y (1 - y) for the output y of a sigmoid and its gradient g."""

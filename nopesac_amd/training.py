@@ -76,9 +76,17 @@ parameters (the reference's full-model clip - HeadTrainer.clip_grad_norm sees on
 WarmupMultiStepLR schedule, averages gradients across ranks and saves / resumes its state, in a fixed number of launches.
 HeadTrainer.step_from_cfg remains the single-trainer form, and the yardstick that ModelOptimizer is held to bit for bit.
 
-What this is NOT: one forward of the meta-architecture in training mode that drives all trainers - each trainer is called by its user.
-The image, the plane sets and their appearance features are inputs of the stages, as they are of the reference functions, and
-receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is discrete and carries none.  Gated
+The two-view half of the training forward (siamese_planeTR.py:237-299: the plane head's outputs of both views feed the matching head
+and the camera head, nothing detached on the way) is TwoViewLosses: the matched queries of every image are gathered to a prefix on the
+device (csrc/two_view_train.hip: match_compact, its scatter back, corr_compact) for MatchingHeadTrainer, and the camera head's `_Aux`
+passes run with the PREDICTED planes on the tape (plane_grads: _GeoSequence around ops.geo_sequence, and the geo_local cotangent of
+_ScoreMaps - the two backward kernels of the same file), so the refinement losses reach plane_param and, through hs, the decoder.
+joint_backward is one backward over several trainers; ModelOptimizer steps them.
+
+What this is NOT: the driver from images to an optimiser step - one forward of the meta-architecture in training mode that calls every
+trainer - each trainer (and TwoViewLosses) is called by its user.  The image and the backbone maps are inputs of the stages, as they are
+of the reference functions, and receive no gradient beyond `input_grads`; the assignment between the matcher and the camera head is
+discrete and carries none.  Gated
 against torch.autograd on the oracle (tests/test_training_gpu.py, tests/test_pose_net_training_gpu.py, tests/test_matcher_training_gpu.py)
 and against float64 restatements pinned to the reference (tests/test_plane_criterion_gpu.py, tests/test_plane_heads_training_gpu.py, tests/test_plane_decoder_training_gpu.py, tests/test_plane_pyramid_training_gpu.py, tests/test_plane_encoder_training_gpu.py, tests/test_backbone_training_gpu.py)."""
 from __future__ import annotations
@@ -230,6 +238,28 @@ def _mlp_stack(P: Dict[str, torch.Tensor], q: str, x, last_act: int = ops.ACT_NO
     return _linear(x, P[f"{q}.layers.{i}.weight"], P[f"{q}.layers.{i}.bias"], last_act)
 
 
+class _GeoSequence(torch.autograd.Function):
+    """ops.geo_sequence with the PLANES on the tape (plane_grads): (geo_local, geo_enc, m), the backward is one launch of
+    ops.geo_sequence_backward.  The pose is a constant, as in the reference (the detached initial pose, camera_head.py:353-368)."""
+
+    @staticmethod
+    def forward(ctx, A0, planes1, planes2, n1, n2, init_trans, init_rot, warp_in_ref: bool):
+        planes1, planes2 = planes1.contiguous(), planes2.contiguous()
+        geo_local, _gg, _sig, geo_enc, m = ops.geo_sequence(A0, planes1, planes2, n1, n2, init_trans, init_rot, warp_in_ref)
+        ctx.warp_in_ref = bool(warp_in_ref)
+        ctx.save_for_backward(A0, planes1, planes2, n1, n2, init_trans, init_rot)
+        ctx.mark_non_differentiable(m)
+        return geo_local, geo_enc, m
+
+    @staticmethod
+    def backward(ctx, g_local, g_enc, _m):
+        A0, planes1, planes2, n1, n2, init_trans, init_rot = ctx.saved_tensors
+        B, nq, _ = A0.shape
+        z = lambda t, d: torch.zeros(B, nq, d, device=A0.device, dtype=torch.float32) if t is None else t.contiguous()
+        g1, g2 = ops.geo_sequence_backward(A0, planes1, planes2, n1, n2, init_trans, init_rot, z(g_local, 6), z(g_enc, 8), ctx.warp_in_ref)
+        return None, g1, g2, None, None, None, None, None
+
+
 class _ScoreMaps(torch.autograd.Function):
     @staticmethod
     def forward(ctx, geo_local, rot_raw, trans_raw, init_rot, init_trans, m):
@@ -248,7 +278,11 @@ class _ScoreMaps(torch.autograd.Function):
         g_ns, g_ps, g_l2 = (z(t, ref) for t in (g_ns, g_ps, g_l2))
         g_rot, g_tr, g_ir, g_it = ops.ransac_score_maps_backward(geo_local, rot_raw.contiguous(), trans_raw.contiguous(), init_rot, init_trans, m,
                                                                  g_ns, g_ps, g_l2)
-        return None, g_rot, g_tr, g_ir, g_it, None
+        g_geo = None
+        if ctx.needs_input_grad[0]:                               # (plane_grads: geo_local comes from _GeoSequence)
+            g_geo = ops.ransac_score_maps_backward_geo(geo_local, rot_raw.contiguous(), trans_raw.contiguous(), init_rot, init_trans, m,
+                                                       g_ns, g_ps, g_l2)
+        return g_geo, g_rot, g_tr, g_ir, g_it, None
 
 
 class _Vote(torch.autograd.Function):
@@ -847,13 +881,19 @@ class RefineTrainer(HeadTrainer):
         return _linear(x, self.params[f"{PREFIX}{name}.weight"], self.params[f"{PREFIX}{name}.bias"], act)
 
     def losses(self, A0, planes1, planes2, n1, n2, init_trans, init_rot, init_trans_feat, init_rot_feat, gt_pose, suffix: str = "",
-               weight: float = 1.0) -> Dict[str, torch.Tensor]:
+               weight: float = 1.0, plane_grads: bool = False) -> Dict[str, torch.Tensor]:
         """The seven losses of __forward_PlaneCamRefHead (camera_head.py:883-921) with the autograd tape attached.  The feature / pose inputs
-        may require grad (their gradients land in `input_grads` after backward())."""
+        may require grad (their gradients land in `input_grads` after backward()).  plane_grads: planes1 / planes2 that require grad are on
+        the tape as well - through the 8-d encoder input and through the hypothesis-by-plane distance maps, under the detached initial
+        pose as in the reference (get_pred_geo_sequence, camera_head.py:1352-1425) - and their gradients land in `input_grads` too.  Off,
+        the launches and the bits are those of the plane-free tape."""
         P, nq = self.params, self.nq
         B = A0.shape[0]
-        with torch.no_grad():
-            geo_local, _gg, _sig, geo_enc, m = ops.geo_sequence(A0, planes1, planes2, n1, n2, init_trans.detach(), init_rot.detach(), self.warp_in_ref)
+        if plane_grads:
+            geo_local, geo_enc, m = _GeoSequence.apply(A0, planes1, planes2, n1, n2, init_trans.detach(), init_rot.detach(), self.warp_in_ref)
+        else:
+            with torch.no_grad():
+                geo_local, _gg, _sig, geo_enc, m = ops.geo_sequence(A0, planes1, planes2, n1, n2, init_trans.detach(), init_rot.detach(), self.warp_in_ref)
         rows = B * nq
         geo = self._mlp(geo_enc.view(rows, 8), "geo_encoder")
         s1 = self._mlp(geo, "geo_proj_s1")
@@ -876,7 +916,10 @@ class RefineTrainer(HeadTrainer):
                                              fused_tran.view(B, nq, 256), w("rots"), bb("rots"), w("trans"), bb("trans"), rots_all, trans_all,
                                              dn_sum, dl2_sum, init_rot.detach(), init_trans.detach(), m)
         lv = _Losses.apply(pr, pt, ar, at, sr, st, l2, rots_all, trans_all, m, gt_pose, float(weight))
-        self._watch({"init_trans_feat": init_trans_feat, "init_rot_feat": init_rot_feat, "init_trans": init_trans, "init_rot": init_rot})
+        watched = {"init_trans_feat": init_trans_feat, "init_rot_feat": init_rot_feat, "init_trans": init_trans, "init_rot": init_rot}
+        if plane_grads:
+            watched.update(planes1=planes1, planes2=planes2)
+        self._watch(watched)
         self.last = {"pred_rot": pr, "pred_trans": pt, "avg_rot": ar, "avg_trans": at, "score_rot": sr, "score_trans": st, "m": m}
         return {"%s_%s" % (nm, suffix): lv[i] for i, nm in enumerate(ops.PLANE_CAM_REF_LOSS_NAMES)}
 
@@ -1029,8 +1072,10 @@ class CameraHeadTrainer(RefineTrainer):
         return rec_trans, rec_rot, trans_feat, rot_feat, rot_c, tr_in
 
     def camera_head_losses(self, head, feats: dict, B: int, gt_planes1, gt_planes2, gt_n1, gt_n2, gt_assignment, gt_pose, planes1=None, planes2=None,
-                           n1=None, n2=None, assignment=None, rand_rot=None, rand_trans=None) -> Dict[str, torch.Tensor]:
-        """All losses of the training-mode forward (the 34 of PlaneCameraHead.forward_train) with the autograd tape attached."""
+                           n1=None, n2=None, assignment=None, rand_rot=None, rand_trans=None, plane_grads: bool = False) -> Dict[str, torch.Tensor]:
+        """All losses of the training-mode forward (the 34 of PlaneCameraHead.forward_train) with the autograd tape attached.  plane_grads
+        puts the PREDICTED planes of the _Aux passes on the tape (RefineTrainer.losses; their gradients land in `input_grads` under
+        planes1 / planes2); the ground-truth planes are data."""
         inputs = {}
         if self.conv_stacks:
             fm = {}
@@ -1060,13 +1105,15 @@ class CameraHeadTrainer(RefineTrainer):
             return rec_t, rec_r, rec_tf, rec_rf
 
         rec_t, rec_r, rec_tf, rec_rf = rec(trans0, rot0, "_initCamRec")
-        passes = [("", gt_planes1, gt_planes2, gt_n1, gt_n2, gt_assignment, head.plane_cam_weight)]
+        passes = [("", gt_planes1, gt_planes2, gt_n1, gt_n2, gt_assignment, head.plane_cam_weight, False)]
         if assignment is not None:
-            passes.append(("_Aux", planes1, planes2, n1, n2, assignment, head.plane_cam_weight_predplane))
+            passes.append(("_Aux", planes1, planes2, n1, n2, assignment, head.plane_cam_weight_predplane, bool(plane_grads)))
+            if plane_grads:
+                inputs.update(planes1=planes1, planes2=planes2)
         self.recorded = {"trans": [trans0, rec_t], "rot": [rot0, rec_r]}
-        for sfx, pl1, pl2, c1, c2, A, w in passes:
+        for sfx, pl1, pl2, c1, c2, A, w, pg in passes:
             for name, it, ir, itf, irf in (("initCamRef", trans0, rot0, tf0, rf0), ("initRecCamRef", rec_t, rec_r, rec_tf, rec_rf)):
-                losses.update(self.losses(A, pl1, pl2, c1, c2, it, ir, itf, irf, gt_pose, suffix=name + sfx, weight=w))
+                losses.update(self.losses(A, pl1, pl2, c1, c2, it, ir, itf, irf, gt_pose, suffix=name + sfx, weight=w, plane_grads=pg))
                 self.recorded["trans"] += [self.last["avg_trans"], self.last["pred_trans"]]
                 self.recorded["rot"] += [self.last["avg_rot"], self.last["pred_rot"]]
         if rand_rot is not None:
@@ -2088,3 +2135,108 @@ def plane_corr_matrix(gt_corrs: torch.Tensor, match1: torch.Tensor, match2: torc
     MatchingHeadTrainer.matching_losses takes: gt_corrs int32 [B, K, 2] on the device (rows padded with -1), match1 / match2 = the two
     views' indices["match_q"][0] -> uint8 [B, nq+1, nq+1].  One launch, no host sync."""
     return ops.plane_corr_matrix(gt_corrs.contiguous(), match1.contiguous(), match2.contiguous(), nq)
+
+
+# ---- the two-view half of the training forward (siamese_planeTR.py:237-299) ----------------------------------------------------------------
+class _MatchCompact(torch.autograd.Function):
+    """ops.match_compact with the queries on the tape: (x_c, params_c, order, rank, bad); the backward is the scatter back through `rank`.
+    params_c carries no gradient (the matcher detaches its geometry, matching_head.py:98-99)."""
+
+    @staticmethod
+    def forward(ctx, x, params, match_q, n):
+        x_c, params_c, order, rank, bad = ops.match_compact(x.contiguous(), params.detach().contiguous(), match_q.contiguous(), n.contiguous())
+        ctx.save_for_backward(rank)
+        ctx.mark_non_differentiable(params_c, order, rank, bad)
+        return x_c, params_c, order, rank, bad
+
+    @staticmethod
+    def backward(ctx, g_x_c, _p, _o, _r, _b):
+        (rank,) = ctx.saved_tensors
+        return ops.match_compact_backward(g_x_c.contiguous(), rank), None, None, None
+
+
+_RAND_POSE_SALT = 0x52414E44504F5345       # keeps the draws apart from augment.sample_params' for the same (seed, step, row)
+
+
+def sample_rand_poses(count: int, seed: int = 0, step: int = 0):
+    """The AIM's random poses (camera_head.py:688-691, :716): a rotation vector uniform in (-2.5, 2.5)^3 turned into a unit quaternion
+    (w, x, y, z), a translation uniform in (-2.5, 2.5)^3 -> (rot f32 [count,4], trans f32 [count,3]) on the host.  Every row is a
+    function of (seed, step, row) alone, as in augment.sample_params."""
+    import numpy as np
+    from .augment import _uniforms
+    u = _uniforms(int(seed) ^ _RAND_POSE_SALT, int(step), np.arange(count, dtype=np.int64), 6)
+    v = (u[:, :3] * 2.0 - 1.0) * 2.5
+    theta = np.linalg.norm(v, axis=1, keepdims=True)
+    axis = v / np.maximum(theta, 1e-300)
+    q = np.concatenate([np.cos(theta / 2), np.sin(theta / 2) * axis], 1)
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    return torch.from_numpy(q.astype(np.float32)), torch.from_numpy(((u[:, 3:] - 0.5) * 5.0).astype(np.float32))
+
+
+def joint_backward(trainers, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
+    """One backward over the sum of `losses` (already weighted, or under `loss_weights`) of a graph that runs through several trainers:
+    clears every trainer, differentiates once and returns {state-dict key: gradient} over all of them, each trainer's `.grads` /
+    `.input_grads` filled.  The general form of BackboneTrainer.joined_backward."""
+    trainers = list(trainers)
+    for t in trainers:
+        t._clear_grads()
+    total = None
+    for k, v in losses.items():
+        term = v * float(loss_weights.get(k, 1.0)) if loss_weights else v
+        total = term if total is None else total + term
+    total.backward()
+    out: Dict[str, torch.Tensor] = {}
+    for t in trainers:
+        out.update(t._collect())
+    return out
+
+
+class TwoViewLosses:
+    """What siamese_planeTR.py:240-297 adds to the loss dict, from the plane head's outputs of both views: the matching head's embedding
+    loss on the matched queries (gathered to a prefix on the device, ops.match_compact) and the camera head's losses with the predicted
+    planes on the tape (camera_head_losses(plane_grads=True)) - nothing is detached between the plane head and the two-view heads but
+    what the reference detaches.  `camera_head` is the inference head: it supplies the loss weights and switches.
+
+        two_view = TwoViewLosses(matcher, camera, model.camera_head_list[0])
+        plane_losses, idx = heads.losses(hs, p1, pair["targets"])
+        tv = two_view.losses(hs[-1], heads.last["pred_params"], idx["match_q"][0][:B], idx["match_q"][0][B:], n[:B], n[B:], pair, feats, B)
+        grads = joint_backward([heads, matcher, camera], {**heads.criterion.weighted(plane_losses), **tv})"""
+
+    def __init__(self, matcher: "MatchingHeadTrainer", camera: "CameraHeadTrainer", camera_head):
+        self.matcher, self.camera, self.camera_head = matcher, camera, camera_head
+        self.bad: Optional[torch.Tensor] = None
+
+    def check(self):
+        """ValueError if the last losses() call met a match_q / n that breaks match_compact's contract (one host read)."""
+        ops.match_compact_check(self.bad)
+
+    def losses(self, query_feat, pred_params, match1, match2, n1, n2, pair: dict, feats: dict, B: int, seed: int = 0, step: int = 0):
+        """query_feat [2B,nq,256] (the last layer of hs, view-1 images first), pred_params [2B,nq,3], match1 / match2 int32 [B,nmax] (the
+        last layer's match_q of the two views), n1 / n2 int32 [B] on the device, pair = TargetMapper.pair_targets(...), feats = the
+        backbone maps -> losses_emb_0 and the camera head's 32 losses (34 with the head's rand_cam_on)."""
+        nq, dev = self.matcher.nq, query_feat.device
+        _require(query_feat.shape == (2 * B, nq, 256) and pred_params.shape == (2 * B, nq, 3),
+                 "TwoViewLosses: query_feat [2B,nq,256], pred_params [2B,nq,3]; got %s, %s" % (tuple(query_feat.shape), tuple(pred_params.shape)))
+        n_all = torch.cat([n1, n2]).contiguous()
+        x_c, params_c, order, _rank, self.bad = _MatchCompact.apply(query_feat, pred_params, torch.cat([match1, match2]), n_all)
+        gt_corr = plane_corr_matrix(pair["gt_corrs"], match1, match2, nq)
+        corr_c = ops.corr_compact(gt_corr, order[:B].contiguous(), order[B:].contiguous(), n1.contiguous(), n2.contiguous())
+        gt_pose = pair["gt_pose"]
+        out = dict(self.matcher.matching_losses(x_c, n_all, gt_pose, params_c[:B], params_c[B:], corr_c, suffix="0"))
+        # the camera head: ground-truth planes with the ground-truth correspondences, then all nq predicted planes with gt_corr[:, :nq, :nq]
+        t = pair["targets"]
+        gt_planes = torch.zeros(2 * B, nq, 3, device=dev, dtype=torch.float32)
+        nmax = min(t["plane_params"].shape[1], nq)
+        gt_planes[:, :nmax] = t["plane_params"][:, :nmax]
+        corrs = pair["gt_corrs"].long()
+        valid = (corrs >= 0).all(-1) & (corrs < nq).all(-1)
+        flat = (corrs[..., 0].clamp(0, nq - 1) * nq + corrs[..., 1].clamp(0, nq - 1))
+        gt_A = torch.zeros(B, nq * nq, device=dev, dtype=torch.float32).scatter_add_(1, flat, valid.float()).clamp_(max=1.0).view(B, nq, nq)
+        full = torch.full((B,), nq, device=dev, dtype=torch.int32)
+        rand_rot = rand_trans = None
+        if getattr(self.camera_head, "rand_cam_on", False):
+            rand_rot, rand_trans = (r.to(dev) for r in sample_rand_poses(B * max(1, 64 // B), seed, step))
+        out.update(self.camera.camera_head_losses(self.camera_head, feats, B, gt_planes[:B], gt_planes[B:], t["n"][:B].contiguous(),
+                                                  t["n"][B:].contiguous(), gt_A, gt_pose, pred_params[:B], pred_params[B:], full, full,
+                                                  gt_corr[:, :nq, :nq].float().contiguous(), rand_rot, rand_trans, plane_grads=True))
+        return out
