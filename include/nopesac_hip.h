@@ -1231,10 +1231,17 @@ nps_status nopesac_desc_dot_backward(const float* d_desc_dot, const float* d0, c
  *                pixel adds nothing to loss_q or d_params;
  *   ws           nopesac_plane_criterion_workspace_floats(L, B, nq, nmax, h, w) floats, shared by the three entries (the loss entry's
  *                content must survive until its backward entry has run); the count is a value, 0 for a non-positive dimension
- *                (never negative). */
+ *                (never negative);
+ *   groups       G view groups (0 or 1: none; else 2..NPS_PLANE_MAX_GROUPS, dividing B, or NPS_E_ARG): group g is the batch elements
+ *                [g B/G, (g+1) B/G) of every layer's block, as forward_single sees one view at a time.  The loss and gradient entries
+ *                then take num_masks, the matched count, the class weight sum and the batch divisor of loss_center_pixel / loss_q per
+ *                group: losses and g_losses are [G][6 L + 2], num_masks_groups (HOST, G floats; null: num_masks for every group) the
+ *                per-group overrides.  Group g's losses and every gradient element of its images have the bits of an ungrouped call
+ *                on those images alone.  The cost and assignment entries are per image and ignore it. */
 #define NPS_PLANE_MAX_QUERIES 128
 #define NPS_PLANE_MAX_TARGETS 50
 #define NPS_PLANE_MAX_LAYERS 8
+#define NPS_PLANE_MAX_GROUPS 8
 typedef struct nopesac_plane_criterion {
     const float* pred_logits;
     const float* pred_mask_logits;
@@ -1251,7 +1258,7 @@ typedef struct nopesac_plane_criterion {
     const float* tgt_pixel_centers;
     const float* depth;
     const float* k_inv_dot_xy1;
-    int L, B, nq, nmax, h, w, H, W, num_classes, reserved;
+    int L, B, nq, nmax, h, w, H, W, num_classes, groups;
     float cost_class, cost_mask, cost_dice, cost_center, cost_param, cost_offset, cost_angle;
     float eos_coef, num_masks, reserved_f;
     float* cost;
@@ -1269,6 +1276,7 @@ typedef struct nopesac_plane_criterion {
     float* d_pixel_centers;
     float* ws;
     int64_t ws_floats;
+    const float* num_masks_groups;
 } nopesac_plane_criterion;
 int64_t nopesac_plane_criterion_workspace_floats(int L, int B, int nq, int nmax, int h, int w);
 /* plane_centers [B, nmax, 2] = centroid of (x / W, y / H) over each mask (0 at j >= n[b]), computed in f64 from the exact integer sums
@@ -1427,6 +1435,35 @@ nps_status nopesac_bn_train_backward_f32(const float* dy, const float* src, int 
                                          const float* gamma, const float* beta, const float* mean, const float* rstd, int act, int batch_stats,
                                          float* dsrc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats, void* stream);
 nps_status nopesac_upsample2x_bilinear_backward_f32(const float* du, float* dx, int B, int H, int W, int C, void* stream);
+/* The same three launchers on VIEW GROUPS: `groups` = G (0 or 1: none, the entries above bit for bit; else 2..NPS_BN_TRAIN_MAX_GROUPS,
+ * dividing B, or NPS_E_ARG) cuts the B images (the rows of the matrix form) into G groups of B / G consecutive ones - the two views of a
+ * 2B-image batch, view 1 first - each with its own batch statistics, as G module calls on the groups would have them (reference top_down
+ * under forward_single per view, siamese_planeTR.py:228-235).  One launch per stage whatever G is; a group's rows are cut into blocks of
+ * NPS_BN_TRAIN_RPS from the group's first row and its partials are finished on their own, so every per-group result has the bits of
+ * an ungrouped call on that group's sub-tensor.  Both input forms, the addend included; the upsampling and its adjoint never cross an
+ * image, so they never cross a group.
+ *  stats:    mean, var, rstd are [G][C]; running_mean / running_var [C] take the groups' statistics one after the other (in a
+ *            register, stored once), the variance unbiased with the group's n: what G module calls in a row leave.
+ *  apply:    y = act(gamma (v - mean_g) rstd_g + beta) (+ addend), g = the row's group.
+ *  backward: per group S2_g = sum dz xhat and S1_g = sum dz over its rows -> group_sums [G][2][C] (S2_g, then S1_g; needed for G > 1,
+ *            16-byte aligned; not written for G <= 1), dsrc of its rows from them with n = the group's rows; dgamma = sum_g S2_g and
+ *            dbeta = sum_g S1_g, added in group order.  No atomics.
+ * ws: at least NPS_BN_TRAIN_GROUPS_WORKSPACE_FLOATS(G, n, C) floats, n = all rows of v (= NPS_BN_TRAIN_WORKSPACE_FLOATS(n, C) at G = 1);
+ * nopesac_bn_train_groups_workspace_floats writes the macro's value into *floats (a status entry: NPS_E_ARG and 0 for groups outside
+ * 0..NPS_BN_TRAIN_MAX_GROUPS, n <= 0, C <= 0 or n not a multiple of G). */
+#define NPS_BN_TRAIN_MAX_GROUPS 8
+#define NPS_BN_TRAIN_GROUPS_WORKSPACE_FLOATS(G, n, C) ((int64_t)(G) * (((int64_t)(n) / (G) + NPS_BN_TRAIN_RPS - 1) / NPS_BN_TRAIN_RPS) * 2 * (C))
+nps_status nopesac_bn_train_groups_workspace_floats(int groups, int64_t n, int C, int64_t* floats);
+nps_status nopesac_bn_train_groups_stats_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, int groups, float eps,
+                                             float momentum, float* mean, float* var, float* rstd, float* running_mean, float* running_var,
+                                             float* ws, int64_t ws_floats, void* stream);
+nps_status nopesac_bn_train_groups_apply_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, int groups,
+                                             const float* gamma, const float* beta, const float* mean, const float* rstd, int act,
+                                             const float* addend, float* y, void* stream);
+nps_status nopesac_bn_train_groups_backward_f32(const float* dy, const float* src, int up, int B, int H, int W, int C, int64_t src_cstride,
+                                                int groups, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                                int act, int batch_stats, float* dsrc, float* dgamma, float* dbeta, float* group_sums,
+                                                float* ws, int64_t ws_floats, void* stream);
 
 /* ---- training-mode BatchNorm of the camera head's conv stacks on GROUPED batch statistics (csrc/camera_bn_train.hip;
  * training.CameraHeadTrainer(batch_stats=True); reference Conv2d + nn.BatchNorm2d(eps 0.001, momentum 0.01) + LeakyReLU, camera_modules.py:36-48) --

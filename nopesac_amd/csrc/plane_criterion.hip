@@ -21,6 +21,7 @@ namespace nps {
 constexpr int PC_MAXQ = NPS_PLANE_MAX_QUERIES;
 constexpr int PC_MAXT = NPS_PLANE_MAX_TARGETS;
 constexpr int PC_MAXL = NPS_PLANE_MAX_LAYERS;
+constexpr int PC_MAXG = NPS_PLANE_MAX_GROUPS;
 constexpr int PC_COST_BLOCKS = 16;     // workgroups per image of the cost partials (each walks 64-pixel chunks blk, blk + 16, ...)
 constexpr int PC_CHUNK = 64;           // low-resolution pixels per chunk: one per lane
 constexpr int PC_LS = PC_CHUNK + 1;    // LDS row stride of the chunk tiles
@@ -55,10 +56,13 @@ template <int NW> __device__ __forceinline__ float block_sum(float v, float* red
     return t;
 }
 __device__ __forceinline__ int pc_n(const int* n, int b, int nmax) { return min(max(n[b], 0), nmax); }
-__device__ __forceinline__ float pc_num_masks(const int* n, int B, int nmax, float override_) {
+// View groups: group g is the images [g Bg, (g + 1) Bg) of every layer's block, Bg = B / G.  Every batch-wide reduction of the loss and
+// gradient kernels runs over one group, in the order a call on those images alone would take, so a group keeps that call's bits.
+struct PcGroups { int G; float nm[PC_MAXG]; };   // nm[g]: the group's num_masks override (<= 0: max(sum of its n, 1))
+__device__ __forceinline__ float pc_num_masks(const int* n, int b0, int Bg, int nmax, float override_) {
     if (override_ > 0.f) return override_;
     int t = 0;
-    for (int b = 0; b < B; ++b) t += pc_n(n, b, nmax);
+    for (int b = b0; b < b0 + Bg; ++b) t += pc_n(n, b, nmax);
     return (float)max(t, 1);
 }
 // sigmoid and the two softplus values of one logit: sp0 = BCE against 0, sp1 = BCE against 1
@@ -519,18 +523,20 @@ __global__ __launch_bounds__(128) void pc_image_kernel(const float* __restrict__
     }
 }
 
-// losses [6 L + 2]: per layer (ce, mask, dice, center_ins, param_l1, param_cos), then center_pixel and q of the last layer.  q_stats [B, 2]
+// losses [G][6 L + 2], one workgroup per view group: per layer (ce, mask, dice, center_ins, param_l1, param_cos), then center_pixel and q of
+// the last layer, each over the group's Bg images in their order.  q_stats [B, 2]
 __global__ __launch_bounds__(64) void pc_final_kernel(const float* __restrict__ img, const float* __restrict__ cpix_part,
-                                                      const float* __restrict__ q_part, const int* __restrict__ n, int L, int B, int nmax,
-                                                      int nbands, int HW, float num_masks_override, int with_pixel, float* __restrict__ losses,
+                                                      const float* __restrict__ q_part, const int* __restrict__ n, int L, int B, int Bg, int nmax,
+                                                      int nbands, int HW, PcGroups pg, int with_pixel, float* __restrict__ losses,
                                                       float* __restrict__ q_stats) {
-    const int t = threadIdx.x;
-    const float nm = pc_num_masks(n, B, nmax, num_masks_override);
+    const int t = threadIdx.x, grp = blockIdx.x, b0 = grp * Bg;
+    const float nm = pc_num_masks(n, b0, Bg, nmax, pg.nm[grp]);
+    losses += (long long)grp * (6 * L + 2);
     int matched = 0;
-    for (int b = 0; b < B; ++b) matched += pc_n(n, b, nmax);
+    for (int b = b0; b < b0 + Bg; ++b) matched += pc_n(n, b, nmax);
     if (t < L) {
         float s[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int b = 0; b < B; ++b)
+        for (int b = b0; b < b0 + Bg; ++b)
 #pragma unroll
             for (int c = 0; c < 7; ++c) s[c] += img[((long long)t * B + b) * 8 + c];
         float* o = losses + t * 6;
@@ -544,18 +550,18 @@ __global__ __launch_bounds__(64) void pc_final_kernel(const float* __restrict__ 
     if (t == 62) {
         float a = 0.f;
         if (with_pixel)
-            for (int k = 0; k < B * nbands; ++k) a += cpix_part[k];
-        losses[6 * L] = a / ((float)B * (float)HW);
+            for (int k = 0; k < Bg * nbands; ++k) a += cpix_part[(long long)b0 * nbands + k];
+        losses[6 * L] = a / ((float)Bg * (float)HW);
     }
     if (t == 63) {
         float a = 0.f;
-        for (int b = 0; b < B; ++b) {
+        for (int b = b0; b < b0 + Bg; ++b) {
             float s = 0.f, c = 0.f;
             for (int k = 0; k < PC_QCHUNKS; ++k) { s += q_part[((long long)b * PC_QCHUNKS + k) * 2]; c += q_part[((long long)b * PC_QCHUNKS + k) * 2 + 1]; }
             q_stats[2 * b] = s; q_stats[2 * b + 1] = c;
             a += c > 0.f ? s / c : 0.f;
         }
-        losses[6 * L + 1] = a / (float)B;
+        losses[6 * L + 1] = a / (float)Bg;
     }
 }
 
@@ -566,8 +572,8 @@ __global__ __launch_bounds__(64) void pc_final_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void pc_mask_bwd_kernel(const float* __restrict__ mlog, long long s_i, long long s_q, long long s_y, long long s_x,
                                                           const uint8_t* __restrict__ masks, const int* __restrict__ n,
                                                           const int* __restrict__ match_gt, const float* __restrict__ mask_stats,
-                                                          const float* __restrict__ g, int B, int nq, int nmax, int h, int w, int H, int W, int s,
-                                                          float num_masks_override, float* __restrict__ dml) {
+                                                          const float* __restrict__ g, int B, int Bg, int gstride, int nq, int nmax, int h,
+                                                          int w, int H, int W, int s, PcGroups pg, float* __restrict__ dml) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int band = blockIdx.x, q = blockIdx.y, i = blockIdx.z, b = i % B, layer = i / B, tid = threadIdx.x, y0 = band * PC_BAND;
     const int rows = min(PC_BAND, h - y0);
@@ -583,7 +589,9 @@ __global__ __launch_bounds__(256) void pc_mask_bwd_kernel(const float* __restric
         smem[e] = src[y * s_y + x * s_x];
     }
     __syncthreads();
-    const float nm = pc_num_masks(n, B, nmax, num_masks_override);
+    const int grp = b / Bg;
+    const float nm = pc_num_masks(n, grp * Bg, Bg, nmax, pg.nm[grp]);
+    g += (long long)grp * gstride;
     const float gm = g[layer * 6 + 1] / (nm * (float)H * (float)W), gd = g[layer * 6 + 2] / nm;
     const float* st = mask_stats + ((long long)i * nmax + j) * 4;
     const float D1 = st[2] + st[3] + 1.f, N1 = 2.f * st[1] + 1.f;
@@ -622,7 +630,7 @@ __global__ __launch_bounds__(256) void pc_mask_bwd_kernel(const float* __restric
 }
 
 __global__ __launch_bounds__(256) void pc_cpix_bwd_kernel(const float* __restrict__ pixc, long long s_b, long long s_c, long long s_y, long long s_x,
-                                                          const float* __restrict__ gt, const float* __restrict__ g, int L, int B, int h, int w,
+                                                          const float* __restrict__ gt, const float* __restrict__ g, int L, int Bg, int h, int w,
                                                           int H, int W, int s, float* __restrict__ dpix) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int band = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, y0 = band * PC_BAND, plane = (PC_BAND + 2) * w;
@@ -632,7 +640,7 @@ __global__ __launch_bounds__(256) void pc_cpix_bwd_kernel(const float* __restric
         smem[e] = pixc[(long long)b * s_b + c * s_c + y * s_y + x * s_x];
     }
     __syncthreads();
-    const float scale = g[6 * L] / ((float)B * (float)H * (float)W), inv_s = (float)h / (float)H;
+    const float scale = g[(long long)(b / Bg) * (6 * L + 2) + 6 * L] / ((float)Bg * (float)H * (float)W), inv_s = (float)h / (float)H;
     for (int e = tid; e < rows * w; e += 256) {
         const int y = y0 + e / w, x = e % w;
         int Ya, Yb, Xa, Xb;
@@ -702,13 +710,15 @@ __global__ __launch_bounds__(128) void pc_small_bwd_kernel(const float* __restri
                                                            const float* __restrict__ tparams, const int* __restrict__ n,
                                                            const int* __restrict__ match_gt, const float* __restrict__ g,
                                                            const float* __restrict__ q_part, const float* __restrict__ q_stats, int L, int B,
-                                                           int nq, int nmax, float eos, float* __restrict__ dlog, float* __restrict__ dcen,
+                                                           int Bg, int nq, int nmax, float eos, float* __restrict__ dlog, float* __restrict__ dcen,
                                                            float* __restrict__ dpar) {
     const int i = blockIdx.x, b = i % B, layer = i / B, q = threadIdx.x;
     if (q >= nq) return;
+    const int grp = b / Bg;
+    g += (long long)grp * (6 * L + 2);
     int matched = 0;
     float wsum = 0.f;
-    for (int k = 0; k < B; ++k) { const int nk = pc_n(n, k, nmax); matched += nk; wsum += (float)nk + eos * (float)(nq - nk); }
+    for (int k = grp * Bg; k < (grp + 1) * Bg; ++k) { const int nk = pc_n(n, k, nmax); matched += nk; wsum += (float)nk + eos * (float)(nq - nk); }
     const int j = match_gt[(long long)i * nq + q];
     const bool on = j >= 0 && j < pc_n(n, b, nmax);
     const float* z = logits + ((long long)i * nq + q) * 2;
@@ -742,7 +752,7 @@ __global__ __launch_bounds__(128) void pc_small_bwd_kernel(const float* __restri
 #pragma unroll
                     for (int e = 0; e < 3; ++e) G[e] += q_part[(((long long)b * nmax + j) * PC_QCHUNKS + c) * 3 + e];
                 const float r2 = np_ * np_, gp = (G[0] * p[0] + G[1] * p[1] + G[2] * p[2]);
-                const float kq = g[6 * L + 1] / ((float)B * cnt);
+                const float kq = g[6 * L + 1] / ((float)Bg * cnt);
 #pragma unroll
                 for (int e = 0; e < 3; ++e) dp[e] += kq * (G[e] / r2 - 2.f * p[e] * gp / (r2 * r2));      // p' = p / |p|^2
             }
@@ -786,6 +796,14 @@ __global__ __launch_bounds__(256) void pc_corr_matrix_kernel(const int* __restri
 static int pc_scale(int h, int w, int H, int W) {
     if (h <= 0 || w <= 0 || H <= 0 || W <= 0 || H % h != 0 || W % w != 0 || H / h != W / w) return 0;
     return H / h;
+}
+// the groups of an argument block: G = 1 for groups 0 or 1; false if G does not divide B or exceeds PC_MAXG
+static bool pc_groups(const nopesac_plane_criterion* a, PcGroups& pg) {
+    const int G = a->groups <= 1 ? 1 : a->groups;
+    if (a->groups < 0 || G > PC_MAXG || a->B % G != 0) return false;
+    pg.G = G;
+    for (int g = 0; g < PC_MAXG; ++g) pg.nm[g] = g < G ? (a->num_masks_groups ? a->num_masks_groups[g] : a->num_masks) : 0.f;
+    return true;
 }
 static const char* pc_check_n(const int32_t* n_host, int B, int nq) {
     for (int b = 0; b < B; ++b)
@@ -866,6 +884,8 @@ extern "C" int nopesac_plane_losses(const nopesac_plane_criterion* a, void* stre
                       a->depth && a->k_inv_dot_xy1 && a->match_q && a->match_gt && (!a->pixel_centers || a->tgt_pixel_centers),
                   "plane_losses: null input");
     NPS_CHECK_ARG(a->losses && a->mask_stats && a->q_valid && a->q_stats, "plane_losses: null output");
+    PcGroups pg;
+    NPS_CHECK_ARG(pc_groups(a, pg), "plane_losses: groups=%d must be 0..%d and divide B=%d", a->groups, PC_MAXG, a->B);
     hipStream_t st = (hipStream_t)stream;
     const int LB = a->L * a->B, s = pc_scale(a->h, a->w, a->H, a->W), nb = pc_bands(a->h), HW = a->H * a->W;
     float* mask_part = a->ws;
@@ -883,8 +903,8 @@ extern "C" int nopesac_plane_losses(const nopesac_plane_criterion* a, void* stre
                                                             a->nq, a->nmax, HW, a->q_valid, q_part);
     pc_image_kernel<<<LB, 128, 0, st>>>(a->pred_logits, a->pred_centers, a->pred_params, a->tgt_centers, a->tgt_params, a->n, a->match_q,
                                         a->match_gt, a->B, a->nq, a->nmax, nb, HW, a->eos_coef, mask_part, a->mask_stats, img);
-    pc_final_kernel<<<1, 64, 0, st>>>(img, cpix_part, q_part, a->n, a->L, a->B, a->nmax, nb, HW, a->num_masks, a->pixel_centers ? 1 : 0, a->losses,
-                                      a->q_stats);
+    pc_final_kernel<<<pg.G, 64, 0, st>>>(img, cpix_part, q_part, a->n, a->L, a->B, a->B / pg.G, a->nmax, nb, HW, pg, a->pixel_centers ? 1 : 0,
+                                         a->losses, a->q_stats);
     NPS_LAUNCH_RET();
 }
 
@@ -896,22 +916,25 @@ extern "C" int nopesac_plane_losses_backward(const nopesac_plane_criterion* a, v
                   "plane_losses_backward: null input");
     NPS_CHECK_ARG(a->d_logits && a->d_mask_logits && a->d_centers && a->d_params && (!a->pixel_centers || a->d_pixel_centers),
                   "plane_losses_backward: null output");
+    PcGroups pg;
+    NPS_CHECK_ARG(pc_groups(a, pg), "plane_losses_backward: groups=%d must be 0..%d and divide B=%d", a->groups, PC_MAXG, a->B);
+    const int Bg = a->B / pg.G;
     hipStream_t st = (hipStream_t)stream;
     const int LB = a->L * a->B, s = pc_scale(a->h, a->w, a->H, a->W), nb = pc_bands(a->h), HW = a->H * a->W;
     float* q_part = a->ws + pc_ws_loss(a->L, a->B, a->nmax, a->h) - (int64_t)a->B * a->nmax * PC_QCHUNKS * 3;
     const size_t lds = (size_t)(PC_BAND + 2) * a->w * sizeof(float);
     NPS_CHECK_ARG(2 * lds <= 60 * 1024, "plane_losses_backward: w=%d too wide for the row band in LDS", a->w);
     pc_mask_bwd_kernel<<<dim3(nb, a->nq, LB), 256, lds, st>>>(a->pred_mask_logits, a->ml_stride_i, a->ml_stride_q, a->ml_stride_y, a->ml_stride_x,
-                                                              a->masks, a->n, a->match_gt, a->mask_stats, a->g_losses, a->B, a->nq, a->nmax, a->h,
-                                                              a->w, a->H, a->W, s, a->num_masks, a->d_mask_logits);
+                                                              a->masks, a->n, a->match_gt, a->mask_stats, a->g_losses, a->B, Bg, 6 * a->L + 2, a->nq,
+                                                              a->nmax, a->h, a->w, a->H, a->W, s, pg, a->d_mask_logits);
     if (a->pixel_centers)
         pc_cpix_bwd_kernel<<<dim3(nb, a->B), 256, 2 * lds, st>>>(a->pixel_centers, a->pc_stride_b, a->pc_stride_c, a->pc_stride_y, a->pc_stride_x,
-                                                                 a->tgt_pixel_centers, a->g_losses, a->L, a->B, a->h, a->w, a->H, a->W, s,
+                                                                 a->tgt_pixel_centers, a->g_losses, a->L, Bg, a->h, a->w, a->H, a->W, s,
                                                                  a->d_pixel_centers);
     pc_q_bwd_kernel<<<dim3(PC_QCHUNKS, a->nmax, a->B), 256, 0, st>>>(a->pred_params, a->masks, a->n, a->match_q, a->depth, a->k_inv_dot_xy1,
                                                                      a->q_valid, a->nq, a->nmax, HW, q_part);
     pc_small_bwd_kernel<<<LB, 128, 0, st>>>(a->pred_logits, a->pred_centers, a->pred_params, a->tgt_centers, a->tgt_params, a->n, a->match_gt,
-                                            a->g_losses, q_part, a->q_stats, a->L, a->B, a->nq, a->nmax, a->eos_coef, a->d_logits, a->d_centers,
+                                            a->g_losses, q_part, a->q_stats, a->L, a->B, Bg, a->nq, a->nmax, a->eos_coef, a->d_logits, a->d_centers,
                                             a->d_params);
     NPS_LAUNCH_RET();
 }

@@ -13,6 +13,12 @@
 // C, the channel stride and every pointer are multiples of 4 floats (checked by the entry points; the pyramid's 256 channels are).
 // Deterministic: no atomics; every cross-workgroup sum goes through per-block partials in the caller's workspace and is finished in a
 // fixed order.  Every load is unconditional from a clamped address and the value is selected afterwards; stores are guarded by the counts.
+//
+// View groups: the rows may be cut into G groups of ng = n / G consecutive rows (whole images: the two views of a 2B-image batch), each
+// with its own statistics, as G module calls on the groups would have them.  A group's rows are cut into Sg = ceil(ng / BT_RPS) blocks
+// from the group's first row - the partition an ungrouped call on those rows makes - and its partials are finished on their own in the
+// ungrouped order, so every per-group result has the bits of an ungrouped call on the group's sub-tensor; one launch per stage covers
+// all groups.  The upsampling and its adjoint never cross an image, so they never cross a group.
 #include "common.h"
 
 #include <cstdint>
@@ -67,11 +73,13 @@ __device__ __forceinline__ f32x4 src_value(const Src& s, long long r, int ch) {
 __device__ __forceinline__ f32x4 sum4(const f32x4 (*sh)[64], int cl) { return (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]); }
 
 // the block's geometry: lane cl of wave rl works on channels ch .. ch + 3 (clamped to chc for the loads) of rows r0 + rl, r0 + rl + 4, ...
-// (the wave index is made a scalar, so that the row's index arithmetic runs once per wave)
+// (the wave index is made a scalar, so that the row's index arithmetic runs once per wave); block y = grp * Sg + z is block z of group grp,
+// whose rows are [grp ng, (grp + 1) ng)
 #define BT_BLOCK_GEOMETRY()                                                                              \
     const int cl = threadIdx.x & 63, rl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);              \
     const int ch = (blockIdx.x * 64 + cl) * 4, chc = min(ch, C - 4);                                     \
-    const long long r0 = (long long)blockIdx.y * BT_RPS, r1 = min(n, r0 + BT_RPS)
+    const int grp = blockIdx.y / Sg;                                                                     \
+    const long long gbeg = grp * ng, r0 = gbeg + (long long)(blockIdx.y - grp * Sg) * BT_RPS, r1 = min(gbeg + ng, r0 + BT_RPS)
 
 // a wave's rows, BT_ROWS_IN_FLIGHT at a time: the loads of rows r, r + 4, ... are issued together, each from an address clamped to the
 // block's last row, and a row beyond it is left out of the sums afterwards (the condition is the same for the whole wave); the sums
@@ -82,8 +90,8 @@ constexpr int BT_ROWS_IN_FLIGHT = 4;
 #define BT_LIVE(r, u) (r + 4 * (u) < r1)
 
 // ---- statistics, first launch: per block of BT_RPS rows and per channel the block's mean and its sum of squares about that mean (two
-// passes over the block's rows; the second one hits the cache) -> part[block][2][C].
-__global__ __launch_bounds__(256) void bn_train_stats_kernel(Src s, long long n, int C, float* __restrict__ part) {
+// passes over the block's rows; the second one hits the cache) -> part[group][block][2][C].
+__global__ __launch_bounds__(256) void bn_train_stats_kernel(Src s, long long ng, int Sg, int C, float* __restrict__ part) {
     __shared__ f32x4 sh[4][64];
     BT_BLOCK_GEOMETRY();
     f32x4 a = 0.f;
@@ -123,7 +131,8 @@ __global__ __launch_bounds__(256) void bn_train_stats_kernel(Src s, long long n,
 // blocks are cut into BT_SEGMENTS runs of K = ceil(S / BT_SEGMENTS) consecutive blocks, a thread merges one run in block order, and the
 // runs are merged in run order (a chain of K + BT_SEGMENTS dependent steps instead of S: S = 2400 at the workload) -> mean, biased
 // variance, rstd = 1 / sqrt(var + eps) and, if given, the running statistics updated in place (the variance with n / (n - 1)).
-// Block: 16 channels x BT_SEGMENTS runs.
+// Block: 16 channels x BT_SEGMENTS runs.  Groups are finished one after the other by the same block, each from its own Sg partials of
+// its ng rows (above: S = Sg, n = ng); the running statistics stay in a register and take the groups' statistics in group order, as G module calls would leave them.
 constexpr int BT_SEGMENTS = 16;
 
 struct Moments {
@@ -140,31 +149,41 @@ __device__ __forceinline__ void chan_merge(Moments& a, long long nb, float mb, f
     a.n = nt;
 }
 
-__global__ __launch_bounds__(256) void bn_train_finish_kernel(const float* __restrict__ part, int S, long long n, int C, float eps, float mom,
-                                                              float* __restrict__ mean, float* __restrict__ var, float* __restrict__ rstd,
-                                                              float* __restrict__ run_mean, float* __restrict__ run_var) {
+__global__ __launch_bounds__(256) void bn_train_finish_kernel(const float* __restrict__ part, int G, int Sg, long long ng, int C, float eps,
+                                                              float mom, float* __restrict__ mean, float* __restrict__ var,
+                                                              float* __restrict__ rstd, float* __restrict__ run_mean,
+                                                              float* __restrict__ run_var) {
     __shared__ float smu[BT_SEGMENTS][16], sm2[BT_SEGMENTS][16];
     const int c = threadIdx.x & 15, seg = threadIdx.x >> 4;
     const int ch = blockIdx.x * 16 + c, chc = min(ch, C - 1);
-    const int K = (S + BT_SEGMENTS - 1) / BT_SEGMENTS;
-    const int z0 = min(seg * K, S), z1 = min(z0 + K, S);
-    Moments m{0, 0.f, 0.f};
-    for (int z = z0; z < z1; ++z)
-        chan_merge(m, min((long long)BT_RPS, n - (long long)z * BT_RPS), part[(long long)z * 2 * C + chc], part[(long long)z * 2 * C + C + chc]);
-    smu[seg][c] = m.mu;
-    sm2[seg][c] = m.m2;
-    __syncthreads();
-    if (seg != 0 || ch >= C) return;
-    for (int j = 1; j < BT_SEGMENTS; ++j) {                    // run j holds the rows [j K RPS, (j + 1) K RPS) that exist
-        const long long lo = min(n, (long long)j * K * BT_RPS), hi = min(n, (long long)(j + 1) * K * BT_RPS);
-        chan_merge(m, hi - lo, smu[j][c], sm2[j][c]);
+    const int K = (Sg + BT_SEGMENTS - 1) / BT_SEGMENTS;
+    const int z0 = min(seg * K, Sg), z1 = min(z0 + K, Sg);
+    const bool owner = seg == 0 && ch < C;
+    float rm = run_mean ? run_mean[chc] : 0.f, rv = run_var ? run_var[chc] : 0.f;
+    for (int grp = 0; grp < G; ++grp) {
+        const float* pg = part + (long long)grp * Sg * 2 * C;
+        Moments m{0, 0.f, 0.f};
+        for (int z = z0; z < z1; ++z)
+            chan_merge(m, min((long long)BT_RPS, ng - (long long)z * BT_RPS), pg[(long long)z * 2 * C + chc], pg[(long long)z * 2 * C + C + chc]);
+        smu[seg][c] = m.mu;
+        sm2[seg][c] = m.m2;
+        __syncthreads();
+        if (owner) {
+            for (int j = 1; j < BT_SEGMENTS; ++j) {            // run j holds the rows [j K RPS, (j + 1) K RPS) that exist
+                const long long lo = min(ng, (long long)j * K * BT_RPS), hi = min(ng, (long long)(j + 1) * K * BT_RPS);
+                chan_merge(m, hi - lo, smu[j][c], sm2[j][c]);
+            }
+            const float v = m.m2 / (float)ng;
+            mean[(long long)grp * C + ch] = m.mu;
+            var[(long long)grp * C + ch] = v;
+            rstd[(long long)grp * C + ch] = 1.f / sqrtf(v + eps);
+            rm = (1.f - mom) * rm + mom * m.mu;
+            rv = (1.f - mom) * rv + mom * (v * ((float)ng / (float)(ng - 1)));
+        }
+        __syncthreads();
     }
-    const float v = m.m2 / (float)n;
-    mean[ch] = m.mu;
-    var[ch] = v;
-    rstd[ch] = 1.f / sqrtf(v + eps);
-    if (run_mean) run_mean[ch] = (1.f - mom) * run_mean[ch] + mom * m.mu;
-    if (run_var) run_var[ch] = (1.f - mom) * run_var[ch] + mom * (v * ((float)n / (float)(n - 1)));
+    if (owner && run_mean) run_mean[ch] = rm;
+    if (owner && run_var) run_var[ch] = rv;
 }
 
 // z = gamma xhat + beta, xhat = (v - mean) rstd: ONE expression for the forward and for the gate the backward recomputes
@@ -180,7 +199,10 @@ __device__ __forceinline__ f32x4 bn_gate(f32x4 g, f32x4 z, int relu) {
 }
 
 // ---- y = act(z) (+ addend): one thread per channel quad
-__global__ __launch_bounds__(256) void bn_train_apply_kernel(Src s, long long n, int C, const float* __restrict__ gamma,
+// the statistics' offset of row r: its group's [C] block of mean / rstd (0 without groups: no division)
+__device__ __forceinline__ long long bn_group_offset(long long r, int G, long long ng, int C) { return G > 1 ? (r / ng) * C : 0; }
+
+__global__ __launch_bounds__(256) void bn_train_apply_kernel(Src s, long long n, int G, long long ng, int C, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, const float* __restrict__ mean,
                                                              const float* __restrict__ rstd, int relu, const float* __restrict__ addend,
                                                              float* __restrict__ y) {
@@ -188,7 +210,8 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(Src s, long long n,
     const long long total = n * CV;
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int ch = (int)(i % CV) * 4;
-        const f32x4 z = bn_z(bn_xhat(src_value(s, i / CV, ch), ld4(mean + ch), ld4(rstd + ch)), ld4(gamma + ch), ld4(beta + ch));
+        const long long go = bn_group_offset(i / CV, G, ng, C);
+        const f32x4 z = bn_z(bn_xhat(src_value(s, i / CV, ch), ld4(mean + go + ch), ld4(rstd + go + ch)), ld4(gamma + ch), ld4(beta + ch));
         f32x4 o = bn_gate(z, z, relu);
         if (addend) o += ld4(addend + i * 4);
         st4(y + i * 4, o);
@@ -196,13 +219,13 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(Src s, long long n,
 }
 
 // ---- backward, first launch: dz = g [z > 0]; per block of BT_RPS rows the partials of dgamma = sum dz xhat and dbeta = sum dz
-__global__ __launch_bounds__(256) void bn_train_bwd_reduce_kernel(const float* __restrict__ g, Src s, long long n, int C,
+__global__ __launch_bounds__(256) void bn_train_bwd_reduce_kernel(const float* __restrict__ g, Src s, long long ng, int Sg, int C,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                   const float* __restrict__ mean, const float* __restrict__ rstd, int relu,
                                                                   float* __restrict__ part) {
     __shared__ f32x4 sg[4][64], sb[4][64];
     BT_BLOCK_GEOMETRY();
-    const f32x4 ga = ld4(gamma + chc), be = ld4(beta + chc), mu = ld4(mean + chc), rs = ld4(rstd + chc);
+    const f32x4 ga = ld4(gamma + chc), be = ld4(beta + chc), mu = ld4(mean + (long long)grp * C + chc), rs = ld4(rstd + (long long)grp * C + chc);
     f32x4 ag = 0.f, ab = 0.f;
     BT_FOR_ROWS(r) {
         f32x4 v[BT_ROWS_IN_FLIGHT], gv[BT_ROWS_IN_FLIGHT];
@@ -232,22 +255,34 @@ __global__ __launch_bounds__(256) void bn_train_bwd_reduce_kernel(const float* _
 }
 
 // ---- per-channel partial sums [S][2][C] -> a[C], b[C] in a fixed order: BT_SEGMENTS runs of consecutive blocks summed in block order
-// by a thread each, then the runs in run order.  Block: 16 of the 2 C sums x BT_SEGMENTS runs.
-__global__ __launch_bounds__(256) void bn_train_sum_partials_kernel(const float* __restrict__ part, int S, int C, float* __restrict__ a,
-                                                                    float* __restrict__ b) {
+// by a thread each, then the runs in run order.  Block: 16 of the 2 C sums x BT_SEGMENTS runs.  Groups: each group's S partials are
+// summed on their own -> gsums[group][2][C] (the S2_g = sum dz xhat and S1_g = sum dz the second launch reads; null: G = 1, not written),
+// and a, b take the groups' sums in group order.
+__global__ __launch_bounds__(256) void bn_train_sum_partials_kernel(const float* __restrict__ part, int G, int Sg, int C, float* __restrict__ a,
+                                                                    float* __restrict__ b, float* __restrict__ gsums) {
     __shared__ float sh[BT_SEGMENTS][16];
     const int c = threadIdx.x & 15, seg = threadIdx.x >> 4;
     const int i = blockIdx.x * 16 + c, ic = min(i, 2 * C - 1);
-    const int K = (S + BT_SEGMENTS - 1) / BT_SEGMENTS;
-    const int z0 = min(seg * K, S), z1 = min(z0 + K, S);
-    float s = 0.f;
-    for (int z = z0; z < z1; ++z) s += part[(long long)z * 2 * C + ic];
-    sh[seg][c] = s;
-    __syncthreads();
-    if (seg != 0 || i >= 2 * C) return;
-    for (int j = 1; j < BT_SEGMENTS; ++j) s += sh[j][c];
-    if (i < C) a[i] = s;
-    else b[i - C] = s;
+    const int K = (Sg + BT_SEGMENTS - 1) / BT_SEGMENTS;
+    const int z0 = min(seg * K, Sg), z1 = min(z0 + K, Sg);
+    const bool owner = seg == 0 && i < 2 * C;
+    float tot = 0.f;
+    for (int grp = 0; grp < G; ++grp) {
+        const float* pg = part + (long long)grp * Sg * 2 * C;
+        float s = 0.f;
+        for (int z = z0; z < z1; ++z) s += pg[(long long)z * 2 * C + ic];
+        sh[seg][c] = s;
+        __syncthreads();
+        if (owner) {
+            for (int j = 1; j < BT_SEGMENTS; ++j) s += sh[j][c];
+            if (gsums) gsums[(long long)grp * 2 * C + i] = s;
+            tot = grp == 0 ? s : tot + s;
+        }
+        __syncthreads();
+    }
+    if (!owner) return;
+    if (i < C) a[i] = tot;
+    else b[i - C] = tot;
 }
 
 // the per-channel constants of the second backward launch
@@ -267,8 +302,9 @@ __device__ __forceinline__ f32x4 bn_dv(f32x4 gv, f32x4 v, const BnBwd& k, int re
     return (k.ga * k.rs) * ((dz - k.mb) - xh * k.mg);
 }
 
-// ---- backward, second launch, plain form: dv per element
-__global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(const float* __restrict__ g, Src s, long long n, int C,
+// ---- backward, second launch, plain form: dv per element.  dgamma / dbeta here are the sums of the element's group: [C] each without
+// groups, else gsums' [group][2][C] (the caller passes gsums, gsums + C), inv_n = 1 / ng.
+__global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(const float* __restrict__ g, Src s, long long n, int G, long long ng, int C,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                  const float* __restrict__ dgamma, const float* __restrict__ dbeta, int relu,
@@ -277,7 +313,8 @@ __global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(const float* __
     const long long total = n * CV;
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int ch = (int)(i % CV) * 4;
-        const BnBwd k = bn_bwd_consts(gamma, beta, mean, rstd, dgamma, dbeta, inv_n, ch);
+        const long long go = bn_group_offset(i / CV, G, ng, C);
+        const BnBwd k = bn_bwd_consts(gamma, beta, mean + go, rstd + go, dgamma + 2 * go, dbeta + 2 * go, inv_n, ch);
         st4(dv + i * 4, bn_dv(ld4(g + i * 4), ld4(s.p + (i / CV) * s.cs + ch), k, relu));
     }
 }
@@ -335,7 +372,7 @@ __global__ __launch_bounds__(256) void upsample2x_bilinear_bwd_kernel(const floa
 
 // ---- backward, second launch, upsampled form: dt = up2^T(dv) with dv evaluated inside the gather and never written.  One thread per
 // channel quad of a pixel of t: its 3 x 3 neighbourhood of t (clamped) gives up2(t) at the 4 x 4 outputs, g is read at those 16 pixels.
-__global__ __launch_bounds__(256) void bn_train_bwd_apply_up_kernel(const float* __restrict__ g, Src s, int B, int C,
+__global__ __launch_bounds__(256) void bn_train_bwd_apply_up_kernel(const float* __restrict__ g, Src s, int B, int G, int Bg, int C,
                                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                     const float* __restrict__ dgamma, const float* __restrict__ dbeta, int relu,
@@ -355,7 +392,8 @@ __global__ __launch_bounds__(256) void bn_train_bwd_apply_up_kernel(const float*
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int c = 0; c < 3; ++c) t[a][c] = ld4(s.p + ((b * H + ys[a]) * W + xs[c]) * s.cs + ch);
-        const BnBwd k = bn_bwd_consts(gamma, beta, mean, rstd, dgamma, dbeta, inv_n, ch);
+        const long long go = bn_group_offset(b, G, Bg, C);          // the image's group: the gather stays inside the image
+        const BnBwd k = bn_bwd_consts(gamma, beta, mean + go, rstd + go, dgamma + 2 * go, dbeta + 2 * go, inv_n, ch);
         const long long gbase = b * 4 * H * W;
         f32x4 acc = 0.f;
 #pragma unroll
@@ -408,61 +446,141 @@ static long long bn_train_rows(const char* who, const void* src, int up, int B, 
     return n;
 }
 
+// the groups of a call: G = 1 for groups 0 or 1; else G must divide the B images (rows of the matrix form) -> rows per group, or 0 with
+// the error set
+static long long bn_train_group_rows(const char* who, long long n, int B, int groups, int& G) {
+    G = groups <= 1 ? 1 : groups;
+    if (groups < 0 || G > NPS_BN_TRAIN_MAX_GROUPS || B % G != 0) {
+        nps::set_error("%s: groups=%d must be 0..%d and divide B=%d", who, groups, NPS_BN_TRAIN_MAX_GROUPS, B);
+        return 0;
+    }
+    const long long ng = n / G;
+    if ((long long)G * ((ng + BT_RPS - 1) / BT_RPS) >= 65536) {
+        nps::set_error("%s: %d groups of %lld rows are more blocks than a launch indexes", who, G, ng);
+        return 0;
+    }
+    return ng;
+}
+
 extern "C" int64_t nopesac_bn_train_workspace_floats(int64_t n, int C) { return n > 0 && C > 0 ? NPS_BN_TRAIN_WORKSPACE_FLOATS(n, C) : 0; }
+
+extern "C" int nopesac_bn_train_groups_workspace_floats(int groups, int64_t n, int C, int64_t* floats) {
+    NPS_CHECK_ARG(floats, "bn_train_groups_workspace_floats: null pointer");
+    *floats = 0;
+    const int G = groups <= 1 ? 1 : groups;
+    NPS_CHECK_ARG(groups >= 0 && G <= NPS_BN_TRAIN_MAX_GROUPS && n > 0 && C > 0 && n % G == 0,
+                  "bn_train_groups_workspace_floats: bad arguments groups=%d n=%lld C=%d", groups, (long long)n, C);
+    *floats = NPS_BN_TRAIN_GROUPS_WORKSPACE_FLOATS(G, n, C);
+    return 0;
+}
+
+static int bn_train_stats_launch(const char* who, const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, int groups, float eps,
+                                 float momentum, float* mean, float* var, float* rstd, float* running_mean, float* running_var, float* ws,
+                                 int64_t ws_floats, void* stream) {
+    const long long n = bn_train_rows(who, src, up, B, H, W, C, src_cstride);
+    if (!n) return NPS_E_ARG;
+    int G;
+    const long long ng = bn_train_group_rows(who, n, B, groups, G);
+    if (!ng) return NPS_E_ARG;
+    NPS_CHECK_ARG(mean && var && rstd && ws, "%s: null pointer", who);
+    NPS_CHECK_ARG(quad_aligned({src, ws}), "%s: src and ws must be 16-byte aligned", who);
+    NPS_CHECK_ARG(ng >= 2, "%s: batch statistics need more than one value per channel (n = %lld)", who, ng);
+    NPS_CHECK_ARG(eps > 0.f && momentum >= 0.f && momentum <= 1.f, "%s: eps / momentum out of range", who);
+    NPS_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "%s: running_mean and running_var come together", who);
+    NPS_CHECK_ARG(ws_floats >= NPS_BN_TRAIN_GROUPS_WORKSPACE_FLOATS(G, n, C), "%s: workspace too small", who);
+    const int Sg = (int)((ng + BT_RPS - 1) / BT_RPS);
+    hipStream_t st = (hipStream_t)stream;
+    const Src s{src, up, H, W, (long long)src_cstride};
+    bn_train_stats_kernel<<<dim3((C + 255) / 256, G * Sg), 256, 0, st>>>(s, ng, Sg, C, ws);
+    bn_train_finish_kernel<<<(C + 15) / 16, 256, 0, st>>>(ws, G, Sg, ng, C, eps, momentum, mean, var, rstd, running_mean, running_var);
+    NPS_LAUNCH_RET();
+}
+
+static int bn_train_apply_launch(const char* who, const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, int groups,
+                                 const float* gamma, const float* beta, const float* mean, const float* rstd, int act, const float* addend,
+                                 float* y, void* stream) {
+    const long long n = bn_train_rows(who, src, up, B, H, W, C, src_cstride);
+    if (!n) return NPS_E_ARG;
+    int G;
+    const long long ng = bn_train_group_rows(who, n, B, groups, G);
+    if (!ng) return NPS_E_ARG;
+    NPS_CHECK_ARG(gamma && beta && mean && rstd && y, "%s: null pointer", who);
+    NPS_CHECK_ARG(quad_aligned({src, gamma, beta, mean, rstd, addend, y}), "%s: every pointer must be 16-byte aligned", who);
+    NPS_CHECK_ARG(act == NPS_ACT_NONE || act == NPS_ACT_RELU, "%s: bad act %d", who, act);
+    const Src s{src, up, H, W, (long long)src_cstride};
+    bn_train_apply_kernel<<<grid_for(n * (C / 4)), 256, 0, (hipStream_t)stream>>>(s, n, G, ng, C, gamma, beta, mean, rstd, act == NPS_ACT_RELU, addend, y);
+    NPS_LAUNCH_RET();
+}
+
+static int bn_train_backward_launch(const char* who, const float* dy, const float* src, int up, int B, int H, int W, int C, int64_t src_cstride,
+                                    int groups, const float* gamma, const float* beta, const float* mean, const float* rstd, int act,
+                                    int batch_stats, float* dsrc, float* dgamma, float* dbeta, float* group_sums, float* ws, int64_t ws_floats,
+                                    void* stream) {
+    const long long n = bn_train_rows(who, src, up, B, H, W, C, src_cstride);
+    if (!n) return NPS_E_ARG;
+    int G;
+    const long long ng = bn_train_group_rows(who, n, B, groups, G);
+    if (!ng) return NPS_E_ARG;
+    NPS_CHECK_ARG(dy && gamma && beta && mean && rstd && dsrc && dgamma && dbeta && ws && (G == 1 || group_sums), "%s: null pointer", who);
+    NPS_CHECK_ARG(quad_aligned({dy, src, gamma, beta, mean, rstd, dsrc, dgamma, dbeta, group_sums, ws}), "%s: every pointer must be 16-byte aligned", who);
+    NPS_CHECK_ARG(act == NPS_ACT_NONE || act == NPS_ACT_RELU, "%s: bad act %d", who, act);
+    NPS_CHECK_ARG(ws_floats >= NPS_BN_TRAIN_GROUPS_WORKSPACE_FLOATS(G, n, C), "%s: workspace too small", who);
+    const int Sg = (int)((ng + BT_RPS - 1) / BT_RPS), relu = act == NPS_ACT_RELU;
+    const float inv_n = batch_stats ? 1.f / (float)ng : 0.f;     // stored statistics: mean and rstd are constants, dv = gamma rstd dz
+    hipStream_t st = (hipStream_t)stream;
+    const Src s{src, up, H, W, (long long)src_cstride};
+    float* gsums = G > 1 ? group_sums : nullptr;                 // without groups the second launch reads dgamma / dbeta themselves
+    const float* k1 = gsums ? gsums : dgamma;
+    const float* k2 = gsums ? gsums + C : dbeta;
+    bn_train_bwd_reduce_kernel<<<dim3((C + 255) / 256, G * Sg), 256, 0, st>>>(dy, s, ng, Sg, C, gamma, beta, mean, rstd, relu, ws);
+    bn_train_sum_partials_kernel<<<(2 * C + 15) / 16, 256, 0, st>>>(ws, G, Sg, C, dgamma, dbeta, gsums);
+    if (up)
+        bn_train_bwd_apply_up_kernel<<<grid_for((long long)B * H * W * (C / 4)), 256, 0, st>>>(dy, s, B, G, B / G, C, gamma, beta, mean, rstd, k1, k2, relu, inv_n, dsrc);
+    else
+        bn_train_bwd_apply_kernel<<<grid_for(n * (C / 4)), 256, 0, st>>>(dy, s, n, G, ng, C, gamma, beta, mean, rstd, k1, k2, relu, inv_n, dsrc);
+    NPS_LAUNCH_RET();
+}
 
 extern "C" int nopesac_bn_train_stats_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, float eps, float momentum,
                                           float* mean, float* var, float* rstd, float* running_mean, float* running_var, float* ws,
                                           int64_t ws_floats, void* stream) {
-    const long long n = bn_train_rows("bn_train_stats", src, up, B, H, W, C, src_cstride);
-    if (!n) return NPS_E_ARG;
-    NPS_CHECK_ARG(mean && var && rstd && ws, "bn_train_stats: null pointer");
-    NPS_CHECK_ARG(quad_aligned({src, ws}), "bn_train_stats: src and ws must be 16-byte aligned");
-    NPS_CHECK_ARG(n >= 2, "bn_train_stats: batch statistics need more than one value per channel (n = %lld)", n);
-    NPS_CHECK_ARG(eps > 0.f && momentum >= 0.f && momentum <= 1.f, "bn_train_stats: eps / momentum out of range");
-    NPS_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "bn_train_stats: running_mean and running_var come together");
-    NPS_CHECK_ARG(ws_floats >= nopesac_bn_train_workspace_floats(n, C), "bn_train_stats: workspace too small");
-    const int S = (int)((n + BT_RPS - 1) / BT_RPS);
-    hipStream_t st = (hipStream_t)stream;
-    const Src s{src, up, H, W, (long long)src_cstride};
-    bn_train_stats_kernel<<<dim3((C + 255) / 256, S), 256, 0, st>>>(s, n, C, ws);
-    bn_train_finish_kernel<<<(C + 15) / 16, 256, 0, st>>>(ws, S, n, C, eps, momentum, mean, var, rstd, running_mean, running_var);
-    NPS_LAUNCH_RET();
+    return bn_train_stats_launch("bn_train_stats", src, up, B, H, W, C, src_cstride, 1, eps, momentum, mean, var, rstd, running_mean, running_var, ws,
+                                 ws_floats, stream);
 }
 
 extern "C" int nopesac_bn_train_apply_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, const float* gamma,
                                           const float* beta, const float* mean, const float* rstd, int act, const float* addend, float* y,
                                           void* stream) {
-    const long long n = bn_train_rows("bn_train_apply", src, up, B, H, W, C, src_cstride);
-    if (!n) return NPS_E_ARG;
-    NPS_CHECK_ARG(gamma && beta && mean && rstd && y, "bn_train_apply: null pointer");
-    NPS_CHECK_ARG(quad_aligned({src, gamma, beta, mean, rstd, addend, y}), "bn_train_apply: every pointer must be 16-byte aligned");
-    NPS_CHECK_ARG(act == NPS_ACT_NONE || act == NPS_ACT_RELU, "bn_train_apply: bad act %d", act);
-    const Src s{src, up, H, W, (long long)src_cstride};
-    bn_train_apply_kernel<<<grid_for(n * (C / 4)), 256, 0, (hipStream_t)stream>>>(s, n, C, gamma, beta, mean, rstd, act == NPS_ACT_RELU, addend, y);
-    NPS_LAUNCH_RET();
+    return bn_train_apply_launch("bn_train_apply", src, up, B, H, W, C, src_cstride, 1, gamma, beta, mean, rstd, act, addend, y, stream);
 }
 
 extern "C" int nopesac_bn_train_backward_f32(const float* dy, const float* src, int up, int B, int H, int W, int C, int64_t src_cstride,
                                              const float* gamma, const float* beta, const float* mean, const float* rstd, int act,
                                              int batch_stats, float* dsrc, float* dgamma, float* dbeta, float* ws, int64_t ws_floats,
                                              void* stream) {
-    const long long n = bn_train_rows("bn_train_backward", src, up, B, H, W, C, src_cstride);
-    if (!n) return NPS_E_ARG;
-    NPS_CHECK_ARG(dy && gamma && beta && mean && rstd && dsrc && dgamma && dbeta && ws, "bn_train_backward: null pointer");
-    NPS_CHECK_ARG(quad_aligned({dy, src, gamma, beta, mean, rstd, dsrc, dgamma, dbeta, ws}), "bn_train_backward: every pointer must be 16-byte aligned");
-    NPS_CHECK_ARG(act == NPS_ACT_NONE || act == NPS_ACT_RELU, "bn_train_backward: bad act %d", act);
-    NPS_CHECK_ARG(ws_floats >= nopesac_bn_train_workspace_floats(n, C), "bn_train_backward: workspace too small");
-    const int S = (int)((n + BT_RPS - 1) / BT_RPS), relu = act == NPS_ACT_RELU;
-    const float inv_n = batch_stats ? 1.f / (float)n : 0.f;      // stored statistics: mean and rstd are constants, dv = gamma rstd dz
-    hipStream_t st = (hipStream_t)stream;
-    const Src s{src, up, H, W, (long long)src_cstride};
-    bn_train_bwd_reduce_kernel<<<dim3((C + 255) / 256, S), 256, 0, st>>>(dy, s, n, C, gamma, beta, mean, rstd, relu, ws);
-    bn_train_sum_partials_kernel<<<(2 * C + 15) / 16, 256, 0, st>>>(ws, S, C, dgamma, dbeta);
-    if (up)
-        bn_train_bwd_apply_up_kernel<<<grid_for((long long)B * H * W * (C / 4)), 256, 0, st>>>(dy, s, B, C, gamma, beta, mean, rstd, dgamma, dbeta, relu, inv_n, dsrc);
-    else
-        bn_train_bwd_apply_kernel<<<grid_for(n * (C / 4)), 256, 0, st>>>(dy, s, n, C, gamma, beta, mean, rstd, dgamma, dbeta, relu, inv_n, dsrc);
-    NPS_LAUNCH_RET();
+    return bn_train_backward_launch("bn_train_backward", dy, src, up, B, H, W, C, src_cstride, 1, gamma, beta, mean, rstd, act, batch_stats, dsrc,
+                                    dgamma, dbeta, nullptr, ws, ws_floats, stream);
+}
+
+extern "C" int nopesac_bn_train_groups_stats_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, int groups, float eps,
+                                                 float momentum, float* mean, float* var, float* rstd, float* running_mean, float* running_var,
+                                                 float* ws, int64_t ws_floats, void* stream) {
+    return bn_train_stats_launch("bn_train_groups_stats", src, up, B, H, W, C, src_cstride, groups, eps, momentum, mean, var, rstd, running_mean,
+                                 running_var, ws, ws_floats, stream);
+}
+
+extern "C" int nopesac_bn_train_groups_apply_f32(const float* src, int up, int B, int H, int W, int C, int64_t src_cstride, int groups,
+                                                 const float* gamma, const float* beta, const float* mean, const float* rstd, int act,
+                                                 const float* addend, float* y, void* stream) {
+    return bn_train_apply_launch("bn_train_groups_apply", src, up, B, H, W, C, src_cstride, groups, gamma, beta, mean, rstd, act, addend, y, stream);
+}
+
+extern "C" int nopesac_bn_train_groups_backward_f32(const float* dy, const float* src, int up, int B, int H, int W, int C, int64_t src_cstride,
+                                                    int groups, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                                    int act, int batch_stats, float* dsrc, float* dgamma, float* dbeta, float* group_sums,
+                                                    float* ws, int64_t ws_floats, void* stream) {
+    return bn_train_backward_launch("bn_train_groups_backward", dy, src, up, B, H, W, C, src_cstride, groups, gamma, beta, mean, rstd, act,
+                                    batch_stats, dsrc, dgamma, dbeta, group_sums, ws, ws_floats, stream);
 }
 
 extern "C" int nopesac_upsample2x_bilinear_backward_f32(const float* du, float* dx, int B, int H, int W, int C, void* stream) {

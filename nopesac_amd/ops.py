@@ -1941,52 +1941,94 @@ def bn_train_workspace_floats(n: int, C: int) -> int:
     return int(_C.nopesac_bn_train_workspace_floats(n, C))
 
 
-def bn_train_stats(src: torch.Tensor, *, up: bool = False, eps: float = 1e-5, momentum: float = 0.1, running_mean=None, running_var=None):
+def bn_train_groups_workspace_floats(groups: int, n: int, C: int) -> int:
+    """The library's nopesac_bn_train_groups_workspace_floats, what the view-group launchers check against (n = all rows)."""
+    out = ctypes.c_int64(0)
+    _C.nopesac_bn_train_groups_workspace_floats(int(groups), int(n), int(C), ctypes.addressof(out))
+    return int(out.value)
+
+
+def _bn_train_groups(groups, B: int, what: str) -> int:
+    """The view groups of a training-BatchNorm call: G groups of B / G consecutive images (rows of the matrix form)."""
+    _require(isinstance(groups, int) and not isinstance(groups, bool) and 1 <= groups <= _H.NPS_BN_TRAIN_MAX_GROUPS and B % groups == 0,
+             "%s: 1 <= groups <= %d dividing the %d images (rows) expected, got %r" % (what, _H.NPS_BN_TRAIN_MAX_GROUPS, B, groups))
+    return groups
+
+
+def bn_train_stats(src: torch.Tensor, *, up: bool = False, eps: float = 1e-5, momentum: float = 0.1, running_mean=None, running_var=None,
+                   groups: int = 1):
     """Batch statistics of a training-mode BatchNorm over v = src ([rows, C] or NHWC) or, with `up`, v = upsample2x_bilinear(src) evaluated
     on the fly -> (mean, biased var, rstd = 1 / sqrt(var + eps)), [C] each.  running_mean / running_var (both or neither) are updated in
-    place on the device as torch.nn.BatchNorm2d does (momentum, unbiased variance); no host sync.  One value per channel is refused."""
+    place on the device as torch.nn.BatchNorm2d does (momentum, unbiased variance); no host sync.  One value per channel is refused.
+    groups = G > 1: the images (rows of the matrix form) are G view groups of consecutive ones with their own statistics, [G, C] each,
+    every group's with the bits of a call on its sub-tensor; the running buffers take them in group order, as G module calls would."""
     B, H, W, C, cs, n, _ = _bn_train_src(src, up)
-    _require(n >= 2, "bn_train_stats: more than one value per channel expected")
+    G = _bn_train_groups(groups, B, "bn_train_stats")
+    _require(n // G >= 2, "bn_train_stats: more than one value per channel expected")
     _require((running_mean is None) == (running_var is None), "running_mean and running_var come together")
     if running_mean is not None:
         _bn_vecs(C, running_mean, running_var)
-    mean, var, rstd = (torch.empty(C, device=src.device, dtype=torch.float32) for _ in range(3))
-    ws = scratch(src.device, 4 * bn_train_workspace_floats(n, C))
-    _C.nopesac_bn_train_stats_f32(_p(src), int(up), B, H, W, C, cs, float(eps), float(momentum), _p(mean), _p(var), _p(rstd), _p(running_mean),
-                                  _p(running_var), _p(ws), ws.numel(), _stream())
+    mean, var, rstd = (torch.empty(C if G == 1 else (G, C), device=src.device, dtype=torch.float32) for _ in range(3))
+    if G == 1:
+        ws = scratch(src.device, 4 * bn_train_workspace_floats(n, C))
+        _C.nopesac_bn_train_stats_f32(_p(src), int(up), B, H, W, C, cs, float(eps), float(momentum), _p(mean), _p(var), _p(rstd), _p(running_mean),
+                                      _p(running_var), _p(ws), ws.numel(), _stream())
+    else:
+        ws = scratch(src.device, 4 * bn_train_groups_workspace_floats(G, n, C))
+        _C.nopesac_bn_train_groups_stats_f32(_p(src), int(up), B, H, W, C, cs, G, float(eps), float(momentum), _p(mean), _p(var), _p(rstd),
+                                             _p(running_mean), _p(running_var), _p(ws), ws.numel(), _stream())
     return mean, var, rstd
 
 
-def bn_train_apply(src: torch.Tensor, gamma, beta, mean, rstd, act=ACT_RELU, addend: Optional[torch.Tensor] = None, *, up: bool = False) -> torch.Tensor:
-    """act(gamma (v - mean) rstd + beta) (+ addend, after the activation) for v as in bn_train_stats; act: NONE or RELU.  Dense output."""
+def bn_train_apply(src: torch.Tensor, gamma, beta, mean, rstd, act=ACT_RELU, addend: Optional[torch.Tensor] = None, *, up: bool = False,
+                   groups: int = 1) -> torch.Tensor:
+    """act(gamma (v - mean) rstd + beta) (+ addend, after the activation) for v as in bn_train_stats; act: NONE or RELU.  Dense output.
+    groups = G > 1: mean / rstd are [G, C], each row takes its view group's."""
     B, H, W, C, cs, n, shape = _bn_train_src(src, up)
+    G = _bn_train_groups(groups, B, "bn_train_apply")
     _require(act in (ACT_NONE, ACT_RELU), act)
-    _bn_vecs(C, gamma, beta, mean, rstd)
+    _bn_vecs(C, gamma, beta)
+    _bn_vecs(G * C, mean, rstd)
     if addend is not None:
         _chk(addend, torch.float32)
         _require(tuple(addend.shape) == shape, (tuple(addend.shape), shape))
     y = torch.empty(shape, device=src.device, dtype=torch.float32)
-    _C.nopesac_bn_train_apply_f32(_p(src), int(up), B, H, W, C, cs, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), _p(addend), _p(y), _stream())
+    if G == 1:
+        _C.nopesac_bn_train_apply_f32(_p(src), int(up), B, H, W, C, cs, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), _p(addend), _p(y), _stream())
+    else:
+        _C.nopesac_bn_train_groups_apply_f32(_p(src), int(up), B, H, W, C, cs, G, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), _p(addend),
+                                             _p(y), _stream())
     return y
 
 
-def bn_train_backward(dy: torch.Tensor, src: torch.Tensor, gamma, beta, mean, rstd, act=ACT_RELU, *, up: bool = False, batch_stats: bool = True):
+def bn_train_backward(dy: torch.Tensor, src: torch.Tensor, gamma, beta, mean, rstd, act=ACT_RELU, *, up: bool = False, batch_stats: bool = True,
+                      groups: int = 1, group_sums: bool = False):
     """Backward of bn_train_apply through the batch statistics, from the same input (v is recomputed) -> (dsrc, dgamma, dbeta): plain form
     dsrc = dv, dense in v's shape; with `up` dsrc = the gradient at src [B, H, W, C], the bilinear adjoint of dv gathered in the same launch
     (dv is never written).  batch_stats=False: mean / rstd are stored statistics, constants of the backward (dv = gamma rstd dz).  The
-    addend's gradient is dy itself."""
+    addend's gradient is dy itself.  groups = G > 1: mean / rstd [G, C]; every view group's dsrc comes from its own sums S2_g = sum dz xhat,
+    S1_g = sum dz, and dgamma / dbeta add them in group order; group_sums=True appends them, [G, 2, C] = (S2_g, S1_g)."""
     B, H, W, C, cs, n, shape = _bn_train_src(src, up)
+    G = _bn_train_groups(groups, B, "bn_train_backward")
     _require(act in (ACT_NONE, ACT_RELU), act)
     _chk(dy, torch.float32)
     _require(tuple(dy.shape) == shape, (tuple(dy.shape), shape))
-    _bn_vecs(C, gamma, beta, mean, rstd)
+    _bn_vecs(C, gamma, beta)
+    _bn_vecs(G * C, mean, rstd)
     dsrc = torch.empty(tuple(src.shape) if up else shape, device=src.device, dtype=torch.float32)
     dg = torch.empty(C, device=src.device, dtype=torch.float32)
     db = torch.empty(C, device=src.device, dtype=torch.float32)
-    ws = scratch(src.device, 4 * bn_train_workspace_floats(n, C))
-    _C.nopesac_bn_train_backward_f32(_p(dy), _p(src), int(up), B, H, W, C, cs, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), int(bool(batch_stats)), _p(dsrc), _p(dg),
-                                     _p(db), _p(ws), ws.numel(), _stream())
-    return dsrc, dg, db
+    if G == 1:
+        ws = scratch(src.device, 4 * bn_train_workspace_floats(n, C))
+        _C.nopesac_bn_train_backward_f32(_p(dy), _p(src), int(up), B, H, W, C, cs, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act), int(bool(batch_stats)), _p(dsrc), _p(dg),
+                                         _p(db), _p(ws), ws.numel(), _stream())
+        sums = torch.stack([dg, db])[None] if group_sums else None
+    else:
+        sums = torch.empty(G, 2, C, device=src.device, dtype=torch.float32)
+        ws = scratch(src.device, 4 * bn_train_groups_workspace_floats(G, n, C))
+        _C.nopesac_bn_train_groups_backward_f32(_p(dy), _p(src), int(up), B, H, W, C, cs, G, _p(gamma), _p(beta), _p(mean), _p(rstd), int(act),
+                                                int(bool(batch_stats)), _p(dsrc), _p(dg), _p(db), _p(sums), _p(ws), ws.numel(), _stream())
+    return (dsrc, dg, db, sums) if group_sums else (dsrc, dg, db)
 
 
 def _bn_grouped_src(c: torch.Tensor, groups: int):
@@ -2523,6 +2565,7 @@ def opt_step(layout: OptLayout, sources: torch.Tensor, G: torch.Tensor, M1: Opti
 
 # ---- set criterion of the plane head (csrc/plane_criterion.hip) --------------------------------------------------------------------------
 PLANE_MAX_QUERIES, PLANE_MAX_TARGETS, PLANE_MAX_LAYERS = _lib.H.NPS_PLANE_MAX_QUERIES, _lib.H.NPS_PLANE_MAX_TARGETS, _lib.H.NPS_PLANE_MAX_LAYERS
+PLANE_MAX_GROUPS = _lib.H.NPS_PLANE_MAX_GROUPS
 PLANE_COST_NAMES = ("cost_class", "cost_mask", "cost_dice", "cost_center", "cost_param", "cost_offset", "cost_angle")
 
 
@@ -2542,9 +2585,10 @@ class PlaneCriterionCall:
     """One argument block (nopesac_plane_criterion) for the cost, loss and gradient entries, filled from tensors that it keeps alive.
     preds: pred_logits [L*B, nq, 2], pred_mask_logits [L*B, nq, h, w] in ANY dense stride order, pred_centers [L*B, nq, 2], pred_params
     [L*B, nq, 3], pixel_centers [B, 2, h, w] (any dense stride order) or None; targets: masks, n, n_host, plane_centers, plane_params,
-    pixel_centers, depth, k_inv_dot_xy1."""
+    pixel_centers, depth, k_inv_dot_xy1.  groups = G view groups of B / G consecutive batch elements each (the header's `groups`): the
+    losses become [G, 6 L + 2], num_masks a float for every group or a sequence of G floats; groups=1 is the ungrouped call."""
 
-    def __init__(self, L: int, preds: dict, targets: dict, weights: dict, num_masks: float = 0.0):
+    def __init__(self, L: int, preds: dict, targets: dict, weights: dict, num_masks=0.0, groups: int = 1):
         lg, ml, ce, pa, px = (preds.get(k) for k in ("pred_logits", "pred_mask_logits", "pred_centers", "pred_params", "pixel_centers"))
         for t in (lg, ce, pa, targets["plane_centers"], targets["plane_params"], targets["pixel_centers"], targets["depth"], targets["k_inv_dot_xy1"]):
             _chk(t, torch.float32)
@@ -2556,9 +2600,16 @@ class PlaneCriterionCall:
         _require(LB == L * B and ml.dtype == torch.float32 and lg.shape == (LB, nq, 2) and ce.shape == (LB, nq, 2) and pa.shape == (LB, nq, 3),
                  (ml.shape, lg.shape, ce.shape, pa.shape))
         _require(px is None or (px.shape == (B, 2, h, w) and px.dtype == torch.float32), "pixel_centers")
+        G = int(groups)
+        _require(1 <= G <= PLANE_MAX_GROUPS and B % G == 0, "groups=%d: 1..%d groups that divide B=%d" % (G, PLANE_MAX_GROUPS, B))
+        per_group = isinstance(num_masks, (list, tuple)) or getattr(num_masks, "ndim", 0) == 1          # else one value (or None / 0: the default)
+        if per_group:
+            num_masks = [float(v) for v in num_masks]
+            _require(len(num_masks) == G, "num_masks: %d values for %d groups" % (len(num_masks), G))
         dev = ml.device
         self.keep = (preds, targets)
         self.dims = (L, B, nq, nmax, h, w, H, W)
+        self.groups = G
         self.ml, self.px = ml, px
         f32 = dict(device=dev, dtype=torch.float32)
         ws_floats = int(_C.nopesac_plane_criterion_workspace_floats(L, B, nq, nmax, h, w))
@@ -2566,7 +2617,7 @@ class PlaneCriterionCall:
         self.cost = torch.empty(LB, nq, nmax, **f32)
         self.match_q = torch.empty(LB, nmax, device=dev, dtype=torch.int32)
         self.match_gt = torch.empty(LB, nq, device=dev, dtype=torch.int32)
-        self.losses = torch.empty(6 * L + 2, **f32)
+        self.losses = torch.empty(6 * L + 2, **f32) if G == 1 else torch.empty(G, 6 * L + 2, **f32)
         self.mask_stats = torch.empty(LB, nmax, 4, **f32)
         self.q_valid = torch.empty(B, H, W, device=dev, dtype=torch.uint8)
         self.q_stats = torch.empty(B, 2, **f32)
@@ -2581,7 +2632,10 @@ class PlaneCriterionCall:
         a.L, a.B, a.nq, a.nmax, a.h, a.w, a.H, a.W, a.num_classes = L, B, nq, nmax, h, w, H, W, lg.shape[-1]
         for k in PLANE_COST_NAMES:
             setattr(a, k, float(weights[k]))
-        a.eos_coef, a.num_masks = float(weights["eos_coef"]), float(num_masks or 0.0)
+        a.eos_coef, a.num_masks, a.groups = float(weights["eos_coef"]), (0.0 if per_group else float(num_masks or 0.0)), G
+        if per_group:
+            self.num_masks_groups = (ctypes.c_float * G)(*num_masks)           # read on the host at every launch: kept alive here
+            a.num_masks_groups = ctypes.addressof(self.num_masks_groups)
         a.cost, a.match_q, a.match_gt = _p(self.cost), _p(self.match_q), _p(self.match_gt)
         a.losses, a.mask_stats, a.q_valid, a.q_stats = _p(self.losses), _p(self.mask_stats), _p(self.q_valid), _p(self.q_stats)
         a.ws, a.ws_floats = _p(self.ws), ws_floats
@@ -2601,7 +2655,7 @@ def plane_assign(call: PlaneCriterionCall):
 
 
 def plane_losses(call: PlaneCriterionCall) -> torch.Tensor:
-    """The unweighted losses [6 L + 2] for call.match_q / call.match_gt (criterion.py)."""
+    """The unweighted losses [6 L + 2] ([G, 6 L + 2] of a grouped call) for call.match_q / call.match_gt (criterion.py)."""
     _C.nopesac_plane_losses(ctypes.byref(call.args), _stream())
     return call.losses
 
@@ -2611,7 +2665,7 @@ def plane_losses_backward(call: PlaneCriterionCall, g_losses: torch.Tensor):
     gradients in the stride order of the inputs."""
     _chk(g_losses, torch.float32)
     L, B, nq = call.dims[:3]
-    _require(g_losses.numel() == 6 * L + 2, g_losses.shape)
+    _require(g_losses.numel() == call.groups * (6 * L + 2), g_losses.shape)
     f32 = dict(device=call.ml.device, dtype=torch.float32)
     d_lg, d_ce, d_pa = torch.empty(L * B, nq, 2, **f32), torch.empty(L * B, nq, 2, **f32), torch.empty(L * B, nq, 3, **f32)
     d_ml = torch.empty_strided(call.ml.shape, call.ml.stride(), **f32)

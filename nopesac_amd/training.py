@@ -1225,7 +1225,7 @@ PLANE_LAST_LOSSES = ("loss_center_pixel", "loss_q")
 
 class _PlaneLosses(torch.autograd.Function):
     """ops.plane_losses / ops.plane_losses_backward on a PlaneCriterionCall whose match is already made: (pred_logits, pred_mask_logits,
-    pred_centers, pred_params [L*B, ...], pixel_centers or None) -> losses [6 L + 2].  Bookkeeping only."""
+    pred_centers, pred_params [L*B, ...], pixel_centers or None) -> losses [6 L + 2], or [G, 6 L + 2] of a grouped call.  Bookkeeping only."""
 
     @staticmethod
     def forward(ctx, call, logits, mask_logits, centers, params, pixel_centers):
@@ -1247,7 +1247,13 @@ class PlaneCriterion:
     depth [B, H, W], k_inv_dot_xy1 [B, 3, H, W];
     losses = the reference's names (aux layers with _0, _1, ...), unweighted, attached to autograd; weighted(losses) applies weight_dict
     as forward_single does; indices = {"match_q" int32 [L, B, nmax], "match_gt" int32 [L, B, nq], "n"} on the device, layer 0 = the last
-    decoder layer.  The reference's all-reduce of num_masks over ranks is the caller's: pass the reduced value as num_masks."""
+    decoder layer.  The reference's all-reduce of num_masks over ranks is the caller's: pass the reduced value as num_masks.
+
+    groups = G: the batch is G groups of B / G consecutive images (the two views of a 2B-image pass: groups=2), and every batch-wide
+    normaliser - num_masks, the matched count, the class weight sum, the B of loss_center_pixel and loss_q - is the group's, as the
+    reference's forward_single per view has them (siamese_planeTR.py:228-235).  Each returned loss is ((l_0 + l_1) + ...) / G over the
+    per-group values, summed in group order - the reference's (losses1[k] + losses2[k]) / 2 - and last["group_losses"] keeps the
+    per-group dicts (on the tape: a caller that weighs before it averages, as forward_single does, takes them).  num_masks: one value for every group, or G values.  groups=1 is the ungrouped call, bit for bit."""
 
     def __init__(self, cost_class=1.0, cost_mask=20.0, cost_dice=1.0, cost_center=0.5, cost_param=0.5, cost_offset=0.01, cost_angle=0.0028,
                  eos_coef=0.1, weight_dict: Optional[Dict[str, float]] = None, num_classes: int = 1):
@@ -1288,10 +1294,12 @@ class PlaneCriterion:
             t["plane_centers"], t["pixel_centers"] = ops.plane_targets(t["masks"], n_host, t["n"])
         return t
 
-    def __call__(self, outputs: dict, targets: dict, num_masks: Optional[float] = None):
+    def __call__(self, outputs: dict, targets: dict, num_masks=None, groups: int = 1):
         layers = [outputs] + list(outputs.get("aux_outputs", []))
         L = len(layers)
         B, nq = outputs["pred_logits"].shape[:2]
+        G = int(groups)
+        _require(G >= 1 and B % G == 0, "PlaneCriterion: groups=%d does not divide the batch of %d" % (G, B))
         t = self.prepare_targets(targets)
         if L == 1:
             ml = outputs["pred_mask_logits"]
@@ -1306,20 +1314,33 @@ class PlaneCriterion:
             px = px.contiguous()
         preds = {"pred_logits": stack("pred_logits"), "pred_mask_logits": ml, "pred_centers": stack("pred_centers"),
                  "pred_params": stack("pred_params"), "pixel_centers": px}
-        call = ops.PlaneCriterionCall(L, {k: (None if v is None else v.detach()) for k, v in preds.items()}, t, self.weights, num_masks or 0.0)
+        call = ops.PlaneCriterionCall(L, {k: (None if v is None else v.detach()) for k, v in preds.items()}, t, self.weights,
+                                      0.0 if num_masks is None else num_masks, G)
         ops.plane_match_costs(call)
         ops.plane_assign(call)
         vec = _PlaneLosses.apply(call, preds["pred_logits"], ml, preds["pred_centers"], preds["pred_params"], px)
-        losses = {}
-        for l in range(L):
-            sfx = "" if l == 0 else "_%d" % (l - 1)
-            for k, name in enumerate(PLANE_LAYER_LOSSES):
-                losses[name + sfx] = vec[6 * l + k]
-        if px is not None:
-            losses["loss_center_pixel"] = vec[6 * L]
-        losses["loss_q"] = vec[6 * L + 1]
+
+        def named(v):
+            out = {}
+            for l in range(L):
+                sfx = "" if l == 0 else "_%d" % (l - 1)
+                for k, name in enumerate(PLANE_LAYER_LOSSES):
+                    out[name + sfx] = v[6 * l + k]
+            if px is not None:
+                out["loss_center_pixel"] = v[6 * L]
+            out["loss_q"] = v[6 * L + 1]
+            return out
         nmax = t["masks"].shape[1]
         self.last = {"cost": call.cost.view(L, B, nq, nmax), "targets": t}
+        if G == 1:
+            losses = named(vec)
+            self.last["group_losses"] = [dict(losses)]
+        else:
+            mean = vec[0]
+            for g in range(1, G):                                                # in group order: (l_0 + l_1) / 2 for the two views
+                mean = mean + vec[g]
+            losses = named(mean / G)
+            self.last["group_losses"] = [named(vec[g]) for g in range(G)]
         return losses, {"match_q": call.match_q.view(L, B, nmax), "match_gt": call.match_gt.view(L, B, nq), "n": t["n_host"].tolist()}
 
     def weighted(self, losses: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -1447,13 +1468,13 @@ class PlaneInstanceHeadsTrainer(HeadTrainer):
             out["aux_outputs"] = [layer(l) for l in range(L - 1)]
         return out
 
-    def losses(self, hs: torch.Tensor, p1: torch.Tensor, targets: dict, num_masks: Optional[float] = None):
+    def losses(self, hs: torch.Tensor, p1: torch.Tensor, targets: dict, num_masks=None, groups: int = 1):
         """-> (losses, indices) of PlaneCriterion.from_cfg on forward(hs, p1), the autograd tape attached; hs / p1 may require grad (their
-        gradients land in `input_grads` after backward())."""
+        gradients land in `input_grads` after backward()).  groups: the criterion's view groups (2 for the two views of a 2B batch)."""
         out = self.forward(hs, p1)
         self._watch({"hs": hs, "p1": p1})
         self.last = out
-        return self.criterion(out, targets, num_masks)
+        return self.criterion(out, targets, num_masks, groups)
 
     def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
         """d (sum of the losses under criterion.weighted's weights, or under `loss_weights`) / d parameters -> {state-dict key: gradient}."""
@@ -1636,21 +1657,23 @@ class PlaneDecoderTrainer(ChainedTrainer):
         return self._out
 
     def losses(self, heads: "PlaneInstanceHeadsTrainer", memory: torch.Tensor, pos: torch.Tensor, p1: torch.Tensor, targets: dict, p: float = 0.0,
-               seed: int = 0, step: int = 0, num_masks: Optional[float] = None):
-        """Decoder, then the instance heads, then their PlaneCriterion: -> (losses, indices) of heads.losses on this forward's hs."""
+               seed: int = 0, step: int = 0, num_masks=None, groups: int = 1):
+        """Decoder, then the instance heads, then their PlaneCriterion: -> (losses, indices) of heads.losses on this forward's hs.  groups:
+        the criterion's view groups; the decoder itself couples no two images."""
         self._heads = heads
-        return heads.losses(self.forward(memory, pos, p1.shape[0], p, seed, step), p1, targets, num_masks)
+        return heads.losses(self.forward(memory, pos, p1.shape[0], p, seed, step), p1, targets, num_masks, groups)
 
 
 PYRAMID_CONVS = ("up_conv3", "up_conv2", "up_conv1", "c4_conv", "c3_conv", "c2_conv", "c1_conv", "m_conv_dict.m4")
 PYRAMID_BN_EPS, PYRAMID_BN_MOMENTUM = 1e-5, 0.1                   # nn.BatchNorm2d's defaults (planeTR_head.py:212)
 
 
-def _bn_statistics(src, up: bool, run_mean, run_var, batch_stats: bool):
-    """(mean, rstd) of a pyramid BatchNorm: the batch's (the running buffers are updated in place), or the stored ones."""
+def _bn_statistics(src, up: bool, run_mean, run_var, batch_stats: bool, groups: int = 1):
+    """(mean, rstd) of a pyramid BatchNorm: the batch's - per view group, [groups, C], for groups > 1 - with the running buffers updated
+    in place (group after group), or the stored ones."""
     if batch_stats:
         mean, _var, rstd = ops.bn_train_stats(src, up=up, eps=PYRAMID_BN_EPS, momentum=PYRAMID_BN_MOMENTUM, running_mean=run_mean,
-                                              running_var=run_var)
+                                              running_var=run_var, groups=groups)
         return mean, rstd
     return run_mean, torch.rsqrt(run_var + PYRAMID_BN_EPS)
 
@@ -1661,25 +1684,27 @@ class _ConvBNTrain(torch.autograd.Function):
     stage: relu(bn(conv1x1(up2(x)))) + addend, evaluated as relu(bn(up2(c))) + addend with c = conv1x1(x) at the LOW resolution (the 1x1
     conv commutes with the bilinear interpolation, PlaneTRHead._pyramid); the batch statistics are those of up2(c), which the kernels
     evaluate on the fly, and the backward gathers the bilinear adjoint inside the BatchNorm backward's launch.  The raw conv output is
-    saved; the conv's dgrad / wgrad run at its own (low) resolution."""
+    saved; the conv's dgrad / wgrad run at its own (low) resolution.  groups > 1 (with batch statistics): the images are that many view
+    groups, each normalised by its own statistics; the conv and its gradients are per pixel and take the whole batch."""
 
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, addend, run_mean, run_var, batch_stats: bool, up: bool):
+    def forward(ctx, x, w, gamma, beta, addend, run_mean, run_var, batch_stats: bool, up: bool, groups: int = 1):
         x = x.contiguous()
         c = ops.conv2d(x, _ohwi(w, x.shape[3]))
-        mean, rstd = _bn_statistics(c, up, run_mean, run_var, batch_stats)
-        ctx.conf = (batch_stats, up)
+        G = int(groups) if batch_stats else 1
+        mean, rstd = _bn_statistics(c, up, run_mean, run_var, batch_stats, G)
+        ctx.conf = (batch_stats, up, G)
         ctx.save_for_backward(x, w, c, gamma, beta, mean, rstd)
-        return ops.bn_train_apply(c, gamma, beta, mean, rstd, ops.ACT_RELU, None if addend is None else addend.contiguous(), up=up)
+        return ops.bn_train_apply(c, gamma, beta, mean, rstd, ops.ACT_RELU, None if addend is None else addend.contiguous(), up=up, groups=G)
 
     @staticmethod
     def backward(ctx, g):
         x, w, c, gamma, beta, mean, rstd = ctx.saved_tensors
-        batch_stats, up = ctx.conf
+        batch_stats, up, G = ctx.conf
         g = g.contiguous()
-        dc, dgamma, dbeta = ops.bn_train_backward(g, c, gamma, beta, mean, rstd, ops.ACT_RELU, up=up, batch_stats=batch_stats)
+        dc, dgamma, dbeta = ops.bn_train_backward(g, c, gamma, beta, mean, rstd, ops.ACT_RELU, up=up, batch_stats=batch_stats, groups=G)
         dx, dw = _conv_input_grads(ctx, x, w, dc, 1, 0)
-        return dx, dw, dgamma, dbeta, (g if ctx.needs_input_grad[4] else None), None, None, None, None
+        return dx, dw, dgamma, dbeta, (g if ctx.needs_input_grad[4] else None), None, None, None, None, None
 
 
 class PlanePyramidTrainer(ChainedTrainer):
@@ -1741,10 +1766,15 @@ class PlanePyramidTrainer(ChainedTrainer):
         self._copy_into(head, {**self.params, **self.buffers})
 
     # ---- forward
-    def forward(self, feats: dict, memory: torch.Tensor, B: int, batch_stats: bool = True) -> torch.Tensor:
+    def forward(self, feats: dict, memory: torch.Tensor, B: int, batch_stats: bool = True, groups: int = 1) -> torch.Tensor:
         """feats: res2 .. res5 f32 NHWC ([B, h, w, 256 / 512 / 1024 / 2048], each level twice the next one's size), memory [B*Lm, 256] f32 with
-        Lm = res5's pixels -> p1 [B, h2, w2, 256], the pixel decoder's map at res2's resolution, autograd tape attached."""
+        Lm = res5's pixels -> p1 [B, h2, w2, 256], the pixel decoder's map at res2's resolution, autograd tape attached.
+        groups = G: the B images are G view groups of B / G consecutive ones (groups=2: both views of a pair batch, view 1 first), and every
+        BatchNorm takes its batch statistics per group, updates its running buffers group after group and counts G batches - what the
+        reference's G top_down calls leave; p1 of a group has the bits of a forward on that group alone.  batch_stats=False ignores it."""
         P, Bf = self.params, self.buffers
+        G = int(groups) if batch_stats else 1
+        _require(G >= 1 and B % G == 0, "PlanePyramidTrainer: groups=%d does not divide the batch of %d" % (G, B))
         c = {}
         for k in ("res2", "res3", "res4", "res5"):
             t = feats[k]
@@ -1762,9 +1792,9 @@ class PlanePyramidTrainer(ChainedTrainer):
         def stage(up, x, nm, other):
             q = f"{PLANE_PREFIX}{TOP_DOWN}.{nm}"
             y = _ConvBNTrain.apply(x, P[q + ".0.weight"], P[q + ".1.weight"], P[q + ".1.bias"], other, Bf[q + ".1.running_mean"],
-                                   Bf[q + ".1.running_var"], bs, up)
+                                   Bf[q + ".1.running_var"], bs, up, G)
             if bs:
-                Bf[q + ".1.num_batches_tracked"] += 1
+                Bf[q + ".1.num_batches_tracked"] += G
             return y
         p4 = stage(False, mem.view(B, hc, wc, 256), "m_conv_dict.m4", stage(False, c["res5"], "c4_conv", None))
         p3 = stage(True, p4, "up_conv3", stage(False, c["res4"], "c3_conv", None))
@@ -1773,11 +1803,12 @@ class PlanePyramidTrainer(ChainedTrainer):
         return self._out
 
     def losses(self, heads: "PlaneInstanceHeadsTrainer", feats: dict, memory: torch.Tensor, hs: torch.Tensor, targets: dict,
-               batch_stats: bool = True, num_masks: Optional[float] = None):
+               batch_stats: bool = True, num_masks=None, groups: int = 1):
         """Pyramid, then the instance heads, then their PlaneCriterion: -> (losses, indices) of heads.losses on this forward's p1 (under deep
-        supervision p1 feeds every supervised layer's masks).  hs [L, B, nq, 256]: constants, or PlaneDecoderTrainer.forward's output."""
+        supervision p1 feeds every supervised layer's masks).  hs [L, B, nq, 256]: constants, or PlaneDecoderTrainer.forward's output.
+        groups: the view groups of the BatchNorm statistics and of the criterion alike."""
         self._heads = heads
-        return heads.losses(hs, self.forward(feats, memory, hs.shape[1], batch_stats), targets, num_masks)
+        return heads.losses(hs, self.forward(feats, memory, hs.shape[1], batch_stats, groups), targets, num_masks, groups)
 
 
 class _ConvBiasInPlace(torch.autograd.Function):
@@ -1937,19 +1968,21 @@ class PlaneEncoderTrainer(ChainedTrainer):
 
     # ---- the whole head on one graph
     def losses(self, heads: "PlaneInstanceHeadsTrainer", decoder: "PlaneDecoderTrainer", pyramid: "PlanePyramidTrainer", feats: dict,
-               targets: dict, p: float = 0.0, seed: int = 0, step: int = 0, batch_stats: bool = True, num_masks: Optional[float] = None):
+               targets: dict, p: float = 0.0, seed: int = 0, step: int = 0, batch_stats: bool = True, num_masks=None, groups: int = 1):
         """Encoder, then the decoder and the pyramid on this forward's memory, then the instance heads and their PlaneCriterion:
         -> (losses, indices) of heads.losses.  feats: res2 .. res5 f32 NHWC.  The decoder and the pyramid each take their own view of
-        the one non-leaf memory, so each reports its own path in input_grads["memory"] and the encoder receives their two-term sum."""
+        the one non-leaf memory, so each reports its own path in input_grads["memory"] and the encoder receives their two-term sum.
+        groups: the view groups of the pyramid's BatchNorm statistics and of the criterion (2 for a 2B-image pair batch); the encoder
+        and the decoder couple no two images."""
         res5 = feats["res5"]
         B, h, w = res5.shape[:3]
         memory = self.forward(res5, B, p, seed, step)
         if "res5" in self._inputs:                                  # the leaf the encoder watches is the pyramid's too: both paths sum
             feats = dict(feats, res5=self._inputs["res5"])
         hs = decoder.forward(memory.view_as(memory), self.pos(h, w, res5.device), B, p, seed, step)
-        p1 = pyramid.forward(feats, memory.view_as(memory), B, batch_stats)
+        p1 = pyramid.forward(feats, memory.view_as(memory), B, batch_stats, groups)
         self._heads, self._chain = heads, (decoder, pyramid)
-        return heads.losses(hs, p1, targets, num_masks)
+        return heads.losses(hs, p1, targets, num_masks, groups)
 
     def backward(self, losses: Dict[str, torch.Tensor], loss_weights: Optional[Dict[str, float]] = None) -> Dict[str, torch.Tensor]:
         """The chain's backward: the instance heads' backward runs on through the decoder and the pyramid into the encoder.  -> the
@@ -2198,7 +2231,7 @@ class TwoViewLosses:
     what the reference detaches.  `camera_head` is the inference head: it supplies the loss weights and switches.
 
         two_view = TwoViewLosses(matcher, camera, model.camera_head_list[0])
-        plane_losses, idx = heads.losses(hs, p1, pair["targets"])
+        plane_losses, idx = heads.losses(hs, p1, pair["targets"], groups=2)      # 2B images, view 1 first: the criterion per view
         tv = two_view.losses(hs[-1], heads.last["pred_params"], idx["match_q"][0][:B], idx["match_q"][0][B:], n[:B], n[B:], pair, feats, B)
         grads = joint_backward([heads, matcher, camera], {**heads.criterion.weighted(plane_losses), **tv})"""
 

@@ -2,7 +2,7 @@
 rounds of losses -> backward -> step_from_cfg on fixed-seed inputs at the small shapes of the GPU suites (B = 2, nq = 50 for the camera
 head and the matcher with 5 Sinkhorn iterations, nq = 7 and a 6 x 8 encoder map for the plane head), and the script prints one sha256
 per configuration over the losses, every gradient by sorted key, input_grads, the parameters after both steps, the optimiser state and
-the buffers - and the ordered list of library entry points the rounds called (run-length encoded; --calls count prints only its length
+the buffers (`heads_groups2` / `pyramid_groups2`: the same rounds on view groups) - and the ordered list of library entry points the rounds called (run-length encoded; --calls count prints only its length
 and hash).  Everything on this path is f32 and deterministic, so two commits that compute the same thing print the same text.  Only
 public API of the trainers is used.
 
@@ -158,17 +158,25 @@ def plane_trainers(dev):
             T.PlanePyramidTrainer.from_state_dict(pyr_sd, dev, feature_grads=True))
 
 
-def heads(dev, d):
-    x = plane_inputs(dev)
-    tr, _, _ = plane_trainers(dev)
-    hs, p1 = x["hs"].clone().requires_grad_(True), x["p1"].clone().requires_grad_(True)
+def heads(groups=None):
+    """groups=2: the criterion on view groups (one image each at B = 2), with the per-group losses in the digest."""
+    kw = {} if groups is None else {"groups": groups}
 
-    def one(i):
-        losses, indices = tr.losses(hs, p1, x["targets"])
-        grads = tr.backward(losses)
-        d.add("indices%d" % i, {k: v for k, v in indices.items() if torch.is_tensor(v)})
-        return losses, grads, tr.input_grads
-    rounds(d, {"heads": tr}, one)
+    def run(dev, d):
+        x = plane_inputs(dev)
+        tr, _, _ = plane_trainers(dev)
+        hs, p1 = x["hs"].clone().requires_grad_(True), x["p1"].clone().requires_grad_(True)
+
+        def one(i):
+            losses, indices = tr.losses(hs, p1, x["targets"], **kw)
+            grads = tr.backward(losses)
+            d.add("indices%d" % i, {k: v for k, v in indices.items() if torch.is_tensor(v)})
+            if groups is not None:
+                for g, per in enumerate(tr.criterion.last["group_losses"]):
+                    d.add("group%d.losses%d" % (g, i), per)
+            return losses, grads, tr.input_grads
+        rounds(d, {"heads": tr}, one)
+    return run
 
 
 def decoder(p):
@@ -185,16 +193,21 @@ def decoder(p):
     return run
 
 
-def pyramid(dev, d):
-    x = plane_inputs(dev)
-    hd, _, pyr = plane_trainers(dev)
+def pyramid(groups=None):
+    """groups=2: the BatchNorm statistics and the criterion on view groups (one image each at B = 2)."""
+    kw = {} if groups is None else {"groups": groups}
 
-    def one(i):
-        losses, _ = pyr.losses(hd, x["feats"], x["memory"], x["hs"], x["targets"])
-        grads = pyr.backward(losses)
-        d.add("pyr.grads%d" % i, pyr.grads)
-        return losses, grads, pyr.input_grads
-    rounds(d, {"pyramid": pyr, "heads": hd}, one)
+    def run(dev, d):
+        x = plane_inputs(dev)
+        hd, _, pyr = plane_trainers(dev)
+
+        def one(i):
+            losses, _ = pyr.losses(hd, x["feats"], x["memory"], x["hs"], x["targets"], **kw)
+            grads = pyr.backward(losses)
+            d.add("pyr.grads%d" % i, pyr.grads)
+            return losses, grads, pyr.input_grads
+        rounds(d, {"pyramid": pyr, "heads": hd}, one)
+    return run
 
 
 def shared_memory(dev, d):
@@ -228,9 +241,36 @@ def backbone(dev, d):
     rounds(d, {"backbone": tr}, one)
 
 
-CONFIGS = (("refine", refine), ("camera", camera(False)), ("camera_conv_stacks", camera(True)), ("matcher", matcher), ("heads", heads),
-           ("decoder_p0", decoder(0.0)), ("decoder_p0.1", decoder(0.1)), ("pyramid", pyramid), ("decoder_pyramid_shared_memory", shared_memory),
-           ("backbone", backbone), ("camera_conv_stacks_batch_stats", camera(True, batch_stats=True)))
+def train_step(dev, d):
+    """Two TrainStep steps on two 480 x 640 pairs (the only size the camera head admits), dropout and augmentation on."""
+    import tempfile
+
+    from nopesac_amd.registry import build_model
+    from nopesac_amd.train_step import TrainStep
+    from tests import train_step_forms as F
+    cfg = get_cfg()
+    cfg.merge_from_file(os.path.join(ROOT, "configs", "inference_mp3d.yaml"))
+    cfg.merge_from_list(["MODEL.DEVICE", str(dev), "MODEL.AMD.COMPUTE_DTYPE", "float32", "DATALOADER.AUGMENTATION", True])
+    model = build_model(cfg).eval()
+    model.load_state_dict(synth_state_dict(50))
+    ts = TrainStep.from_model(model, cfg, seed=5)
+    entries = F.pair_entries(2, 480, 640, tempfile.mkdtemp(prefix="digest_"))
+    del CALLS[:]
+    for i in range(ROUNDS):
+        d.add("losses%d" % i, ts.step(entries))
+        d.add("grads%d" % i, {k: p.grad for t in ts.trainers.values() for k, p in t.params.items()})
+    ts.check()
+    for tag, tr in ts.trainers.items():
+        d.add(tag + ".params", tr.params)
+        d.add(tag + ".buffers", getattr(tr, "buffers", {}))
+    sd = ts.optimizer.state_dict()
+    d.add("optimizer", {"%s/%s" % (k, n): v for k, st in sd["state"].items() for n, v in st.items() if torch.is_tensor(v)})
+
+
+CONFIGS = (("refine", refine), ("camera", camera(False)), ("camera_conv_stacks", camera(True)), ("matcher", matcher), ("heads", heads()),
+           ("decoder_p0", decoder(0.0)), ("decoder_p0.1", decoder(0.1)), ("pyramid", pyramid()), ("decoder_pyramid_shared_memory", shared_memory),
+           ("backbone", backbone), ("camera_conv_stacks_batch_stats", camera(True, batch_stats=True)), ("heads_groups2", heads(2)),
+           ("pyramid_groups2", pyramid(2)), ("train_step", train_step))
 
 
 def run_length(names):
