@@ -2,7 +2,8 @@
 // __forward_PixelCameraHead, camera_net/camera_head.py:642-683): conv dgrad / wgrad, inference-mode BatchNorm + (Leaky)ReLU, GroupNorm,
 // 2x2 max-pool, nearest 2x upsample-add and the correlation softmax.  f32 throughout, NHWC activations, caller-allocated buffers.
 // Deterministic: no atomics; every cross-workgroup sum is written as partials and reduced in a fixed order.
-// Gated against float64 torch.autograd (tests/test_conv_backward_gpu.py, tests/test_pose_net_training_gpu.py).
+// Gated against float64 torch.autograd (tests/test_conv_backward_gpu.py, tests/test_pose_net_training_gpu.py); the stride-1 dgrad - the
+// weight rotation bit for bit, then the f32 conv kernel per element - also by tests/test_conv_f32_forms_gpu.py (tests/conv_f32_forms.py).
 #include "common.h"
 
 namespace nps {
